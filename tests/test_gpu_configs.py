@@ -392,6 +392,52 @@ def test_config4_full_size_b256_n8192_on_one_gpu(oracle):
     _full_size_checks(oracle, at, x, gt, [0, 100, 201, 255], hist, emd=False)
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_timed_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps in one window and measures nothing beside the
+    headline; --dump-outputs writes what the timed path computed: bit for bit the metrics and best clouds of W + K attack
+    iterations on bench.py's seeded inputs, recomputed here in a fresh handle (the clock-ramp priming leaves no trace)."""
+    import json, subprocess, sys
+    import torch
+    from geometric_adv_amd import weights as W
+    from geometric_adv_amd.adv_ae import AdvAE, Configuration
+    from geometric_adv_amd.autoencoder import PointNetAE
+    from conftest import cloud
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    K, Wm, b, n = 20, 5, 32, 2048
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(Wm),
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == K and out["warmup"] == Wm and out["n_gpus"] == 1 and out["higher_is_better"] is True
+    assert len(out["windows_ms"]) == 1 and abs(out["ms_per_step"] * K - out["windows_ms"][0]) < 1e-3
+    assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-9 * out["value"]
+    for k in ("roofline", "roofline_chamfer", "cpu_baseline", "secondary", "calibration", "value_all_pairs", "strong_scaling"):
+        assert k not in out
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("metrics", "adversarial_pc_input", "adversarial_pc_recon")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["metrics"].shape == (b, 5) and got["adversarial_pc_input"].shape == got["adversarial_pc_recon"].shape == (b, n, 3)
+
+    w = W.synthetic_weights(n, seed=7)                    # bench.py's weights and rank 0's seeds
+    x, gt = cloud(1002, b, n), cloud(2002, b, n)
+    thresh = Wm + int(0.8 * K) + 1
+    dev = torch.device("cuda:0")
+    ae = PointNetAE(w, n, device=dev)
+    at = AdvAE("adversary", Configuration(batch_size=b, n_points=n, weights=w, loss_adv_type="chamfer", loss_dist_type="chamfer",
+                                          dist_weight_list=[1.0], num_iterations=Wm + K, num_iterations_thresh=thresh,
+                                          learning_rate=0.01), device=dev, ae=ae)
+    at.set_inputs(x, gt, ae.transform(gt), 1.0)
+    at.init_pert(None, reset_optimizer=True)
+    at.run(0, Wm + K, thresh)
+    want = dict(zip(("metrics", "adversarial_pc_input", "adversarial_pc_recon"),
+                    (t.cpu().numpy() for t in at.get_best(torch.as_tensor(ae.get_loss_per_pc(gt)).to(dev)))))
+    for k in got:
+        assert np.array_equal(got[k], want[k]), k
+    assert abs(out["final_mean_target_recon_error"] - float(want["metrics"][:, 4].mean())) <= 1e-5 * abs(out["final_mean_target_recon_error"])
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2 ...` from a bare shell (no torchrun, WORLD_SIZE unset): the parent spawns the two ranks before
     touching the GPU and relays rank 0's line.  The box has one GPU, so GEOADV_BENCH_SHARE_GPU=1 puts both ranks on cuda:0 with
@@ -401,7 +447,7 @@ def test_bench_starts_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["GEOADV_BENCH_SHARE_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--windows", "3"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--windows", "3", "--full"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -14,7 +14,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 # the headline leg only: no secondary legs, no RCCL self-test child (a second profiled process on the GPU whose CSVs the summary
 # would glob, inside the time limit of a counter-serialised pass)
-BENCH="python3 bench.py --steps 40 --warmup 5 --windows 1 --no-cpu-baseline --no-secondary --no-rccl-selftest"
+BENCH="python3 bench.py --full --steps 40 --warmup 5 --windows 1 --no-cpu-baseline --no-secondary --no-rccl-selftest"
 LOOP="python3 tools/attack_breakdown.py 32"
 i=0
 for set in "SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "FETCH_SIZE" "WRITE_SIZE"; do

@@ -13,8 +13,8 @@ python tools/debug/mx_check.py notest > $O/${R}_mx_check.json 2> $O/mx_check.log
 python tools/debug/loss_in_scan_ab.py 32 64 > $O/${R}_loss_in_scan_ab.jsonl 2> $O/lis.log
 python tools/scorer_time.py > $O/${R}_scorer.jsonl 2> $O/scorer.log
 python tools/debug/sweep_small.py > $O/${R}_sweep_small.txt 2> $O/sweep.log
-python bench.py > $O/${R}_bench_default.json 2> $O/bench_default.log
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench_k20.json 2> $O/bench_k20.log
+python bench.py --full > $O/${R}_bench_default.json 2> $O/bench_default.log
+python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_k20.json 2> $O/bench_k20.log
 cut -c1-300 $O/${R}_bench_default.json; echo; cut -c1-300 $O/${R}_bench_k20.json; echo
 rm -rf $O/pmc $O/legs
 ls -la $O | head -60
