@@ -1,0 +1,416 @@
+// geoadv_cls: the PointNet classifier of the reference's semantic evaluation (classifier/pointnet_cls.py:30-84 with
+// classifier/transform_nets.py), inference only, fp32 throughout.
+//
+// Six launches per forward (plus one memset of the three pooled vectors):
+//   chain<1>  T-Net1 per point: tconv1 3->64 (VALU), tconv2 64->128, tconv3 128->1024 -> running max     (pooled[0])
+//   head<T1>  tfc1 1024->512, tfc2 512->256, transform_XYZ 256->9 (+I) = T1; writes W1'[c] = T1 @ W_conv1   (per cloud)
+//   chain<3>  conv1' 3->64 (x @ W1'), conv2 64->64, T-Net2 tconv1 64->64, tconv2 64->128, tconv3 128->1024 -> max
+//   head<T2>  tfc1, tfc2, transform_feat 256->4096 (+I) = T2; writes W3'[c] = T2 @ W_conv3, packed for the MFMA
+//   chain<3>  conv1', conv2, conv3' 64->64 (h @ W3'), conv4 64->128, conv5 128->1024 -> max                  (pooled[2])
+//   head<CLS> fc1, fc2, fc3 256->C: logits, first-max argmax
+// FOLDING: T1 is folded into conv1 and T2 into conv3 (the products x @ T1 @ W and h @ T2 @ W are rounded as x @ (T1 @ W)),
+// per cloud, by the head kernel that computes the transform.  The third chain recomputes conv1 / conv2 (4 288 of its
+// 147 648 multiply-adds per point) instead of storing the 64-wide features of every point.
+//
+// The chain kernel: a workgroup owns a tile of 64 points of one cloud (and a slice of the 1024 pooled columns: small batches
+// split the columns over up to four workgroups, each recomputing the cheap narrow prefix).  The narrow layers run from LDS
+// through layer_gemm (mfma_tile.h, v_mfma_f32_32x32x2_f32); the 1024-wide layer streams 32-column blocks through gemm_chain
+// and folds each block's 64 rows into a per-column max in registers -- the [n x 1024] activation never leaves the CU.  The
+// cross-tile max is an integer atomicMax on the float bits of post-ReLU values (>= +0; a NaN becomes +0 in the ReLU), which
+// is exact and independent of the order of tiles; rows past n are excluded before the max.  Per-point work does not depend
+// on the point's position, so a cloud's logits do not depend on its point order, padding or batch neighbours.
+//
+// Batch norm is folded at create time (eps 1e-3, tf_util.batch_norm_template): y = relu((x @ W) * scale + shift),
+// scale = gamma * rsqrt(var + eps), shift = b * scale + (beta - mean * scale).
+#include "mfma_tile.h"
+#include <math.h>
+#include <string.h>
+#include <vector>
+
+namespace geoadv {
+
+constexpr int CLS_ROWS = 64, CLS_THREADS = 512, CLS_POOL = 1024;
+constexpr int CLS_SA = 68, CLS_SB = 132;          // LDS row strides: buffer A holds 64-wide activations, B up to 128-wide
+constexpr int CLS_MAX_GRID_Y = 65535;
+
+struct ClsLayerDev {                                // one per-point layer
+    PackedLayer L;                                  // packed fragments (mid / wide layers); L.w of cloud c = L.w + c * cloud_stride
+    const float *scale, *shift;
+    int cloud_stride;                               // floats; 0 = shared by all clouds
+};
+struct ClsChainArgs {
+    const float *x;                                 // [b][n][3]
+    const float *w0; int w0_cloud_stride;           // layer 0 (fan-in 3): [3][64] row-major
+    const float *sc0, *sh0;
+    ClsLayerDev mid[3];                             // narrow MFMA layers
+    ClsLayerDev wide;                               // 128 -> 1024, pooled
+    int *pooled;                                    // [b][1024] float bits, zeroed before the launch
+    int n, slices;
+};
+
+// narrow layer: out[64][NOUT] = relu((in @ W) * scale + shift)
+template <int NOUT>
+__device__ __forceinline__ void cls_mid(const float *in, int s_in, const ClsLayerDev &d, int cloud, float *out, int s_out) {
+    PackedLayer L = d.L;
+    L.w += (size_t)cloud * d.cloud_stride;
+    layer_gemm<CLS_ROWS, NOUT, 1>(in, s_in, L, nullptr, [&](int row, int col, float a) {
+        out[row * s_out + col] = fmaxf(a * d.scale[col] + d.shift[col], 0.f);
+    });
+}
+
+template <int NMID>
+__global__ __launch_bounds__(CLS_THREADS, 2) void cls_chain_kernel(ClsChainArgs A, int cloud0) {
+    __shared__ __attribute__((aligned(16))) float bufA[CLS_ROWS * CLS_SA];
+    __shared__ __attribute__((aligned(16))) float bufB[CLS_ROWS * CLS_SB];
+    __shared__ float pts[CLS_ROWS * 3];
+    const int tile = blockIdx.x, cloud = cloud0 + blockIdx.y, slice = blockIdx.z;
+    const int n = A.n, n0 = tile * CLS_ROWS;
+    const int live = n - n0 < CLS_ROWS ? n - n0 : CLS_ROWS;
+    if (threadIdx.x < CLS_ROWS * 3) {
+        const int r = threadIdx.x / 3;
+        pts[threadIdx.x] = r < live ? A.x[((size_t)cloud * n + n0) * 3 + threadIdx.x] : 0.f;
+    }
+    __syncthreads();
+    {   // layer 0: 3 -> 64 on the VALU
+        const float *w0 = A.w0 + (size_t)cloud * A.w0_cloud_stride;
+        for (int e = threadIdx.x; e < CLS_ROWS * 64; e += CLS_THREADS) {
+            const int r = e >> 6, c = e & 63;
+            const float a = pts[3 * r] * w0[c] + pts[3 * r + 1] * w0[64 + c] + pts[3 * r + 2] * w0[128 + c];
+            bufA[r * CLS_SA + c] = fmaxf(a * A.sc0[c] + A.sh0[c], 0.f);
+        }
+    }
+    __syncthreads();
+    if (NMID == 1) {
+        cls_mid<128>(bufA, CLS_SA, A.mid[0], cloud, bufB, CLS_SB);
+    } else {
+        cls_mid<64>(bufA, CLS_SA, A.mid[0], cloud, bufB, CLS_SB);
+        __syncthreads();
+        cls_mid<64>(bufB, CLS_SB, A.mid[1], cloud, bufA, CLS_SA);
+        __syncthreads();
+        cls_mid<128>(bufA, CLS_SA, A.mid[2], cloud, bufB, CLS_SB);
+    }
+    __syncthreads();
+    // the wide layer: 32-column blocks of this workgroup's slice dealt to the 8 waves, both row blocks per wave (RM = 2)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int h = lane >> 5, i = lane & 31;
+    const int nblk = (CLS_POOL / 32) / A.slices;
+    int *pooled = A.pooled + (size_t)cloud * CLS_POOL;
+    for (int j = wave; j < nblk; j += CLS_THREADS / 64) {
+        const int cb = slice * nblk + j;
+        f32x16 acc[2] = {};
+        gemm_chain<2>(bufB, CLS_SB, 0, A.wide.L, cb, 0, 128 / 8, acc);
+        const int col = cb * 32 + i;
+        const float sc = A.wide.scale[col], sh = A.wide.shift[col];
+        int m = 0;                                   // +0.0f: the ReLU's floor, and the identity of the max
+#pragma unroll
+        for (int rm = 0; rm < 2; ++rm)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rm * 32 + acc_row(r, h);
+                const int v = __float_as_int(fmaxf(acc[rm][r] * sc + sh, 0.f));
+                if (row < live) m = max(m, v);
+            }
+        m = max(m, __shfl_xor(m, 32));
+        if (h == 0 && m > 0) atomicMax(pooled + col, m);
+    }
+}
+
+enum { CLS_HEAD_T1 = 0, CLS_HEAD_T2 = 1, CLS_HEAD_CLS = 2 };
+struct ClsHeadArgs {
+    const int *pooled;                              // [b][1024] float bits
+    const float *w1, *sc1, *sh1;                    // 1024 -> 512
+    const float *w2, *sc2, *sh2;                    // 512 -> 256
+    const float *w3, *b3;                           // 256 -> M, linear (b3 carries the identity for the transforms)
+    int M;
+    float *t_out, *t_user;                          // T1 / T2: [b][M] (t_user may be null); CLS: logits [b][M]
+    const float *fold_w;                            // T1: conv1 weights [3][64]; T2: conv3 weights [64][64]
+    float *fold_out;                                // T1: W1' [b][3][64]; T2: W3' packed [b][4096]
+    int *labels;                                    // CLS: [b]
+};
+
+template <int MODE>
+__global__ __launch_bounds__(CLS_THREADS) void cls_head_kernel(ClsHeadArgs H, int cloud0) {
+    __shared__ float in[CLS_POOL], h1[512], part[512], h2[256];
+    __shared__ float tv[MODE == CLS_HEAD_T1 ? 16 : 4096];
+    const int c = cloud0 + blockIdx.x, t = threadIdx.x;
+    for (int k = t; k < CLS_POOL; k += CLS_THREADS) in[k] = __int_as_float(H.pooled[(size_t)c * CLS_POOL + k]);
+    __syncthreads();
+    {
+        float a = 0.f;
+        const float *w = H.w1 + t;
+#pragma unroll 8
+        for (int k = 0; k < CLS_POOL; ++k) a = fmaf(in[k], w[(size_t)k * 512], a);
+        h1[t] = fmaxf(a * H.sc1[t] + H.sh1[t], 0.f);
+    }
+    __syncthreads();
+    {
+        const int o = t & 255, k0 = (t >> 8) * 256;
+        float a = 0.f;
+        const float *w = H.w2 + o;
+#pragma unroll 8
+        for (int k = k0; k < k0 + 256; ++k) a = fmaf(h1[k], w[(size_t)k * 256], a);
+        part[t] = a;
+    }
+    __syncthreads();
+    if (t < 256) h2[t] = fmaxf((part[t] + part[t + 256]) * H.sc2[t] + H.sh2[t], 0.f);
+    __syncthreads();
+    const int M = H.M;
+    for (int o = t; o < M; o += CLS_THREADS) {
+        float a = 0.f;
+        const float *w = H.w3 + o;
+#pragma unroll 8
+        for (int k = 0; k < 256; ++k) a = fmaf(h2[k], w[(size_t)k * M], a);
+        a = a + H.b3[o];
+        H.t_out[(size_t)c * M + o] = a;
+        if (H.t_user) H.t_user[(size_t)c * M + o] = a;
+        if (MODE != CLS_HEAD_T1) tv[o] = a;
+        else if (o < 16) tv[o] = a;
+    }
+    __syncthreads();
+    if (MODE == CLS_HEAD_T1) {
+        // W1'[k][n] = sum_j T1[k][j] Wc1[j][n]: (x @ T1) @ Wc1 with x a row vector (pointnet_cls.py:38)
+        if (t < 192) {
+            const int k = t >> 6, nn = t & 63;
+            float a = tv[3 * k] * H.fold_w[nn];
+            a = fmaf(tv[3 * k + 1], H.fold_w[64 + nn], a);
+            a = fmaf(tv[3 * k + 2], H.fold_w[128 + nn], a);
+            H.fold_out[(size_t)c * 192 + t] = a;
+        }
+    } else if (MODE == CLS_HEAD_T2) {
+        // W3'[k][n] = sum_j T2[k][j] Wc3[j][n] (pointnet_cls.py:51), written in the 32x32x2 fragment layout (ae.h, K = N = 64)
+        for (int e = t; e < 4096; e += CLS_THREADS) {
+            const int k = e >> 6, nn = e & 63;
+            float a = 0.f;
+            for (int j = 0; j < 64; ++j) a = fmaf(tv[64 * k + j], H.fold_w[64 * j + nn], a);
+            const int cb = nn >> 5, kg = k >> 3, lane = ((k & 7) >> 2) * 32 + (nn & 31), u = k & 3;
+            H.fold_out[(size_t)c * 4096 + ((cb * 8 + kg) * 64 + lane) * 4 + u] = a;
+        }
+    } else if (t == 0) {
+        // np.argmax: the first maximum; a NaN counts as the maximum (the first NaN wins)
+        int best = 0;
+        float bv = tv[0];
+        for (int o = 1; o < M && !(bv != bv); ++o)
+            if (tv[o] > bv || tv[o] != tv[o]) { best = o; bv = tv[o]; }
+        H.labels[c] = best;
+    }
+}
+
+}  // namespace geoadv
+
+using namespace geoadv;
+
+namespace {
+enum {   // GEOADV_CLS_* layer order (include/geoadv.h)
+    T1C1 = 0, T1C2, T1C3, T1F1, T1F2, T1XYZ, C1, C2, T2C1, T2C2, T2C3, T2F1, T2F2, T2FEAT, C3, C4, C5, F1, F2, F3
+};
+const int kIn[GEOADV_CLS_LAYERS] = {3, 64, 128, 1024, 512, 256, 3, 64, 64, 64, 128, 1024, 512, 256, 64, 64, 128, 1024, 512, 256};
+const int kOut[GEOADV_CLS_LAYERS] = {64, 128, 1024, 512, 256, 9, 64, 64, 64, 128, 1024, 512, 256, 4096, 64, 128, 1024, 512, 256, 0};
+bool has_bn(int l) { return l != T1XYZ && l != T2FEAT && l != F3; }
+}  // namespace
+
+struct geoadv_cls {
+    int num_classes;
+    void *arena;
+    const float *raw[GEOADV_CLS_LAYERS];      // row-major [in][out] (head layers, layer 0s, the fold operands)
+    const float *packed[GEOADV_CLS_LAYERS];   // MFMA fragments (per-point layers of fan-in >= 64)
+    const float *scale[GEOADV_CLS_LAYERS], *shift[GEOADV_CLS_LAYERS];
+    const float *bias[GEOADV_CLS_LAYERS];     // linear layers: b (+ the identity for the two transforms)
+};
+
+static inline size_t cls_rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw) {
+    GA_REQUIRE(out && hw, "cls_create: null argument");
+    const int C = hw->num_classes;
+    GA_REQUIRE(C >= 1 && C <= 1024, "cls_create: num_classes %d out of range [1, 1024]", C);
+    for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) {
+        GA_REQUIRE(hw->w[l] && hw->b[l], "cls_create: null weight pointer at layer %d", l);
+        if (has_bn(l))
+            GA_REQUIRE(hw->gamma[l] && hw->beta[l] && hw->mean[l] && hw->var[l], "cls_create: null batch-norm pointer at layer %d", l);
+        else
+            GA_REQUIRE(!hw->gamma[l] && !hw->beta[l] && !hw->mean[l] && !hw->var[l],
+                       "cls_create: layer %d has no batch norm: its batch-norm pointers must be NULL", l);
+    }
+    int outw[GEOADV_CLS_LAYERS];
+    for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) outw[l] = l == F3 ? C : kOut[l];
+    std::vector<float> host;
+    auto reserve = [&](size_t count) { size_t off = cls_rup(host.size(), 64); host.resize(off + count, 0.f); return off; };
+    size_t o_raw[GEOADV_CLS_LAYERS], o_pk[GEOADV_CLS_LAYERS], o_sc[GEOADV_CLS_LAYERS], o_sh[GEOADV_CLS_LAYERS], o_b[GEOADV_CLS_LAYERS];
+    for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) {
+        const int K = kIn[l], N = outw[l];
+        o_raw[l] = reserve((size_t)K * N);
+        memcpy(&host[o_raw[l]], hw->w[l], sizeof(float) * K * N);
+        o_pk[l] = 0;
+        if (l == T1C2 || l == T1C3 || l == C2 || l == T2C1 || l == T2C2 || l == T2C3 || l == C4 || l == C5) {   // MFMA operands
+            o_pk[l] = reserve((size_t)K * N);
+            const float *W = hw->w[l];
+            const int kg = K / 8;
+            for (int cb = 0; cb < N / 32; ++cb)
+                for (int t = 0; t < kg; ++t)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int u = 0; u < 4; ++u) {
+                            const int k = 8 * t + 4 * (lane >> 5) + u, n = 32 * cb + (lane & 31);
+                            host[o_pk[l] + (((size_t)cb * kg + t) * 64 + lane) * 4 + u] = W[(size_t)k * N + n];
+                        }
+        }
+        o_sc[l] = o_sh[l] = o_b[l] = 0;
+        if (has_bn(l)) {
+            o_sc[l] = reserve(N);
+            o_sh[l] = reserve(N);
+            for (int c = 0; c < N; ++c) {
+                const float inv = hw->gamma[l][c] * (1.0f / sqrtf(hw->var[l][c] + 1e-3f));
+                host[o_sc[l] + c] = inv;
+                host[o_sh[l] + c] = hw->b[l][c] * inv + (hw->beta[l][c] - hw->mean[l][c] * inv);
+            }
+        } else {
+            o_b[l] = reserve(N);
+            for (int c = 0; c < N; ++c) host[o_b[l] + c] = hw->b[l][c];
+            // transform_nets.py: biases += [1,0,0,0,1,0,0,0,1] / eye(64).flatten() -- added here, once
+            if (l == T1XYZ) for (int d = 0; d < 3; ++d) host[o_b[l] + 4 * d] += 1.0f;
+            if (l == T2FEAT) for (int d = 0; d < 64; ++d) host[o_b[l] + 65 * d] += 1.0f;
+        }
+    }
+    geoadv_cls *m = new geoadv_cls();
+    m->num_classes = C;
+    const size_t bytes = sizeof(float) * host.size();
+    if (hipMalloc(&m->arena, bytes) != hipSuccess) {
+        delete m;
+        set_error("cls_create: hipMalloc of %zu bytes failed", bytes);
+        return GEOADV_ENOMEM;
+    }
+    const hipError_t e = hipMemcpy(m->arena, host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(m->arena);
+        delete m;
+        set_error("cls_create: upload failed: %s", hipGetErrorString(e));
+        return GEOADV_EHIP;
+    }
+    const float *base = static_cast<const float *>(m->arena);
+    for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) {
+        m->raw[l] = base + o_raw[l];
+        m->packed[l] = o_pk[l] ? base + o_pk[l] : nullptr;
+        m->scale[l] = has_bn(l) ? base + o_sc[l] : nullptr;
+        m->shift[l] = has_bn(l) ? base + o_sh[l] : nullptr;
+        m->bias[l] = has_bn(l) ? nullptr : base + o_b[l];
+    }
+    *out = m;
+    return GEOADV_OK;
+}
+
+extern "C" void geoadv_cls_destroy(geoadv_cls *cls) {
+    if (!cls) return;
+    (void)hipFree(cls->arena);
+    delete cls;
+}
+
+namespace {
+struct ClsScratch {
+    int *pooled;             // [3][b][1024]
+    float *t1, *w1f;         // [b][9], [b][192]
+    float *t2, *w3p;         // [b][4096] each
+    size_t bytes;
+};
+ClsScratch carve_cls(void *base, int b) {
+    ClsScratch s;
+    char *p = static_cast<char *>(base);
+    auto take = [&](size_t bytes) { char *q = p; p += cls_rup(bytes, 256); return q; };
+    s.pooled = reinterpret_cast<int *>(take(sizeof(int) * 3 * (size_t)b * CLS_POOL));
+    s.t1 = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 9));
+    s.w1f = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 192));
+    s.t2 = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 4096));
+    s.w3p = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 4096));
+    s.bytes = (size_t)(p - static_cast<char *>(base));
+    return s;
+}
+int chunk_of(int b) { return b < CLS_MAX_GRID_Y ? b : CLS_MAX_GRID_Y; }
+ClsLayerDev layer_dev(const geoadv_cls *m, int l, int K, int N) {
+    return ClsLayerDev{PackedLayer{m->packed[l], K, N}, m->scale[l], m->shift[l], 0};
+}
+}  // namespace
+
+extern "C" size_t geoadv_cls_workspace_bytes(const geoadv_cls *cls, int b, int n) {
+    (void)n;
+    if (!cls || b <= 0) return 256;
+    return carve_cls(nullptr, chunk_of(b)).bytes + 256;
+}
+
+extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const float *pc, float *logits, int *labels,
+                                  float *transform_in, float *transform_feat, void *workspace, void *stream) {
+    GA_REQUIRE(cls, "cls_forward: null handle");
+    GA_REQUIRE(b >= 1, "cls_forward: batch %d must be >= 1", b);
+    GA_REQUIRE(n >= 1 && n <= 16384, "cls_forward: n %d out of range [1, 16384]", n);
+    GA_REQUIRE(pc && workspace, "cls_forward: null point cloud or workspace");
+    hipStream_t st = as_stream(stream);
+    const int C = cls->num_classes;
+    const int tiles = cdiv(n, CLS_ROWS);
+    void *aligned = reinterpret_cast<void *>(cls_rup(reinterpret_cast<size_t>(workspace), 256));
+    const int bc = chunk_of(b);
+    const ClsScratch s = carve_cls(aligned, bc);
+    // column slices: small batches split the 1024 pooled columns over up to 4 workgroups (each recomputes its tile's narrow
+    // layers, ~7 % of a chain's work) so that the launch covers the 256 CUs
+    int slices = 1;
+    while (slices < 4 && (size_t)tiles * b * slices < 2 * kCUs) slices *= 2;
+
+    ClsChainArgs ca{};
+    ca.x = pc;
+    ca.n = n;
+    ca.slices = slices;
+    ClsHeadArgs ha{};
+    for (int c0 = 0; c0 < b; c0 += bc) {
+        const int nb = std::min(bc, b - c0);
+        const float *x = pc + (size_t)c0 * n * 3;
+        GA_HIP(hipMemsetAsync(s.pooled, 0, sizeof(int) * 3 * (size_t)nb * CLS_POOL, st));
+        const dim3 grid(tiles, nb, slices);
+        // T-Net1 chain
+        ca.x = x;
+        ca.w0 = cls->raw[T1C1]; ca.w0_cloud_stride = 0; ca.sc0 = cls->scale[T1C1]; ca.sh0 = cls->shift[T1C1];
+        ca.mid[0] = layer_dev(cls, T1C2, 64, 128);
+        ca.wide = layer_dev(cls, T1C3, 128, 1024);
+        ca.pooled = s.pooled;
+        hipLaunchKernelGGL(cls_chain_kernel<1>, grid, dim3(CLS_THREADS), 0, st, ca, 0);
+        GA_LAUNCH_CHECK();
+        ha.pooled = s.pooled;
+        ha.w1 = cls->raw[T1F1]; ha.sc1 = cls->scale[T1F1]; ha.sh1 = cls->shift[T1F1];
+        ha.w2 = cls->raw[T1F2]; ha.sc2 = cls->scale[T1F2]; ha.sh2 = cls->shift[T1F2];
+        ha.w3 = cls->raw[T1XYZ]; ha.b3 = cls->bias[T1XYZ]; ha.M = 9;
+        ha.t_out = s.t1; ha.t_user = transform_in ? transform_in + (size_t)c0 * 9 : nullptr;
+        ha.fold_w = cls->raw[C1]; ha.fold_out = s.w1f; ha.labels = nullptr;
+        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_T1>, dim3(nb), dim3(CLS_THREADS), 0, st, ha, 0);
+        GA_LAUNCH_CHECK();
+        // conv1', conv2, T-Net2 chain
+        ca.w0 = s.w1f; ca.w0_cloud_stride = 192; ca.sc0 = cls->scale[C1]; ca.sh0 = cls->shift[C1];
+        ca.mid[0] = layer_dev(cls, C2, 64, 64);
+        ca.mid[1] = layer_dev(cls, T2C1, 64, 64);
+        ca.mid[2] = layer_dev(cls, T2C2, 64, 128);
+        ca.wide = layer_dev(cls, T2C3, 128, 1024);
+        ca.pooled = s.pooled + (size_t)nb * CLS_POOL;
+        hipLaunchKernelGGL(cls_chain_kernel<3>, grid, dim3(CLS_THREADS), 0, st, ca, 0);
+        GA_LAUNCH_CHECK();
+        ha.pooled = ca.pooled;
+        ha.w1 = cls->raw[T2F1]; ha.sc1 = cls->scale[T2F1]; ha.sh1 = cls->shift[T2F1];
+        ha.w2 = cls->raw[T2F2]; ha.sc2 = cls->scale[T2F2]; ha.sh2 = cls->shift[T2F2];
+        ha.w3 = cls->raw[T2FEAT]; ha.b3 = cls->bias[T2FEAT]; ha.M = 4096;
+        ha.t_out = s.t2; ha.t_user = transform_feat ? transform_feat + (size_t)c0 * 4096 : nullptr;
+        ha.fold_w = cls->raw[C3]; ha.fold_out = s.w3p;
+        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_T2>, dim3(nb), dim3(CLS_THREADS), 0, st, ha, 0);
+        GA_LAUNCH_CHECK();
+        // conv1', conv2, conv3' .. conv5 chain
+        ca.mid[1] = ClsLayerDev{PackedLayer{s.w3p, 64, 64}, cls->scale[C3], cls->shift[C3], 4096};
+        ca.mid[2] = layer_dev(cls, C4, 64, 128);
+        ca.wide = layer_dev(cls, C5, 128, 1024);
+        ca.pooled = s.pooled + 2 * (size_t)nb * CLS_POOL;
+        hipLaunchKernelGGL(cls_chain_kernel<3>, grid, dim3(CLS_THREADS), 0, st, ca, 0);
+        GA_LAUNCH_CHECK();
+        ha.pooled = ca.pooled;
+        ha.w1 = cls->raw[F1]; ha.sc1 = cls->scale[F1]; ha.sh1 = cls->shift[F1];
+        ha.w2 = cls->raw[F2]; ha.sc2 = cls->scale[F2]; ha.sh2 = cls->shift[F2];
+        ha.w3 = cls->raw[F3]; ha.b3 = cls->bias[F3]; ha.M = C;
+        ha.t_out = logits ? logits + (size_t)c0 * C : s.t2;      // (t2 is free again: [b][4096] >= [b][C])
+        ha.t_user = nullptr;
+        ha.fold_w = nullptr; ha.fold_out = nullptr;
+        ha.labels = labels ? labels + c0 : reinterpret_cast<int *>(s.t1);
+        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_CLS>, dim3(nb), dim3(CLS_THREADS), 0, st, ha, 0);
+        GA_LAUNCH_CHECK();
+    }
+    return GEOADV_OK;
+}

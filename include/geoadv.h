@@ -299,6 +299,58 @@ int geoadv_ae_forward(const geoadv_ae *ae, int b, const float *pc, float *latent
 int geoadv_ae_decode(const geoadv_ae *ae, int b, const float *latent, float *recon, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PointNet classifier of the semantic evaluation: classifier/pointnet_cls.py:30-84 (get_model) with the
+ * T-Nets of classifier/transform_nets.py, inference only (is_training = False: batch norm from the moving
+ * statistics with eps 1e-3, dropout the identity), fp32.  csrc/classifier.hip.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct geoadv_cls geoadv_cls;
+
+/* The 20 weight layers, in this order.  Every w is [fan_in, fan_out] row-major (conv2d's W[1,kw,Cin,Cout] squeezed:
+ * conv1 / transform_net1's tconv1 are [3,64]), b is [fan_out].  gamma / beta / mean / var (the batch norm's variables and
+ * moving statistics, [fan_out]) are given for every layer but TXYZ, TFEAT and FC3, whose BN pointers must be NULL.
+ * TXYZ / TFEAT take the variables as stored: the identity (transform_nets.py) is added by the library. */
+#define GEOADV_CLS_LAYERS    20
+#define GEOADV_CLS_T1_CONV1   0   /* transform_net1/tconv1   3 -> 64    */
+#define GEOADV_CLS_T1_CONV2   1   /* transform_net1/tconv2  64 -> 128   */
+#define GEOADV_CLS_T1_CONV3   2   /* transform_net1/tconv3 128 -> 1024  */
+#define GEOADV_CLS_T1_FC1     3   /* transform_net1/tfc1  1024 -> 512   */
+#define GEOADV_CLS_T1_FC2     4   /* transform_net1/tfc2   512 -> 256   */
+#define GEOADV_CLS_TXYZ       5   /* transform_net1/transform_XYZ 256 -> 9 (+I) */
+#define GEOADV_CLS_CONV1      6   /* conv1   3 -> 64  */
+#define GEOADV_CLS_CONV2      7   /* conv2  64 -> 64  */
+#define GEOADV_CLS_T2_CONV1   8   /* transform_net2/tconv1  64 -> 64    */
+#define GEOADV_CLS_T2_CONV2   9   /* transform_net2/tconv2  64 -> 128   */
+#define GEOADV_CLS_T2_CONV3  10   /* transform_net2/tconv3 128 -> 1024  */
+#define GEOADV_CLS_T2_FC1    11   /* transform_net2/tfc1  1024 -> 512   */
+#define GEOADV_CLS_T2_FC2    12   /* transform_net2/tfc2   512 -> 256   */
+#define GEOADV_CLS_TFEAT     13   /* transform_net2/transform_feat 256 -> 4096 (+I) */
+#define GEOADV_CLS_CONV3     14   /* conv3  64 -> 64   */
+#define GEOADV_CLS_CONV4     15   /* conv4  64 -> 128  */
+#define GEOADV_CLS_CONV5     16   /* conv5 128 -> 1024 */
+#define GEOADV_CLS_FC1       17   /* fc1  1024 -> 512  */
+#define GEOADV_CLS_FC2       18   /* fc2   512 -> 256  */
+#define GEOADV_CLS_FC3       19   /* fc3   256 -> num_classes, linear */
+typedef struct geoadv_cls_weights {
+    int num_classes;                              /* 1 ... 1024 (13 in the reference's scripts) */
+    const float *w[GEOADV_CLS_LAYERS], *b[GEOADV_CLS_LAYERS];
+    const float *gamma[GEOADV_CLS_LAYERS], *beta[GEOADV_CLS_LAYERS];
+    const float *mean[GEOADV_CLS_LAYERS], *var[GEOADV_CLS_LAYERS];
+} geoadv_cls_weights;
+
+/* Uploads the HOST weights (batch norm folded into a per-channel scale / shift, the per-point layers packed for MFMA).
+ * Allocates device memory; synchronous.  The handle is immutable afterwards (any number of threads / streams may use it). */
+int  geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *host_weights);
+void geoadv_cls_destroy(geoadv_cls *cls);
+/* Device scratch of geoadv_cls_forward for a batch of b clouds of n points. */
+size_t geoadv_cls_workspace_bytes(const geoadv_cls *cls, int b, int n);
+/* PointNetClassifier.classify (classifier/pointnet_classifier.py:62-82) without its batch-size restriction:
+ * pc[b,n,3] -> logits[b,num_classes] and labels[b] (int32, np.argmax: the first maximum).  transform_in[b,3,3] (T1) and
+ * transform_feat[b,64,64] (T2) return the two T-Nets' matrices.  Any of the four outputs may be NULL.  1 <= n <= 16384,
+ * b >= 1, else GEOADV_EINVAL.  A cloud with non-finite coordinates affects no other cloud's results. */
+int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const float *pc, float *logits, int *labels,
+                       float *transform_in, float *transform_feat, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The attack loop: AdvAE (src/adv_ae.py:30-251) + Adversary (src/adversary.py:9-57).
  * One handle = one batch slot of `batch` clouds with device-resident state
  * (pert, Adam m/v/beta powers, best-so-far outputs).
