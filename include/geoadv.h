@@ -351,6 +351,53 @@ int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const float *pc, flo
                        float *transform_in, float *transform_feat, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AtlasNet auto-encoder of the transfer experiment: transfer/atlasnet/model/model_blocks.py (PointNet encoder :28-60,
+ * Mapping2Dto3D decoder :63-105) in eval mode (atlasnet.py:45-67, train=False: the fixed template points), batch norm
+ * from the running statistics with eps 1e-5, fp32.  csrc/atlasnet.hip.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct geoadv_atlas geoadv_atlas;
+
+#define GEOADV_ATLAS_ENC_LAYERS      5   /* conv1 3->64, conv2 64->128, conv3 128->1024 (BN, no ReLU), lin1, lin2 1024->1024 */
+#define GEOADV_ATLAS_MAX_DEC_LAYERS  7   /* per primitive: conv1 dim->1024, conv2 1024->512, num_layers x 512->512, last_conv 512->3 */
+typedef struct geoadv_atlas_config {
+    int nb_primitives;          /* 1 ... 128 */
+    int points_per_primitive;   /* template points per primitive (g * g for the SQUARE template), 1 ... 65536 */
+    int dim_template;           /* 2 or 3 */
+    int bottleneck_size;        /* 1024 */
+    int hidden_neurons;         /* 512 */
+    int num_layers;             /* 0 ... 4 */
+    int activation;             /* 0 = relu (the only one supported) */
+    int decoder_bn;             /* 1: the decoder has its batch norms; 0: remove_all_batchNorms (the encoder keeps its own) */
+} geoadv_atlas_config;
+/* Every w is [fan_in, fan_out] row-major (torch's Conv1d / Linear weight [out, in(, 1)] transposed), b is [fan_out].  The
+ * encoder's five layers all have batch norm.  Decoder layer l of primitive p lives at dec_*[l] + p * (size of one primitive's
+ * array), layers in the order conv1, conv2, conv_list[0 .. num_layers), last_conv (index 2 + num_layers).  The decoder's BN
+ * pointers are given for every layer but last_conv when decoder_bn = 1, and must all be NULL otherwise. */
+typedef struct geoadv_atlas_weights {
+    const float *enc_w[GEOADV_ATLAS_ENC_LAYERS], *enc_b[GEOADV_ATLAS_ENC_LAYERS];
+    const float *enc_gamma[GEOADV_ATLAS_ENC_LAYERS], *enc_beta[GEOADV_ATLAS_ENC_LAYERS];
+    const float *enc_mean[GEOADV_ATLAS_ENC_LAYERS], *enc_var[GEOADV_ATLAS_ENC_LAYERS];
+    const float *dec_w[GEOADV_ATLAS_MAX_DEC_LAYERS], *dec_b[GEOADV_ATLAS_MAX_DEC_LAYERS];
+    const float *dec_gamma[GEOADV_ATLAS_MAX_DEC_LAYERS], *dec_beta[GEOADV_ATLAS_MAX_DEC_LAYERS];
+    const float *dec_mean[GEOADV_ATLAS_MAX_DEC_LAYERS], *dec_var[GEOADV_ATLAS_MAX_DEC_LAYERS];
+} geoadv_atlas_weights;
+
+/* Uploads the HOST weights and the HOST template points host_template[nb_primitives, points_per_primitive, dim_template]
+ * (batch norm folded into a per-channel scale / shift, the per-point layers packed for MFMA).  Allocates device memory;
+ * synchronous.  The handle is immutable afterwards.  Unsupported configurations return GEOADV_EINVAL. */
+int  geoadv_atlas_create(geoadv_atlas **out, const geoadv_atlas_config *config, const geoadv_atlas_weights *host_weights,
+                         const float *host_template);
+void geoadv_atlas_destroy(geoadv_atlas *atlas);
+/* Device scratch of geoadv_atlas_forward for a batch of b clouds of n points. */
+size_t geoadv_atlas_workspace_bytes(const geoadv_atlas *atlas, int b, int n);
+/* EncoderDecoder.forward(x, train=False) followed by fuse_primitives (training/trainer_loss.py:36-45): pc[b,n,3] ->
+ * recon[b, nb_primitives * points_per_primitive, 3], primitive-major; latent[b,1024] (may be NULL) returns the encoder's
+ * output.  1 <= n <= 16384, b >= 1, else GEOADV_EINVAL.  A cloud's results do not depend on b, on its position in the
+ * batch or on the order of its points; a cloud with non-finite coordinates affects no other cloud. */
+int geoadv_atlas_forward(const geoadv_atlas *atlas, int b, int n, const float *pc, float *latent, float *recon,
+                         void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The attack loop: AdvAE (src/adv_ae.py:30-251) + Adversary (src/adversary.py:9-57).
  * One handle = one batch slot of `batch` clouds with device-resident state
  * (pert, Adam m/v/beta powers, best-so-far outputs).
