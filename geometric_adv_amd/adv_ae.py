@@ -51,7 +51,7 @@ class Configuration:
                                                  # a batch that hands most clouds back switches off FOR THAT BATCH (adapt_source_search);
                                                  # "pinned": True without that policy (timing independent of the data)
         self.emd_reference_weights = bool(emd_reference_weights)   # True: the EMD term's plan from the CPU op's expf arguments (ops.approx_match)
-        self.encoder_arith = encoder_arith                         # None (library default: "bf16x3"), "bf16x3" or "f32": autoencoder.ENCODER_ARITH; of the model this handle creates
+        self.encoder_arith = encoder_arith                         # None (library default: "f16x2" where the model is inside its window, else "bf16x3"), "f16x2", "bf16x3" or "f32": autoencoder.ENCODER_ARITH; of the model this handle creates
         self.emd_dense_levels = bool(emd_dense_levels)             # True: this handle's EMD sweeps all dense (GEOADV_EMD_DENSE_LEVELS; per handle, nothing process-wide)
         # alternative code paths with the same results (geoadv_attack_config; the parity tests run each against the default)
         self.recompute_backward = bool(recompute_backward)   # encoder backward re-runs the forward instead of reading ReLU masks

@@ -271,6 +271,20 @@ extern "C" int geoadv_ae_create(geoadv_ae **out, const geoadv_ae_weights *hw) {
             if (sw[L] == 0.f) { h2_ok = false; sw[L] = 1.f; }
             h2_unscale[L] = 1.f / (act_scale[L - 1] * sw[L]);
         }
+        // The window of the error bound (encoder_x3.h): every channel that is not identically zero carried at a magnitude of at
+        // least H2_CHANNEL_MIN after scaling -- an activation channel by s_j sqrt(gamma^2 + beta^2), a weight column by its largest
+        // S_w(L) |w|.  A channel far below its layer's power of two would work on subnormal second pieces.
+        for (int j = 0; j < ENC_L - 1; ++j)
+            for (int c = 0; c < C[j + 1]; ++c) {
+                const double m = std::hypot((double)hw->bn_gamma[j][c], (double)hw->bn_beta[j][c]);
+                if (m > 0.0 && act_scale[j] * m < H2_CHANNEL_MIN) h2_ok = false;
+            }
+        for (int L = 1; L < ENC_L; ++L)
+            for (int c = 0; c < C[L + 1]; ++c) {
+                float mx = 0.f;
+                for (int k = 0; k < C[L]; ++k) mx = std::max(mx, std::fabs(hw->enc_w[L][(size_t)k * C[L + 1] + c]));
+                if (mx > 0.f && (double)sw[L] * mx < H2_CHANNEL_MIN) h2_ok = false;
+            }
         float *c = &host[o_h2c];
         const float *x3c = &host[o_x3c];
         auto fold = [&](float v, float factor) {            // v * factor, factor a power of two: exact unless it leaves the normal range
@@ -365,7 +379,8 @@ extern "C" int geoadv_ae_set_encoder_arith(geoadv_ae *ae, int arith) {
     GA_REQUIRE(known_arith(arith), "ae_set_encoder_arith: unknown arithmetic %d", arith);
     GA_REQUIRE(arith != GEOADV_ENC_ARITH_F16X2 || ae->d.enc_h2,
                "ae_set_encoder_arith: this model's weights / batch-norm constants do not scale into the fp16 range exactly "
-               "(non-finite, or a constant that would leave the normal fp32 range): f16x2 is not available for it");
+               "(non-finite, a constant that would leave the normal fp32 range, or a channel whose scaled magnitude falls below 2^-3: "
+               "encoder_x3.h): f16x2 is not available for it");
     // an attack handle caches a forward (pool partials, masks) in the tile layout of the arithmetic it ran under and recomputes in
     // it: switching under a live handle would make the two disagree -- refused, not silently accepted
     GA_REQUIRE(arith == ae->d.enc_arith || ae->attack_refs.load() == 0,

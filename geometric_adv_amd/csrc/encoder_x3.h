@@ -24,10 +24,28 @@
 // gamma = 1, beta = 0: ae.hip) -- the second piece of every scaled activation >= 2^-3 is a normal fp16 number, smaller ones
 // keep an ABSOLUTE error <= 2^-25 / s_j, the pipe honours fp16 subnormals --, a layer's weights so that the largest magnitude
 // lies in [2^13, 2^14).  The scales ride in the constants of the epilogue (scale' = scale s_L / (s_{L-1} S_w), shift' = s_L
-// shift: the next layer's scaled activation comes out of the same fma, bit for bit s_L times the unscaled one).  Measured against float64 (tools/bf16x3_probe.py modes 5-7, profiles/r06_f16x2_probe.jsonl): rms error
-// 0.44-0.52 units of 2^-24 |a|.|w| -- the fp32 chain's.  RANGE: a scaled activation above 65504 (an activation >= 1023.5 x its
-// layer's batch-norm magnitude) would
-// round to an fp16 infinity; every epilogue keeps a running maximum (one v_max3_f32 per two values) and a workgroup that sees
+// shift: the next layer's scaled activation comes out of the same fma, bit for bit s_L times the unscaled one).
+//
+// ERROR BOUND (a', w' the scaled operands, a' = a0 + a1 + ra, w' = w0 + w1 + rw; units u = 2^-24 |a||w| of one product):
+//   a scaled x in [2^e, 2^(e+1)) leaves x - x0 <= 2^(e-11); its second piece x1 is normal for x >= 2^-3 and rounds it to
+//   |rx| <= 2^(e-23) <= 2^-23 |x| for x >= 2^-2 (below: |rx| <= 2^-25, half the fp16 subnormal spacing -- absolute)
+//   dropped a1 w1, |a1| <= 2^-11 |a'|, |w1| <= 2^-11 |w'| ................................ 4 u
+//   remainders ra (w0 + w1) and rw (a0 + a1) ............................................ 2 u + 2 u
+//   the three piece products themselves ................................................. exact (11 x 11 bits)
+// => |a'w' - (a1 w0 + a0 w1 + a0 w0)| <= 8.01 u inside the window, plus 2^-25 |w'| (2^-25 |a'|) for an operand below 2^-2.
+// The piece products are then summed in the fp32 accumulator as the fp32 chain sums its products (sixteen-k blocks, rounded
+// or truncated; nothing is assumed about the pipe's order), so the f16x2 chain is the fp32 chain plus at most 8.01 u a product.
+// For the latent, in units of 2^-24 of the last layer's chain |scale_4| (|h_3|.|W_4| + |b_4| + |mean_4|) + |beta_4| per element,
+// that is held to 16 u -- 8 for the pieces, 8 for the accumulation and what the earlier layers hand on (the fp32 chain itself
+// measures 2-5 u on the randomized model) -- and to 1.25 x the fp32 chain's error + 4 u on the same clouds
+// (tests/test_gpu_encoder_f16x2_bounds.py; measured inside the window: at most 3.9 u, the fp32 chain 1.8-4.6).
+// WINDOW: the absolute 2^-25 terms are what a single power of two per layer cannot keep small for a channel far below its
+// layer's scale, so f16x2 is served only while every channel that is not identically zero has a scaled magnitude >=
+// H2_CHANNEL_MIN = 2^-3, the smallest scaled value whose second piece is a normal fp16 number: an activation channel
+// s_j sqrt(gamma^2 + beta^2), a weight column its largest S_w(L) |w| (ae.hip: else the default is bf16x3 and an explicit f16x2
+// is refused).  Measured outside it: a channel set at 2^-6 gives up to 34 u, 2^-7 up to 11 u (weights), 2^-10 up to 500 u.
+// RANGE: a scaled activation above 65504 (an activation >= 1023.5 x its layer's batch-norm magnitude) would round to an fp16
+// infinity; every epilogue keeps a running maximum (one v_max3_f32 per two values) and a workgroup that sees
 // one poisons its pool partial with +inf and raises DeviceAE::range_flag (geoadv_ae_status: GEOADV_ERANGE) -- never silent.
 #pragma once
 #include "ae.h"
@@ -49,6 +67,7 @@ __host__ __device__ constexpr size_t xp_image_words(int np) { return (size_t)X3_
 constexpr int X3_STEP_WORDS = xp_step_words(3);
 constexpr size_t X3_IMAGE_WORDS = xp_image_words(3), H2_IMAGE_WORDS = xp_image_words(2);
 constexpr float H2_ACT_LIMIT = 65504.f;       // largest finite fp16: a scaled activation above it trips the range guard
+constexpr double H2_CHANNEL_MIN = 0.125;      // smallest scaled channel magnitude f16x2 is served for (ERROR BOUND above; ae.hip)
 // the constants the forward keeps in LDS, as one block (DeviceAE::enc_x3_consts): W0 [3][64], scale0 [64], shift0 [64], then
 // [scale | shift] of layers 1 (128 + 128), 2 (128 + 128), 3 (256 + 256), 4 (128 + 128)
 constexpr int X3_CONST_FLOATS = 320 + 2 * (128 + 128 + 256 + 128);
