@@ -7,15 +7,22 @@ how well it reconstructs the attack's TARGET shapes, with the reference's flags 
   - PointNet: this project's PointNetAE (the victim's architecture, other weights) from
     <transfer_ae_folder>/models.ckpt-<transfer_ae_restore_epoch> (or weights.npz),
   - AtlasNet: atlasnet.AtlasNetAE from <transfer_ae_folder>/network.pth and options.json,
-  - FoldingNet: refused.  Its Graph_Pooling draws neighbours with an unseeded np.random.choice
-    (transfer/foldingnet/foldingnet.py:36-39), so not even the reference reproduces its own output.
+  - FoldingNet: foldingnet.FoldingNetAE from <transfer_ae_folder>/checkpoint_<transfer_ae_restore_epoch>.pth.  Its
+    Graph_Pooling draws neighbours with np.random.choice (transfer/foldingnet/foldingnet.py:36-39), which the reference
+    never seeds, so not even the reference reproduces its own output.  Here --graph_seed is required (without it
+    FoldingNet is refused before any file is read), and --graph_sampling picks how it is used: 'device' (default) draws on
+    the GPU from (seed, cloud ordinal, pool layer, point); 'reference' draws with np.random.RandomState(seed).choice on
+    the host in the reference's order, reproducing a reference run that called np.random.seed(seed) first (13 to 36 ms of
+    host time per cloud).
 
 Differences forced by the environment, as in run_classifier:
   - the attack's configuration is read from <eval>/<attack_folder>/attack_configuration.json (run_attack writes it in place of
     the pickled Configuration); the transfer configuration is written as transfer_configuration.json,
   - the distance weight of every attack comes from analysis_results/source_target_norm_min_idx.npy; without it, an attack run
     with a single distance weight uses weight 0 (what that file would hold),
-  - AtlasNet's reconstruction has nb_primitives * g * g points, whatever that is (the reference's buffer fixes 2500).
+  - AtlasNet's reconstruction has nb_primitives * g * g points, whatever that is (the reference's buffer fixes 2500),
+  - FoldingNet takes clouds of any 17 ... 16384 points (the reference's covariance buffer fixes 2048); its reconstruction
+    has 2025 points.
 Outputs (only when the transfer folder differs from the victim's, as in the reference, :220-222), per class under
 <transfer_ae_folder>/eval/<output_folder_name>/<class>/: transferred_pc_recon.npy [1, n, P, 3] and transfer_metrics.npy
 [1, n, 4] (transferred target recon error, transferred target NRE, the attack's target recon error and NRE).
@@ -42,6 +49,11 @@ def build_parser():
     p.add_argument('--attack_folder', type=str, default='attack_res')
     p.add_argument('--output_folder_name', type=str, default='attack_res_transfer')
     p.add_argument('--top_dir', type=str, default='.', help='root that the folder flags are relative to')
+    p.add_argument('--graph_seed', type=int, default=None,
+                   help="FoldingNet: seed of the graph pooling's neighbour draws (required for FoldingNet)")
+    p.add_argument('--graph_sampling', type=str, default='device', choices=['device', 'reference'],
+                   help="FoldingNet: 'device' draws on the GPU; 'reference' reproduces np.random.seed(graph_seed) followed "
+                        "by the reference's np.random.choice calls")
     return p
 
 
@@ -58,10 +70,10 @@ def _select_dist_weight(load_dir, num_pc, n_weights):
 def main(argv=None):
     flags = build_parser().parse_args(argv)
     assert flags.transfer_ae_type in AE_TYPES, 'wrong ae_type: %s.' % flags.transfer_ae_type
-    if flags.transfer_ae_type == 'FoldingNet':
-        raise SystemExit('run_transfer: --transfer_ae_type FoldingNet is not supported: its Graph_Pooling draws neighbours '
-                         'with an unseeded np.random.choice (foldingnet.py:36-39), so its reconstructions are not '
-                         'reproducible, not even by the reference')
+    if flags.transfer_ae_type == 'FoldingNet' and flags.graph_seed is None:
+        raise SystemExit('run_transfer: --transfer_ae_type FoldingNet needs --graph_seed: its Graph_Pooling draws neighbours '
+                         'with an unseeded np.random.choice (foldingnet.py:36-39), so without a seed its reconstructions '
+                         'are not reproducible, not even by the reference')
     print('Run transfer flags:', flags)
 
     from .attack_data import create_dir, get_quantity_at_index, load_data, prepare_data_for_attack
@@ -75,7 +87,8 @@ def main(argv=None):
     with open(osp.join(attack_path, 'attack_configuration.json')) as f:
         conf = json.load(f)
     conf.update(attack_path=attack_path, transfer_ae_restore_epoch=flags.transfer_ae_restore_epoch,
-                transfer_ae_type=flags.transfer_ae_type, transfer_ae_folder=flags.transfer_ae_folder)
+                transfer_ae_type=flags.transfer_ae_type, transfer_ae_folder=flags.transfer_ae_folder,
+                graph_seed=flags.graph_seed, graph_sampling=flags.graph_sampling)
     with open(osp.join(output_path, 'transfer_configuration.json'), 'w') as f:
         json.dump(conf, f)
 
@@ -94,6 +107,10 @@ def main(argv=None):
     if flags.transfer_ae_type == 'AtlasNet':
         from .atlasnet import AtlasNetAE
         ae = AtlasNetAE(transfer_ae_dir)
+    elif flags.transfer_ae_type == 'FoldingNet':
+        from .foldingnet import FoldingNetAE
+        ae = FoldingNetAE(transfer_ae_dir, epoch=flags.transfer_ae_restore_epoch, seed=flags.graph_seed,
+                          sampling=flags.graph_sampling)
     else:
         from .autoencoder import PointNetAE
         from .run_attack import victim_weights_path

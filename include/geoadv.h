@@ -398,6 +398,51 @@ int geoadv_atlas_forward(const geoadv_atlas *atlas, int b, int n, const float *p
                          void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FoldingNet auto-encoder of the transfer experiment: transfer/foldingnet/foldingnet.py (FoldingNetEnc_with_graph :57-104,
+ * Graph_Pooling :14-54, FoldingNetDec :107-189) with the graph of prepare_graph.py:24-73 (16 neighbours, covariance,
+ * symmetric adjacency), eval mode, batch norm from the running statistics with eps 1e-5, fp32.  csrc/foldingnet.hip.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct geoadv_fold geoadv_fold;
+
+#define GEOADV_FOLD_ENC_LAYERS  7   /* conv1 12->64, conv2 64->64, conv3 64->64, conv4 64->128, conv5 128->1024, fc1 1024->512
+                                       (batch norms bn1 .. bn6), fc2 512->512 (no batch norm)                                 */
+#define GEOADV_FOLD_DEC_LAYERS  6   /* fold1.conv1 514->512, fold1.conv2 512->512, fold1.conv3 512->3, the same for fold2 (515) */
+#define GEOADV_FOLD_PICKS_GIVEN  0  /* the 16 neighbour positions of every point and pool layer come from the caller           */
+#define GEOADV_FOLD_PICKS_DEVICE 1  /* drawn on the device from (seed, cloud ordinal, pool layer, point): csrc/foldingnet.hip   */
+/* Every w is [fan_in, fan_out] row-major (torch's weight [out, in(, 1)] transposed), b is [fan_out].  The first 512 rows of
+ * a fold's conv1 act on the code, the last 2 (fold1: grid x, y) or 3 (fold2: p1) on the point.  fc2's batch-norm pointers
+ * must be NULL, all others given. */
+typedef struct geoadv_fold_weights {
+    const float *enc_w[GEOADV_FOLD_ENC_LAYERS], *enc_b[GEOADV_FOLD_ENC_LAYERS];
+    const float *enc_gamma[GEOADV_FOLD_ENC_LAYERS], *enc_beta[GEOADV_FOLD_ENC_LAYERS];
+    const float *enc_mean[GEOADV_FOLD_ENC_LAYERS], *enc_var[GEOADV_FOLD_ENC_LAYERS];
+    const float *dec_w[GEOADV_FOLD_DEC_LAYERS], *dec_b[GEOADV_FOLD_DEC_LAYERS];
+} geoadv_fold_weights;
+
+/* Uploads the HOST weights (batch norm folded, the per-point layers packed for MFMA).  Allocates device memory;
+ * synchronous.  The handle is immutable afterwards. */
+int  geoadv_fold_create(geoadv_fold **out, const geoadv_fold_weights *host_weights);
+void geoadv_fold_destroy(geoadv_fold *fold);
+/* Device scratch of geoadv_fold_graph / geoadv_fold_forward for a batch of b clouds of n points. */
+size_t geoadv_fold_workspace_bytes(const geoadv_fold *fold, int b, int n);
+/* build_graph (prepare_graph.py:45-104) of pc[b,n,3]: degree[b,n] (the symmetric adjacency's row lengths, >= 16),
+ * knn[b,n,16] (the 17 nearest neighbours by squared distance, the existing kNN kernel's order and tie rule, column 0
+ * dropped) and cov[b,n,9] (np.cov of those 16 neighbours, ddof 1, row-major 3x3).  Any output may be NULL.
+ * 17 <= n <= 16384, b >= 1, else GEOADV_EINVAL. */
+int geoadv_fold_graph(const geoadv_fold *fold, int b, int n, const float *pc, int *degree, int *knn, float *cov,
+                      void *workspace, void *stream);
+/* FoldingNet_graph.forward of pc[b,n,3] (the graph is rebuilt here).  picks[2,b,n,16] are positions in each point's
+ * sorted adjacency row, pool layer major: read with GEOADV_FOLD_PICKS_GIVEN (required; a position outside [0, degree)
+ * is clamped into the row, never read outside it), written with GEOADV_FOLD_PICKS_DEVICE (may be NULL), where cloud k of
+ * the batch draws with ordinal cloud_offset + k.  cols[2,b,n,16] returns the neighbour indices the picks resolve to,
+ * code[b,512] the encoder's output, p1[b,2025,3] fold1's output and recon[b,2025,3] the reconstruction; each may be NULL.
+ * 17 <= n <= 16384, b >= 1, cloud_offset >= 0, else GEOADV_EINVAL.  A cloud with non-finite coordinates affects no
+ * other cloud. */
+int geoadv_fold_forward(const geoadv_fold *fold, int b, int n, const float *pc, int sampling, unsigned long long seed,
+                        long long cloud_offset, int *picks, int *cols, float *code, float *p1, float *recon,
+                        void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The attack loop: AdvAE (src/adv_ae.py:30-251) + Adversary (src/adversary.py:9-57).
  * One handle = one batch slot of `batch` clouds with device-resident state
  * (pert, Adam m/v/beta powers, best-so-far outputs).
