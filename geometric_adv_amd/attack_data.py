@@ -75,3 +75,16 @@ def get_quantity_at_index(quantity_list, index):
 def create_dir(path):
     os.makedirs(path, exist_ok=True)
     return path
+
+
+def select_dist_weight(load_dir, num_pc, n_weights):
+    """The distance weight of every attack of a class: <load_dir>/analysis_results/source_target_norm_min_idx.npy (written by
+    evaluate_attack) when it exists; without it, an attack run with a single distance weight uses weight 0 (what that file
+    would hold), and one with several is refused."""
+    idx_file = osp.join(load_dir, 'analysis_results', 'source_target_norm_min_idx.npy')
+    if osp.exists(idx_file):
+        return np.load(idx_file)
+    if n_weights == 1:
+        return np.zeros(num_pc, dtype=np.int64)
+    raise FileNotFoundError('%s is missing: the attack used %d distance weights, and that file selects one per attack '
+                            '(run geometric_adv_amd.evaluate_attack first)' % (idx_file, n_weights))

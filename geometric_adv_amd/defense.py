@@ -1,6 +1,7 @@
 """The two defenses (defender/get_knn_dists_per_point.py + defender/run_defense_surface.py:187-207 with
-src/adversary_utils.get_outlier_pc_inlier_pc; defender/run_defense_critical.py:180-196 with src/ae_utils.py:12-80), logic
-only -- the file / CLI plumbing is out of scope.
+src/adversary_utils.get_outlier_pc_inlier_pc; defender/run_defense_critical.py:180-196 with src/ae_utils.py:12-80), the
+logic; the commands with the reference's files are get_knn_dists_per_point, run_defense_surface and run_defense_critical
+(defense_cli.py).
 
 Everything between the adversarial clouds and the defended reconstructions runs on the GPU (round 4): the fused kNN kernel,
 the outlier / critical-point packing kernels (csrc/defense.hip, the reference does them with per-cloud numpy loops), the

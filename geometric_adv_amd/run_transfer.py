@@ -57,16 +57,6 @@ def build_parser():
     return p
 
 
-def _select_dist_weight(load_dir, num_pc, n_weights):
-    idx_file = osp.join(load_dir, 'analysis_results', 'source_target_norm_min_idx.npy')
-    if osp.exists(idx_file):
-        return np.load(idx_file)
-    if n_weights == 1:
-        return np.zeros(num_pc, dtype=np.int64)
-    raise FileNotFoundError('%s is missing: the attack used %d distance weights, and that file selects one per attack'
-                            % (idx_file, n_weights))
-
-
 def main(argv=None):
     flags = build_parser().parse_args(argv)
     assert flags.transfer_ae_type in AE_TYPES, 'wrong ae_type: %s.' % flags.transfer_ae_type
@@ -76,7 +66,7 @@ def main(argv=None):
                          'are not reproducible, not even by the reference')
     print('Run transfer flags:', flags)
 
-    from .attack_data import create_dir, get_quantity_at_index, load_data, prepare_data_for_attack
+    from .attack_data import create_dir, get_quantity_at_index, load_data, prepare_data_for_attack, select_dist_weight
 
     data_path = osp.join(flags.top_dir, flags.ae_folder, 'eval')
     files = [f for f in os.listdir(data_path) if osp.isfile(osp.join(data_path, f))]
@@ -138,7 +128,7 @@ def main(argv=None):
         adversarial_pc_input = np.load(osp.join(load_dir, 'adversarial_pc_input.npy'))
         adversarial_pc_recon = np.load(osp.join(load_dir, 'adversarial_pc_recon.npy'))
         adversarial_metrics = np.load(osp.join(load_dir, 'adversarial_metrics.npy'))
-        sel = _select_dist_weight(load_dir, adversarial_pc_input.shape[1], n_weights)
+        sel = select_dist_weight(load_dir, adversarial_pc_input.shape[1], n_weights)
         adversarial_pc_input, adversarial_pc_recon, adversarial_metrics = [
             np.expand_dims(q, axis=0) for q in
             get_quantity_at_index([adversarial_pc_input, adversarial_pc_recon, adversarial_metrics], sel)]
