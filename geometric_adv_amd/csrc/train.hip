@@ -42,9 +42,10 @@ struct FwdArgs {
     PackedLayer W;               // packed W_i (layers >= 1);  layer 0: W.w = canonical [3][64]
     const float *bias;           // b_i
     float *out;                  // a_i [R][COUT]
-    float2 *psum;                // [tiles][COUT] (sum a, sum a^2) over the 64 rows of the tile
+    float2 *psum;                // [tiles][COUT] (sum a, sum a^2) over the 64 rows of the tile; layer 0: of a - row_shift
     int tiles;                   // 64-row tiles (the persistent forward kernel deals them round-robin)
     int *zero; int zero_count;   // layer 0 only: ints to clear on the way (the pool's maxima and tie counts: a memset launch less per step)
+    float *row_shift;            // layer 0 only: [64] a of the batch's first row, written by block 0
 };
 
 __global__ __launch_bounds__(TR_THREADS) void train_fwd0_kernel(FwdArgs A) {
@@ -57,14 +58,20 @@ __global__ __launch_bounds__(TR_THREADS) void train_fwd0_kernel(FwdArgs A) {
     __syncthreads();
     const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
     const float w0 = A.W.w[c], w1 = A.W.w[64 + c], w2 = A.W.w[128 + c], b = A.bias[c];
+    // The partial sums are taken of a - K, K = a of the batch's first row: a = x . W + b follows any translation of the
+    // clouds, and fp32 sums of a^2 would lose the variance to it (E[a^2] - mean^2 cancels ~ (mean / std)^2 digits).  Shifted,
+    // the sums see only the spread; bn_finalize adds the shift back in double.
+    const float K = fmaf(A.in[2], w2, fmaf(A.in[1], w1, A.in[0] * w0)) + b;
+    if (blockIdx.x == 0 && threadIdx.x < 64) A.row_shift[c] = K;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int row = g * 8 + r;
         const float a = fmaf(pts[row * 3 + 2], w2, fmaf(pts[row * 3 + 1], w1, pts[row * 3] * w0)) + b;
         A.out[(row0 + row) * 64 + c] = a;
-        s1 += a;
-        s2 = fmaf(a, a, s2);
+        const float d = a - K;
+        s1 += d;
+        s2 = fmaf(d, d, s2);
     }
     red[g][c] = make_float2(s1, s2);
     __syncthreads();
@@ -295,6 +302,7 @@ __device__ __forceinline__ bool tile_partial_totals(const float2 *part, int tile
 struct BnArgs {
     int mode; double *totals, *local_totals;
     const float2 *psum; int tiles; int C; double inv_rows;
+    const float *row_shift;                   // layer 0: the partials are of a - row_shift[c] (train_fwd0_kernel); else null
     const float *gamma, *beta;
     float *mean, *inv_std, *scale, *shift;    // batch mean, rsqrt(var + eps), gamma * inv_std, beta - mean * scale
     float *mov_mean, *mov_var; float one_minus_decay;
@@ -306,6 +314,11 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(BnArgs A) {
     bool mine = threadIdx.x < RED_CH;
     if (A.mode != 2) {
         mine = tile_partial_totals(A.psum, A.tiles, A.C, blockIdx.x, s1, s2);
+        if (mine && A.row_shift) {            // sums of a - K -> sums of a (in double; what ranks add up is then shift-free)
+            const double K = A.row_shift[c], rows = (double)A.tiles * TR_ROWS;
+            s2 += K * (2.0 * s1 + rows * K);
+            s1 += rows * K;
+        }
         if (mine && A.mode == 1) { A.totals[c] = s1; A.totals[A.C + c] = s2; }
         if (A.mode == 1) return;
     } else if (mine) { s1 = A.totals[c]; s2 = A.totals[A.C + c]; }
@@ -316,7 +329,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(BnArgs A) {
         const float istd = (float)(1.0 / sqrt(var + (double)BN_EPS));
         const float sc = A.gamma[c] * istd;
         A.mean[c] = (float)mean; A.inv_std[c] = istd; A.scale[c] = sc;
-        A.shift[c] = A.beta[c] - (float)mean * sc;
+        A.shift[c] = (float)((double)A.beta[c] - mean * (double)sc);    // one rounding: mean * sc may be far larger than beta
         A.mov_mean[c] -= (A.mov_mean[c] - (float)mean) * A.one_minus_decay;
         A.mov_var[c] -= (A.mov_var[c] - (float)var) * A.one_minus_decay;
     }
@@ -515,33 +528,34 @@ __global__ void fill_f32_kernel(float *p, float v, size_t count) {
 // dV2[k][n] = sum_b d2[b][k] * g[b][n]; dc2[n] = sum_b g[b][n].  Block (bx, by) of (ceil(n3/64), 256/32), 256 threads = 64 columns x 4
 // groups of 8 k (was: 128 columns x 32 k on HALF the block's threads -- under one wave per SIMD, 20 us of pure latency)
 constexpr int DOW_COLS = 64;
+constexpr int DOW_GB = 64;                                 // clouds per chunk: their gradients requested at once (one round trip for B = 50)
 __device__ __forceinline__ void fc_out_bwd_w_block(const float *d2, const float *g, float *dV2, float *dc2, int batch, int n3,
                                                    const int bx, const int by) {
-    extern __shared__ __align__(16) float xs[];            // [batch][32]
+    __shared__ __align__(16) float xs[DOW_GB * 32];        // this chunk's d2[b][k0 .. k0 + 32): any batch fits, chunk by chunk
     const int k0 = by * 32;
-    for (int e = threadIdx.x; e < batch * 32; e += 256) xs[e] = d2[(size_t)(e >> 5) * 256 + k0 + (e & 31)];
-    __syncthreads();
     const int col = threadIdx.x & 63, kq = threadIdx.x >> 6;     // this thread: column n, k in [k0 + 8 kq, k0 + 8 kq + 8)
-    const int n = bx * DOW_COLS + col;
-    if (n >= n3) return;
+    const int n = bx * DOW_COLS + col;                     // (n3 = 3 * n_points is a multiple of 64: every column is real)
+    const int nl = min(n, n3 - 1);                         // (every thread reaches the barriers)
     float acc[8] = {};
     float gs = 0.f;
-    constexpr int GB = 64;                                 // rows' gradients requested at once (ascending order kept): one round
-    for (int b0 = 0; b0 < batch; b0 += GB) {               // trip for the default batch of 50
-        float gvv[GB];
+    for (int b0 = 0; b0 < batch; b0 += DOW_GB) {           // ascending order kept
+        if (b0 > 0) __syncthreads();                       // the previous chunk's reads of xs are done
+        for (int e = threadIdx.x; e < DOW_GB * 32; e += 256)                 // rows past the batch: zeros
+            xs[e] = b0 + (e >> 5) < batch ? d2[(size_t)(b0 + (e >> 5)) * 256 + k0 + (e & 31)] : 0.f;
+        __syncthreads();
+        float gvv[DOW_GB];
 #pragma unroll
-        for (int u = 0; u < GB; ++u) gvv[u] = g[(size_t)min(b0 + u, batch - 1) * n3 + n];
+        for (int u = 0; u < DOW_GB; ++u) gvv[u] = g[(size_t)min(b0 + u, batch - 1) * n3 + nl];
 #pragma unroll
-        for (int u = 0; u < GB; ++u) {
-            if (b0 + u >= batch) break;
-            const int b = b0 + u;
-            const float gv = gvv[u];
+        for (int u = 0; u < DOW_GB; ++u) {
+            const float gv = b0 + u < batch ? gvv[u] : 0.f;  // (adds exact zeros past the batch: a break there spilled gvv to scratch)
             gs += gv;
-            const float4 x0 = *reinterpret_cast<const float4 *>(&xs[b * 32 + 8 * kq]), x1 = *reinterpret_cast<const float4 *>(&xs[b * 32 + 8 * kq + 4]);
+            const float4 x0 = *reinterpret_cast<const float4 *>(&xs[u * 32 + 8 * kq]), x1 = *reinterpret_cast<const float4 *>(&xs[u * 32 + 8 * kq + 4]);
             acc[0] = fmaf(x0.x, gv, acc[0]); acc[1] = fmaf(x0.y, gv, acc[1]); acc[2] = fmaf(x0.z, gv, acc[2]); acc[3] = fmaf(x0.w, gv, acc[3]);
             acc[4] = fmaf(x1.x, gv, acc[4]); acc[5] = fmaf(x1.y, gv, acc[5]); acc[6] = fmaf(x1.z, gv, acc[6]); acc[7] = fmaf(x1.w, gv, acc[7]);
         }
     }
+    if (n >= n3) return;
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) dV2[(size_t)(k0 + 8 * kq + kk) * n3 + n] = acc[kk];
     if (by == 0 && kq == 0) dc2[n] = gs;
@@ -1150,6 +1164,7 @@ struct geoadv_trainer {
     float *emd_temp, *emd_cost;        // loss 'emd': scratch of geoadv_emd_cost_grad1, per-cloud match costs
     int world;                         // ranks sharing the batch statistics (synchronised BN); 1 = local
     double *xbuf, *lbuf;               // [10][512] per-phase totals: exchanged (all-reduced by the host) / local copy
+    float *row_shift0;                 // [64] shift of layer 0's partial sums (train_fwd0_kernel)
 };
 
 static int trainer_repack(geoadv_trainer *t, hipStream_t st) {
@@ -1219,7 +1234,7 @@ extern "C" int geoadv_trainer_create(geoadv_trainer **out, const geoadv_ae_weigh
     const size_t o_loss = take(256);
     const bool emd = cfg->loss == GEOADV_TRAIN_LOSS_EMD;
     const size_t o_et = take(emd ? 4 * geoadv_emd_cost_grad1_temp_floats(B, n, n) + 8 : 0), o_ec = take(emd ? 4 * (size_t)B : 0);
-    const size_t o_xb = take(8 * 10 * 512), o_lb = take(8 * 10 * 512);
+    const size_t o_xb = take(8 * 10 * 512), o_lb = take(8 * 10 * 512), o_rs = take(4 * 64);
     t->arena_bytes = off;
     if (hipMalloc(reinterpret_cast<void **>(&t->arena), off) != hipSuccess) {
         set_error("trainer_create: hipMalloc of %zu bytes failed", off);
@@ -1245,6 +1260,7 @@ extern "C" int geoadv_trainer_create(geoadv_trainer **out, const geoadv_ae_weigh
     t->loss_type = cfg->loss; t->emd_temp = emd ? F(o_et) : nullptr; t->emd_cost = emd ? F(o_ec) : nullptr;
     t->world = 1;
     t->xbuf = reinterpret_cast<double *>(t->arena + o_xb); t->lbuf = reinterpret_cast<double *>(t->arena + o_lb);
+    t->row_shift0 = F(o_rs);
     // upload parameters
     std::vector<float> host(P, 0.f);
     const int dd[4] = {128, 256, 256, 3 * n};
@@ -1291,7 +1307,7 @@ extern "C" void geoadv_trainer_destroy(geoadv_trainer *t) {
 template <int CIN, int COUT>
 static int launch_fwd(geoadv_trainer *t, int i, hipStream_t st) {
     FwdArgs a;
-    a.zero = nullptr; a.zero_count = 0;
+    a.zero = nullptr; a.zero_count = 0; a.row_shift = nullptr;
     a.in = t->act[i - 1]; a.pscale = t->bn_scale[i - 1]; a.pshift = t->bn_shift[i - 1];
     a.W = PackedLayer{t->packed_fwd[i], CIN, COUT};
     a.bias = t->params + t->L.b[i]; a.out = t->act[i]; a.psum = t->psum;
@@ -1317,6 +1333,7 @@ static int launch_bn(geoadv_trainer *t, int i, int mode, int slot, hipStream_t s
     BnArgs a;
     a.mode = mode; a.totals = t->xbuf + 512 * slot; a.local_totals = t->lbuf + 512 * slot;
     a.psum = t->psum; a.tiles = t->tiles; a.C = ENC[i + 1]; a.inv_rows = 1.0 / ((double)t->R * t->world);
+    a.row_shift = i == 0 ? t->row_shift0 : nullptr;
     a.gamma = t->params + t->L.gamma[i]; a.beta = t->params + t->L.beta[i];
     a.mean = t->bn_mean[i]; a.inv_std = t->bn_istd[i]; a.scale = t->bn_scale[i]; a.shift = t->bn_shift[i];
     a.mov_mean = t->mov_mean[i]; a.mov_var = t->mov_var[i]; a.one_minus_decay = t->one_minus_decay;
@@ -1400,6 +1417,7 @@ static int run_phase(geoadv_trainer *t, int phase, const float *x, const float *
             a.W = PackedLayer{t->params + t->L.w[0], 3, 64};
             a.bias = t->params + t->L.b[0]; a.out = t->act[0]; a.psum = t->psum;
             a.zero = t->zbits; a.zero_count = 2 * B * 128;           // zbits and cnt are adjacent; nothing reads them before phase 5
+            a.row_shift = t->row_shift0;
             train_fwd0_kernel<<<t->tiles, TR_THREADS, 0, st>>>(a);
             GA_LAUNCH_CHECK();
         } else if (i == 1) rc = launch_fwd<64, 128>(t, 1, st);
@@ -1446,7 +1464,7 @@ static int run_phase(geoadv_trainer *t, int phase, const float *x, const float *
         // ---- decoder backward: three launches, each = weight gradient + data gradient of one layer side by side ----
         da.d2 = t->d2; da.g = t->g_recon; da.V2 = V2; da.dV2 = t->grads + t->L.v[2]; da.dc2 = t->grads + t->L.c[2]; da.dd2 = t->dd2;
         da.batch = B; da.n3 = n3; da.dist1 = t->dist1; da.dist2 = t->dist2;
-        dec_out_bwd_kernel<<<cdiv(n3, DOW_COLS) * 8 + (256 / DOX_K) * cdiv(B, DOX_B) + 1, 256, sizeof(float) * B * 32, st>>>(da);
+        dec_out_bwd_kernel<<<cdiv(n3, DOW_COLS) * 8 + (256 / DOX_K) * cdiv(B, DOX_B) + 1, 256, 0, st>>>(da);
         fc_bwd_kernel<true><<<256 + B, 256, 0, st>>>(t->d1, t->dd2, V1, t->grads + t->L.v[1], t->grads + t->L.c[1], t->dd1, B, 256);
         fc_bwd_kernel<false><<<128 + B, 256, 0, st>>>(z, t->dd1, V0, t->grads + t->L.v[0], t->grads + t->L.c[0], t->dz, B, 128);
         GA_LAUNCH_CHECK();
@@ -1581,6 +1599,29 @@ extern "C" int geoadv_trainer_export(geoadv_trainer *t, const geoadv_ae_weights 
         GA_REQUIRE(dst->dec_w[k] && dst->dec_b[k], "trainer_export: null destination at decoder layer %d", k);
         memcpy(const_cast<float *>(dst->dec_w[k]), &host[t->L.v[k]], sizeof(float) * (size_t)dd[k] * dd[k + 1]);
         memcpy(const_cast<float *>(dst->dec_b[k]), &host[t->L.c[k]], sizeof(float) * dd[k + 1]);
+    }
+    return GEOADV_OK;
+}
+
+// Read-only test view of what the last step kept (see include/geoadv.h): a device pointer and its element count.
+extern "C" int geoadv_trainer_state(const geoadv_trainer *t, int what, int layer, const void **ptr, size_t *count) {
+    GA_REQUIRE(t && ptr && count, "trainer_state: null argument");
+    const bool per_layer = what >= GEOADV_TRAIN_STATE_ACT && what <= GEOADV_TRAIN_STATE_BN_SHIFT;
+    GA_REQUIRE(!per_layer || (layer >= 0 && layer < ENC_L), "trainer_state: layer %d out of range [0, %d)", layer, ENC_L);
+    const size_t C = per_layer ? (size_t)ENC[layer + 1] : 0, Bn = (size_t)t->B * t->N;
+    switch (what) {
+        case GEOADV_TRAIN_STATE_ACT: *ptr = t->act[layer]; *count = Bn * C; break;
+        case GEOADV_TRAIN_STATE_BN_MEAN: *ptr = t->bn_mean[layer]; *count = C; break;
+        case GEOADV_TRAIN_STATE_BN_INV_STD: *ptr = t->bn_istd[layer]; *count = C; break;
+        case GEOADV_TRAIN_STATE_BN_SCALE: *ptr = t->bn_scale[layer]; *count = C; break;
+        case GEOADV_TRAIN_STATE_BN_SHIFT: *ptr = t->bn_shift[layer]; *count = C; break;
+        case GEOADV_TRAIN_STATE_IDX1: *ptr = t->idx1; *count = Bn; break;
+        case GEOADV_TRAIN_STATE_IDX2: *ptr = t->idx2; *count = Bn; break;
+        case GEOADV_TRAIN_STATE_POOL_MAX: *ptr = t->zbits; *count = (size_t)t->B * 128; break;
+        case GEOADV_TRAIN_STATE_POOL_TIES: *ptr = t->cnt; *count = (size_t)t->B * 128; break;
+        case GEOADV_TRAIN_STATE_DEC1: *ptr = t->d1; *count = (size_t)t->B * 256; break;
+        case GEOADV_TRAIN_STATE_DEC2: *ptr = t->d2; *count = (size_t)t->B * 256; break;
+        default: GA_REQUIRE(false, "trainer_state: unknown item %d", what);
     }
     return GEOADV_OK;
 }

@@ -130,6 +130,38 @@ class PointNetAETrainer:
         with torch.cuda.device(self.device):
             return torch.as_tensor(a, device=self.device)
 
+    _STATE = {"act": 0, "mean": 1, "inv_std": 2, "scale": 3, "shift": 4, "idx1": 5, "idx2": 6, "pool_max": 7, "pool_ties": 8,
+               "d1": 9, "d2": 10}                           # GEOADV_TRAIN_STATE_*
+
+    def _state_view(self, what, layer=0):
+        """Read-only test view (no copy) of what the last step kept on the device (geoadv_trainer_state): the pre-BN
+        activations a_layer [B*n, C], the batch BN constants (mean, inv_std, scale, shift), the Chamfer matches, the pooled
+        code's bit patterns and tie counts, the decoder's hidden activations."""
+        p, cnt = C.c_void_p(), C.c_size_t()
+        _lib.check(_lib.lib().geoadv_trainer_state(self._h, self._STATE[what], int(layer), C.byref(p), C.byref(cnt)), "trainer_state")
+        class _Arr:
+            pass
+        a = _Arr()
+        typestr = "<i4" if what in ("idx1", "idx2", "pool_max", "pool_ties") else "<f4"
+        a.__cuda_array_interface__ = {"shape": (int(cnt.value),), "typestr": typestr, "data": (p.value, False), "version": 2}
+        with torch.cuda.device(self.device):
+            return torch.as_tensor(a, device=self.device)
+
+    def saved_state(self):
+        """Host copies of everything _state_view exposes, shaped: {"act": [a_0..a_4], "mean"/"inv_std"/"scale"/"shift":
+        [per layer], "idx1"/"idx2": [B, n], "pool_max": float [B, 128], "pool_ties": [B, 128], "d1"/"d2": [B, 256]}."""
+        torch.cuda.synchronize(self.device)
+        B, n = self.batch_size, self.n_points
+        out = {k: [self._state_view(k, i).cpu().numpy().copy() for i in range(5)] for k in ("act", "mean", "inv_std", "scale", "shift")}
+        out["act"] = [a.reshape(B * n, -1) for a in out["act"]]
+        for k in ("idx1", "idx2"):
+            out[k] = self._state_view(k).cpu().numpy().reshape(B, n).copy()
+        out["pool_max"] = self._state_view("pool_max").cpu().numpy().view(np.float32).reshape(B, 128).copy()
+        out["pool_ties"] = self._state_view("pool_ties").cpu().numpy().reshape(B, 128).copy()
+        for k in ("d1", "d2"):
+            out[k] = self._state_view(k).cpu().numpy().reshape(B, 256).copy()
+        return out
+
     def _set_world(self, world):
         if world != self._world_set:
             with torch.cuda.device(self.device):

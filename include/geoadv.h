@@ -606,6 +606,26 @@ int geoadv_trainer_fetch(geoadv_trainer *t, float *loss, float *recon, void *str
  * offsets26 = enc_w[5], enc_b[5], bn_gamma[5], bn_beta[5], dec_w[3], dec_b[3] (in floats). */
 int geoadv_trainer_buffers(geoadv_trainer *t, float **params, float **grads, size_t *count);
 int geoadv_trainer_layout(const geoadv_trainer *t, size_t *offsets26);
+/* Read-only TEST view of what the last forward_backward kept on the device: *ptr and its element *count for
+ *   GEOADV_TRAIN_STATE_ACT         float [batch*n][C_layer]  pre-BN activations a_layer (layer 0..4)
+ *   GEOADV_TRAIN_STATE_BN_MEAN / _INV_STD / _SCALE / _SHIFT   float [C_layer]  the batch statistics of layer `layer` and
+ *                                  their folded form (the ReLU passes where fmaf(a, scale, shift) > 0)
+ *   GEOADV_TRAIN_STATE_IDX1 / _IDX2   int [batch][n]  the Chamfer matches (loss 'chamfer')
+ *   GEOADV_TRAIN_STATE_POOL_MAX    int [batch][128]  bit patterns of the max-pooled code; _POOL_TIES: rows attaining it
+ *   GEOADV_TRAIN_STATE_DEC1 / _DEC2   float [batch][256]  the decoder's hidden activations (after their ReLU)
+ * The pointers stay valid for the handle's life; the next step overwrites what they point to. */
+#define GEOADV_TRAIN_STATE_ACT         0
+#define GEOADV_TRAIN_STATE_BN_MEAN     1
+#define GEOADV_TRAIN_STATE_BN_INV_STD  2
+#define GEOADV_TRAIN_STATE_BN_SCALE    3
+#define GEOADV_TRAIN_STATE_BN_SHIFT    4
+#define GEOADV_TRAIN_STATE_IDX1        5
+#define GEOADV_TRAIN_STATE_IDX2        6
+#define GEOADV_TRAIN_STATE_POOL_MAX    7
+#define GEOADV_TRAIN_STATE_POOL_TIES   8
+#define GEOADV_TRAIN_STATE_DEC1        9
+#define GEOADV_TRAIN_STATE_DEC2        10
+int geoadv_trainer_state(const geoadv_trainer *t, int what, int layer, const void **ptr, size_t *count);
 /* Downloads the current variables (and moving averages) into the HOST buffers `dst` points to -- what
  * saver.save writes (autoencoder.py:213-215); feed them to geoadv_ae_create to attack the trained model. */
 int geoadv_trainer_export(geoadv_trainer *t, const geoadv_ae_weights *dst, void *stream);
