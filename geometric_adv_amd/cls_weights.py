@@ -179,3 +179,63 @@ def synthetic_weights(num_classes=13, seed=0):
     w["transform_net2/transform_feat/biases"] = rng.standard_normal(4096) * 0.02
     forward64(w, calibration_batch(), calibrate=True)
     return {k: np.asarray(v, dtype=np.float32) for k, v in w.items()}
+
+
+# ---- training (cls_trainer.py, train_classifier.py) --------------------------------------------------------------------------
+STEP_NAME = "Variable"                     # train_classifier.py: batch = tf.Variable(0), the unnamed global step counter
+
+
+def trainable_names():
+    """The trainable variables (weights, biases, bn/gamma, bn/beta) in LAYERS order."""
+    out = []
+    for scope, _, _, bn, _ in LAYERS:
+        out += [scope + "/weights", scope + "/biases"]
+        if bn:
+            out += [scope + "/bn/gamma", scope + "/bn/beta"]
+    return out
+
+
+def slot_names(optimizer="adam"):
+    """Names of the optimizer's variables as the TF 1.13 optimizers create them: `<var>/Adam`, `<var>/Adam_1` and
+    beta1_power / beta2_power (AdamOptimizer), or `<var>/Momentum` (MomentumOptimizer)."""
+    if optimizer == "adam":
+        return [v + s for v in trainable_names() for s in ("/Adam", "/Adam_1")] + ["beta1_power", "beta2_power"]
+    if optimizer == "momentum":
+        return [v + "/Momentum" for v in trainable_names()]
+    raise ValueError("optimizer must be 'adam' or 'momentum', got %r" % (optimizer,))
+
+
+def xavier_bound(scope, num_classes=13):
+    """TF's xavier_initializer() bound sqrt(6 / (fan_in + fan_out)) with its fan rule: a conv kernel [kh, kw, Cin, Cout] has
+    fan_in = kh * kw * Cin and fan_out = kh * kw * Cout (so conv1 / tconv1 [1, 3, 1, 64]: 3 and 192), a matrix its two sides."""
+    shape = dict((s, sh) for s, _, _, _, sh in LAYERS)[scope]
+    shape = tuple(num_classes if d is None else d for d in shape)
+    if len(shape) == 4:
+        fan_in, fan_out = shape[0] * shape[1] * shape[2], shape[0] * shape[1] * shape[3]
+    else:
+        fan_in, fan_out = shape
+    return float(np.sqrt(6.0 / (fan_in + fan_out)))
+
+
+def initial_weights(num_classes=13, seed=0):
+    """The variables as tf.global_variables_initializer leaves them (pointnet_cls.py / transform_nets.py / tf_util.py):
+    weights U(-b, b) with b = xavier_bound (numpy-seeded: TF's own draws are not reproducible), biases 0, gamma 1, beta 0,
+    transform_XYZ / transform_feat weights and biases 0, moving-average shadows 0 (zero slots)."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for scope, _, fo, bn, shape in LAYERS:
+        fo = num_classes if fo is None else fo
+        shape = tuple(num_classes if d is None else d for d in shape)
+        if scope.endswith("transform_XYZ") or scope.endswith("transform_feat"):
+            w[scope + "/weights"] = np.zeros(shape, np.float32)
+        else:
+            b = xavier_bound(scope, num_classes)
+            w[scope + "/weights"] = rng.uniform(-b, b, shape).astype(np.float32)
+        w[scope + "/biases"] = np.zeros(fo, np.float32)
+        if bn:
+            names = bn_names(scope)
+            w[names["gamma"]] = np.ones(fo, np.float32)
+            w[names["beta"]] = np.zeros(fo, np.float32)
+            w[names["mean"]] = np.zeros(fo, np.float32)
+            w[names["var"]] = np.zeros(fo, np.float32)
+    return w

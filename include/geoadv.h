@@ -351,6 +351,61 @@ int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const float *pc, flo
                        float *transform_in, float *transform_feat, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PointNet classifier TRAINING step (classifier/train_classifier.py train_one_epoch: sess.run([train_op, loss, pred]) at
+ * is_training = True): batch norm from the batch's moments, differentiated through; dropout keep 0.7 after fc1 and fc2;
+ * loss = mean softmax cross entropy + 0.001 * l2_loss(T2 T2^T - I); AdamOptimizer or MomentumOptimizer with the
+ * staircase learning-rate and bn_decay schedules of the global step `batch`.  csrc/cls_train.hip (which states the
+ * dropout generator exactly).  One handle = one model with a fixed batch and point count; no process-wide state.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct geoadv_cls_trainer geoadv_cls_trainer;
+#define GEOADV_CLS_OPT_ADAM     0
+#define GEOADV_CLS_OPT_MOMENTUM 1
+typedef struct geoadv_cls_train_config {
+    int   batch;            /* BATCH_SIZE (32)                                                     */
+    int   n_points;         /* NUM_POINT (2048); 1 ... 16384, batch * n_points <= 2^20            */
+    int   optimizer;        /* GEOADV_CLS_OPT_ADAM / _MOMENTUM                                     */
+    float learning_rate;    /* BASE_LEARNING_RATE (0.001)                                          */
+    float momentum;         /* MOMENTUM (0.9), momentum only                                       */
+    int   decay_step;       /* DECAY_STEP (200000), in samples                                     */
+    float decay_rate;       /* DECAY_RATE (0.7)                                                    */
+    int   initial_step;     /* the step counter `batch` to start from (0, or a restored value)      */
+    int   dropout_seed;     /* key of the dropout generator                                        */
+} geoadv_cls_train_config;
+/* init: HOST values of every variable (mean / var = the moving averages).  Optimizer slots start at zero and the beta
+ * powers at 0.9 / 0.999; geoadv_cls_trainer_set_slots restores them (flat, in the parameter layout). */
+int  geoadv_cls_trainer_create(geoadv_cls_trainer **out, const geoadv_cls_weights *init, const geoadv_cls_train_config *cfg);
+void geoadv_cls_trainer_destroy(geoadv_cls_trainer *t);
+int  geoadv_cls_trainer_set_slots(geoadv_cls_trainer *t, const float *slot1, const float *slot2, float beta1_power, float beta2_power);
+/* x: device [batch][n][3], labels: device int32 [batch]; loss (device float, of the PRE-update variables) and pred (device
+ * int32 [batch], argmax of the logits) may be NULL.  Updates the variables, slots, moving averages and the step counter. */
+int geoadv_cls_trainer_step(geoadv_cls_trainer *t, const float *x, const int *labels, float *loss, int *pred, void *stream);
+/* Device pointers of the flat parameter / gradient buffers (`count` floats each); offsets80[4 l + f] = where layer l's
+ * weights [in][out] (f 0), biases (1), bn/gamma (2), bn/beta (3) sit ((size_t)-1: none); moving_offsets20[l] = where its
+ * moving statistics sit in the MOVING_MEAN / MOVING_VAR arenas (may be NULL). */
+int geoadv_cls_trainer_buffers(geoadv_cls_trainer *t, float **params, float **grads, size_t *count);
+int geoadv_cls_trainer_layout(const geoadv_cls_trainer *t, size_t *offsets80, size_t *moving_offsets20);
+/* The step counter and Adam's beta powers as they stand (after the last step). */
+int geoadv_cls_trainer_counters(const geoadv_cls_trainer *t, long long *step, float *beta1_power, float *beta2_power);
+/* Read-only TEST / export view of the device state: *ptr and its element count.
+ *   BN_MEAN / BN_VAR / MOVING_MEAN / MOVING_VAR  float [C_layer]  batch statistics of the last step / moving averages
+ *   DROPOUT_MASK   float [batch][512 | 256]   layer 0 = fc1, 1 = fc2 (0 / 1)
+ *   POOL_ARGMAX    int [batch][1024]          pool 0 = T-Net1, 1 = T-Net2, 2 = conv5: the point of the first maximum
+ *   T1 / T2 float [batch][9 | 4096], LOGITS float [batch][num_classes]   of the last step's forward
+ *   SLOT1 / SLOT2  float [count]              Adam m / v, or Momentum's accumulator (SLOT1), in the parameter layout */
+#define GEOADV_CLS_STATE_BN_MEAN       0
+#define GEOADV_CLS_STATE_BN_VAR        1
+#define GEOADV_CLS_STATE_MOVING_MEAN   2
+#define GEOADV_CLS_STATE_MOVING_VAR    3
+#define GEOADV_CLS_STATE_DROPOUT_MASK  4
+#define GEOADV_CLS_STATE_POOL_ARGMAX   5
+#define GEOADV_CLS_STATE_T1            6
+#define GEOADV_CLS_STATE_T2            7
+#define GEOADV_CLS_STATE_LOGITS        8
+#define GEOADV_CLS_STATE_SLOT1         9
+#define GEOADV_CLS_STATE_SLOT2        10
+int geoadv_cls_trainer_state(const geoadv_cls_trainer *t, int what, int layer, const void **ptr, size_t *count);
+
+/* ------------------------------------------------------------------------------------------
  * AtlasNet auto-encoder of the transfer experiment: transfer/atlasnet/model/model_blocks.py (PointNet encoder :28-60,
  * Mapping2Dto3D decoder :63-105) in eval mode (atlasnet.py:45-67, train=False: the fixed template points), batch norm
  * from the running statistics with eps 1e-5, fp32.  csrc/atlasnet.hip.
