@@ -19,7 +19,7 @@ from .classifier import PointNetClassifier, _ClsWeights
 
 OPTIMIZERS = {"adam": 0, "momentum": 1}               # GEOADV_CLS_OPT_*
 _STATE = {"bn_mean": 0, "bn_var": 1, "moving_mean": 2, "moving_var": 3, "dropout_mask": 4, "pool_argmax": 5, "t1": 6,
-          "t2": 7, "logits": 8, "slot1": 9, "slot2": 10}
+          "t2": 7, "logits": 8, "slot1": 9, "slot2": 10, "pre_bn": 11, "bn_inv": 12, "bn_shift": 13}
 
 
 class _ClsTrainConfig(C.Structure):
@@ -115,17 +115,23 @@ class PointNetClassifierTrainer:
         with torch.cuda.device(self.device):
             return torch.as_tensor(a, device=self.device)
 
-    def state(self, what, layer=0):
+    def state(self, what, layer=0, device=False):
         """Host copy of what the last step kept (geoadv_cls_trainer_state): 'bn_mean' / 'bn_var' / 'moving_mean' /
-        'moving_var' of a BN layer (GEOADV_CLS_* index), 'dropout_mask' 0 / 1, 'pool_argmax' 0 / 1 / 2, 't1', 't2', 'logits',
-        'slot1', 'slot2'."""
+        'moving_var' / 'bn_inv' / 'bn_shift' of a BN layer (GEOADV_CLS_* index), 'pre_bn' of a BN layer ([rows][C]: B * N
+        rows for a per-point layer, B for an fc layer), 'dropout_mask' 0 / 1, 'pool_argmax' 0 / 1 / 2, 't1', 't2', 'logits',
+        'slot1', 'slot2'.  device=True returns a view of the device buffer instead: it aliases the handle's memory, so it
+        changes with the next step and dangles once this trainer is destroyed -- drop the view before the trainer."""
         p, cnt = C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().geoadv_cls_trainer_state(self._h, _STATE[what], int(layer), C.byref(p), C.byref(cnt)),
                    "cls_trainer_state")
         torch.cuda.synchronize(self.device)
-        a = self._raw(p.value, cnt.value, "<i4" if what == "pool_argmax" else "<f4").cpu().numpy().copy()
+        a = self._raw(p.value, cnt.value, "<i4" if what == "pool_argmax" else "<f4")
         B = self.batch_size
         shapes = {"dropout_mask": (B, -1), "pool_argmax": (B, 1024), "t1": (B, 3, 3), "t2": (B, 64, 64), "logits": (B, -1)}
+        if what == "pre_bn":
+            shapes["pre_bn"] = (-1, self._shapes()[int(layer)][2])
+        if not device:
+            a = a.cpu().numpy().copy()
         return a.reshape(shapes[what]) if what in shapes else a
 
     def counters(self):

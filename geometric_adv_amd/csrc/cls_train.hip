@@ -871,6 +871,14 @@ extern "C" int geoadv_cls_trainer_state(const geoadv_cls_trainer *t, int what, i
         *ptr = base + t->o_mv[layer]; *count = t->out[layer];
         return GEOADV_OK;
     }
+    case GEOADV_CLS_STATE_PRE_BN:
+        GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "cls_trainer_state: layer %d has no batch norm", layer);
+        *ptr = t->a[layer]; *count = (size_t)(per_point(layer) ? t->R : t->B) * t->out[layer];
+        return GEOADV_OK;
+    case GEOADV_CLS_STATE_BN_INV: case GEOADV_CLS_STATE_BN_SHIFT:
+        GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "cls_trainer_state: layer %d has no batch norm", layer);
+        *ptr = (what == GEOADV_CLS_STATE_BN_INV ? t->inv : t->shift) + t->o_mv[layer]; *count = t->out[layer];
+        return GEOADV_OK;
     case GEOADV_CLS_STATE_DROPOUT_MASK:
         GA_REQUIRE(layer == 0 || layer == 1, "cls_trainer_state: dropout layer %d must be 0 or 1", layer);
         *ptr = t->mask[layer]; *count = B * (layer == 0 ? 512 : 256);

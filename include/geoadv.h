@@ -391,7 +391,11 @@ int geoadv_cls_trainer_counters(const geoadv_cls_trainer *t, long long *step, fl
  *   DROPOUT_MASK   float [batch][512 | 256]   layer 0 = fc1, 1 = fc2 (0 / 1)
  *   POOL_ARGMAX    int [batch][1024]          pool 0 = T-Net1, 1 = T-Net2, 2 = conv5: the point of the first maximum
  *   T1 / T2 float [batch][9 | 4096], LOGITS float [batch][num_classes]   of the last step's forward
- *   SLOT1 / SLOT2  float [count]              Adam m / v, or Momentum's accumulator (SLOT1), in the parameter layout */
+ *   SLOT1 / SLOT2  float [count]              Adam m / v, or Momentum's accumulator (SLOT1), in the parameter layout
+ *   PRE_BN         float [rows][C_layer]      the stored pre-BN activation a of a BN layer; rows = batch * n_points for a
+ *                                             per-point layer, batch for an fc layer
+ *   BN_INV / BN_SHIFT  float [C_layer]        the folded constants of a BN layer: the step's ReLU input is
+ *                                             a * inv + shift, two fp32 roundings (no contraction) */
 #define GEOADV_CLS_STATE_BN_MEAN       0
 #define GEOADV_CLS_STATE_BN_VAR        1
 #define GEOADV_CLS_STATE_MOVING_MEAN   2
@@ -403,6 +407,9 @@ int geoadv_cls_trainer_counters(const geoadv_cls_trainer *t, long long *step, fl
 #define GEOADV_CLS_STATE_LOGITS        8
 #define GEOADV_CLS_STATE_SLOT1         9
 #define GEOADV_CLS_STATE_SLOT2        10
+#define GEOADV_CLS_STATE_PRE_BN       11
+#define GEOADV_CLS_STATE_BN_INV       12
+#define GEOADV_CLS_STATE_BN_SHIFT     13
 int geoadv_cls_trainer_state(const geoadv_cls_trainer *t, int what, int layer, const void **ptr, size_t *count);
 
 /* ------------------------------------------------------------------------------------------

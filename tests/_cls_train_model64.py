@@ -5,6 +5,16 @@ The forward is written out in torch float64 on the CPU and differentiated by aut
 would not pick by itself made explicit: the max pool passes its gradient to the FIRST maximum of each (cloud, channel)
 (a gather at numpy's argmax), and dropout multiplies by the generator's mask.  test_cls_train_host.py checks this model
 against central finite differences and the schedules at their edges; test_gpu_cls_train.py checks the HIP step against it.
+
+Pins: the step's discrete decisions can be fixed to given ones instead of fp64's own -- the ReLU masks of every batch-norm
+layer (pins["relu"][scope]), the pools' rows (force_argmax) and the dropout masks (pins["dropout"]).  Pinning fp64's own
+decisions reproduces the unpinned model bit for bit; pin_disagreements() says how far from its boundary each pinned decision
+that fp64 would take otherwise lies.  test_gpu_cls_train_pinned.py pins the model to the HIP step's decisions.
+
+perturb (tests only) restates the step wrongly, to show that a comparison would catch it: "dropout_grad_unscaled" (the
+dropout backward without 1 / 0.7), "bn_no_m2" = scope (that batch norm's backward without its xhat * mean(g xhat) term),
+"fc_var_unbiased" (the fc batch norms' variance over B - 1), "t1_transposed" (x T1^T), "pool_also" = three [B][1024] row
+arrays that receive each pooled gradient as well (crediting a second maximum).
 """
 import numpy as np
 import torch
@@ -52,14 +62,20 @@ def _shapes(nc):
         yield scope, fi, (nc if fo is None else fo), bn
 
 
-def forward(params, x, labels, masks, force_argmax=None, reg_weight=0.001):
+def forward(params, x, labels, masks, force_argmax=None, reg_weight=0.001, pins=None, perturb=None):
     """params: {trainable name: float64 tensor} (weights as [fan_in, fan_out]); returns (loss, extras dict).
     reg_weight: the regulariser's weight (0.001 in pointnet_cls.get_loss; tests vary it to size its gradient).
     force_argmax: three [B][1024] index arrays that replace the pools' first maxima (None = compute them).
-    extras: relu_margin[scope] = the smallest |ReLU input| of the layer; pool_gap[i] = [B][1024] gap between the largest
-    and second-largest pooled value (0 where the maximum is attained twice)."""
-    ex = {"mean": {}, "var": {}, "argmax": [], "relu_margin": {}, "pool_gap": []}
+    pins: {"relu": {scope: bool mask}} ([B * N][C] or [B][C]) replaces relu(z) by z * mask in the layers it names.
+    perturb: see the module docstring (None = the step as it is).
+    extras: relu_margin[scope] = the smallest |ReLU input| of the layer (at flat index relu_closest[scope]); relu_mask[scope]
+    = fp64's own ReLU decisions ([rows][C] bool); pool_gap[i] = [B][1024] gap between the largest
+    and second-largest pooled value (0 where the maximum is attained twice); disagree = what pin_disagreements reports."""
+    ex = {"mean": {}, "var": {}, "argmax": [], "relu_margin": {}, "relu_closest": {}, "relu_mask": {}, "pool_gap": [],
+          "disagree": {}}
     P = params
+    relu_pins = (pins or {}).get("relu", {})
+    perturb = perturb or {}
 
     def lin(h, s):
         return h @ P[s + "/weights"] + P[s + "/biases"]
@@ -67,42 +83,83 @@ def forward(params, x, labels, masks, force_argmax=None, reg_weight=0.001):
     def bn_relu(a, s):
         flat = a.reshape(-1, a.shape[-1])
         m = flat.mean(0)
-        v = ((flat - m) ** 2).mean(0)
+        if a.dim() == 2 and perturb.get("fc_var_unbiased"):
+            v = ((flat - m) ** 2).sum(0) / (flat.shape[0] - 1)
+        else:
+            v = ((flat - m) ** 2).mean(0)
         ex["mean"][s], ex["var"][s] = m.detach(), v.detach()
+        if perturb.get("bn_no_m2") == s:
+            v = v.detach()                              # drops exactly the xhat * mean(g xhat) term of the backward
         z = (a - m) / torch.sqrt(v + EPS) * P[s + "/bn/gamma"] + P[s + "/bn/beta"]
-        ex["relu_margin"][s] = float(z.detach().abs().min())
-        return torch.relu(z)
+        zd = z.detach()
+        ex["relu_margin"][s] = float(zd.abs().min())
+        ex["relu_closest"][s] = int(zd.abs().argmin())  # flat index of that input
+        ex["relu_mask"][s] = (zd > 0).numpy().reshape(-1, zd.shape[-1])
+        ex["own"] = torch.relu(zd)                      # fp64's own ReLU output, for the pool's disagreement report
+        if s not in relu_pins:
+            return torch.relu(z)
+        mask = torch.as_tensor(np.asarray(relu_pins[s], bool)).reshape(z.shape)
+        differ = mask != (zd > 0)
+        ex["disagree"][s] = (int(differ.sum()), float(zd.abs()[differ].max()) if bool(differ.any()) else 0.0)
+        return z * mask
 
     def layer(h, s):
         return bn_relu(lin(h, s), s)
 
     def pool(y):
         yn = y.detach().numpy()
-        top2 = -np.partition(-yn, 1, axis=1)[:, :2, :]
-        ex["pool_gap"].append(top2[:, 0, :] - top2[:, 1, :])
+        if yn.shape[1] > 1:
+            top2 = -np.partition(-yn, 1, axis=1)[:, :2, :]
+            ex["pool_gap"].append(top2[:, 0, :] - top2[:, 1, :])
+        else:                                           # one point: no runner-up
+            ex["pool_gap"].append(np.full((yn.shape[0], yn.shape[2]), np.inf))
         idx = np.argmax(yn, axis=1)                     # first maximum
+        i = len(ex["argmax"])
         if force_argmax is not None:
-            idx = np.asarray(force_argmax[len(ex["argmax"])], np.int64)
+            idx = np.asarray(force_argmax[i], np.int64)
+            own = ex["own"].numpy()
+            first = np.argmax(own, axis=1)
+            differ = first != idx
+            gap = own.max(axis=1) - np.take_along_axis(own, idx[:, None, :], 1)[:, 0, :]
+            ex["disagree"]["pool%d" % i] = (int(differ.sum()), float(gap[differ].max()) if differ.any() else 0.0)
         ex["argmax"].append(idx)
-        return torch.gather(y, 1, torch.from_numpy(idx)[:, None, :]).squeeze(1)
+        out = torch.gather(y, 1, torch.from_numpy(idx)[:, None, :]).squeeze(1)
+        if "pool_also" in perturb:
+            also = torch.gather(y, 1, torch.from_numpy(np.asarray(perturb["pool_also"][i], np.int64))[:, None, :]).squeeze(1)
+            out = out + (also - also.detach())
+        return out
 
     def tnet(h, p, k, last):
         g = pool(layer(layer(layer(h, p + "/tconv1"), p + "/tconv2"), p + "/tconv3"))
         g = layer(layer(g, p + "/tfc1"), p + "/tfc2")
         return (lin(g, p + "/" + last) + torch.eye(k, dtype=torch.float64).reshape(-1)).reshape(-1, k, k)
 
+    def dropout(h, mask):
+        if perturb.get("dropout_grad_unscaled"):
+            hm = h * mask
+            return hm + (hm / KEEP - hm).detach()
+        return h / KEEP * mask
+
     t1 = tnet(x, "transform_net1", 3, "transform_XYZ")
-    h2 = layer(layer(x @ t1, "conv1"), "conv2")
+    h2 = layer(layer(x @ (t1.transpose(1, 2) if perturb.get("t1_transposed") else t1), "conv1"), "conv2")
     t2 = tnet(h2, "transform_net2", 64, "transform_feat")
     g = pool(layer(layer(layer(h2 @ t2, "conv3"), "conv4"), "conv5"))
-    g = layer(g, "fc1") / KEEP * masks[0]
-    g = layer(g, "fc2") / KEEP * masks[1]
+    g = dropout(layer(g, "fc1"), masks[0])
+    g = dropout(layer(g, "fc2"), masks[1])
     logits = lin(g, "fc3")
     ce = torch.nn.functional.cross_entropy(logits, labels)
     e = t2 @ t2.transpose(1, 2) - torch.eye(64, dtype=torch.float64)
     loss = ce + reg_weight * 0.5 * (e ** 2).sum()
+    ex.pop("own", None)
     ex.update(logits=logits.detach().numpy(), t1=t1.detach().numpy(), t2=t2.detach().numpy())
     return loss, ex
+
+
+def pin_disagreements(res):
+    """Where a pinned step's (or forward's extras') decisions differ from fp64's own: {scope: (count, largest fp64 |z| of
+    such a ReLU input)} for each pinned layer and {"pool<i>": (count, largest fp64 maximum minus the fp64 value at the pinned
+    row)} for each forced pool.  A pin is legitimate where that distance is within rounding of fp32."""
+    return dict(res["disagree"])
 
 
 def to_params(weights, nc):
@@ -118,15 +175,19 @@ def to_params(weights, nc):
 
 
 def step(weights, x, labels, nc, step_k=0, seed=0, optimizer="adam", lr=0.001, momentum=0.9, decay_step=200000,
-         decay_rate=0.7, slots=None, force_argmax=None):
+         decay_rate=0.7, slots=None, force_argmax=None, pins=None, reg_weight=0.001, perturb=None):
     """One training step in float64.  weights: cls_weights-named dict (moving averages included); slots: {'m', 'v', 'b1p',
-    'b2p'} (Adam) or {'acc'} (Momentum) keyed by trainable name, None = fresh.  Returns a dict: loss, logits, t1, t2,
-    grads, new_weights (cls_weights names, stored shapes), slots, mean / var (batch statistics), argmax (3 pools), masks."""
+    'b2p'} (Adam) or {'acc'} (Momentum) keyed by trainable name, None = fresh.  pins: forward's, plus "dropout" = the two
+    masks to use instead of the generator's.  Returns a dict: loss, logits, t1, t2, grads, new_weights (cls_weights names,
+    stored shapes), slots, mean / var (batch statistics), argmax (3 pools), masks, disagree (see pin_disagreements)."""
     B = x.shape[0]
     params = {k: v.clone().requires_grad_(True) for k, v in to_params(weights, nc).items()}
-    masks = [keep_mask(seed, step_k, 0, B, 512), keep_mask(seed, step_k, 1, B, 256)]
+    if pins is not None and "dropout" in pins:
+        masks = [np.asarray(m, np.float64) for m in pins["dropout"]]
+    else:
+        masks = [keep_mask(seed, step_k, 0, B, 512), keep_mask(seed, step_k, 1, B, 256)]
     loss, ex = forward(params, torch.tensor(np.asarray(x, np.float64)), torch.tensor(np.asarray(labels, np.int64)),
-                       [torch.tensor(m) for m in masks], force_argmax)
+                       [torch.tensor(m) for m in masks], force_argmax, reg_weight=reg_weight, pins=pins, perturb=perturb)
     loss.backward()
     grads = {k: v.grad.numpy().copy() for k, v in params.items()}
     cur_lr, bn_decay = schedule(step_k, B, lr, decay_step, decay_rate)
@@ -162,4 +223,5 @@ def step(weights, x, labels, nc, step_k=0, seed=0, optimizer="adam", lr=0.001, m
     return dict(loss=float(loss.item()), logits=ex["logits"], t1=ex["t1"], t2=ex["t2"], grads=grads, new_weights=new_weights,
                 slots=out_slots, mean={k: v.numpy() for k, v in ex["mean"].items()},
                 var={k: v.numpy() for k, v in ex["var"].items()}, argmax=ex["argmax"], masks=masks, lr=cur_lr, bn_decay=bn_decay,
-                relu_margin=ex["relu_margin"], pool_gap=ex["pool_gap"])
+                relu_margin=ex["relu_margin"], relu_closest=ex["relu_closest"], relu_mask=ex["relu_mask"], pool_gap=ex["pool_gap"],
+                disagree=ex["disagree"])

@@ -62,6 +62,55 @@ def test_model_step_is_deterministic_and_moves_every_variable():
     assert not still, still
 
 
+def _own_pins(ref):
+    return {"relu": {k: v.copy() for k, v in ref["relu_mask"].items()}, "dropout": [m.copy() for m in ref["masks"]]}
+
+
+def test_own_decisions_pinned_reproduce_the_model_bit_for_bit():
+    """Pinning fp64's own ReLU masks, pool rows and dropout masks changes nothing and reports no disagreement."""
+    w, x, y = _tiny(3, B=3, N=16)
+    ref = M.step(w, x, y, 4, seed=2)
+    got = M.step(w, x, y, 4, seed=2, pins=_own_pins(ref), force_argmax=ref["argmax"])
+    assert got["loss"] == ref["loss"]
+    for k in ref["grads"]:
+        assert np.array_equal(got["grads"][k], ref["grads"][k]), k
+    for k in ("logits", "t1", "t2"):
+        assert np.array_equal(got[k], ref[k]), k
+    rep = M.pin_disagreements(got)
+    assert set(rep) == set(ref["relu_mask"]) | {"pool0", "pool1", "pool2"}
+    assert all(v == (0, 0.0) for v in rep.values()), rep
+
+
+@pytest.mark.parametrize("scope", ["conv4", "transform_net1/tfc1"])
+def test_a_flipped_relu_pin_moves_the_gradients_and_is_reported(scope):
+    """Flipping the pin of the layer's ReLU input closest to zero: one disagreement, reported at that input's |z|; the
+    gradients move (the row's share through the flipped unit).  tfc1 has no dropout that could hide the flip."""
+    w, x, y = _tiny(4, B=3, N=16)
+    ref = M.step(w, x, y, 4, seed=1)
+    pins = _own_pins(ref)
+    flat = pins["relu"][scope].reshape(-1)
+    i = ref["relu_closest"][scope]
+    flat[i] = not flat[i]
+    got = M.step(w, x, y, 4, seed=1, pins=pins, force_argmax=ref["argmax"])
+    rep = M.pin_disagreements(got)
+    assert rep[scope] == (1, ref["relu_margin"][scope]), rep[scope]
+    # later layers move by the flipped unit's share: only inputs that close to zero may change side there
+    assert all(v[1] < 1e-5 for k, v in rep.items() if k != scope), rep
+    moved = max(float(np.abs(got["grads"][k] - g).max()) for k, g in ref["grads"].items())
+    assert moved > 1e-9, moved
+
+
+def test_a_forced_pool_row_is_reported_with_its_gap():
+    w, x, y = _tiny(5, B=2, N=16)
+    ref = M.step(w, x, y, 4, seed=0)
+    arg = [a.copy() for a in ref["argmax"]]
+    arg[2][1, 7] = (arg[2][1, 7] + 1) % 16
+    got = M.step(w, x, y, 4, seed=0, pins=_own_pins(ref), force_argmax=arg)
+    cnt, gap = M.pin_disagreements(got)["pool2"]
+    assert cnt == 1 and gap > 0
+    assert not np.array_equal(got["grads"]["conv5/weights"], ref["grads"]["conv5/weights"])
+
+
 @pytest.mark.parametrize("B,decay_step", [(32, 200000), (7, 100)])
 def test_schedule_staircase_edges(B, decay_step):
     k_edge = -(-decay_step // B)                  # first step with k * B >= decay_step
