@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, atlas_weights as AW, ops
+from ._model import DeviceModel
 
 N_ENC = len(AW.ENC_LAYERS)
 N_DEC = 3 + AW.MAX_LAYERS
@@ -32,7 +33,9 @@ class _AtlasWeights(C.Structure):
                 for f in ("w", "b", "gamma", "beta", "mean", "var")]
 
 
-class AtlasNetAE:
+class AtlasNetAE(DeviceModel):
+    _destroy = "geoadv_atlas_destroy"
+
     def __init__(self, transfer_ae_folder=None, options=None, state=None, batch_size=32, device=None):
         """Weights and options from <transfer_ae_folder>/network.pth and options.json (atlas_weights.load), unless
         `state` (a {key: array} dict without the `module.` prefix) and `options` are given.  batch_size only sets the chunk
@@ -67,26 +70,6 @@ class AtlasNetAE:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_atlas_create(C.byref(self._h), C.byref(cfg), C.byref(hw),
                                                       self.template.ctypes.data_as(C.c_void_p)), "atlas_create")
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                _lib.lib().geoadv_atlas_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _as_dev(self, x):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
-        t = t.to(self.device, dtype=torch.float32).contiguous()
-        if t.dim() != 3 or t.shape[2] != 3:
-            raise ValueError("point clouds must be of shape (batch, points, 3); got %s" % (tuple(t.shape),))
-        return t
 
     def forward(self, x):
         """(latent (b, 1024), recon (b, P, 3)) float32 device tensors of EncoderDecoder.forward(x, train=False), fused
@@ -100,10 +83,8 @@ class AtlasNetAE:
             return latent, recon
         L = _lib.lib()
         with torch.cuda.device(dev):
-            need = L.geoadv_atlas_workspace_bytes(self._h, b, n)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
-            st = L.geoadv_atlas_forward(self._h, b, n, _lib.ptr(x), _lib.ptr(latent), _lib.ptr(recon), _lib.ptr(self._ws),
+            ws = self._workspace(L.geoadv_atlas_workspace_bytes(self._h, b, n))
+            st = L.geoadv_atlas_forward(self._h, b, n, _lib.ptr(x), _lib.ptr(latent), _lib.ptr(recon), _lib.ptr(ws),
                                         _lib.stream_handle())
         _lib.check(st, "atlas_forward")
         return latent, recon

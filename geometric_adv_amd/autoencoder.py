@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops, weights as W
+from ._model import DeviceModel
 
 
 class _AEWeights(C.Structure):
@@ -24,8 +25,9 @@ class _AEWeights(C.Structure):
 ENCODER_ARITH = {"f32": 0, "bf16x3": 1, "f16x2": 2}     # GEOADV_ENC_ARITH_*
 
 
-class PointNetAE:
+class PointNetAE(DeviceModel):
     """PointNet-style encoder + FC decoder with frozen weights on one GPU."""
+    _destroy = "geoadv_ae_destroy"
 
     def __init__(self, weights, n_points, ae_name=W.AE_NAME, device=None, encoder_arith=None):
         """weights: dict of TF-variable-name -> array (see weights.py), or a path to such an .npz, or a
@@ -60,7 +62,6 @@ class PointNetAE:
             _lib.check(_lib.lib().geoadv_ae_create(C.byref(self._h), C.byref(hw)), "ae_create")
         if encoder_arith is not None:
             self.set_encoder_arith(encoder_arith)
-        self._ws = None
 
     def set_encoder_arith(self, arith):
         """Switch the encoder kernels' arithmetic (ENCODER_ARITH); not while another thread uses this model."""
@@ -77,18 +78,6 @@ class PointNetAE:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_ae_status(self._h, _lib.stream_handle()), "ae_status")
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                _lib.lib().geoadv_ae_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
     def _as_dev(self, a):
         t = torch.as_tensor(np.asarray(a, dtype=np.float32)) if not isinstance(a, torch.Tensor) else a
         t = t.to(self.device, dtype=torch.float32).contiguous()
@@ -103,11 +92,9 @@ class PointNetAE:
         latent = torch.empty((b, self._kb), dtype=torch.float32, device=self.device)
         recon = torch.empty((b, self.n_points, 3), dtype=torch.float32, device=self.device) if want_recon else None
         with torch.cuda.device(self.device):
-            need = _lib.lib().geoadv_ae_workspace_bytes(self._h, b)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(_lib.lib().geoadv_ae_workspace_bytes(self._h, b))
             st = _lib.lib().geoadv_ae_forward(self._h, b, _lib.ptr(pc), _lib.ptr(latent), _lib.ptr(recon),
-                                              _lib.ptr(self._ws), _lib.stream_handle())
+                                              _lib.ptr(ws), _lib.stream_handle())
         _lib.check(st, "ae_forward")
         return recon, (latent if self.bneck == self._kb else latent[:, :self.bneck].contiguous())
 
@@ -120,11 +107,9 @@ class PointNetAE:
         latent = torch.empty((b, self._kb), dtype=torch.float32, device=self.device)
         idx = torch.empty((b, self._kb), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            need = _lib.lib().geoadv_ae_workspace_bytes(self._h, b)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(_lib.lib().geoadv_ae_workspace_bytes(self._h, b))
             st = _lib.lib().geoadv_ae_critical(self._h, b, _lib.ptr(pc), _lib.ptr(latent), _lib.ptr(idx),
-                                               _lib.ptr(self._ws), _lib.stream_handle())
+                                               _lib.ptr(ws), _lib.stream_handle())
         _lib.check(st, "ae_critical")
         if self.bneck != self._kb:
             latent, idx = latent[:, :self.bneck].contiguous(), idx[:, :self.bneck].contiguous()
@@ -167,10 +152,8 @@ class PointNetAE:
             z = torch.cat([z, torch.zeros((b, self._kb - self.bneck), dtype=torch.float32, device=self.device)], dim=1).contiguous()
         recon = torch.empty((b, self.n_points, 3), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            need = _lib.lib().geoadv_ae_workspace_bytes(self._h, b)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
-            st = _lib.lib().geoadv_ae_decode(self._h, b, _lib.ptr(z), _lib.ptr(recon), _lib.ptr(self._ws), _lib.stream_handle())
+            ws = self._workspace(_lib.lib().geoadv_ae_workspace_bytes(self._h, b))
+            st = _lib.lib().geoadv_ae_decode(self._h, b, _lib.ptr(z), _lib.ptr(recon), _lib.ptr(ws), _lib.stream_handle())
         _lib.check(st, "ae_decode")
         return recon
 

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, cls_weights as CW
+from ._model import DeviceModel
 
 N_LAYERS = len(CW.LAYERS)
 
@@ -26,7 +27,9 @@ class _ClsWeights(C.Structure):
                 ("mean", C.c_void_p * N_LAYERS), ("var", C.c_void_p * N_LAYERS)]
 
 
-class PointNetClassifier:
+class PointNetClassifier(DeviceModel):
+    _destroy = "geoadv_cls_destroy"
+
     def __init__(self, classifier_path, restore_epoch=CW.DEFAULT_EPOCH, num_points=2048, batch_size=10, num_classes=13,
                  weights=None, device=None):
         """Weights from <classifier_path>/model-%03d.ckpt (restore_epoch), unless `weights` is given: a {name: array} dict
@@ -54,26 +57,6 @@ class PointNetClassifier:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_cls_create(C.byref(self._h), C.byref(hw)), "cls_create")
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                _lib.lib().geoadv_cls_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _as_dev(self, x):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
-        t = t.to(self.device, dtype=torch.float32).contiguous()
-        if t.dim() != 3 or t.shape[2] != 3:
-            raise ValueError("point clouds must be of shape (batch, points, 3); got %s" % (tuple(t.shape),))
-        return t
 
     def forward(self, x, transforms=False):
         """(logits (b, C) float32, labels (b,) int32[, T1 (b, 3, 3), T2 (b, 64, 64)]) as device tensors, one call."""
@@ -88,11 +71,9 @@ class PointNetClassifier:
             return (logits, labels, t1, t2) if transforms else (logits, labels)
         L = _lib.lib()
         with torch.cuda.device(dev):
-            need = L.geoadv_cls_workspace_bytes(self._h, b, n)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+            ws = self._workspace(L.geoadv_cls_workspace_bytes(self._h, b, n))
             st = L.geoadv_cls_forward(self._h, b, n, _lib.ptr(x), _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(t1),
-                                      _lib.ptr(t2), _lib.ptr(self._ws), _lib.stream_handle())
+                                      _lib.ptr(t2), _lib.ptr(ws), _lib.stream_handle())
         _lib.check(st, "cls_forward")
         return (logits, labels, t1, t2) if transforms else (logits, labels)
 

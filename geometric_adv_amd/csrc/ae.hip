@@ -1,6 +1,6 @@
 // geoadv_ae: device-resident, MFMA-packed weights of the victim auto-encoder + plain forward
 // (AdversaryAutoEncoder.restore_ae_model / reconstruct, src/adversary_autoencoder.py:42-51,75-91).
-#include "ae.h"
+#include "host_util.h"
 #include <cmath>
 #include "encoder_x3.h"
 #include <math.h>
@@ -19,34 +19,6 @@ int launch_decoder_fc2(const DeviceAE &A, int b, const float *d2, float *recon, 
                        size_t fill_count = 0);
 int launch_latent_fc(const DeviceAE &A, int b, const float *z, float *d2, hipStream_t stream);
 int encoder_tiles_max(int n);
-
-static inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// B[k][n] for k < K, n < N taken from src through `at(k, n)`; zero padded to (Kp, Np).
-template <class F>
-static void pack_fragments(std::vector<float> &dst, size_t off, int K, int N, int Kp, int Np, F at) {
-    const int kg = Kp / 8;
-    for (int cb = 0; cb < Np / 32; ++cb)
-        for (int t = 0; t < kg; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int u = 0; u < 4; ++u) {
-                    const int k = 8 * t + 4 * (lane >> 5) + u, n = 32 * cb + (lane & 31);
-                    dst[off + (((size_t)cb * kg + t) * 64 + lane) * 4 + u] = (k < K && n < N) ? at(k, n) : 0.f;
-                }
-}
-
-// the 16x16x4 packing (ae.h)
-template <class F>
-static void pack_fragments16(std::vector<float> &dst, size_t off, int K, int N, int Kp, int Np, F at) {
-    const int kg = Kp / 16;
-    for (int cb = 0; cb < Np / 16; ++cb)
-        for (int t = 0; t < kg; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int u = 0; u < 4; ++u) {
-                    const int k = 16 * t + 4 * (lane >> 4) + u, n = 16 * cb + (lane & 15);
-                    dst[off + (((size_t)cb * kg + t) * 64 + lane) * 4 + u] = (k < K && n < N) ? at(k, n) : 0.f;
-                }
-}
 
 // bf16 pieces of an fp32 (encoder_x3.h): round to nearest even, the remainders exact
 static inline uint16_t bf16_rne(float f) {
@@ -151,18 +123,17 @@ struct ForwardScratch {
 ForwardScratch carve_forward_scratch(void *base, int b, int n_points) {
     ForwardScratch s;
     const size_t tiles = encoder_tiles_max(n_points);     // (the forward picks its tile height per launch: encoder.hip)
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { char *q = p; p += rup(bytes, 256); return q; };
-    s.pmax = reinterpret_cast<float *>(take(sizeof(float) * b * tiles * 128));
-    s.parg = reinterpret_cast<int *>(take(sizeof(int) * b * tiles * 128));
-    s.pcnt = reinterpret_cast<int *>(take(sizeof(int) * b * tiles * 128));
-    s.z = reinterpret_cast<float *>(take(sizeof(float) * b * 128));
-    s.crit = reinterpret_cast<int *>(take(sizeof(int) * b * 128));
-    s.zcnt = reinterpret_cast<int *>(take(sizeof(int) * b * 128));
-    s.dense = reinterpret_cast<int *>(take(sizeof(int) * b));
-    s.d1 = reinterpret_cast<float *>(take(sizeof(float) * b * 256));
-    s.d2 = reinterpret_cast<float *>(take(sizeof(float) * b * 256));
-    s.bytes = (size_t)(p - static_cast<char *>(base));
+    Carver cv(base);
+    s.pmax = cv.take<float>(b * tiles * 128);
+    s.parg = cv.take<int>(b * tiles * 128);
+    s.pcnt = cv.take<int>(b * tiles * 128);
+    s.z = cv.take<float>(b * 128);
+    s.crit = cv.take<int>(b * 128);
+    s.zcnt = cv.take<int>(b * 128);
+    s.dense = cv.take<int>(b);
+    s.d1 = cv.take<float>(b * 256);
+    s.d2 = cv.take<float>(b * 256);
+    s.bytes = cv.bytes();
     return s;
 }
 
@@ -204,30 +175,30 @@ extern "C" int geoadv_ae_create(geoadv_ae **out, const geoadv_ae_weights *hw) {
     const int *C = hw->enc_dims;
     const int n3 = 3 * n, n3p32 = (int)rup(n3, 32), n3p8 = (int)rup(n3, 8);
     // arena layout (floats)
-    std::vector<float> host;
-    auto reserve = [&](size_t count) { size_t off = rup(host.size(), 64); host.resize(off + count, 0.f); return off; };
-    size_t o_w0 = reserve(3 * C[1]);
+    HostArena arena;
+    std::vector<float> &host = arena.host;
+    size_t o_w0 = arena.reserve(3 * C[1]);
     size_t o_fwd[ENC_L] = {0}, o_bwd[ENC_L] = {0}, o_bwd16[ENC_L] = {0}, o_scale[ENC_L], o_shift[ENC_L];
     for (int i = 1; i < ENC_L; ++i) {
-        o_fwd[i] = reserve((size_t)C[i] * C[i + 1]);
-        o_bwd[i] = reserve((size_t)C[i] * C[i + 1]);
-        o_bwd16[i] = reserve((size_t)C[i] * C[i + 1]);
+        o_fwd[i] = arena.reserve((size_t)C[i] * C[i + 1]);
+        o_bwd[i] = arena.reserve((size_t)C[i] * C[i + 1]);
+        o_bwd16[i] = arena.reserve((size_t)C[i] * C[i + 1]);
     }
-    for (int i = 0; i < ENC_L; ++i) { o_scale[i] = reserve(C[i + 1]); o_shift[i] = reserve(C[i + 1]); }
-    size_t o_v0 = reserve(128 * 256), o_c0 = reserve(256), o_v1 = reserve(256 * 256), o_c1 = reserve(256);
-    size_t o_v0t = reserve(256 * 128), o_v1t = reserve(256 * 256);
-    size_t o_d2f = reserve((size_t)256 * n3p32), o_d2b = reserve((size_t)n3p8 * 256), o_c2 = reserve(n3);
-    size_t o_x3 = reserve(X3_IMAGE_WORDS), o_x3c = reserve(X3_CONST_FLOATS);
-    size_t o_h2 = reserve(H2_IMAGE_WORDS), o_h2c = reserve(X3_CONST_FLOATS), o_flag = reserve(1);
+    for (int i = 0; i < ENC_L; ++i) { o_scale[i] = arena.reserve(C[i + 1]); o_shift[i] = arena.reserve(C[i + 1]); }
+    size_t o_v0 = arena.reserve(128 * 256), o_c0 = arena.reserve(256), o_v1 = arena.reserve(256 * 256), o_c1 = arena.reserve(256);
+    size_t o_v0t = arena.reserve(256 * 128), o_v1t = arena.reserve(256 * 256);
+    size_t o_d2f = arena.reserve((size_t)256 * n3p32), o_d2b = arena.reserve((size_t)n3p8 * 256), o_c2 = arena.reserve(n3);
+    size_t o_x3 = arena.reserve(X3_IMAGE_WORDS), o_x3c = arena.reserve(X3_CONST_FLOATS);
+    size_t o_h2 = arena.reserve(H2_IMAGE_WORDS), o_h2c = arena.reserve(X3_CONST_FLOATS), o_flag = arena.reserve(1);
 
     memcpy(&host[o_w0], hw->enc_w[0], sizeof(float) * 3 * C[1]);
     for (int i = 1; i < ENC_L; ++i) {
         const float *W = hw->enc_w[i];
         const int K = C[i], N = C[i + 1];
-        pack_fragments(host, o_fwd[i], K, N, K, N, [&](int k, int nn) { return W[(size_t)k * N + nn]; });
+        pack_fragments(&host[o_fwd[i]], K, N, K, N, [&](int k, int nn) { return W[(size_t)k * N + nn]; });
         // transposed product: B[k][nn] = W[nn][k], K' = N, N' = K
-        pack_fragments(host, o_bwd[i], N, K, N, (int)rup(K, 32), [&](int k, int nn) { return W[(size_t)nn * N + k]; });
-        pack_fragments16(host, o_bwd16[i], N, K, N, K, [&](int k, int nn) { return W[(size_t)nn * N + k]; });   // (widths are multiples of 64)
+        pack_fragments(&host[o_bwd[i]], N, K, N, (int)rup(K, 32), [&](int k, int nn) { return W[(size_t)nn * N + k]; });
+        pack_fragments16(&host[o_bwd16[i]], N, K, N, K, [&](int k, int nn) { return W[(size_t)nn * N + k]; });   // (widths are multiples of 64)
     }
     for (int i = 0; i < ENC_L; ++i)
         for (int c = 0; c < C[i + 1]; ++c) {
@@ -315,8 +286,8 @@ extern "C" int geoadv_ae_create(geoadv_ae **out, const geoadv_ae_weights *hw) {
         for (int t = 0; t < 256; ++t) host[o_v1t + (size_t)t * 256 + k] = hw->dec_w[1][(size_t)k * 256 + t];
     {
         const float *V2 = hw->dec_w[2];
-        pack_fragments(host, o_d2f, 256, n3, 256, n3p32, [&](int k, int nn) { return V2[(size_t)k * n3 + nn]; });
-        pack_fragments(host, o_d2b, n3, 256, n3p8, 256, [&](int k, int nn) { return V2[(size_t)nn * n3 + k]; });
+        pack_fragments(&host[o_d2f], 256, n3, 256, n3p32, [&](int k, int nn) { return V2[(size_t)k * n3 + nn]; });
+        pack_fragments(&host[o_d2b], n3, 256, n3p8, 256, [&](int k, int nn) { return V2[(size_t)nn * n3 + k]; });
     }
     memcpy(&host[o_c2], hw->dec_b[2], sizeof(float) * n3);
     {
@@ -326,18 +297,10 @@ extern "C" int geoadv_ae_create(geoadv_ae **out, const geoadv_ae_weights *hw) {
     }
 
     geoadv_ae *ae = new geoadv_ae();
-    ae->arena_bytes = sizeof(float) * host.size();
-    if (hipMalloc(&ae->arena, ae->arena_bytes) != hipSuccess) {
+    ae->arena_bytes = arena.bytes();
+    if (int rc = arena.upload("ae_create", &ae->arena)) {
         delete ae;
-        set_error("ae_create: hipMalloc of %zu bytes failed", sizeof(float) * host.size());
-        return GEOADV_ENOMEM;
-    }
-    hipError_t e = hipMemcpy(ae->arena, host.data(), ae->arena_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(ae->arena);
-        delete ae;
-        set_error("ae_create: upload failed: %s", hipGetErrorString(e));
-        return GEOADV_EHIP;
+        return rc;
     }
     const float *base = static_cast<const float *>(ae->arena);
     DeviceAE &d = ae->d;
@@ -432,8 +395,7 @@ extern "C" int geoadv_ae_forward(const geoadv_ae *ae, int b, const float *pc, fl
     GA_REQUIRE(pc && workspace, "ae_forward: null pointer");
     GA_REQUIRE(b <= 65535, "ae_forward: batch %d exceeds 65535", b);
     hipStream_t st = as_stream(stream);
-    void *aligned = reinterpret_cast<void *>(rup(reinterpret_cast<size_t>(workspace), 256));
-    ForwardScratch s = carve_forward_scratch(aligned, b, ae->d.n_points);
+    ForwardScratch s = carve_forward_scratch(workspace, b, ae->d.n_points);
     if (int rc = run_forward(ae->d, b, pc, nullptr, nullptr, s, recon, st)) return rc;
     if (latent) GA_HIP(hipMemcpyAsync(latent, s.z, sizeof(float) * (size_t)b * 128, hipMemcpyDeviceToDevice, st));
     return GEOADV_OK;
@@ -446,8 +408,7 @@ extern "C" int geoadv_ae_critical(const geoadv_ae *ae, int b, const float *pc, f
     GA_REQUIRE(pc && workspace, "ae_critical: null pointer");
     GA_REQUIRE(b <= 65535, "ae_critical: batch %d exceeds 65535", b);
     hipStream_t st = as_stream(stream);
-    void *aligned = reinterpret_cast<void *>(rup(reinterpret_cast<size_t>(workspace), 256));
-    ForwardScratch s = carve_forward_scratch(aligned, b, ae->d.n_points);
+    ForwardScratch s = carve_forward_scratch(workspace, b, ae->d.n_points);
     if (int rc = run_forward(ae->d, b, pc, nullptr, nullptr, s, nullptr, st)) return rc;
     if (latent) GA_HIP(hipMemcpyAsync(latent, s.z, sizeof(float) * (size_t)b * 128, hipMemcpyDeviceToDevice, st));
     if (arg_idx) GA_HIP(hipMemcpyAsync(arg_idx, s.crit, sizeof(int) * (size_t)b * 128, hipMemcpyDeviceToDevice, st));
@@ -460,8 +421,7 @@ extern "C" int geoadv_ae_decode(const geoadv_ae *ae, int b, const float *latent,
     GA_REQUIRE(latent && recon && workspace, "ae_decode: null pointer");
     GA_REQUIRE(b <= 65535, "ae_decode: batch %d exceeds 65535", b);
     hipStream_t st = as_stream(stream);
-    void *aligned = reinterpret_cast<void *>(rup(reinterpret_cast<size_t>(workspace), 256));
-    ForwardScratch s = carve_forward_scratch(aligned, b, ae->d.n_points);
+    ForwardScratch s = carve_forward_scratch(workspace, b, ae->d.n_points);
     if (int rc = launch_latent_fc(ae->d, b, latent, s.d2, st)) return rc;
     return launch_decoder_fc2(ae->d, b, s.d2, recon, st);
 }

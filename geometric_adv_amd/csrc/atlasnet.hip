@@ -3,8 +3,8 @@
 //
 // Four launches per forward (plus one memset of the pooled keys), per chunk of clouds:
 //   atlas_enc_kernel      conv1 3->64 (VALU), conv2 64->128, conv3 128->1024 (BN, NO ReLU) -> running max          (keys)
-//   atlas_fc_kernel       lin1 1024->1024, BN, ReLU                                          (batched over clouds: M = b)
-//   atlas_fc_kernel       lin2 1024->1024, BN, ReLU = the latent z; its epilogue forms c[b][p] = s1_p * z_b + t1_p
+//   fc_batched_kernel     lin1 1024->1024, BN, ReLU                                          (batched over clouds: M = b)
+//   fc_batched_kernel     lin2 1024->1024, BN, ReLU = the latent z; its epilogue forms c[b][p] = s1_p * z_b + t1_p
 //   atlas_decoder_kernel  per (primitive, 64-row tile of that primitive's (cloud, template point) rows):
 //                         relu(s1 * (W1 t) + c) generated as the A operand of conv2 1024->512, the hidden 512->512
 //                         layers in LDS, last_conv 512->3 on the VALU, written straight to recon[b][p * g2 + t][:]
@@ -20,27 +20,16 @@
 //
 // Every per-row / per-point computation is independent of the row's position in its tile and no sum is split by batch
 // size, so a cloud's outputs do not depend on b, on its position in the batch or on its point order.
-#include "mfma_tile.h"
+#include "point_tile.h"
+#include "host_util.h"
 #include <math.h>
 #include <string.h>
-#include <vector>
 
 namespace geoadv {
 
-constexpr int AT_ROWS = 64, AT_THREADS = 512, AT_LAT = 1024, AT_HID = 512;
-constexpr int AT_SA = 68, AT_SB = 132;            // encoder LDS row strides (64- and 128-wide activations)
-constexpr int AT_SH = AT_HID + 4;                 // decoder LDS row stride: 512-wide activations / 512-wide layer-1 chunks
+constexpr int AT_LAT = PT_POOL;                   // the latent: the pooled layer's width, and the FC layers'
 constexpr int AT_MAX_NB = 128, AT_MAX_L = 4;
-constexpr int AT_FC_CLOUDS = 8, AT_FC_THREADS = 256;
-constexpr size_t AT_DEC_LDS = sizeof(float) * (AT_ROWS * AT_SH + 2 * 3 * AT_ROWS + 3 * AT_ROWS) + sizeof(int) * 2 * AT_ROWS;
-
-__device__ __forceinline__ unsigned atlas_key(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float atlas_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+constexpr size_t AT_DEC_LDS = sizeof(float) * (PT_ROWS * PT_SH + 2 * 3 * PT_ROWS + 3 * PT_ROWS) + sizeof(int) * 2 * PT_ROWS;
 
 // ------------------------------------------------------------------------------------------------ encoder per-point chain
 struct AtlasEncArgs {
@@ -52,102 +41,21 @@ struct AtlasEncArgs {
     int n, slices;
 };
 
-__global__ __launch_bounds__(AT_THREADS, 2) void atlas_enc_kernel(AtlasEncArgs A) {
-    __shared__ __attribute__((aligned(16))) float bufA[AT_ROWS * AT_SA];
-    __shared__ __attribute__((aligned(16))) float bufB[AT_ROWS * AT_SB];
-    __shared__ float pts[AT_ROWS * 3];
+__global__ __launch_bounds__(PT_THREADS, 2) void atlas_enc_kernel(AtlasEncArgs A) {
+    __shared__ __attribute__((aligned(16))) float bufA[PT_ROWS * PT_SA];
+    __shared__ __attribute__((aligned(16))) float bufB[PT_ROWS * PT_SB];
+    __shared__ float pts[PT_ROWS * 3];
     const int tile = blockIdx.x, cloud = blockIdx.y, slice = blockIdx.z;
-    const int n = A.n, n0 = tile * AT_ROWS;
-    const int live = n - n0 < AT_ROWS ? n - n0 : AT_ROWS;
-    if (threadIdx.x < AT_ROWS * 3) {
-        const int r = threadIdx.x / 3;
-        pts[threadIdx.x] = r < live ? A.x[((size_t)cloud * n + n0) * 3 + threadIdx.x] : 0.f;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < AT_ROWS * 64; e += AT_THREADS) {      // conv1 3 -> 64 on the VALU
-        const int r = e >> 6, c = e & 63;
-        const float a = pts[3 * r] * A.w0[c] + pts[3 * r + 1] * A.w0[64 + c] + pts[3 * r + 2] * A.w0[128 + c];
-        bufA[r * AT_SA + c] = fmaxf(a * A.sc0[c] + A.sh0[c], 0.f);
-    }
-    __syncthreads();
-    layer_gemm<AT_ROWS, 128, 1>(bufA, AT_SA, A.l1, nullptr, [&](int row, int col, float a) {
-        bufB[row * AT_SB + col] = fmaxf(a * A.sc1[col] + A.sh1[col], 0.f);
+    const int n = A.n, n0 = tile * PT_ROWS;
+    const int live = n - n0 < PT_ROWS ? n - n0 : PT_ROWS;
+    load_points_conv1(A.x + ((size_t)cloud * n + n0) * 3, live, A.w0, A.sc0, A.sh0, pts, bufA);
+    layer_gemm<PT_ROWS, 128, 1>(bufA, PT_SA, A.l1, nullptr, [&](int row, int col, float a) {
+        bufB[row * PT_SB + col] = fmaxf(a * A.sc1[col] + A.sh1[col], 0.f);
     });
     __syncthreads();
-    // conv3: 32-column blocks of this workgroup's slice dealt to the 8 waves, both row blocks per wave; the max over the
-    // tile's live rows is taken in registers, then across tiles by the atomic on the keys
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int h = lane >> 5, i = lane & 31;
-    const int nblk = (AT_LAT / 32) / A.slices;
-    unsigned *keys = A.keys + (size_t)cloud * AT_LAT;
-    for (int j = wave; j < nblk; j += AT_THREADS / 64) {
-        const int cb = slice * nblk + j;
-        f32x16 acc[2] = {};
-        gemm_chain<2>(bufB, AT_SB, 0, A.l2, cb, 0, 128 / 8, acc);
-        const int col = cb * 32 + i;
-        const float sc = A.sc2[col], sh = A.sh2[col];
-        unsigned m = 0;                              // below the key of every float
-#pragma unroll
-        for (int rm = 0; rm < 2; ++rm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rm * 32 + acc_row(r, h);
-                const unsigned v = atlas_key(acc[rm][r] * sc + sh);
-                if (row < live) m = max(m, v);
-            }
-        m = max(m, (unsigned)__shfl_xor((int)m, 32));
-        if (h == 0 && m != 0) atomicMax(keys + col, m);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ FC head (M = b)
-// One workgroup: 64 output columns (a lane each) x 8 clouds, the 1024 inputs split in four quarters over the 4 waves and
-// summed in a fixed order -- the same for every cloud, whatever the batch size.
-struct AtlasFcArgs {
-    const unsigned *keys;                           // input as pooled keys [b][1024] (lin1), or
-    const float *in;                                // as floats [b][1024] (lin2)
-    const float *w, *sc, *sh;                       // [1024][1024] row-major, folded BN
-    float *out;                                     // [b][1024]
-    const float *s1, *t1;                           // non-null: c[b][p][:] = s1[p] * out + t1[p]   (decoder layer 1)
-    float *c;
-    int nb, b;
-};
-
-__global__ __launch_bounds__(AT_FC_THREADS) void atlas_fc_kernel(AtlasFcArgs F) {
-    __shared__ float xin[AT_FC_CLOUDS][AT_LAT];
-    __shared__ float part[4][AT_FC_CLOUDS][64];
-    const int c0 = blockIdx.y * AT_FC_CLOUDS, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = blockIdx.x * 64 + lane;
-    for (int e = threadIdx.x; e < AT_FC_CLOUDS * AT_LAT; e += AT_FC_THREADS) {
-        const int j = e >> 10, k = e & (AT_LAT - 1), c = c0 + j;
-        float v = 0.f;
-        if (c < F.b) v = F.keys ? atlas_unkey(F.keys[(size_t)c * AT_LAT + k]) : F.in[(size_t)c * AT_LAT + k];
-        xin[j][k] = v;
-    }
-    __syncthreads();
-    float acc[AT_FC_CLOUDS] = {};
-    const int k0 = wave * (AT_LAT / 4);
-    const float *w = F.w + (size_t)k0 * AT_LAT + col;
-#pragma unroll 8
-    for (int k = 0; k < AT_LAT / 4; ++k) {
-        const float wv = w[(size_t)k * AT_LAT];
-#pragma unroll
-        for (int j = 0; j < AT_FC_CLOUDS; ++j) acc[j] = fmaf(xin[j][k0 + k], wv, acc[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < AT_FC_CLOUDS; ++j) part[wave][j][lane] = acc[j];
-    __syncthreads();
-    for (int e = threadIdx.x; e < AT_FC_CLOUDS * 64; e += AT_FC_THREADS) {
-        const int j = e >> 6, l = e & 63, c = c0 + j;
-        if (c >= F.b) continue;
-        const int o = blockIdx.x * 64 + l;
-        const float s = (part[0][j][l] + part[1][j][l]) + (part[2][j][l] + part[3][j][l]);
-        const float y = fmaxf(s * F.sc[o] + F.sh[o], 0.f);
-        F.out[(size_t)c * AT_LAT + o] = y;
-        if (F.c)
-            for (int p = 0; p < F.nb; ++p)
-                F.c[((size_t)c * F.nb + p) * AT_LAT + o] = fmaf(F.s1[(size_t)p * AT_LAT + o], y, F.t1[(size_t)p * AT_LAT + o]);
-    }
+    // conv3, pooled on the keys of the unrectified values
+    pooled_wide_layer(bufB, PT_SB, A.l2, A.sc2, A.sh2, slice, A.slices, live, A.keys + (size_t)cloud * AT_LAT,
+                      [](float v) { return float_key(v); });
 }
 
 // ------------------------------------------------------------------------------------------------ decoder chain
@@ -162,28 +70,13 @@ struct AtlasDecArgs {
     int b, nb, g2, dim, num_layers, tiles, blocks;
 };
 
-// relu((acc * scale + shift)) of a wave's 2 x 2 (column block, row block) accumulators into the LDS activation tile
-__device__ __forceinline__ void atlas_dec_epilogue(float *H, const f32x16 (&acc)[2][2], int cb0, const float *sc,
-                                                   const float *sh) {
-    const int lane = threadIdx.x & 63, h = lane >> 5, i = lane & 31;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int col = (cb0 + q) * 32 + i;
-        const float s = sc[col], t = sh[col];
-#pragma unroll
-        for (int rm = 0; rm < 2; ++rm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) H[(rm * 32 + acc_row(r, h)) * AT_SH + col] = fmaxf(acc[q][rm][r] * s + t, 0.f);
-    }
-}
-
-__global__ __launch_bounds__(AT_THREADS) void atlas_decoder_kernel(AtlasDecArgs A) {
+__global__ __launch_bounds__(PT_THREADS) void atlas_decoder_kernel(AtlasDecArgs A) {
     extern __shared__ __attribute__((aligned(16))) float at_lds[];
-    float *H = at_lds;                                          // [64][AT_SH]
-    float *part = H + AT_ROWS * AT_SH;                          // [2][64 * 3] last_conv partial sums (two halves of K)
-    float *tp = part + 2 * 3 * AT_ROWS;                         // [64][3] template coordinates of the tile's rows
-    int *rcloud = reinterpret_cast<int *>(tp + 3 * AT_ROWS);    // [64] cloud of each row
-    int *rpoint = rcloud + AT_ROWS;                             // [64] template point of each row
+    float *H = at_lds;                                          // [64][PT_SH]
+    float *part = H + PT_ROWS * PT_SH;                          // [2][64 * 3] last_conv partial sums (two halves of K)
+    float *tp = part + 2 * 3 * PT_ROWS;                         // [64][3] template coordinates of the tile's rows
+    int *rcloud = reinterpret_cast<int *>(tp + 3 * PT_ROWS);    // [64] cloud of each row
+    int *rpoint = rcloud + PT_ROWS;                             // [64] template point of each row
     // XCD-aware order: the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, so workgroup g is given the
     // logical tile (g % 8) * (grid / 8) + g / 8 -- each XCD walks a contiguous range of tiles and keeps one primitive's
     // 4 MB of decoder weights in its L2 while it does.  (Placement only changes speed.)
@@ -191,9 +84,9 @@ __global__ __launch_bounds__(AT_THREADS) void atlas_decoder_kernel(AtlasDecArgs 
     const int logical = (g & 7) * per + (g >> 3);
     if (logical >= A.blocks) return;
     const int p = __builtin_amdgcn_readfirstlane(logical / A.tiles), tile = logical - p * A.tiles;
-    const int rows = A.b * A.g2, r0 = tile * AT_ROWS;
-    const int live = rows - r0 < AT_ROWS ? rows - r0 : AT_ROWS;
-    if (threadIdx.x < AT_ROWS) {
+    const int rows = A.b * A.g2, r0 = tile * PT_ROWS;
+    const int live = rows - r0 < PT_ROWS ? rows - r0 : PT_ROWS;
+    if (threadIdx.x < PT_ROWS) {
         const int r = r0 + (threadIdx.x < live ? threadIdx.x : 0);     // padding rows repeat the tile's first row
         const int c = r / A.g2, t = r - c * A.g2;
         rcloud[threadIdx.x] = c;
@@ -203,16 +96,16 @@ __global__ __launch_bounds__(AT_THREADS) void atlas_decoder_kernel(AtlasDecArgs 
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int cb0 = 2 * wave;                                   // the wave's two 32-column blocks of the 512 outputs
-    f32x16 acc[2][2];
     // conv2 1024 -> 512, its A operand generated in two 512-wide K chunks: relu(s1 * (W1 t) + c[cloud][p])
     {
-        const PackedLayer L{A.l2w + (size_t)p * AT_LAT * AT_HID, AT_LAT, AT_HID};
+        const PackedLayer L{A.l2w + (size_t)p * AT_LAT * PT_HID, AT_LAT, PT_HID};
         const float *w1 = A.w1s + (size_t)p * A.dim * AT_LAT;
+        f32x16 acc[2][2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) acc[q][0] = acc[q][1] = f32x16{};
         for (int ch = 0; ch < 2; ++ch) {
-            const int k0 = ch * AT_HID;
-            for (int e = threadIdx.x; e < AT_ROWS * (AT_HID / 4); e += AT_THREADS) {
+            const int k0 = ch * PT_HID;
+            for (int e = threadIdx.x; e < PT_ROWS * (PT_HID / 4); e += PT_THREADS) {
                 const int r = e >> 7, k = k0 + 4 * (e & 127);
                 const float4 cv = *reinterpret_cast<const float4 *>(A.c + ((size_t)rcloud[r] * A.nb + p) * AT_LAT + k);
                 float v[4] = {cv.x, cv.y, cv.z, cv.w};
@@ -222,54 +115,29 @@ __global__ __launch_bounds__(AT_THREADS) void atlas_decoder_kernel(AtlasDecArgs 
                     v[0] = fmaf(wv.x, td, v[0]); v[1] = fmaf(wv.y, td, v[1]);
                     v[2] = fmaf(wv.z, td, v[2]); v[3] = fmaf(wv.w, td, v[3]);
                 }
-                *reinterpret_cast<float4 *>(H + r * AT_SH + (k - k0)) =
+                *reinterpret_cast<float4 *>(H + r * PT_SH + (k - k0)) =
                     make_float4(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
             }
             __syncthreads();
             // gemm_chain reads A at in + row * s_in + 8 t for k-groups t in [64 ch, 64 ch + 64): the chunk starts at H
 #pragma unroll
-            for (int q = 0; q < 2; ++q) gemm_chain<2>(H - k0, AT_SH, 0, L, cb0 + q, k0 / 8, k0 / 8 + AT_HID / 8, acc[q]);
+            for (int q = 0; q < 2; ++q) gemm_chain<2>(H - k0, PT_SH, 0, L, cb0 + q, k0 / 8, k0 / 8 + PT_HID / 8, acc[q]);
             __syncthreads();
         }
-        atlas_dec_epilogue(H, acc, cb0, A.sc2 + (size_t)p * AT_HID, A.sh2 + (size_t)p * AT_HID);
+        dec512_epilogue<true>(H, acc, cb0, A.sc2 + (size_t)p * PT_HID, A.sh2 + (size_t)p * PT_HID);
         __syncthreads();
     }
-    // conv_list: 512 -> 512, in place in H (every wave has read all of H before the barrier that precedes the epilogue)
+    // conv_list: 512 -> 512, in place in H
     for (int l = 0; l < A.num_layers; ++l) {
         const size_t pl = (size_t)p * A.num_layers + l;
-        const PackedLayer L{A.lhw + pl * AT_HID * AT_HID, AT_HID, AT_HID};
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            acc[q][0] = acc[q][1] = f32x16{};
-            gemm_chain<2>(H, AT_SH, 0, L, cb0 + q, 0, AT_HID / 8, acc[q]);
-        }
-        __syncthreads();
-        atlas_dec_epilogue(H, acc, cb0, A.sch + pl * AT_HID, A.shh + pl * AT_HID);
-        __syncthreads();
+        dec512_hidden<true>(H, PackedLayer{A.lhw + pl * PT_HID * PT_HID, PT_HID, PT_HID}, A.sch + pl * PT_HID, A.shh + pl * PT_HID);
     }
-    // last_conv 512 -> 3 on the VALU: 192 (row, coordinate) outputs x two halves of K
-    {
-        const float *wl = A.wl + (size_t)p * AT_HID * 3;
-        if (threadIdx.x < 2 * 3 * AT_ROWS) {
-            const int half = threadIdx.x / (3 * AT_ROWS), o = threadIdx.x - half * 3 * AT_ROWS;
-            const int r = o / 3, d = o - 3 * r;
-            const float *hr = H + r * AT_SH + half * (AT_HID / 2);
-            const float *wk = wl + half * (AT_HID / 2) * 3 + d;
-            float a = 0.f;
-#pragma unroll 8
-            for (int k = 0; k < AT_HID / 2; ++k) a = fmaf(hr[k], wk[3 * k], a);
-            part[threadIdx.x] = a;
-        }
-        __syncthreads();
-        if (threadIdx.x < 3 * AT_ROWS) {
-            const int r = threadIdx.x / 3, d = threadIdx.x - 3 * r;
-            if (r < live) {
-                const float y = (part[threadIdx.x] + part[threadIdx.x + 3 * AT_ROWS]) + A.bl[p * 3 + d];
-                const size_t P = (size_t)A.nb * A.g2;
-                A.recon[((size_t)rcloud[r] * P + (size_t)p * A.g2 + rpoint[r]) * 3 + d] = y;
-            }
-        }
-    }
+    // last_conv 512 -> 3, written straight to the reconstruction
+    dec512_last(H, A.wl + (size_t)p * PT_HID * 3, A.bl + p * 3, part, [&](int o, float y) {
+        const int r = o / 3, d = o - 3 * r;
+        const size_t P = (size_t)A.nb * A.g2;
+        if (r < live) A.recon[((size_t)rcloud[r] * P + (size_t)p * A.g2 + rpoint[r]) * 3 + d] = y;
+    });
 }
 
 }  // namespace geoadv
@@ -286,35 +154,6 @@ struct geoadv_atlas {
     const float *l2w, *sc2, *sh2, *lhw, *sch, *shh, *wl, *bl;
 };
 
-namespace {
-inline size_t at_rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// W [K][N] row-major -> 32x32x2 fragments (ae.h): dst[((cb * K/8 + t) * 64 + lane) * 4 + u] = W[8t + 4(lane>>5) + u][32cb + (lane&31)]
-void at_pack(float *dst, const float *W, int K, int N) {
-    const int kg = K / 8;
-    for (int cb = 0; cb < N / 32; ++cb)
-        for (int t = 0; t < kg; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int u = 0; u < 4; ++u) {
-                    const int k = 8 * t + 4 * (lane >> 5) + u, n = 32 * cb + (lane & 31);
-                    dst[(((size_t)cb * kg + t) * 64 + lane) * 4 + u] = W[(size_t)k * N + n];
-                }
-}
-// folded batch norm of N channels: scale, shift (with the layer's bias); no BN: scale 1, shift b
-void at_fold(float *sc, float *sh, int N, const float *b, const float *g, const float *be, const float *m, const float *v) {
-    for (int c = 0; c < N; ++c) {
-        if (g) {
-            const float inv = g[c] * (1.0f / sqrtf(v[c] + 1e-5f));
-            sc[c] = inv;
-            sh[c] = (b[c] - m[c]) * inv + be[c];
-        } else {
-            sc[c] = 1.f;
-            sh[c] = b[c];
-        }
-    }
-}
-}  // namespace
-
 extern "C" int geoadv_atlas_create(geoadv_atlas **out, const geoadv_atlas_config *cfg, const geoadv_atlas_weights *hw,
                                    const float *host_template) {
     GA_REQUIRE(out && cfg && hw && host_template, "atlas_create: null argument");
@@ -323,7 +162,7 @@ extern "C" int geoadv_atlas_create(geoadv_atlas **out, const geoadv_atlas_config
     GA_REQUIRE(G2 >= 1 && G2 <= 65536, "atlas_create: points_per_primitive %d out of range [1, 65536]", G2);
     GA_REQUIRE(DIM == 2 || DIM == 3, "atlas_create: dim_template %d is not 2 or 3", DIM);
     GA_REQUIRE(cfg->bottleneck_size == AT_LAT, "atlas_create: bottleneck_size %d is not %d", cfg->bottleneck_size, AT_LAT);
-    GA_REQUIRE(cfg->hidden_neurons == AT_HID, "atlas_create: hidden_neurons %d is not %d", cfg->hidden_neurons, AT_HID);
+    GA_REQUIRE(cfg->hidden_neurons == PT_HID, "atlas_create: hidden_neurons %d is not %d", cfg->hidden_neurons, PT_HID);
     GA_REQUIRE(NL >= 0 && NL <= AT_MAX_L, "atlas_create: num_layers %d out of range [0, %d]", NL, AT_MAX_L);
     GA_REQUIRE(cfg->activation == 0, "atlas_create: activation %d is not 0 (relu)", cfg->activation);
     GA_REQUIRE(cfg->decoder_bn == 0 || cfg->decoder_bn == 1, "atlas_create: decoder_bn %d is not 0 or 1", cfg->decoder_bn);
@@ -342,68 +181,59 @@ extern "C" int geoadv_atlas_create(geoadv_atlas **out, const geoadv_atlas_config
                        "atlas_create: decoder layer %d has no batch norm: its batch-norm pointers must be NULL", l);
     }
     static const int eout[5] = {64, 128, AT_LAT, AT_LAT, AT_LAT};
-    std::vector<float> host;
-    auto reserve = [&](size_t count) { size_t off = at_rup(host.size(), 64); host.resize(off + count, 0.f); return off; };
+    HostArena arena;
+    std::vector<float> &host = arena.host;
     size_t o_w0, o_esc[5], o_esh[5], o_pk1, o_pk2, o_lin[2];
-    o_w0 = reserve(3 * 64);
+    o_w0 = arena.reserve(3 * 64);
     memcpy(&host[o_w0], hw->enc_w[0], sizeof(float) * 3 * 64);
-    o_pk1 = reserve(64 * 128);
-    at_pack(&host[o_pk1], hw->enc_w[1], 64, 128);
-    o_pk2 = reserve((size_t)128 * AT_LAT);
-    at_pack(&host[o_pk2], hw->enc_w[2], 128, AT_LAT);
+    o_pk1 = arena.reserve(64 * 128);
+    pack_fragments(&host[o_pk1], hw->enc_w[1], 64, 128);
+    o_pk2 = arena.reserve((size_t)128 * AT_LAT);
+    pack_fragments(&host[o_pk2], hw->enc_w[2], 128, AT_LAT);
     for (int q = 0; q < 2; ++q) {
-        o_lin[q] = reserve((size_t)AT_LAT * AT_LAT);
+        o_lin[q] = arena.reserve((size_t)AT_LAT * AT_LAT);
         memcpy(&host[o_lin[q]], hw->enc_w[3 + q], sizeof(float) * AT_LAT * AT_LAT);
     }
     for (int l = 0; l < 5; ++l) {
-        o_esc[l] = reserve(eout[l]);
-        o_esh[l] = reserve(eout[l]);
-        at_fold(&host[o_esc[l]], &host[o_esh[l]], eout[l], hw->enc_b[l], hw->enc_gamma[l], hw->enc_beta[l], hw->enc_mean[l],
+        o_esc[l] = arena.reserve(eout[l]);
+        o_esh[l] = arena.reserve(eout[l]);
+        fold_bn_torch(&host[o_esc[l]], &host[o_esh[l]], eout[l], hw->enc_b[l], hw->enc_gamma[l], hw->enc_beta[l], hw->enc_mean[l],
                 hw->enc_var[l]);
     }
     const bool bn = cfg->decoder_bn != 0;
     auto dec_bn = [&](int l, int p, int N, float *sc, float *sh) {
         const size_t o = (size_t)p * N;
-        at_fold(sc, sh, N, hw->dec_b[l] + o, bn ? hw->dec_gamma[l] + o : nullptr, bn ? hw->dec_beta[l] + o : nullptr,
+        fold_bn_torch(sc, sh, N, hw->dec_b[l] + o, bn ? hw->dec_gamma[l] + o : nullptr, bn ? hw->dec_beta[l] + o : nullptr,
                 bn ? hw->dec_mean[l] + o : nullptr, bn ? hw->dec_var[l] + o : nullptr);
     };
-    const size_t o_tmpl = reserve((size_t)NB * G2 * DIM);
+    const size_t o_tmpl = arena.reserve((size_t)NB * G2 * DIM);
     memcpy(&host[o_tmpl], host_template, sizeof(float) * NB * G2 * DIM);
-    const size_t o_w1s = reserve((size_t)NB * DIM * AT_LAT), o_s1 = reserve((size_t)NB * AT_LAT), o_t1 = reserve((size_t)NB * AT_LAT);
-    const size_t o_l2w = reserve((size_t)NB * AT_LAT * AT_HID), o_sc2 = reserve((size_t)NB * AT_HID), o_sh2 = reserve((size_t)NB * AT_HID);
+    const size_t o_w1s = arena.reserve((size_t)NB * DIM * AT_LAT), o_s1 = arena.reserve((size_t)NB * AT_LAT), o_t1 = arena.reserve((size_t)NB * AT_LAT);
+    const size_t o_l2w = arena.reserve((size_t)NB * AT_LAT * PT_HID), o_sc2 = arena.reserve((size_t)NB * PT_HID), o_sh2 = arena.reserve((size_t)NB * PT_HID);
     const size_t nh = (size_t)NB * NL;
-    const size_t o_lhw = reserve(nh * AT_HID * AT_HID + 1), o_sch = reserve(nh * AT_HID + 1), o_shh = reserve(nh * AT_HID + 1);
-    const size_t o_wl = reserve((size_t)NB * AT_HID * 3), o_bl = reserve((size_t)NB * 3);
+    const size_t o_lhw = arena.reserve(nh * PT_HID * PT_HID + 1), o_sch = arena.reserve(nh * PT_HID + 1), o_shh = arena.reserve(nh * PT_HID + 1);
+    const size_t o_wl = arena.reserve((size_t)NB * PT_HID * 3), o_bl = arena.reserve((size_t)NB * 3);
     for (int p = 0; p < NB; ++p) {
         float *s1 = &host[o_s1 + (size_t)p * AT_LAT], *t1 = &host[o_t1 + (size_t)p * AT_LAT];
         dec_bn(0, p, AT_LAT, s1, t1);
         const float *w1 = hw->dec_w[0] + (size_t)p * DIM * AT_LAT;
         for (int d = 0; d < DIM; ++d)
             for (int k = 0; k < AT_LAT; ++k) host[o_w1s + ((size_t)p * DIM + d) * AT_LAT + k] = s1[k] * w1[(size_t)d * AT_LAT + k];
-        at_pack(&host[o_l2w + (size_t)p * AT_LAT * AT_HID], hw->dec_w[1] + (size_t)p * AT_LAT * AT_HID, AT_LAT, AT_HID);
-        dec_bn(1, p, AT_HID, &host[o_sc2 + (size_t)p * AT_HID], &host[o_sh2 + (size_t)p * AT_HID]);
+        pack_fragments(&host[o_l2w + (size_t)p * AT_LAT * PT_HID], hw->dec_w[1] + (size_t)p * AT_LAT * PT_HID, AT_LAT, PT_HID);
+        dec_bn(1, p, PT_HID, &host[o_sc2 + (size_t)p * PT_HID], &host[o_sh2 + (size_t)p * PT_HID]);
         for (int l = 0; l < NL; ++l) {
             const size_t pl = (size_t)p * NL + l;
-            at_pack(&host[o_lhw + pl * AT_HID * AT_HID], hw->dec_w[2 + l] + (size_t)p * AT_HID * AT_HID, AT_HID, AT_HID);
-            dec_bn(2 + l, p, AT_HID, &host[o_sch + pl * AT_HID], &host[o_shh + pl * AT_HID]);
+            pack_fragments(&host[o_lhw + pl * PT_HID * PT_HID], hw->dec_w[2 + l] + (size_t)p * PT_HID * PT_HID, PT_HID, PT_HID);
+            dec_bn(2 + l, p, PT_HID, &host[o_sch + pl * PT_HID], &host[o_shh + pl * PT_HID]);
         }
-        memcpy(&host[o_wl + (size_t)p * AT_HID * 3], hw->dec_w[NDL - 1] + (size_t)p * AT_HID * 3, sizeof(float) * AT_HID * 3);
+        memcpy(&host[o_wl + (size_t)p * PT_HID * 3], hw->dec_w[NDL - 1] + (size_t)p * PT_HID * 3, sizeof(float) * PT_HID * 3);
         memcpy(&host[o_bl + (size_t)p * 3], hw->dec_b[NDL - 1] + (size_t)p * 3, sizeof(float) * 3);
     }
     geoadv_atlas *m = new geoadv_atlas();
     m->cfg = *cfg;
-    const size_t bytes = sizeof(float) * host.size();
-    if (hipMalloc(&m->arena, bytes) != hipSuccess) {
+    if (int rc = arena.upload("atlas_create", &m->arena)) {
         delete m;
-        set_error("atlas_create: hipMalloc of %zu bytes failed", bytes);
-        return GEOADV_ENOMEM;
-    }
-    const hipError_t e = hipMemcpy(m->arena, host.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(m->arena);
-        delete m;
-        set_error("atlas_create: upload failed: %s", hipGetErrorString(e));
-        return GEOADV_EHIP;
+        return rc;
     }
     const float *base = static_cast<const float *>(m->arena);
     m->e_w0 = base + o_w0;
@@ -431,15 +261,14 @@ struct AtlasScratch {
     float *c;                // [bc][nb][1024]
     size_t bytes;
 };
-AtlasScratch carve_atlas(void *base, int bc, int nb) {
+AtlasScratch carve_atlas(void *workspace, int bc, int nb) {
     AtlasScratch s;
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { char *q = p; p += at_rup(bytes, 256); return q; };
-    s.keys = reinterpret_cast<unsigned *>(take(sizeof(unsigned) * (size_t)bc * AT_LAT));
-    s.h1 = reinterpret_cast<float *>(take(sizeof(float) * (size_t)bc * AT_LAT));
-    s.z = reinterpret_cast<float *>(take(sizeof(float) * (size_t)bc * AT_LAT));
-    s.c = reinterpret_cast<float *>(take(sizeof(float) * (size_t)bc * nb * AT_LAT));
-    s.bytes = (size_t)(p - static_cast<char *>(base));
+    Carver cv(workspace);
+    s.keys = cv.take<unsigned>((size_t)bc * AT_LAT);
+    s.h1 = cv.take<float>((size_t)bc * AT_LAT);
+    s.z = cv.take<float>((size_t)bc * AT_LAT);
+    s.c = cv.take<float>((size_t)bc * nb * AT_LAT);
+    s.bytes = cv.bytes();
     return s;
 }
 // clouds per chunk: bounds the per-(cloud, primitive) layer-1 shifts at 8192 x 4 KiB and the grids' y extents
@@ -471,12 +300,10 @@ extern "C" int geoadv_atlas_forward(const geoadv_atlas *atlas, int b, int n, con
     const geoadv_atlas_config &cf = atlas->cfg;
     const int NB = cf.nb_primitives, G2 = cf.points_per_primitive;
     const size_t P = (size_t)NB * G2;
-    const int tiles = cdiv(n, AT_ROWS);
-    void *aligned = reinterpret_cast<void *>(at_rup(reinterpret_cast<size_t>(workspace), 256));
+    const int tiles = cdiv(n, PT_ROWS);
     const int bc = atlas_chunk(b, NB);
-    const AtlasScratch s = carve_atlas(aligned, bc, NB);
-    int slices = 1;    // small batches split conv3's 1024 columns over up to 4 workgroups per tile (as classifier.hip)
-    while (slices < 4 && (size_t)tiles * b * slices < 2 * kCUs) slices *= 2;
+    const AtlasScratch s = carve_atlas(workspace, bc, NB);
+    const int slices = pooled_slices(tiles, b);
 
     AtlasEncArgs ea{};
     ea.w0 = atlas->e_w0; ea.sc0 = atlas->e_sc[0]; ea.sh0 = atlas->e_sh[0];
@@ -487,18 +314,18 @@ extern "C" int geoadv_atlas_forward(const geoadv_atlas *atlas, int b, int n, con
         const int nbc = std::min(bc, b - c0);
         GA_HIP(hipMemsetAsync(s.keys, 0, sizeof(unsigned) * (size_t)nbc * AT_LAT, st));
         ea.x = pc + (size_t)c0 * n * 3;
-        hipLaunchKernelGGL(atlas_enc_kernel, dim3(tiles, nbc, slices), dim3(AT_THREADS), 0, st, ea);
+        hipLaunchKernelGGL(atlas_enc_kernel, dim3(tiles, nbc, slices), dim3(PT_THREADS), 0, st, ea);
         GA_LAUNCH_CHECK();
-        const dim3 fg(AT_LAT / 64, cdiv(nbc, AT_FC_CLOUDS));
-        AtlasFcArgs fa{};
+        const dim3 fg(AT_LAT / 64, cdiv(nbc, FC_CLOUDS));
+        FcBatchedArgs fa{};
         fa.keys = s.keys; fa.w = atlas->e_lin[0]; fa.sc = atlas->e_sc[3]; fa.sh = atlas->e_sh[3];
-        fa.out = s.h1; fa.nb = NB; fa.b = nbc;
-        hipLaunchKernelGGL(atlas_fc_kernel, fg, dim3(AT_FC_THREADS), 0, st, fa);
+        fa.out = s.h1; fa.N = AT_LAT; fa.b = nbc; fa.relu = 1; fa.nb = NB;
+        hipLaunchKernelGGL(fc_batched_kernel<AT_LAT>, fg, dim3(FC_THREADS), 0, st, fa);
         GA_LAUNCH_CHECK();
         float *z = latent ? latent + (size_t)c0 * AT_LAT : s.z;
         fa.keys = nullptr; fa.in = s.h1; fa.w = atlas->e_lin[1]; fa.sc = atlas->e_sc[4]; fa.sh = atlas->e_sh[4];
         fa.out = z; fa.s1 = atlas->s1; fa.t1 = atlas->t1; fa.c = s.c;
-        hipLaunchKernelGGL(atlas_fc_kernel, fg, dim3(AT_FC_THREADS), 0, st, fa);
+        hipLaunchKernelGGL(fc_batched_kernel<AT_LAT>, fg, dim3(FC_THREADS), 0, st, fa);
         GA_LAUNCH_CHECK();
         AtlasDecArgs da{};
         da.tmpl = atlas->tmpl; da.w1s = atlas->w1s; da.c = s.c;
@@ -507,10 +334,10 @@ extern "C" int geoadv_atlas_forward(const geoadv_atlas *atlas, int b, int n, con
         da.wl = atlas->wl; da.bl = atlas->bl;
         da.recon = recon + (size_t)c0 * P * 3;
         da.b = nbc; da.nb = NB; da.g2 = G2; da.dim = cf.dim_template; da.num_layers = cf.num_layers;
-        da.tiles = cdiv(nbc * G2, AT_ROWS);
+        da.tiles = cdiv(nbc * G2, PT_ROWS);
         da.blocks = da.tiles * NB;
         const int grid = cdiv(da.blocks, 8) * 8;
-        hipLaunchKernelGGL(atlas_decoder_kernel, dim3(grid), dim3(AT_THREADS), AT_DEC_LDS, st, da);
+        hipLaunchKernelGGL(atlas_decoder_kernel, dim3(grid), dim3(PT_THREADS), AT_DEC_LDS, st, da);
         GA_LAUNCH_CHECK();
     }
     return GEOADV_OK;

@@ -275,8 +275,6 @@ struct geoadv_attack {
 
 namespace {
 
-inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 int prof_flush(geoadv_attack *at) {
     if (at->marks.empty()) return GEOADV_OK;
     GA_HIP(hipStreamSynchronize(at->prof_stream));

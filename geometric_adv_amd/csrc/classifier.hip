@@ -14,23 +14,21 @@
 //
 // The chain kernel: a workgroup owns a tile of 64 points of one cloud (and a slice of the 1024 pooled columns: small batches
 // split the columns over up to four workgroups, each recomputing the cheap narrow prefix).  The narrow layers run from LDS
-// through layer_gemm (mfma_tile.h, v_mfma_f32_32x32x2_f32); the 1024-wide layer streams 32-column blocks through gemm_chain
-// and folds each block's 64 rows into a per-column max in registers -- the [n x 1024] activation never leaves the CU.  The
-// cross-tile max is an integer atomicMax on the float bits of post-ReLU values (>= +0; a NaN becomes +0 in the ReLU), which
+// through layer_gemm (mfma_tile.h, v_mfma_f32_32x32x2_f32); the 1024-wide layer (point_tile.h: pooled_wide_layer, shared with
+// AtlasNet and FoldingNet) streams 32-column blocks through gemm_chain and folds each block's 64 rows into a per-column max in registers -- the [n x 1024] activation never leaves the CU.  The
+// cross-tile max is an unsigned atomicMax on the float bits of post-ReLU values (>= +0; a NaN becomes +0 in the ReLU), which
 // is exact and independent of the order of tiles; rows past n are excluded before the max.  Per-point work does not depend
 // on the point's position, so a cloud's logits do not depend on its point order, padding or batch neighbours.
 //
 // Batch norm is folded at create time (eps 1e-3, tf_util.batch_norm_template): y = relu((x @ W) * scale + shift),
 // scale = gamma * rsqrt(var + eps), shift = b * scale + (beta - mean * scale).
-#include "mfma_tile.h"
+#include "point_tile.h"
+#include "host_util.h"
 #include <math.h>
 #include <string.h>
-#include <vector>
 
 namespace geoadv {
 
-constexpr int CLS_ROWS = 64, CLS_THREADS = 512, CLS_POOL = 1024;
-constexpr int CLS_SA = 68, CLS_SB = 132;          // LDS row strides: buffer A holds 64-wide activations, B up to 128-wide
 constexpr int CLS_MAX_GRID_Y = 65535;
 
 struct ClsLayerDev {                                // one per-point layer
@@ -44,7 +42,7 @@ struct ClsChainArgs {
     const float *sc0, *sh0;
     ClsLayerDev mid[3];                             // narrow MFMA layers
     ClsLayerDev wide;                               // 128 -> 1024, pooled
-    int *pooled;                                    // [b][1024] float bits, zeroed before the launch
+    unsigned *pooled;                               // [b][1024] float bits, zeroed before the launch
     int n, slices;
 };
 
@@ -53,71 +51,39 @@ template <int NOUT>
 __device__ __forceinline__ void cls_mid(const float *in, int s_in, const ClsLayerDev &d, int cloud, float *out, int s_out) {
     PackedLayer L = d.L;
     L.w += (size_t)cloud * d.cloud_stride;
-    layer_gemm<CLS_ROWS, NOUT, 1>(in, s_in, L, nullptr, [&](int row, int col, float a) {
+    layer_gemm<PT_ROWS, NOUT, 1>(in, s_in, L, nullptr, [&](int row, int col, float a) {
         out[row * s_out + col] = fmaxf(a * d.scale[col] + d.shift[col], 0.f);
     });
 }
 
 template <int NMID>
-__global__ __launch_bounds__(CLS_THREADS, 2) void cls_chain_kernel(ClsChainArgs A, int cloud0) {
-    __shared__ __attribute__((aligned(16))) float bufA[CLS_ROWS * CLS_SA];
-    __shared__ __attribute__((aligned(16))) float bufB[CLS_ROWS * CLS_SB];
-    __shared__ float pts[CLS_ROWS * 3];
+__global__ __launch_bounds__(PT_THREADS, 2) void cls_chain_kernel(ClsChainArgs A, int cloud0) {
+    __shared__ __attribute__((aligned(16))) float bufA[PT_ROWS * PT_SA];     // 64-wide activations
+    __shared__ __attribute__((aligned(16))) float bufB[PT_ROWS * PT_SB];     // up to 128-wide
+    __shared__ float pts[PT_ROWS * 3];
     const int tile = blockIdx.x, cloud = cloud0 + blockIdx.y, slice = blockIdx.z;
-    const int n = A.n, n0 = tile * CLS_ROWS;
-    const int live = n - n0 < CLS_ROWS ? n - n0 : CLS_ROWS;
-    if (threadIdx.x < CLS_ROWS * 3) {
-        const int r = threadIdx.x / 3;
-        pts[threadIdx.x] = r < live ? A.x[((size_t)cloud * n + n0) * 3 + threadIdx.x] : 0.f;
-    }
-    __syncthreads();
-    {   // layer 0: 3 -> 64 on the VALU
-        const float *w0 = A.w0 + (size_t)cloud * A.w0_cloud_stride;
-        for (int e = threadIdx.x; e < CLS_ROWS * 64; e += CLS_THREADS) {
-            const int r = e >> 6, c = e & 63;
-            const float a = pts[3 * r] * w0[c] + pts[3 * r + 1] * w0[64 + c] + pts[3 * r + 2] * w0[128 + c];
-            bufA[r * CLS_SA + c] = fmaxf(a * A.sc0[c] + A.sh0[c], 0.f);
-        }
-    }
-    __syncthreads();
+    const int n = A.n, n0 = tile * PT_ROWS;
+    const int live = n - n0 < PT_ROWS ? n - n0 : PT_ROWS;
+    load_points_conv1(A.x + ((size_t)cloud * n + n0) * 3, live, A.w0 + (size_t)cloud * A.w0_cloud_stride, A.sc0, A.sh0, pts, bufA);
     if (NMID == 1) {
-        cls_mid<128>(bufA, CLS_SA, A.mid[0], cloud, bufB, CLS_SB);
+        cls_mid<128>(bufA, PT_SA, A.mid[0], cloud, bufB, PT_SB);
     } else {
-        cls_mid<64>(bufA, CLS_SA, A.mid[0], cloud, bufB, CLS_SB);
+        cls_mid<64>(bufA, PT_SA, A.mid[0], cloud, bufB, PT_SB);
         __syncthreads();
-        cls_mid<64>(bufB, CLS_SB, A.mid[1], cloud, bufA, CLS_SA);
+        cls_mid<64>(bufB, PT_SB, A.mid[1], cloud, bufA, PT_SA);
         __syncthreads();
-        cls_mid<128>(bufA, CLS_SA, A.mid[2], cloud, bufB, CLS_SB);
+        cls_mid<128>(bufA, PT_SA, A.mid[2], cloud, bufB, PT_SB);
     }
     __syncthreads();
-    // the wide layer: 32-column blocks of this workgroup's slice dealt to the 8 waves, both row blocks per wave (RM = 2)
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int h = lane >> 5, i = lane & 31;
-    const int nblk = (CLS_POOL / 32) / A.slices;
-    int *pooled = A.pooled + (size_t)cloud * CLS_POOL;
-    for (int j = wave; j < nblk; j += CLS_THREADS / 64) {
-        const int cb = slice * nblk + j;
-        f32x16 acc[2] = {};
-        gemm_chain<2>(bufB, CLS_SB, 0, A.wide.L, cb, 0, 128 / 8, acc);
-        const int col = cb * 32 + i;
-        const float sc = A.wide.scale[col], sh = A.wide.shift[col];
-        int m = 0;                                   // +0.0f: the ReLU's floor, and the identity of the max
-#pragma unroll
-        for (int rm = 0; rm < 2; ++rm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rm * 32 + acc_row(r, h);
-                const int v = __float_as_int(fmaxf(acc[rm][r] * sc + sh, 0.f));
-                if (row < live) m = max(m, v);
-            }
-        m = max(m, __shfl_xor(m, 32));
-        if (h == 0 && m > 0) atomicMax(pooled + col, m);
-    }
+    // the wide layer, pooled on the float bits of the post-ReLU values: non-negative floats order like their bits, +0 (the
+    // ReLU's floor, and what a NaN becomes) is the identity of the max and is never sent to the atomic
+    pooled_wide_layer(bufB, PT_SB, A.wide.L, A.wide.scale, A.wide.shift, slice, A.slices, live, A.pooled + (size_t)cloud * PT_POOL,
+                      [](float v) { return __float_as_uint(fmaxf(v, 0.f)); });
 }
 
 enum { CLS_HEAD_T1 = 0, CLS_HEAD_T2 = 1, CLS_HEAD_CLS = 2 };
 struct ClsHeadArgs {
-    const int *pooled;                              // [b][1024] float bits
+    const unsigned *pooled;                         // [b][1024] float bits
     const float *w1, *sc1, *sh1;                    // 1024 -> 512
     const float *w2, *sc2, *sh2;                    // 512 -> 256
     const float *w3, *b3;                           // 256 -> M, linear (b3 carries the identity for the transforms)
@@ -129,17 +95,17 @@ struct ClsHeadArgs {
 };
 
 template <int MODE>
-__global__ __launch_bounds__(CLS_THREADS) void cls_head_kernel(ClsHeadArgs H, int cloud0) {
-    __shared__ float in[CLS_POOL], h1[512], part[512], h2[256];
+__global__ __launch_bounds__(PT_THREADS) void cls_head_kernel(ClsHeadArgs H, int cloud0) {
+    __shared__ float in[PT_POOL], h1[512], part[512], h2[256];
     __shared__ float tv[MODE == CLS_HEAD_T1 ? 16 : 4096];
     const int c = cloud0 + blockIdx.x, t = threadIdx.x;
-    for (int k = t; k < CLS_POOL; k += CLS_THREADS) in[k] = __int_as_float(H.pooled[(size_t)c * CLS_POOL + k]);
+    for (int k = t; k < PT_POOL; k += PT_THREADS) in[k] = __uint_as_float(H.pooled[(size_t)c * PT_POOL + k]);
     __syncthreads();
     {
         float a = 0.f;
         const float *w = H.w1 + t;
 #pragma unroll 8
-        for (int k = 0; k < CLS_POOL; ++k) a = fmaf(in[k], w[(size_t)k * 512], a);
+        for (int k = 0; k < PT_POOL; ++k) a = fmaf(in[k], w[(size_t)k * 512], a);
         h1[t] = fmaxf(a * H.sc1[t] + H.sh1[t], 0.f);
     }
     __syncthreads();
@@ -155,7 +121,7 @@ __global__ __launch_bounds__(CLS_THREADS) void cls_head_kernel(ClsHeadArgs H, in
     if (t < 256) h2[t] = fmaxf((part[t] + part[t + 256]) * H.sc2[t] + H.sh2[t], 0.f);
     __syncthreads();
     const int M = H.M;
-    for (int o = t; o < M; o += CLS_THREADS) {
+    for (int o = t; o < M; o += PT_THREADS) {
         float a = 0.f;
         const float *w = H.w3 + o;
 #pragma unroll 8
@@ -178,7 +144,7 @@ __global__ __launch_bounds__(CLS_THREADS) void cls_head_kernel(ClsHeadArgs H, in
         }
     } else if (MODE == CLS_HEAD_T2) {
         // W3'[k][n] = sum_j T2[k][j] Wc3[j][n] (pointnet_cls.py:51), written in the 32x32x2 fragment layout (ae.h, K = N = 64)
-        for (int e = t; e < 4096; e += CLS_THREADS) {
+        for (int e = t; e < 4096; e += PT_THREADS) {
             const int k = e >> 6, nn = e & 63;
             float a = 0.f;
             for (int j = 0; j < 64; ++j) a = fmaf(tv[64 * k + j], H.fold_w[64 * j + nn], a);
@@ -217,8 +183,6 @@ struct geoadv_cls {
     const float *bias[GEOADV_CLS_LAYERS];     // linear layers: b (+ the identity for the two transforms)
 };
 
-static inline size_t cls_rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw) {
     GA_REQUIRE(out && hw, "cls_create: null argument");
     const int C = hw->num_classes;
@@ -233,37 +197,29 @@ extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw)
     }
     int outw[GEOADV_CLS_LAYERS];
     for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) outw[l] = l == F3 ? C : kOut[l];
-    std::vector<float> host;
-    auto reserve = [&](size_t count) { size_t off = cls_rup(host.size(), 64); host.resize(off + count, 0.f); return off; };
+    HostArena arena;
+    std::vector<float> &host = arena.host;
     size_t o_raw[GEOADV_CLS_LAYERS], o_pk[GEOADV_CLS_LAYERS], o_sc[GEOADV_CLS_LAYERS], o_sh[GEOADV_CLS_LAYERS], o_b[GEOADV_CLS_LAYERS];
     for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) {
         const int K = kIn[l], N = outw[l];
-        o_raw[l] = reserve((size_t)K * N);
+        o_raw[l] = arena.reserve((size_t)K * N);
         memcpy(&host[o_raw[l]], hw->w[l], sizeof(float) * K * N);
         o_pk[l] = 0;
         if (l == T1C2 || l == T1C3 || l == C2 || l == T2C1 || l == T2C2 || l == T2C3 || l == C4 || l == C5) {   // MFMA operands
-            o_pk[l] = reserve((size_t)K * N);
-            const float *W = hw->w[l];
-            const int kg = K / 8;
-            for (int cb = 0; cb < N / 32; ++cb)
-                for (int t = 0; t < kg; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int u = 0; u < 4; ++u) {
-                            const int k = 8 * t + 4 * (lane >> 5) + u, n = 32 * cb + (lane & 31);
-                            host[o_pk[l] + (((size_t)cb * kg + t) * 64 + lane) * 4 + u] = W[(size_t)k * N + n];
-                        }
+            o_pk[l] = arena.reserve((size_t)K * N);
+            pack_fragments(&host[o_pk[l]], hw->w[l], K, N);
         }
         o_sc[l] = o_sh[l] = o_b[l] = 0;
-        if (has_bn(l)) {
-            o_sc[l] = reserve(N);
-            o_sh[l] = reserve(N);
+        if (has_bn(l)) {   // TF's fold, eps 1e-3 -- not host_util.h's fold_bn_torch, which rounds the shift differently
+            o_sc[l] = arena.reserve(N);
+            o_sh[l] = arena.reserve(N);
             for (int c = 0; c < N; ++c) {
                 const float inv = hw->gamma[l][c] * (1.0f / sqrtf(hw->var[l][c] + 1e-3f));
                 host[o_sc[l] + c] = inv;
                 host[o_sh[l] + c] = hw->b[l][c] * inv + (hw->beta[l][c] - hw->mean[l][c] * inv);
             }
         } else {
-            o_b[l] = reserve(N);
+            o_b[l] = arena.reserve(N);
             for (int c = 0; c < N; ++c) host[o_b[l] + c] = hw->b[l][c];
             // transform_nets.py: biases += [1,0,0,0,1,0,0,0,1] / eye(64).flatten() -- added here, once
             if (l == T1XYZ) for (int d = 0; d < 3; ++d) host[o_b[l] + 4 * d] += 1.0f;
@@ -272,18 +228,9 @@ extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw)
     }
     geoadv_cls *m = new geoadv_cls();
     m->num_classes = C;
-    const size_t bytes = sizeof(float) * host.size();
-    if (hipMalloc(&m->arena, bytes) != hipSuccess) {
+    if (int rc = arena.upload("cls_create", &m->arena)) {
         delete m;
-        set_error("cls_create: hipMalloc of %zu bytes failed", bytes);
-        return GEOADV_ENOMEM;
-    }
-    const hipError_t e = hipMemcpy(m->arena, host.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(m->arena);
-        delete m;
-        set_error("cls_create: upload failed: %s", hipGetErrorString(e));
-        return GEOADV_EHIP;
+        return rc;
     }
     const float *base = static_cast<const float *>(m->arena);
     for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) {
@@ -305,21 +252,20 @@ extern "C" void geoadv_cls_destroy(geoadv_cls *cls) {
 
 namespace {
 struct ClsScratch {
-    int *pooled;             // [3][b][1024]
+    unsigned *pooled;        // [3][b][1024]
     float *t1, *w1f;         // [b][9], [b][192]
     float *t2, *w3p;         // [b][4096] each
     size_t bytes;
 };
-ClsScratch carve_cls(void *base, int b) {
+ClsScratch carve_cls(void *workspace, int b) {
     ClsScratch s;
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { char *q = p; p += cls_rup(bytes, 256); return q; };
-    s.pooled = reinterpret_cast<int *>(take(sizeof(int) * 3 * (size_t)b * CLS_POOL));
-    s.t1 = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 9));
-    s.w1f = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 192));
-    s.t2 = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 4096));
-    s.w3p = reinterpret_cast<float *>(take(sizeof(float) * (size_t)b * 4096));
-    s.bytes = (size_t)(p - static_cast<char *>(base));
+    Carver cv(workspace);
+    s.pooled = cv.take<unsigned>(3 * (size_t)b * PT_POOL);
+    s.t1 = cv.take<float>((size_t)b * 9);
+    s.w1f = cv.take<float>((size_t)b * 192);
+    s.t2 = cv.take<float>((size_t)b * 4096);
+    s.w3p = cv.take<float>((size_t)b * 4096);
+    s.bytes = cv.bytes();
     return s;
 }
 int chunk_of(int b) { return b < CLS_MAX_GRID_Y ? b : CLS_MAX_GRID_Y; }
@@ -342,14 +288,10 @@ extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const flo
     GA_REQUIRE(pc && workspace, "cls_forward: null point cloud or workspace");
     hipStream_t st = as_stream(stream);
     const int C = cls->num_classes;
-    const int tiles = cdiv(n, CLS_ROWS);
-    void *aligned = reinterpret_cast<void *>(cls_rup(reinterpret_cast<size_t>(workspace), 256));
+    const int tiles = cdiv(n, PT_ROWS);
     const int bc = chunk_of(b);
-    const ClsScratch s = carve_cls(aligned, bc);
-    // column slices: small batches split the 1024 pooled columns over up to 4 workgroups (each recomputes its tile's narrow
-    // layers, ~7 % of a chain's work) so that the launch covers the 256 CUs
-    int slices = 1;
-    while (slices < 4 && (size_t)tiles * b * slices < 2 * kCUs) slices *= 2;
+    const ClsScratch s = carve_cls(workspace, bc);
+    const int slices = pooled_slices(tiles, b);     // (each slice recomputes its tile's narrow layers, ~7 % of a chain's work)
 
     ClsChainArgs ca{};
     ca.x = pc;
@@ -359,7 +301,7 @@ extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const flo
     for (int c0 = 0; c0 < b; c0 += bc) {
         const int nb = std::min(bc, b - c0);
         const float *x = pc + (size_t)c0 * n * 3;
-        GA_HIP(hipMemsetAsync(s.pooled, 0, sizeof(int) * 3 * (size_t)nb * CLS_POOL, st));
+        GA_HIP(hipMemsetAsync(s.pooled, 0, sizeof(unsigned) * 3 * (size_t)nb * PT_POOL, st));
         const dim3 grid(tiles, nb, slices);
         // T-Net1 chain
         ca.x = x;
@@ -367,7 +309,7 @@ extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const flo
         ca.mid[0] = layer_dev(cls, T1C2, 64, 128);
         ca.wide = layer_dev(cls, T1C3, 128, 1024);
         ca.pooled = s.pooled;
-        hipLaunchKernelGGL(cls_chain_kernel<1>, grid, dim3(CLS_THREADS), 0, st, ca, 0);
+        hipLaunchKernelGGL(cls_chain_kernel<1>, grid, dim3(PT_THREADS), 0, st, ca, 0);
         GA_LAUNCH_CHECK();
         ha.pooled = s.pooled;
         ha.w1 = cls->raw[T1F1]; ha.sc1 = cls->scale[T1F1]; ha.sh1 = cls->shift[T1F1];
@@ -375,7 +317,7 @@ extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const flo
         ha.w3 = cls->raw[T1XYZ]; ha.b3 = cls->bias[T1XYZ]; ha.M = 9;
         ha.t_out = s.t1; ha.t_user = transform_in ? transform_in + (size_t)c0 * 9 : nullptr;
         ha.fold_w = cls->raw[C1]; ha.fold_out = s.w1f; ha.labels = nullptr;
-        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_T1>, dim3(nb), dim3(CLS_THREADS), 0, st, ha, 0);
+        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_T1>, dim3(nb), dim3(PT_THREADS), 0, st, ha, 0);
         GA_LAUNCH_CHECK();
         // conv1', conv2, T-Net2 chain
         ca.w0 = s.w1f; ca.w0_cloud_stride = 192; ca.sc0 = cls->scale[C1]; ca.sh0 = cls->shift[C1];
@@ -383,8 +325,8 @@ extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const flo
         ca.mid[1] = layer_dev(cls, T2C1, 64, 64);
         ca.mid[2] = layer_dev(cls, T2C2, 64, 128);
         ca.wide = layer_dev(cls, T2C3, 128, 1024);
-        ca.pooled = s.pooled + (size_t)nb * CLS_POOL;
-        hipLaunchKernelGGL(cls_chain_kernel<3>, grid, dim3(CLS_THREADS), 0, st, ca, 0);
+        ca.pooled = s.pooled + (size_t)nb * PT_POOL;
+        hipLaunchKernelGGL(cls_chain_kernel<3>, grid, dim3(PT_THREADS), 0, st, ca, 0);
         GA_LAUNCH_CHECK();
         ha.pooled = ca.pooled;
         ha.w1 = cls->raw[T2F1]; ha.sc1 = cls->scale[T2F1]; ha.sh1 = cls->shift[T2F1];
@@ -392,14 +334,14 @@ extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const flo
         ha.w3 = cls->raw[T2FEAT]; ha.b3 = cls->bias[T2FEAT]; ha.M = 4096;
         ha.t_out = s.t2; ha.t_user = transform_feat ? transform_feat + (size_t)c0 * 4096 : nullptr;
         ha.fold_w = cls->raw[C3]; ha.fold_out = s.w3p;
-        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_T2>, dim3(nb), dim3(CLS_THREADS), 0, st, ha, 0);
+        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_T2>, dim3(nb), dim3(PT_THREADS), 0, st, ha, 0);
         GA_LAUNCH_CHECK();
         // conv1', conv2, conv3' .. conv5 chain
         ca.mid[1] = ClsLayerDev{PackedLayer{s.w3p, 64, 64}, cls->scale[C3], cls->shift[C3], 4096};
         ca.mid[2] = layer_dev(cls, C4, 64, 128);
         ca.wide = layer_dev(cls, C5, 128, 1024);
-        ca.pooled = s.pooled + 2 * (size_t)nb * CLS_POOL;
-        hipLaunchKernelGGL(cls_chain_kernel<3>, grid, dim3(CLS_THREADS), 0, st, ca, 0);
+        ca.pooled = s.pooled + 2 * (size_t)nb * PT_POOL;
+        hipLaunchKernelGGL(cls_chain_kernel<3>, grid, dim3(PT_THREADS), 0, st, ca, 0);
         GA_LAUNCH_CHECK();
         ha.pooled = ca.pooled;
         ha.w1 = cls->raw[F1]; ha.sc1 = cls->scale[F1]; ha.sh1 = cls->shift[F1];
@@ -409,7 +351,7 @@ extern "C" int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const flo
         ha.t_user = nullptr;
         ha.fold_w = nullptr; ha.fold_out = nullptr;
         ha.labels = labels ? labels + c0 : reinterpret_cast<int *>(s.t1);
-        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_CLS>, dim3(nb), dim3(CLS_THREADS), 0, st, ha, 0);
+        hipLaunchKernelGGL(cls_head_kernel<CLS_HEAD_CLS>, dim3(nb), dim3(PT_THREADS), 0, st, ha, 0);
         GA_LAUNCH_CHECK();
     }
     return GEOADV_OK;

@@ -38,7 +38,6 @@ namespace geoadv {
 
 constexpr int CT_TILE = 64, CT_KT = 32, CT_THREADS = 256, CT_LDS = CT_TILE + 4;
 constexpr float CT_KEEP = 0.7f, CT_EPS = 1e-3f;
-constexpr unsigned long long CT_GOLDEN = 0x9e3779b97f4a7c15ull;
 constexpr unsigned CT_KEEP_BELOW = 11744051u;
 
 // C[z] = alpha * sum_k A(i, k) B(k, j) (+ bias[j]) (+ C[z] if accumulate); element (i, k) of batch z at
@@ -168,13 +167,8 @@ __global__ __launch_bounds__(256) void ct_colsum_final_kernel(const double2 *par
     out[c] = (float)s;
 }
 
-__device__ __forceinline__ unsigned long long ct_mix(unsigned long long z) {
-    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
-    z ^= z >> 27; z *= 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
 __device__ __forceinline__ float ct_keep(unsigned long long seed, long long step, int layer, int cloud, int ch) {
-    const unsigned long long h = ct_mix(ct_mix(seed + CT_GOLDEN * (unsigned long long)(step + 1)) ^
+    const unsigned long long h = mix64(mix64(seed + kGolden64 * (unsigned long long)(step + 1)) ^
                                         (((unsigned long long)layer << 48) | ((unsigned long long)cloud << 24) | (unsigned long long)ch));
     return (unsigned)(h >> 40) < CT_KEEP_BELOW ? 1.f : 0.f;
 }

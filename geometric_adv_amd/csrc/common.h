@@ -32,6 +32,7 @@ void set_error(const char *fmt, ...);
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 constexpr int kWave = 64;   // gfx950 wavefront
 constexpr int kCUs = 256;   // MI355X: 8 XCDs x 32 CUs -- launch-SHAPE decisions only (grid sizes, slice widths): nothing is wrong on a smaller
@@ -55,6 +56,15 @@ struct DeviceOnce {
 };
 
 #ifdef __HIPCC__
+// splitmix64's finaliser and its increment: the counter-based generators of the dropout masks (cls_train.hip) and of
+// FoldingNet's neighbour sampling (foldingnet.hip)
+constexpr unsigned long long kGolden64 = 0x9e3779b97f4a7c15ull;
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
 // In-kernel stamps for a DIAGNOSTIC build only (-DGA_STAMPS, tools/debug/build_variants.sh; the shipped library contains none
 // of this): thread 0 of a workgroup writes the 100 MHz wall clock (s_memrealtime) at phase boundaries into a per-translation-unit
 // array -- kernel slot K, linear block id, stamp index 0..7 -- read back through the getter GA_STAMPS_GETTER defines.

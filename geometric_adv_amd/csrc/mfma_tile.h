@@ -1,5 +1,7 @@
-// MFMA tile helpers shared by the encoder kernels (encoder.hip) and the training kernels (train.hip):
-// fragment loads, the B-fragment register ring, and layer_gemm = [ROWS x K] LDS tile @ packed weights.
+// MFMA tile helpers: fragment loads, the B-fragment register ring, gemm_chain and layer_gemm = [ROWS x K] LDS tile @ packed
+// weights.  Users: the attack's encoder kernels (encoder.hip), the auto-encoder and classifier training kernels (train.hip,
+// cls_train.hip), and -- through point_tile.h, which builds the shared per-point / per-row tile code on these -- the three
+// inference models (classifier.hip, atlasnet.hip, foldingnet.hip).
 #pragma once
 #include "ae.h"
 

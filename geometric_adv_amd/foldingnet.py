@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib, fold_weights as FW, ops
+from ._model import DeviceModel
 
 G2 = FW.GRID * FW.GRID
 K = FW.NUM_NEIGHBOURS
@@ -38,7 +39,9 @@ class _FoldWeights(C.Structure):
                [("dec_" + f, C.c_void_p * len(FW.DEC_LAYERS)) for f in ("w", "b")]
 
 
-class FoldingNetAE:
+class FoldingNetAE(DeviceModel):
+    _destroy = "geoadv_fold_destroy"
+
     def __init__(self, folder=None, epoch=None, state=None, seed=None, sampling="device", batch_size=32, device=None):
         """Weights from <folder>/checkpoint_<epoch>.pth (fold_weights.load), unless `state` ({key: array}) is given.
         seed (an int) keys the neighbour sampling; sampling is 'device' or 'reference' (see the module docstring).
@@ -71,32 +74,6 @@ class FoldingNetAE:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_fold_create(C.byref(self._h), C.byref(hw)), "fold_create")
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                _lib.lib().geoadv_fold_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _as_dev(self, x):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
-        t = t.to(self.device, dtype=torch.float32).contiguous()
-        if t.dim() != 3 or t.shape[2] != 3:
-            raise ValueError("point clouds must be of shape (batch, points, 3); got %s" % (tuple(t.shape),))
-        return t
-
-    def _workspace(self, b, n):
-        need = _lib.lib().geoadv_fold_workspace_bytes(self._h, b, n)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def graph(self, x):
         """(degree (b, n) int32, knn (b, n, 16) int32, cov (b, n, 9) float32) device tensors of build_graph: the symmetric
@@ -108,7 +85,7 @@ class FoldingNetAE:
         knn = torch.empty((b, n, K), dtype=torch.int32, device=dev)
         cov = torch.empty((b, n, 9), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            ws = self._workspace(b, n)
+            ws = self._workspace(_lib.lib().geoadv_fold_workspace_bytes(self._h, b, n))
             st = _lib.lib().geoadv_fold_graph(self._h, b, n, _lib.ptr(x), _lib.ptr(deg), _lib.ptr(knn), _lib.ptr(cov),
                                               _lib.ptr(ws), _lib.stream_handle())
         _lib.check(st, "fold_graph")
@@ -146,7 +123,7 @@ class FoldingNetAE:
         out["picks"] = pk
         s = (self.seed if seed is None else int(seed)) & ((1 << 64) - 1)
         with torch.cuda.device(dev):
-            ws = self._workspace(b, n)
+            ws = self._workspace(_lib.lib().geoadv_fold_workspace_bytes(self._h, b, n))
             st = _lib.lib().geoadv_fold_forward(self._h, b, n, _lib.ptr(x), mode, C.c_ulonglong(s), C.c_longlong(int(cloud_offset)),
                                                 _lib.ptr(pk), _lib.ptr(out["cols"]), _lib.ptr(out["code"]),
                                                 _lib.ptr(out.get("p1")), _lib.ptr(out["recon"]), _lib.ptr(ws),
