@@ -29,119 +29,20 @@
 // lr = max(base * decay_rate^floor(k B / decay_step), 1e-5), bn_decay = min(0.99, 1 - 0.5 * 0.5^floor(k B / decay_step)).
 // Moving statistics: ExponentialMovingAverage(bn_decay) of the moments tensors (zero slots, zero_debias = False):
 // shadow -= (shadow - batch_stat) * (1 - bn_decay).
-#include "mfma_tile.h"
+#include "train_tile.h"
 #include <math.h>
 #include <string.h>
 #include <vector>
 
 namespace geoadv {
 
-constexpr int CT_TILE = 64, CT_KT = 32, CT_THREADS = 256, CT_LDS = CT_TILE + 4;
 constexpr float CT_KEEP = 0.7f, CT_EPS = 1e-3f;
 constexpr unsigned CT_KEEP_BELOW = 11744051u;
-
-// C[z] = alpha * sum_k A(i, k) B(k, j) (+ bias[j]) (+ C[z] if accumulate); element (i, k) of batch z at
-// A[z * sAz + i * sAi + k * sAk], (k, j) at B[z * sBz + k * sBk + j * sBj], C row-major with row stride ldc.
-// ksplit > 1: block z * ksplit + s writes the partial of its K range to P[(s * batch + z) * M * N] and ct_splitk_reduce adds
-// the ksplit partials in ascending order in double.
-struct GemmArgs {
-    const float *A; long long sAi, sAk, sAz;
-    const float *B; long long sBk, sBj, sBz;
-    float *C; long long ldc, sCz;
-    const float *bias;
-    float alpha;
-    int M, N, K, batch, ksplit, accumulate;
-    float *P;
-};
-
-__global__ __launch_bounds__(CT_THREADS) void ct_gemm_kernel(GemmArgs g) {
-    __shared__ float As[CT_KT][CT_LDS], Bs[CT_KT][CT_LDS];
-    const int z = blockIdx.z / g.ksplit, s = blockIdx.z % g.ksplit;
-    const int i0 = blockIdx.y * CT_TILE, j0 = blockIdx.x * CT_TILE;
-    const int kchunk = ((g.K + g.ksplit - 1) / g.ksplit + CT_KT - 1) / CT_KT * CT_KT;
-    const int kb = s * kchunk, ke = min(g.K, kb + kchunk);
-    const float *A = g.A + z * g.sAz, *B = g.B + z * g.sBz;
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, h = lane >> 5, li = lane & 31;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    const bool a_kfast = g.sAk == 1, b_jfast = g.sBj == 1;
-    f32x16 acc = {};
-    for (int k0 = kb; k0 < ke; k0 += CT_KT) {
-#pragma unroll
-        for (int q = 0; q < CT_KT * CT_TILE / CT_THREADS; ++q) {
-            const int e = t + q * CT_THREADS;
-            int r, k;
-            if (a_kfast) { r = e / CT_KT; k = e % CT_KT; } else { k = e / CT_TILE; r = e % CT_TILE; }
-            const int gi = i0 + r, gk = k0 + k;
-            As[k][r] = (gi < g.M && gk < ke) ? A[gi * g.sAi + gk * g.sAk] : 0.f;
-            int c, kk;
-            if (b_jfast) { kk = e / CT_TILE; c = e % CT_TILE; } else { c = e / CT_KT; kk = e % CT_KT; }
-            const int gj = j0 + c, gk2 = k0 + kk;
-            Bs[kk][c] = (gj < g.N && gk2 < ke) ? B[gk2 * g.sBk + gj * g.sBj] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < CT_KT; kk += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + h][wr + li], Bs[kk + h][wc + li], acc, 0, 0, 0);
-        __syncthreads();
-    }
-    const int col = j0 + wc + li;
-    if (col >= g.N) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = i0 + wr + acc_row(r, h);
-        if (row >= g.M) continue;
-        if (g.ksplit > 1) {
-            g.P[((size_t)(s * g.batch + z) * g.M + row) * g.N + col] = acc[r];
-        } else {
-            float v = acc[r] * g.alpha;
-            if (g.bias) v = v + g.bias[col];
-            float *c = g.C + z * g.sCz + (size_t)row * g.ldc + col;
-            *c = g.accumulate ? *c + v : v;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void ct_splitk_reduce(GemmArgs g) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t per = (size_t)g.M * g.N;
-    if (e >= per * g.batch) return;
-    const int z = (int)(e / per);
-    const int row = (int)((e % per) / g.N), col = (int)(e % g.N);
-    double a = 0.0;
-    for (int s = 0; s < g.ksplit; ++s) a += (double)g.P[(size_t)s * per * g.batch + e];
-    float v = (float)a * g.alpha;
-    if (g.bias) v = v + g.bias[col];
-    float *c = g.C + z * g.sCz + (size_t)row * g.ldc + col;
-    *c = g.accumulate ? *c + v : v;
-}
 
 // ---- batch norm -----------------------------------------------------------------------------------------------------------
 // The folded constants: inv = gamma / sqrt(var + eps), shift = beta - mean * inv; y = relu(a * inv + shift).  The backward
 // recomputes the same expression, so its ReLU mask is the forward's bit for bit.
 __device__ __forceinline__ float ct_pre(float a, float inv, float shift) { return a * inv + shift; }
-
-// Column partials over a chunk of rows in double, fixed order: MODE 0 = (sum a, sum a^2), MODE 1 = (sum a, 0).
-// grid (ceil(C / 64), chunks), block 256 = 64 columns x 4 row phases.
-template <int MODE>
-__global__ __launch_bounds__(256) void ct_colsum_kernel(const float *a, int R, int C, int rows_per_chunk, double2 *part) {
-    __shared__ double2 red[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
-    const int r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    double s = 0.0, q = 0.0;
-    if (c < C)
-        for (int r = r0 + ph; r < r1; r += 4) {
-            const double v = (double)a[(size_t)r * C + c];
-            s += v;
-            if (MODE == 0) q += v * v;
-        }
-    red[ph][threadIdx.x & 63] = make_double2(s, q);
-    __syncthreads();
-    if (ph == 0 && c < C) {
-        double2 o = red[0][threadIdx.x];
-        for (int p = 1; p < 4; ++p) { o.x += red[p][threadIdx.x].x; o.y += red[p][threadIdx.x].y; }
-        part[(size_t)blockIdx.y * C + c] = o;
-    }
-}
 
 // Batch statistics from the partials: mean, population variance, folded constants.  One thread per column.
 __global__ __launch_bounds__(256) void ct_bn_stats_kernel(const double2 *part, int chunks, int C, double inv_rows, const float *gamma,
@@ -156,15 +57,6 @@ __global__ __launch_bounds__(256) void ct_bn_stats_kernel(const double2 *part, i
     const float mf = (float)m, vf = (float)v;
     const float iv = gamma[c] * (1.0f / sqrtf(vf + CT_EPS));
     mean[c] = mf; var[c] = vf; inv[c] = iv; shift[c] = beta[c] - mf * iv;
-}
-
-// Column sums -> a gradient vector (conv / fc bias): out[c] = sum of the partials (the .x field), fixed order.
-__global__ __launch_bounds__(256) void ct_colsum_final_kernel(const double2 *part, int chunks, int C, float *out) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0;
-    for (int k = 0; k < chunks; ++k) s += part[(size_t)k * C + c].x;
-    out[c] = (float)s;
 }
 
 __device__ __forceinline__ float ct_keep(unsigned long long seed, long long step, int layer, int cloud, int ch) {
@@ -263,17 +155,6 @@ __global__ __launch_bounds__(256) void ct_bn_bwd_pool_part_kernel(const float *d
         q += (double)gv * (double)((av - m) * rs);
     }
     part[c] = make_double2(s, q);
-}
-
-// Pass 2: dbeta, dgamma (into the gradient arena) and the means m1 = dbeta / R, m2 = dgamma / R.
-__global__ __launch_bounds__(256) void ct_bn_bwd_final_kernel(const double2 *part, int chunks, int C, double inv_rows, float *dgamma,
-                                                              float *dbeta, float *m1, float *m2) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < chunks; ++k) { s += part[(size_t)k * C + c].x; q += part[(size_t)k * C + c].y; }
-    dbeta[c] = (float)s; dgamma[c] = (float)q;
-    m1[c] = (float)(s * inv_rows); m2[c] = (float)(q * inv_rows);
 }
 
 // Pass 3: da = gamma * rs * (g - m1 - xhat * m2).  MODE 0 dense dy, 1 dense dy through dropout, 2 pool (dpool at the argmax row).
@@ -393,7 +274,6 @@ const int kOut[NL] = {64, 128, 1024, 512, 256, 9, 64, 64, 64, 128, 1024, 512, 25
 bool bn_of(int l) { return l != T1XYZ && l != T2FEAT && l != F3; }
 bool per_point(int l) { return l <= T1C3 || (l >= C1 && l <= T2C3) || (l >= C3 && l <= C5); }
 bool pooled_layer(int l) { return l == T1C3 || l == T2C3 || l == C5; }
-constexpr size_t CT_PARTIAL_FLOATS = (size_t)16 << 20;     // split-K partials (64 MB)
 }  // namespace
 
 struct geoadv_cls_trainer {
@@ -434,23 +314,7 @@ struct Run {
 
     // C = alpha * A B (+ bias) (+ C)
     void gemm(GemmArgs g) {
-        if (err != hipSuccess) return;
-        const int gx = cdiv(g.N, CT_TILE), gy = cdiv(g.M, CT_TILE);
-        int ks = 1;
-        const long long blocks = (long long)gx * gy * g.batch;
-        if (blocks < 512 && g.K >= 4 * CT_KT) {
-            ks = (int)std::min<long long>(cdiv(g.K, 4 * CT_KT), 512 / blocks);
-            while (ks > 1 && (size_t)ks * g.batch * g.M * g.N > CT_PARTIAL_FLOATS) --ks;
-        }
-        g.ksplit = ks;
-        g.P = t->partials;
-        hipLaunchKernelGGL(ct_gemm_kernel, dim3(gx, gy, g.batch * ks), dim3(CT_THREADS), 0, st, g);
-        check();
-        if (ks > 1) {
-            const size_t total = (size_t)g.batch * g.M * g.N;
-            hipLaunchKernelGGL(ct_splitk_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g);
-            check();
-        }
+        if (err == hipSuccess) err = ct_launch_gemm(g, t->partials, st);
     }
     static GemmArgs plain(const float *A, const float *B, float *C, int M, int N, int K) {
         GemmArgs g{};

@@ -1,0 +1,801 @@
+// geoadv_fold_trainer: one TRAINING step of the FoldingNet auto-encoder (transfer/foldingnet/train_foldingnet.py:76-117:
+// FoldingNet_graph in train mode, ChamferLoss(points, recon), torch.optim.Adam with weight decay) on gfx950, fp32 in and out.
+//
+// Graph (foldingnet.py): in = cat(xyz, cov) 12 wide; conv1..conv3 (64) each BN + ReLU; graph pool 1 + ReLU; conv4 (128) BN
+// ReLU; graph pool 2 + ReLU; conv5 (1024) BN, NO ReLU; max over points; fc1 (512) BN ReLU; fc2 (512) = the code; fold1 on
+// [code, grid] 514 -> 512 -> 512 -> 3 (ReLU, no BN) = mid; fold2 on [code, mid] 515 -> 512 -> 512 -> 3 = recon.
+// BatchNorm1d in train mode: eps 1e-5, the BIASED batch variance normalises (bn1..5 over batch * n rows, bn6 over the batch
+// clouds), running = 0.9 running + 0.1 batch with the UNBIASED variance.  The graph (16-NN, covariance, symmetric adjacency)
+// and the picks of both pools come from foldingnet.hip's kernels (fold_graph.h), the Chamfer scan and its gradient from
+// geoadv_nn_distance / geoadv_nn_distance_grad.
+//
+// FORM: the direct one, as cls_train.hip.  STORED for the backward: the pre-BN activation of every BN layer, the post-ReLU
+// outputs of conv1..conv4 and of the four hidden decoder layers, both pools' outputs and winners, the global maximum's rows.
+// RECOMPUTED: every ReLU mask of a BN layer (a * inv + shift > 0, the forward's expression bit for bit) and xhat.
+// GEMMs on v_mfma_f32_32x32x2_f32 with fixed-order split-K (train_tile.h), batch statistics as per-chunk double partials
+// added in a fixed order, no float atomics anywhere: two steps from the same state are bitwise identical.
+//
+// Decoder: the 512 code rows of each fold's first layer act once per cloud, s = code . W[0:512] + b; per grid point only the
+// 2 (grid) or 3 (mid) point rows are added.  Backward, d s = the column sums of d pre over the cloud's 2025 points, then
+// d code = d s . W[0:512]^T and d W[0:512] = code^T d s: products of batch rows, not batch * 2025.
+//
+// Pool backward (the reference's Graph_Pooling cannot be differentiated at batch > 1; this is the derivative of what its
+// forward computes): every (point, channel) of a pool sends its gradient to the ONE element that attained the maximum --
+// the point itself first, then the lowest of the 16 pick slots (strict > in that order) -- and only if that maximum is
+// positive (the ReLU that follows; the pools' inputs are ReLU outputs, so a maximum is positive or zero).  Gathered by
+// destination: point j adds, in ascending order of i over its sorted adjacency row (the adjacency is symmetric, so every
+// i that can have picked j is there), the gradients of the (i, channel) whose winner is j.
+// conv5's BN has no ReLU and gamma may be negative: the maximum over points is taken of a * inv + shift itself, and the
+// first maximal row gets the gradient.
+//
+// Adam (torch.optim.Adam, lr, betas .9 / .999, eps 1e-8, weight_decay): g += wd * p on EVERY parameter; m += (g - m) * 0.1;
+// v = 0.999 v + 0.001 g g; p -= lr / (1 - 0.9^t) * m / (sqrt(v) / sqrt(1 - 0.999^t) + eps), t = steps taken including this.
+#include "train_tile.h"
+#include "fold_graph.h"
+#include <math.h>
+#include <string.h>
+#include <vector>
+
+namespace geoadv {
+
+constexpr float FT_EPS = 1e-5f;
+constexpr int FT_NB = 16, FT_GRID = 45, FT_G2 = FT_GRID * FT_GRID, FT_CODE = 512, FT_LAT = 1024;
+
+__device__ __forceinline__ float ft_pre(float a, float inv, float shift) { return a * inv + shift; }
+
+// in[r][0:3] = xyz, in[r][3:12] = cov
+__global__ __launch_bounds__(256) void ft_input_kernel(const float *x, const float *cov, int R, float *in) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= R * 12) return;
+    const int r = e / 12, k = e - 12 * r;
+    in[e] = k < 3 ? x[(size_t)r * 3 + k] : cov[(size_t)r * 9 + k - 3];
+}
+
+// Batch statistics from the partials: mean, biased variance, folded constants.  One thread per column.
+__global__ __launch_bounds__(256) void ft_bn_stats_kernel(const double2 *part, int chunks, int C, double inv_rows, const float *gamma,
+                                                          const float *beta, float *mean, float *var, float *inv, float *shift) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double s = 0.0, q = 0.0;
+    for (int k = 0; k < chunks; ++k) { s += part[(size_t)k * C + c].x; q += part[(size_t)k * C + c].y; }
+    const double m = s * inv_rows;
+    double v = q * inv_rows - m * m;
+    if (v < 0.0) v = 0.0;
+    const float mf = (float)m, vf = (float)v;
+    const float iv = gamma[c] * (1.0f / sqrtf(vf + FT_EPS));
+    mean[c] = mf; var[c] = vf; inv[c] = iv; shift[c] = beta[c] - mf * iv;
+}
+
+__global__ __launch_bounds__(256) void ft_bn_relu_kernel(const float *a, size_t total, int C, const float *inv, const float *shift, float *y) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int c = (int)(e % C);
+    y[e] = fmaxf(ft_pre(a[e], inv[c], shift[c]), 0.f);
+}
+
+// Graph pool + ReLU of h [B n][C]: g = relu(max(h_i, h over the 16 columns)); win = the row (in the cloud) that attained a
+// positive maximum -- the point itself first, then the lowest slot -- or -1.
+__global__ __launch_bounds__(256) void ft_graph_pool_kernel(const float *h, const int *cols, int n, int C, size_t total, float *g, int *win) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int c = (int)(e % C);
+    const size_t r = e / C;
+    const size_t base = r / n * n;
+    float v = h[e];
+    int w = (int)(r - base);
+    const int *cl = cols + r * FT_NB;
+#pragma unroll 4
+    for (int t = 0; t < FT_NB; ++t) {
+        const int j = (unsigned)cl[t] < (unsigned)n ? cl[t] : 0;
+        const float u = h[(base + j) * C + c];
+        if (u > v) { v = u; w = j; }
+    }
+    const bool pos = v > 0.f;
+    g[e] = pos ? v : 0.f;
+    win[e] = pos ? w : -1;
+}
+
+// Max over the n rows of each cloud of a * inv + shift (no ReLU): the maximum and its FIRST row.  grid (ceil(C / 64), B).
+__global__ __launch_bounds__(256) void ft_gmax_kernel(const float *a, int n, int C, const float *inv, const float *shift, float *pooled,
+                                                      int *arg) {
+    __shared__ float mv[4][64];
+    __shared__ int mi[4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6, b = blockIdx.y;
+    float best = -INFINITY;
+    int bi = 0;
+    if (c < C) {
+        const float iv = inv[c], sh = shift[c];
+        if (ph < n) best = ft_pre(a[((size_t)b * n + ph) * C + c], iv, sh), bi = ph;
+        for (int r = ph + 4; r < n; r += 4) {
+            const float v = ft_pre(a[((size_t)b * n + r) * C + c], iv, sh);
+            if (v > best) { best = v; bi = r; }
+        }
+    }
+    mv[ph][threadIdx.x & 63] = best;
+    mi[ph][threadIdx.x & 63] = bi;
+    __syncthreads();
+    if (ph == 0 && c < C) {
+        for (int p = 1; p < 4 && p < n; ++p) {
+            const float v = mv[p][threadIdx.x];
+            const int i = mi[p][threadIdx.x];
+            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+        }
+        pooled[(size_t)b * C + c] = best;
+        arg[(size_t)b * C + c] = bi;
+    }
+}
+
+// A fold's first layer: H[r][k] = relu(s[cloud(r)][k] + sum_d pts[r][d] * wp[d][k]), D = 2 (the grid) or 3 (mid)
+template <int D>
+__global__ __launch_bounds__(256) void ft_fold_l1_kernel(const float *s, const float *pts, const float *wp, size_t total, float *H) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int k = (int)(e % FT_CODE);
+    const size_t r = e / FT_CODE;
+    float v = s[r / FT_G2 * FT_CODE + k];
+#pragma unroll
+    for (int d = 0; d < D; ++d) v = fmaf(wp[d * FT_CODE + k], pts[r * D + d], v);
+    H[e] = fmaxf(v, 0.f);
+}
+
+__global__ __launch_bounds__(256) void ft_relu_kernel(float *y, size_t total) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < total) y[e] = fmaxf(y[e], 0.f);
+}
+
+// d = H > 0 ? d : 0 (the backward of a ReLU whose output H was stored)
+__global__ __launch_bounds__(256) void ft_mask_kernel(float *d, const float *H, size_t total) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < total) d[e] = H[e] > 0.f ? d[e] : 0.f;
+}
+
+// out = sum d1 / (B n) + sum d2 / (B m): one block, strided double sums added in a fixed order
+__global__ __launch_bounds__(256) void ft_loss_kernel(const float *d1, size_t c1, const float *d2, size_t c2, float *out) {
+    __shared__ double r1[256], r2[256];
+    double s = 0.0, q = 0.0;
+    for (size_t e = threadIdx.x; e < c1; e += 256) s += (double)d1[e];
+    for (size_t e = threadIdx.x; e < c2; e += 256) q += (double)d2[e];
+    r1[threadIdx.x] = s; r2[threadIdx.x] = q;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0, b = 0.0;
+        for (int i = 0; i < 256; ++i) { a += r1[i]; b += r2[i]; }
+        out[0] = (float)(a / (double)c1 + b / (double)c2);
+    }
+}
+
+// BN backward of a ReLU layer, dense dy:  g = dy * [a * inv + shift > 0].  Pass 1: (sum g, sum g * xhat) per chunk.
+__global__ __launch_bounds__(256) void ft_bn_bwd_part_kernel(const float *dy, const float *a, int R, int C, int rows_per_chunk,
+                                                             const float *mean, const float *var, const float *inv, const float *shift,
+                                                             double2 *part) {
+    __shared__ double2 red[4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
+    const int r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+    double s = 0.0, q = 0.0;
+    if (c < C) {
+        const float rs = 1.0f / sqrtf(var[c] + FT_EPS), m = mean[c], iv = inv[c], sh = shift[c];
+        for (int r = r0 + ph; r < r1; r += 4) {
+            const size_t e = (size_t)r * C + c;
+            const float av = a[e];
+            const float gv = ft_pre(av, iv, sh) > 0.f ? dy[e] : 0.f;
+            s += (double)gv;
+            q += (double)gv * (double)((av - m) * rs);
+        }
+    }
+    red[ph][threadIdx.x & 63] = make_double2(s, q);
+    __syncthreads();
+    if (ph == 0 && c < C) {
+        double2 o = red[0][threadIdx.x];
+        for (int p = 1; p < 4; ++p) { o.x += red[p][threadIdx.x].x; o.y += red[p][threadIdx.x].y; }
+        part[(size_t)blockIdx.y * C + c] = o;
+    }
+}
+
+// Pass 1 of conv5's BN (no ReLU), whose g is dpool at the maximum's row of each (cloud, channel): clouds in ascending order.
+__global__ __launch_bounds__(256) void ft_bn_bwd_gmax_part_kernel(const float *dpool, const int *arg, const float *a, int B, int n, int C,
+                                                                  const float *mean, const float *var, double2 *part) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float rs = 1.0f / sqrtf(var[c] + FT_EPS), m = mean[c];
+    double s = 0.0, q = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const float av = a[((size_t)b * n + arg[(size_t)b * C + c]) * C + c];
+        const float gv = dpool[(size_t)b * C + c];
+        s += (double)gv;
+        q += (double)gv * (double)((av - m) * rs);
+    }
+    part[c] = make_double2(s, q);
+}
+
+// Pass 3: da = gamma * rs * (g - m1 - xhat * m2).  GMAX false: dense dy through the ReLU; true: dpool at the maximum's row.
+template <bool GMAX>
+__global__ __launch_bounds__(256) void ft_bn_bwd_apply_kernel(const float *dy, const int *arg, const float *a, size_t total, int n, int C,
+                                                              const float *mean, const float *var, const float *gamma, const float *inv,
+                                                              const float *shift, const float *m1, const float *m2, float *da) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int c = (int)(e % C);
+    const size_t r = e / C;
+    const float av = a[e];
+    float gv = 0.f;
+    if (GMAX) {
+        const size_t b = r / n;
+        if (arg[b * C + c] == (int)(r - b * n)) gv = dy[b * C + c];
+    } else if (ft_pre(av, inv[c], shift[c]) > 0.f) {
+        gv = dy[e];
+    }
+    const float rs = 1.0f / sqrtf(var[c] + FT_EPS);
+    const float xh = (av - mean[c]) * rs;
+    da[e] = gamma[c] * rs * (gv - m1[c] - xh * m2[c]);
+}
+
+// BN backward of an fc layer (rows = the batch's clouds, a few to a few hundred), one thread per column, all in double
+// from the stored activation: with few rows g - mean(g) - xhat mean(g xhat) cancels almost completely (two rows: all but
+// eps / (var + eps) of it), and xhat rounded to fp32 would decide what is left.  The ReLU mask is the forward's fp32 test.
+__global__ __launch_bounds__(256) void ft_bn_bwd_fc_kernel(const float *dy, const float *a, int R, int C, const float *gamma,
+                                                           const float *inv, const float *shift, float *dgamma, float *dbeta,
+                                                           float *da) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double m = 0.0, v = 0.0;
+    for (int r = 0; r < R; ++r) m += (double)a[(size_t)r * C + c];
+    m /= R;
+    for (int r = 0; r < R; ++r) { const double d = (double)a[(size_t)r * C + c] - m; v += d * d; }
+    v /= R;
+    const double rs = 1.0 / sqrt(v + (double)FT_EPS);
+    const float iv = inv[c], sh = shift[c];
+    double s = 0.0, q = 0.0;
+    for (int r = 0; r < R; ++r) {
+        const size_t e = (size_t)r * C + c;
+        const double gv = ft_pre(a[e], iv, sh) > 0.f ? (double)dy[e] : 0.0;
+        s += gv;
+        q += gv * (((double)a[e] - m) * rs);
+    }
+    dbeta[c] = (float)s; dgamma[c] = (float)q;
+    const double m1 = s / R, m2 = q / R, gr = (double)gamma[c] * rs;
+    for (int r = 0; r < R; ++r) {
+        const size_t e = (size_t)r * C + c;
+        const double gv = ft_pre(a[e], iv, sh) > 0.f ? (double)dy[e] : 0.0;
+        da[e] = (float)(gr * (gv - m1 - ((double)a[e] - m) * rs * m2));
+    }
+}
+
+// Pool backward, gathered by destination: dh[j][c] = [win[j][c] == j] dg[j][c] + sum over i != j in j's sorted adjacency row,
+// ascending, of [win[i][c] == j] dg[i][c].
+__global__ __launch_bounds__(256) void ft_pool_bwd_kernel(const float *dg, const int *win, const int *off, const int *deg, const int *col,
+                                                          int n, int C, size_t total, float *dh) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int c = (int)(e % C);
+    const size_t r = e / C;
+    const size_t cloud = r / n, base = cloud * n;
+    const int j = (int)(r - base);
+    float s = win[e] == j ? dg[e] : 0.f;
+    const int *row = col + cloud * 32 * n + off[r];
+    const int d = deg[r];
+    for (int p = 0; p < d; ++p) {
+        const int i = row[p];
+        if ((unsigned)i >= (unsigned)n || i == j) continue;
+        const size_t f = (base + i) * C + c;
+        if (win[f] == j) s += dg[f];
+    }
+    dh[e] = s;
+}
+
+// out[k][c] = (float) part[k][c].x: the per-chunk column sums as a matrix (chunk = cloud)
+__global__ __launch_bounds__(256) void ft_part_rows_kernel(const double2 *part, int count, float *out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < count) out[e] = (float)part[e].x;
+}
+
+// torch.optim.Adam with weight decay; bc1 = 1 - beta1^t, bc2s = sqrt(1 - beta2^t)
+__global__ __launch_bounds__(256) void ft_adam_kernel(float *p, float *m, float *v, const float *g, size_t count, float lr, float wd, float bc1, float bc2s) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    const float gv = g[e] + wd * p[e];
+    const float mn = m[e] + (gv - m[e]) * (1.f - 0.9f);
+    const float vn = v[e] * 0.999f + (gv * gv) * (1.f - 0.999f);
+    m[e] = mn; v[e] = vn;
+    const float denom = sqrtf(vn) / bc2s + 1e-8f;
+    p[e] = p[e] - (lr / bc1) * (mn / denom);
+}
+
+// running = 0.9 running + 0.1 stat * scale (scale = rows / (rows - 1) for the variance, 1 for the mean)
+__global__ __launch_bounds__(256) void ft_running_kernel(float *running, const float *stat, const float *scale, size_t count) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    const float s = scale ? stat[e] * scale[e] : stat[e];
+    running[e] = running[e] * (1.f - 0.1f) + 0.1f * s;
+}
+
+}  // namespace geoadv
+
+using namespace geoadv;
+
+namespace {
+// layers: conv1..conv5, fc1, fc2 (encoder), fold1.conv1..3, fold2.conv1..3
+enum { E1 = 0, E2, E3, E4, E5, F1, F2, D0, D1, D2, D3, D4, D5, NL };
+const int kIn[NL] = {12, 64, 64, 64, 128, FT_LAT, FT_CODE, FT_CODE + 2, 512, 512, FT_CODE + 3, 512, 512};
+const int kOut[NL] = {64, 64, 64, 128, FT_LAT, FT_CODE, FT_CODE, 512, 512, 3, 512, 512, 3};
+bool bn_of(int l) { return l <= F1; }
+}  // namespace
+
+struct geoadv_fold_trainer {
+    int B, n, R, rows;                             // rows = B * 2025
+    float lr, wd;
+    long long step, ordinal;
+    unsigned long long seed;
+    size_t o_w[NL], o_b[NL], o_g[NL], o_be[NL], o_mv[NL], P, MV;
+    std::vector<void *> allocs;
+    float *params, *grads, *slot1, *slot2;
+    float *run_mean, *run_var, *bat_mean, *bat_var, *inv, *shift, *m1, *m2, *unbias;   // flat over the BN layers (o_mv)
+    float *in0, *a[6], *h[4], *g1, *g2, *pooled, *h6, *code, *s, *H[4], *mid, *recon, *grid;
+    int *win1, *win2, *arg, *picks;
+    float *d1, *d2, *gd1, *gd2, *dx, *drecon, *dmid, *loss, *mid_loss;
+    int *i1, *i2;
+    float *X, *Y, *Z, *ds, *dcode, *dsm1, *dsm2, *partials;
+    double2 *part;
+    void *graph_ws;
+    FoldTrainGraph graph;
+};
+
+namespace {
+template <class T> T *dev_alloc(geoadv_fold_trainer *t, size_t count, hipError_t &err) {
+    void *p = nullptr;
+    if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T) + 16);
+    if (err == hipSuccess) { t->allocs.push_back(p); err = hipMemset(p, 0, count * sizeof(T) + 16); }
+    return static_cast<T *>(p);
+}
+
+inline unsigned blocks_of(size_t total) { return (unsigned)((total + 255) / 256); }
+
+struct Run {
+    geoadv_fold_trainer *t;
+    hipStream_t st;
+    hipError_t err = hipSuccess;
+
+    void check() { if (err == hipSuccess) err = hipGetLastError(); }
+    void gemm(GemmArgs g) { if (err == hipSuccess) err = ct_launch_gemm(g, t->partials, st); }
+    float *W(int l) { return t->params + t->o_w[l]; }
+    int rows(int l) const { return l <= E5 ? t->R : l <= F2 ? t->B : t->rows; }
+
+    // out = in @ W_l[k0 : k0 + K] + (bias ? b_l : 0)
+    void linear_fwd(int l, const float *in, float *out, int M, int k0, int K, bool bias) {
+        const int N = kOut[l];
+        GemmArgs g{};
+        g.A = in; g.sAi = K; g.sAk = 1;
+        g.B = W(l) + (size_t)k0 * N; g.sBk = N; g.sBj = 1;
+        g.C = out; g.ldc = N;
+        g.bias = bias ? t->params + t->o_b[l] : nullptr;
+        g.alpha = 1.f; g.M = M; g.N = N; g.K = K; g.batch = 1;
+        gemm(g);
+    }
+    void colsum(int mode, const float *a, int R, int C, int rpc) {
+        if (err != hipSuccess) return;
+        const dim3 grid(cdiv(C, 64), cdiv(R, rpc));
+        if (mode == 0) hipLaunchKernelGGL(ct_colsum_kernel<0>, grid, dim3(256), 0, st, a, R, C, rpc, t->part);
+        else hipLaunchKernelGGL(ct_colsum_kernel<1>, grid, dim3(256), 0, st, a, R, C, rpc, t->part);
+        check();
+    }
+    static int rpc_of(int R) { return std::max(1, std::min(R, 256)); }
+    void batch_stats(int l) {
+        const int R = rows(l), C = kOut[l], rpc = rpc_of(R);
+        colsum(0, t->a[l], R, C, rpc);
+        if (err != hipSuccess) return;
+        const size_t o = t->o_mv[l];
+        hipLaunchKernelGGL(ft_bn_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, cdiv(R, rpc), C, 1.0 / R,
+                           t->params + t->o_g[l], t->params + t->o_be[l], t->bat_mean + o, t->bat_var + o, t->inv + o, t->shift + o);
+        check();
+    }
+    void bn_relu(int l, float *y) {
+        if (err != hipSuccess) return;
+        const size_t total = (size_t)rows(l) * kOut[l], o = t->o_mv[l];
+        hipLaunchKernelGGL(ft_bn_relu_kernel, dim3(blocks_of(total)), dim3(256), 0, st, t->a[l], total, kOut[l], t->inv + o, t->shift + o, y);
+        check();
+    }
+    void bn_layer(int l, const float *in, float *y) {
+        linear_fwd(l, in, t->a[l], rows(l), 0, kIn[l], true);
+        batch_stats(l);
+        if (y) bn_relu(l, y);
+    }
+    void graph_pool(const float *h, int which, int C, float *g, int *win) {
+        if (err != hipSuccess) return;
+        const size_t total = (size_t)t->R * C;
+        hipLaunchKernelGGL(ft_graph_pool_kernel, dim3(blocks_of(total)), dim3(256), 0, st, h, t->graph.cols + (size_t)which * t->R * FT_NB,
+                           t->n, C, total, g, win);
+        check();
+    }
+    void relu(float *y, size_t total) {
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(ft_relu_kernel, dim3(blocks_of(total)), dim3(256), 0, st, y, total);
+        check();
+    }
+    void mask(float *d, const float *H, size_t total) {
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(ft_mask_kernel, dim3(blocks_of(total)), dim3(256), 0, st, d, H, total);
+        check();
+    }
+    // one fold forward: l0 = its first layer, pts [rows][D] the grid or mid, H1 / H2 its hidden outputs, out [rows][3]
+    void fold_fwd(int l0, const float *pts, int D, float *H1, float *H2, float *out) {
+        linear_fwd(l0, t->code, t->s, t->B, 0, FT_CODE, true);
+        if (err != hipSuccess) return;
+        const size_t total = (size_t)t->rows * 512;
+        const float *wp = W(l0) + (size_t)FT_CODE * 512;
+        if (D == 2) hipLaunchKernelGGL(ft_fold_l1_kernel<2>, dim3(blocks_of(total)), dim3(256), 0, st, t->s, pts, wp, total, H1);
+        else hipLaunchKernelGGL(ft_fold_l1_kernel<3>, dim3(blocks_of(total)), dim3(256), 0, st, t->s, pts, wp, total, H1);
+        check();
+        linear_fwd(l0 + 1, H1, H2, t->rows, 0, 512, true);
+        relu(H2, total);
+        linear_fwd(l0 + 2, H2, out, t->rows, 0, 512, true);
+    }
+    int chamfer(const float *x, const float *pc, float *out) {
+        if (err != hipSuccess) return GEOADV_EHIP;
+        if (int rc = geoadv_nn_distance(t->B, t->n, x, FT_G2, pc, t->d1, t->i1, t->d2, t->i2, st)) return rc;
+        hipLaunchKernelGGL(ft_loss_kernel, dim3(1), dim3(256), 0, st, t->d1, (size_t)t->R, t->d2, (size_t)t->rows, out);
+        check();
+        return GEOADV_OK;
+    }
+
+    // ---- backward pieces ----
+    // dW_l[k0 : k0 + K] = in^T da (in [M][K])
+    void weight_grad(int l, const float *in, const float *da, int M, int k0, int K) {
+        const int N = kOut[l];
+        GemmArgs g{};
+        g.A = in; g.sAi = 1; g.sAk = K;
+        g.B = da; g.sBk = N; g.sBj = 1;
+        g.C = t->grads + t->o_w[l] + (size_t)k0 * N; g.ldc = N;
+        g.alpha = 1.f; g.M = K; g.N = N; g.K = M; g.batch = 1;
+        gemm(g);
+    }
+    void bias_grad(int l, const float *da, int M) {
+        const int C = kOut[l], rpc = rpc_of(M);
+        colsum(1, da, M, C, rpc);
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(ct_colsum_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, cdiv(M, rpc), C, t->grads + t->o_b[l]);
+        check();
+    }
+    // din (=|+=) da W_l[k0 : k0 + K]^T
+    void input_grad(int l, const float *da, float *din, int M, int k0, int K, int accumulate) {
+        const int N = kOut[l];
+        GemmArgs d{};
+        d.A = da; d.sAi = N; d.sAk = 1;
+        d.B = W(l) + (size_t)k0 * N; d.sBk = 1; d.sBj = N;
+        d.C = din; d.ldc = K;
+        d.alpha = 1.f; d.M = M; d.N = K; d.K = N; d.batch = 1; d.accumulate = accumulate;
+        gemm(d);
+    }
+    void linear_bwd(int l, const float *in, const float *da, float *din) {
+        weight_grad(l, in, da, rows(l), 0, kIn[l]);
+        bias_grad(l, da, rows(l));
+        if (din) input_grad(l, da, din, rows(l), 0, kIn[l], 0);
+    }
+    // BN backward of layer l; gmax: dy = dpool [B][C] at the maximum's rows (conv5), else dense dy through the ReLU
+    void bn_bwd(int l, bool gmax, const float *dy, float *da) {
+        if (err != hipSuccess) return;
+        const int R = rows(l), C = kOut[l];
+        const size_t o = t->o_mv[l];
+        const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o;
+        if (l == F1) {
+            hipLaunchKernelGGL(ft_bn_bwd_fc_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, dy, t->a[l], R, C, t->params + t->o_g[l], iv, sh,
+                               t->grads + t->o_g[l], t->grads + t->o_be[l], da);
+            check();
+            return;
+        }
+        int chunks = 1;
+        if (gmax) {
+            hipLaunchKernelGGL(ft_bn_bwd_gmax_part_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, dy, t->arg, t->a[l], t->B, t->n, C, mean, var,
+                               t->part);
+        } else {
+            const int rpc = rpc_of(R);
+            chunks = cdiv(R, rpc);
+            hipLaunchKernelGGL(ft_bn_bwd_part_kernel, dim3(cdiv(C, 64), chunks), dim3(256), 0, st, dy, t->a[l], R, C, rpc, mean, var, iv, sh,
+                               t->part);
+        }
+        check();
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(ct_bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, chunks, C, 1.0 / R, t->grads + t->o_g[l],
+                           t->grads + t->o_be[l], t->m1 + o, t->m2 + o);
+        check();
+        if (err != hipSuccess) return;
+        const size_t total = (size_t)R * C;
+        const float *gam = t->params + t->o_g[l];
+        if (gmax)
+            hipLaunchKernelGGL(ft_bn_bwd_apply_kernel<true>, dim3(blocks_of(total)), dim3(256), 0, st, dy, t->arg, t->a[l], total, t->n, C, mean,
+                               var, gam, iv, sh, t->m1 + o, t->m2 + o, da);
+        else
+            hipLaunchKernelGGL(ft_bn_bwd_apply_kernel<false>, dim3(blocks_of(total)), dim3(256), 0, st, dy, nullptr, t->a[l], total, t->n, C,
+                               mean, var, gam, iv, sh, t->m1 + o, t->m2 + o, da);
+        check();
+    }
+    void pool_bwd(const float *dg, const int *win, int C, float *dh) {
+        if (err != hipSuccess) return;
+        const size_t total = (size_t)t->R * C;
+        hipLaunchKernelGGL(ft_pool_bwd_kernel, dim3(blocks_of(total)), dim3(256), 0, st, dg, win, t->graph.off, t->graph.deg, t->graph.col,
+                           t->n, C, total, dh);
+        check();
+    }
+    // one fold backward: dout [rows][3] -> every gradient of layers l0 .. l0 + 2, dcode (=|+=), dpts [rows][D] (or null)
+    void fold_bwd(int l0, const float *pts, int D, const float *H1, const float *H2, const float *dout, float *dpts, int acc_code) {
+        const int M = t->rows;
+        const size_t total = (size_t)M * 512;
+        weight_grad(l0 + 2, H2, dout, M, 0, 512);
+        bias_grad(l0 + 2, dout, M);
+        input_grad(l0 + 2, dout, t->Y, M, 0, 512, 0);
+        mask(t->Y, H2, total);                                           // d pre of the second layer
+        weight_grad(l0 + 1, H1, t->Y, M, 0, 512);
+        bias_grad(l0 + 1, t->Y, M);
+        input_grad(l0 + 1, t->Y, t->Z, M, 0, 512, 0);
+        mask(t->Z, H1, total);                                           // d pre of the first layer
+        weight_grad(l0, pts, t->Z, M, FT_CODE, D);                       // the point rows
+        if (dpts) input_grad(l0, t->Z, dpts, M, FT_CODE, D, 0);
+        colsum(1, t->Z, M, 512, FT_G2);                                  // chunk = cloud: d s [B][512]
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(ft_part_rows_kernel, dim3(cdiv(t->B * 512, 256)), dim3(256), 0, st, t->part, t->B * 512, t->ds);
+        check();
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(ct_colsum_final_kernel, dim3(2), dim3(256), 0, st, t->part, t->B, 512, t->grads + t->o_b[l0]);
+        check();
+        weight_grad(l0, t->code, t->ds, t->B, 0, FT_CODE);               // the code rows
+        input_grad(l0, t->ds, t->dcode, t->B, 0, FT_CODE, acc_code);
+    }
+};
+
+int run_step(geoadv_fold_trainer *t, const float *x, hipStream_t st) {
+    Run q{t, st};
+    const int B = t->B, R = t->R;
+    // ---- forward ----
+    hipLaunchKernelGGL(ft_input_kernel, dim3(cdiv(R * 12, 256)), dim3(256), 0, st, x, t->graph.cov, R, t->in0);
+    q.check();
+    q.bn_layer(E1, t->in0, t->h[0]);
+    q.bn_layer(E2, t->h[0], t->h[1]);
+    q.bn_layer(E3, t->h[1], t->h[2]);
+    q.graph_pool(t->h[2], 0, 64, t->g1, t->win1);
+    q.bn_layer(E4, t->g1, t->h[3]);
+    q.graph_pool(t->h[3], 1, 128, t->g2, t->win2);
+    q.bn_layer(E5, t->g2, nullptr);
+    if (q.err == hipSuccess) {
+        const size_t o = t->o_mv[E5];
+        hipLaunchKernelGGL(ft_gmax_kernel, dim3(FT_LAT / 64, B), dim3(256), 0, st, t->a[E5], t->n, FT_LAT, t->inv + o, t->shift + o, t->pooled,
+                           t->arg);
+        q.check();
+    }
+    q.bn_layer(F1, t->pooled, t->h6);
+    q.linear_fwd(F2, t->h6, t->code, B, 0, FT_CODE, true);
+    q.fold_fwd(D0, t->grid, 2, t->H[0], t->H[1], t->mid);
+    q.fold_fwd(D3, t->mid, 3, t->H[2], t->H[3], t->recon);
+    if (int rc = q.chamfer(x, t->mid, t->mid_loss)) return rc;
+    if (int rc = q.chamfer(x, t->recon, t->loss)) return rc;
+    if (q.err == hipSuccess)
+        if (int rc = geoadv_nn_distance_grad(B, t->n, x, FT_G2, t->recon, t->gd1, t->i1, t->gd2, t->i2, t->dx, t->drecon, st)) return rc;
+    // ---- backward ----
+    q.fold_bwd(D3, t->mid, 3, t->H[2], t->H[3], t->drecon, t->dmid, 0);
+    q.fold_bwd(D0, t->grid, 2, t->H[0], t->H[1], t->dmid, nullptr, 1);
+    q.linear_bwd(F2, t->h6, t->dcode, t->dsm1);                           // d h6 [B][512]
+    q.bn_bwd(F1, false, t->dsm1, t->dsm2);
+    q.linear_bwd(F1, t->pooled, t->dsm2, t->dsm1);                        // d pooled [B][1024]
+    q.bn_bwd(E5, true, t->dsm1, t->X);                                    // d a5 [R][1024]
+    q.linear_bwd(E5, t->g2, t->X, t->Y);                                  // d g2 [R][128]
+    q.pool_bwd(t->Y, t->win2, 128, t->Z);                                 // d h4
+    q.bn_bwd(E4, false, t->Z, t->Y);                                      // d a4
+    q.linear_bwd(E4, t->g1, t->Y, t->Z);                                  // d g1 [R][64]
+    q.pool_bwd(t->Z, t->win1, 64, t->Y);                                  // d h3
+    q.bn_bwd(E3, false, t->Y, t->Z);
+    q.linear_bwd(E3, t->h[1], t->Z, t->Y);                                // d h2
+    q.bn_bwd(E2, false, t->Y, t->Z);
+    q.linear_bwd(E2, t->h[0], t->Z, t->Y);                                // d h1
+    q.bn_bwd(E1, false, t->Y, t->Z);
+    q.linear_bwd(E1, t->in0, t->Z, nullptr);
+    if (q.err != hipSuccess) {
+        set_error("fold_trainer_step: %s", hipGetErrorString(q.err));
+        return GEOADV_EHIP;
+    }
+    // ---- optimizer, running statistics, counters ----
+    const double tt = (double)(t->step + 1);
+    const float bc1 = (float)(1.0 - pow(0.9, tt)), bc2s = (float)sqrt(1.0 - pow(0.999, tt));
+    hipLaunchKernelGGL(ft_adam_kernel, dim3(blocks_of(t->P)), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, t->lr, t->wd,
+                       bc1, bc2s);
+    GA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ft_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_mean, t->bat_mean, (const float *)nullptr, t->MV);
+    GA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ft_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_var, t->bat_var, t->unbias, t->MV);
+    GA_LAUNCH_CHECK();
+    t->step += 1;
+    return GEOADV_OK;
+}
+}  // namespace
+
+extern "C" int geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoadv_fold_weights *init, const geoadv_fold_train_config *cfg) {
+    GA_REQUIRE(out && init && cfg, "fold_trainer_create: null argument");
+    GA_REQUIRE(cfg->batch != 1, "fold_trainer_create: batch 1 cannot be trained: bn6 (after fc1) takes its statistics over the "
+                                "clouds of the batch and needs at least 2");
+    GA_REQUIRE(cfg->batch >= 2 && cfg->batch <= 1024, "fold_trainer_create: batch %d out of range [2, 1024]", cfg->batch);
+    GA_REQUIRE(cfg->n_points >= 17 && cfg->n_points <= 16384, "fold_trainer_create: n_points %d out of range [17, 16384]", cfg->n_points);
+    GA_REQUIRE((long long)cfg->batch * cfg->n_points <= FOLD_TRAIN_MAX_ROWS, "fold_trainer_create: batch * n_points exceeds 2^17 rows");
+    GA_REQUIRE(cfg->initial_step >= 0 && cfg->initial_ordinal >= 0, "fold_trainer_create: initial_step and initial_ordinal must be >= 0");
+    for (int l = 0; l < GEOADV_FOLD_ENC_LAYERS; ++l) {
+        GA_REQUIRE(init->enc_w[l] && init->enc_b[l], "fold_trainer_create: null encoder weight pointer at layer %d", l);
+        if (bn_of(l))
+            GA_REQUIRE(init->enc_gamma[l] && init->enc_beta[l] && init->enc_mean[l] && init->enc_var[l],
+                       "fold_trainer_create: null batch-norm pointer at encoder layer %d", l);
+    }
+    for (int l = 0; l < GEOADV_FOLD_DEC_LAYERS; ++l)
+        GA_REQUIRE(init->dec_w[l] && init->dec_b[l], "fold_trainer_create: null decoder pointer at layer %d", l);
+    geoadv_fold_trainer *t = new geoadv_fold_trainer();
+    t->B = cfg->batch; t->n = cfg->n_points; t->R = t->B * t->n; t->rows = t->B * FT_G2;
+    t->lr = cfg->learning_rate; t->wd = cfg->weight_decay; t->step = cfg->initial_step; t->ordinal = cfg->initial_ordinal;
+    t->seed = (unsigned long long)cfg->seed;
+    size_t P = 0, MV = 0;
+    auto rup16 = [](size_t v) { return (v + 15) / 16 * 16; };
+    for (int l = 0; l < NL; ++l) {
+        t->o_w[l] = P; P = rup16(P + (size_t)kIn[l] * kOut[l]);
+        t->o_b[l] = P; P = rup16(P + kOut[l]);
+        t->o_g[l] = t->o_be[l] = t->o_mv[l] = 0;
+        if (bn_of(l)) {
+            t->o_g[l] = P; P = rup16(P + kOut[l]);
+            t->o_be[l] = P; P = rup16(P + kOut[l]);
+            t->o_mv[l] = MV; MV = rup16(MV + kOut[l]);
+        }
+    }
+    t->P = P; t->MV = MV;
+    const size_t R = t->R, B = t->B, rows = t->rows;
+    hipError_t e = hipSuccess;
+    t->params = dev_alloc<float>(t, P, e); t->grads = dev_alloc<float>(t, P, e);
+    t->slot1 = dev_alloc<float>(t, P, e); t->slot2 = dev_alloc<float>(t, P, e);
+    for (float **p : {&t->run_mean, &t->run_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2, &t->unbias})
+        *p = dev_alloc<float>(t, MV, e);
+    t->in0 = dev_alloc<float>(t, R * 12, e);
+    for (int l = 0; l <= F1; ++l) t->a[l] = dev_alloc<float>(t, (l <= E5 ? R : B) * kOut[l], e);
+    for (int l = 0; l < 4; ++l) t->h[l] = dev_alloc<float>(t, R * kOut[l], e);
+    t->g1 = dev_alloc<float>(t, R * 64, e); t->g2 = dev_alloc<float>(t, R * 128, e);
+    t->win1 = dev_alloc<int>(t, R * 64, e); t->win2 = dev_alloc<int>(t, R * 128, e);
+    t->pooled = dev_alloc<float>(t, B * FT_LAT, e); t->arg = dev_alloc<int>(t, B * FT_LAT, e);
+    t->h6 = dev_alloc<float>(t, B * 512, e); t->code = dev_alloc<float>(t, B * 512, e); t->s = dev_alloc<float>(t, B * 512, e);
+    for (int i = 0; i < 4; ++i) t->H[i] = dev_alloc<float>(t, rows * 512, e);
+    t->mid = dev_alloc<float>(t, rows * 3, e); t->recon = dev_alloc<float>(t, rows * 3, e); t->grid = dev_alloc<float>(t, rows * 2, e);
+    t->picks = dev_alloc<int>(t, 2 * R * FT_NB, e);
+    t->d1 = dev_alloc<float>(t, R, e); t->i1 = dev_alloc<int>(t, R, e); t->gd1 = dev_alloc<float>(t, R, e);
+    t->d2 = dev_alloc<float>(t, rows, e); t->i2 = dev_alloc<int>(t, rows, e); t->gd2 = dev_alloc<float>(t, rows, e);
+    t->dx = dev_alloc<float>(t, R * 3, e); t->drecon = dev_alloc<float>(t, rows * 3, e); t->dmid = dev_alloc<float>(t, rows * 3, e);
+    t->loss = dev_alloc<float>(t, 1, e); t->mid_loss = dev_alloc<float>(t, 1, e);
+    t->X = dev_alloc<float>(t, R * FT_LAT, e);
+    t->Y = dev_alloc<float>(t, std::max(R * 128, rows * 512), e); t->Z = dev_alloc<float>(t, std::max(R * 128, rows * 512), e);
+    t->ds = dev_alloc<float>(t, B * 512, e); t->dcode = dev_alloc<float>(t, B * 512, e);
+    t->dsm1 = dev_alloc<float>(t, B * FT_LAT, e); t->dsm2 = dev_alloc<float>(t, B * FT_LAT, e);
+    t->partials = dev_alloc<float>(t, CT_PARTIAL_FLOATS, e);
+    t->part = dev_alloc<double2>(t, std::max((size_t)cdiv((int)R, 256) * FT_LAT, (size_t)cdiv((int)rows, 256) * 512) + 1024, e);
+    t->graph_ws = dev_alloc<char>(t, fold_train_graph_bytes(t->B, t->n), e);
+    if (e == hipSuccess) {
+        std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f), hu(MV, 1.f), hg(rows * 2), g1(R, 1.f / (float)R), g2(rows, 1.f / (float)rows);
+        for (int l = 0; l < NL; ++l) {
+            const float *w = l <= F2 ? init->enc_w[l] : init->dec_w[l - D0], *b = l <= F2 ? init->enc_b[l] : init->dec_b[l - D0];
+            memcpy(&hp[t->o_w[l]], w, sizeof(float) * kIn[l] * kOut[l]);
+            memcpy(&hp[t->o_b[l]], b, sizeof(float) * kOut[l]);
+            if (!bn_of(l)) continue;
+            memcpy(&hp[t->o_g[l]], init->enc_gamma[l], sizeof(float) * kOut[l]);
+            memcpy(&hp[t->o_be[l]], init->enc_beta[l], sizeof(float) * kOut[l]);
+            memcpy(&hm[t->o_mv[l]], init->enc_mean[l], sizeof(float) * kOut[l]);
+            memcpy(&hv[t->o_mv[l]], init->enc_var[l], sizeof(float) * kOut[l]);
+            const double rl = l <= E5 ? (double)R : (double)B;
+            for (int c = 0; c < kOut[l]; ++c) hu[t->o_mv[l] + c] = (float)(rl / (rl - 1.0));
+        }
+        for (size_t r = 0; r < rows; ++r) {      // np.linspace(-0.3, 0.3, 45); point p = row * 45 + column is (x_column, y_row)
+            const int p = (int)(r % FT_G2);
+            auto lin = [](int i) { return (float)(i == FT_GRID - 1 ? 0.3 : -0.3 + i * (0.6 / (FT_GRID - 1))); };
+            hg[2 * r] = lin(p % FT_GRID); hg[2 * r + 1] = lin(p / FT_GRID);
+        }
+        auto up = [&](float *dst, const std::vector<float> &src) {
+            if (e == hipSuccess) e = hipMemcpy(dst, src.data(), sizeof(float) * src.size(), hipMemcpyHostToDevice);
+        };
+        up(t->params, hp); up(t->run_mean, hm); up(t->run_var, hv); up(t->unbias, hu); up(t->grid, hg); up(t->gd1, g1); up(t->gd2, g2);
+    }
+    if (e != hipSuccess) {
+        for (void *p : t->allocs) (void)hipFree(p);
+        delete t;
+        set_error("fold_trainer_create: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
+    }
+    *out = t;
+    return GEOADV_OK;
+}
+
+extern "C" void geoadv_fold_trainer_destroy(geoadv_fold_trainer *t) {
+    if (!t) return;
+    for (void *p : t->allocs) (void)hipFree(p);
+    delete t;
+}
+
+extern "C" int geoadv_fold_trainer_set_slots(geoadv_fold_trainer *t, const float *slot1, const float *slot2) {
+    GA_REQUIRE(t, "fold_trainer_set_slots: null handle");
+    if (slot1) GA_HIP(hipMemcpy(t->slot1, slot1, sizeof(float) * t->P, hipMemcpyHostToDevice));
+    if (slot2) GA_HIP(hipMemcpy(t->slot2, slot2, sizeof(float) * t->P, hipMemcpyHostToDevice));
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_fold_trainer_step(geoadv_fold_trainer *t, const float *x, int sampling, int *picks, float *loss, float *mid_loss,
+                                        void *stream) {
+    GA_REQUIRE(t && x, "fold_trainer_step: null argument");
+    GA_REQUIRE(sampling == GEOADV_FOLD_PICKS_GIVEN || sampling == GEOADV_FOLD_PICKS_DEVICE,
+               "fold_trainer_step: sampling %d is not 0 (given) or 1 (device)", sampling);
+    GA_REQUIRE(sampling == GEOADV_FOLD_PICKS_DEVICE || picks, "fold_trainer_step: given sampling needs the picks");
+    hipStream_t st = as_stream(stream);
+    const size_t pick_bytes = sizeof(int) * 2 * (size_t)t->R * FT_NB;
+    if (sampling == GEOADV_FOLD_PICKS_GIVEN) GA_HIP(hipMemcpyAsync(t->picks, picks, pick_bytes, hipMemcpyDeviceToDevice, st));
+    if (int rc = fold_train_graph(t->B, t->n, x, sampling, t->seed, t->ordinal, t->picks, t->graph_ws, st, &t->graph)) return rc;
+    if (int rc = run_step(t, x, st)) return rc;
+    t->ordinal += t->B;
+    if (sampling == GEOADV_FOLD_PICKS_DEVICE && picks) GA_HIP(hipMemcpyAsync(picks, t->picks, pick_bytes, hipMemcpyDeviceToDevice, st));
+    if (loss) GA_HIP(hipMemcpyAsync(loss, t->loss, sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (mid_loss) GA_HIP(hipMemcpyAsync(mid_loss, t->mid_loss, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_fold_trainer_buffers(geoadv_fold_trainer *t, float **params, float **grads, size_t *count) {
+    GA_REQUIRE(t, "fold_trainer_buffers: null handle");
+    if (params) *params = t->params;
+    if (grads) *grads = t->grads;
+    if (count) *count = t->P;
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_fold_trainer_layout(const geoadv_fold_trainer *t, size_t *offsets52, size_t *moving_offsets13) {
+    GA_REQUIRE(t && offsets52, "fold_trainer_layout: null argument");
+    for (int l = 0; l < NL; ++l) {
+        offsets52[4 * l] = t->o_w[l];
+        offsets52[4 * l + 1] = t->o_b[l];
+        offsets52[4 * l + 2] = bn_of(l) ? t->o_g[l] : (size_t)-1;
+        offsets52[4 * l + 3] = bn_of(l) ? t->o_be[l] : (size_t)-1;
+        if (moving_offsets13) moving_offsets13[l] = bn_of(l) ? t->o_mv[l] : (size_t)-1;
+    }
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_fold_trainer_counters(const geoadv_fold_trainer *t, long long *step, long long *ordinal) {
+    GA_REQUIRE(t, "fold_trainer_counters: null handle");
+    if (step) *step = t->step;
+    if (ordinal) *ordinal = t->ordinal;
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_fold_trainer_state(const geoadv_fold_trainer *t, int what, int layer, const void **ptr, size_t *count) {
+    GA_REQUIRE(t && ptr && count, "fold_trainer_state: null argument");
+    const size_t B = t->B, R = t->R, rows = t->rows;
+    switch (what) {
+    case GEOADV_FOLD_STATE_BN_MEAN: case GEOADV_FOLD_STATE_BN_VAR: case GEOADV_FOLD_STATE_RUNNING_MEAN: case GEOADV_FOLD_STATE_RUNNING_VAR:
+    case GEOADV_FOLD_STATE_BN_INV: case GEOADV_FOLD_STATE_BN_SHIFT: {
+        GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "fold_trainer_state: layer %d has no batch norm", layer);
+        const float *base = what == GEOADV_FOLD_STATE_BN_MEAN ? t->bat_mean : what == GEOADV_FOLD_STATE_BN_VAR ? t->bat_var
+                          : what == GEOADV_FOLD_STATE_RUNNING_MEAN ? t->run_mean : what == GEOADV_FOLD_STATE_RUNNING_VAR ? t->run_var
+                          : what == GEOADV_FOLD_STATE_BN_INV ? t->inv : t->shift;
+        *ptr = base + t->o_mv[layer]; *count = kOut[layer];
+        return GEOADV_OK;
+    }
+    case GEOADV_FOLD_STATE_PRE_BN:
+        GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "fold_trainer_state: layer %d has no batch norm", layer);
+        *ptr = t->a[layer]; *count = (layer <= E5 ? R : B) * kOut[layer];
+        return GEOADV_OK;
+    case GEOADV_FOLD_STATE_POOL_WINNER:
+        GA_REQUIRE(layer == 0 || layer == 1, "fold_trainer_state: pool %d must be 0 or 1", layer);
+        *ptr = layer == 0 ? t->win1 : t->win2; *count = R * (layer == 0 ? 64 : 128);
+        return GEOADV_OK;
+    case GEOADV_FOLD_STATE_HIDDEN:
+        GA_REQUIRE(layer >= 0 && layer < 4, "fold_trainer_state: hidden decoder layer %d must be 0 .. 3", layer);
+        *ptr = t->H[layer]; *count = rows * 512;
+        return GEOADV_OK;
+    case GEOADV_FOLD_STATE_CHAMFER_IDX:
+        GA_REQUIRE(layer == 0 || layer == 1, "fold_trainer_state: Chamfer direction %d must be 0 or 1", layer);
+        *ptr = layer == 0 ? t->i1 : t->i2; *count = layer == 0 ? R : rows;
+        return GEOADV_OK;
+    case GEOADV_FOLD_STATE_GMAX_ROW: *ptr = t->arg; *count = B * FT_LAT; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_PICKS: *ptr = t->picks; *count = 2 * R * FT_NB; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_COLS: *ptr = t->graph.cols; *count = t->graph.cols ? 2 * R * FT_NB : 0; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_COV: *ptr = t->graph.cov; *count = t->graph.cov ? R * 9 : 0; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_CODE: *ptr = t->code; *count = B * FT_CODE; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_MID: *ptr = t->mid; *count = rows * 3; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_RECON: *ptr = t->recon; *count = rows * 3; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_SLOT1: *ptr = t->slot1; *count = t->P; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_SLOT2: *ptr = t->slot2; *count = t->P; return GEOADV_OK;
+    default: break;
+    }
+    set_error("fold_trainer_state: unknown state %d", what);
+    return GEOADV_EINVAL;
+}

@@ -34,6 +34,7 @@
 // non-finite coordinates reads and writes only its own rows.
 #include "point_tile.h"
 #include "host_util.h"
+#include "fold_graph.h"
 #include <math.h>
 #include <string.h>
 
@@ -544,6 +545,28 @@ int fold_build_graph(const FoldScratch &s, int bc, int n, const float *pc, int *
     return GEOADV_OK;
 }
 }  // namespace
+
+// ---- the training step's graph (fold_graph.h): the same kernels over the whole batch as one chunk ----
+size_t geoadv::fold_train_graph_bytes(int b, int n) { return carve_fold(nullptr, b, n).bytes + 256; }
+
+int geoadv::fold_train_graph(int b, int n, const float *pc, int sampling, unsigned long long seed, long long ordinal0, int *picks,
+                             void *workspace, hipStream_t st, FoldTrainGraph *out) {
+    if (int rc = fold_check("fold_train_graph", b, n)) return rc;
+    GA_REQUIRE((long long)b * n <= FOLD_TRAIN_MAX_ROWS, "fold_train_graph: batch * n exceeds 2^17 rows");
+    GA_REQUIRE(pc && picks && workspace && out, "fold_train_graph: null argument");
+    const FoldScratch s = carve_fold(workspace, b, n);
+    if (int rc = fold_build_graph(s, b, n, pc, nullptr, nullptr, nullptr, st)) return rc;
+    FoldPick P{};
+    P.deg = s.deg; P.off = s.off; P.col = s.col;
+    P.given = sampling == GEOADV_FOLD_PICKS_GIVEN ? picks : nullptr;
+    P.picks_out = sampling == GEOADV_FOLD_PICKS_DEVICE ? picks : nullptr;
+    P.cols_out = nullptr; P.cols = s.cols; P.seed = seed; P.ordinal0 = ordinal0;
+    P.n = n; P.bc = b; P.b = b; P.c0 = 0;
+    hipLaunchKernelGGL(fold_pick_kernel, dim3(cdiv(n, 256), b, 2), dim3(256), 0, st, P);
+    GA_LAUNCH_CHECK();
+    out->cov = s.cov; out->cols = s.cols; out->off = s.off; out->deg = s.deg; out->col = s.col;
+    return GEOADV_OK;
+}
 
 extern "C" size_t geoadv_fold_workspace_bytes(const geoadv_fold *fold, int b, int n) {
     if (!fold || b <= 0 || n < FN_K || n > 16384) return 256;

@@ -1,0 +1,252 @@
+"""FoldingNetTrainer (transfer/foldingnet/train_foldingnet.py's model, loss and optimizer step) on the MI355X: one
+geoadv_fold_trainer handle (include/geoadv.h; csrc/fold_train.hip) per model.
+
+    tr = FoldingNetTrainer(num_points=2048, batch_size=8, seed=7)
+    loss, mid_loss = tr.train_step(x)            # train mode: batch statistics, one torch-form Adam step
+    recon = tr.eval_step(x)                      # eval mode through FoldingNetAE on the exported weights
+    tr.save('log/foldingnet', 3)                 # checkpoint_3.pth: {'epoch', 'model', 'optimizer'} as the reference's
+
+Neighbour draws: sampling='device' keys the GPU sampler by (seed, cloud ordinal, pool layer, point); the ordinal is the
+running count of clouds this trainer has trained on and is stored in the checkpoint ('graph_ordinal').  'reference' draws
+np.random.RandomState(seed) positions on the host in the reference's order (FoldingNetAE.reference_picks).  train_step(x,
+picks=...) takes explicit positions.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, fold_weights as FW
+from .foldingnet import FoldingNetAE, _FoldWeights, PICKS_DEVICE, PICKS_GIVEN, SAMPLINGS, K, G2
+
+_STATE = {"bn_mean": 0, "bn_var": 1, "running_mean": 2, "running_var": 3, "bn_inv": 4, "bn_shift": 5, "pre_bn": 6,
+          "pool_winner": 7, "gmax_row": 8, "hidden": 9, "picks": 10, "cols": 11, "cov": 12, "code": 13, "mid": 14, "recon": 15,
+          "chamfer_idx": 16, "slot1": 17, "slot2": 18}
+_INT_STATES = ("pool_winner", "gmax_row", "picks", "cols", "chamfer_idx")
+# (state-dict prefix, fan_in, fan_out, conv, BN index or None) in geoadv_fold_trainer_layout's order
+LAYERS = [("encoder." + name, fi, fo, conv, i + 1 if i < 6 else None) for i, (name, fi, fo, conv) in enumerate(FW.ENC_LAYERS)] + \
+         [("decoder." + name, fi, fo, True, None) for name, fi, fo in FW.DEC_LAYERS]
+
+
+class _FoldTrainConfig(C.Structure):
+    """ctypes mirror of geoadv_fold_train_config."""
+    _fields_ = [("batch", C.c_int), ("n_points", C.c_int), ("learning_rate", C.c_float), ("weight_decay", C.c_float),
+                ("seed", C.c_longlong), ("initial_step", C.c_longlong), ("initial_ordinal", C.c_longlong)]
+
+
+def check_batch(batch_size):
+    if int(batch_size) < 2:
+        raise ValueError("batch_size %d cannot be trained: bn6 (after fc1) takes its statistics over the clouds of the batch "
+                         "and needs at least 2" % int(batch_size))
+
+
+class FoldingNetTrainer:
+    def __init__(self, weights=None, num_points=2048, batch_size=8, learning_rate=1e-4, weight_decay=1e-6, seed=0,
+                 sampling="device", step=0, slots=None, ordinal=0, device=None):
+        """weights: {state-dict key: array} (None = fold_weights.initial_weights(seed)).  step / slots: optimizer steps taken
+        and Adam's {'exp_avg': {key: array}, 'exp_avg_sq': {key: array}} to continue from (None = fresh); ordinal: clouds
+        seen so far (the device sampler's next ordinal)."""
+        check_batch(batch_size)
+        if sampling not in SAMPLINGS:
+            raise ValueError("sampling must be one of %s, not %r" % (SAMPLINGS, sampling))
+        if weights is None:
+            weights = FW.initial_weights(seed)
+        weights = {k: v for k, v in FW.strip_prefix(weights).items() if not k.endswith("num_batches_tracked")}
+        FW.validate(weights)
+        self.num_points, self.batch_size = int(num_points), int(batch_size)
+        self.learning_rate, self.weight_decay = float(learning_rate), float(weight_decay)
+        self.seed, self.sampling = int(seed), sampling
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self._rs = np.random.RandomState(self.seed) if sampling == "reference" else None
+        canon = FW.canonical(weights)
+        hw = _FoldWeights()
+        for key, arrays in canon.items():
+            field = getattr(hw, key)
+            for i, a in enumerate(arrays):
+                field[i] = a.ctypes.data if a is not None else None
+        sseed = self.seed & ((1 << 64) - 1)
+        cfg = _FoldTrainConfig(self.batch_size, self.num_points, self.learning_rate, self.weight_decay,
+                               sseed - (1 << 64) if sseed >= (1 << 63) else sseed, int(step), int(ordinal))
+        self._h = C.c_void_p()
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            _lib.check(L.geoadv_fold_trainer_create(C.byref(self._h), C.byref(hw), C.byref(cfg)), "fold_trainer_create")
+        pp, gp, cnt = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        _lib.check(L.geoadv_fold_trainer_buffers(self._h, C.byref(pp), C.byref(gp), C.byref(cnt)), "fold_trainer_buffers")
+        self._count, self._params_ptr, self._grads_ptr = int(cnt.value), pp.value, gp.value
+        offs, moffs = (C.c_size_t * (4 * len(LAYERS)))(), (C.c_size_t * len(LAYERS))()
+        _lib.check(L.geoadv_fold_trainer_layout(self._h, offs, moffs), "fold_trainer_layout")
+        self._offsets = list(offs)
+        self._loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+        self._picks = torch.zeros((2, self.batch_size, self.num_points, K), dtype=torch.int32, device=self.device)
+        self._eval = None
+        self._graph_model = None
+        if slots is not None:
+            s1, s2 = self._flatten(slots["exp_avg"]), self._flatten(slots["exp_avg_sq"])
+            # host pointers as c_void_p: a bare Python int would be passed as a 32-bit C int
+            _lib.check(L.geoadv_fold_trainer_set_slots(self._h, C.c_void_p(s1.ctypes.data), C.c_void_p(s2.ctypes.data)),
+                       "fold_trainer_set_slots")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and self._h.value:
+                _lib.lib().geoadv_fold_trainer_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    # ---- device views --------------------------------------------------------------------------------------
+    def _raw(self, ptr, count, typestr="<f4"):
+        class _Arr:
+            pass
+        a = _Arr()
+        a.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+        with torch.cuda.device(self.device):
+            return torch.as_tensor(a, device=self.device)
+
+    def state(self, what, layer=0, device=False):
+        """Host copy of what the last step kept (geoadv_fold_trainer_state): 'bn_mean' / 'bn_var' / 'running_mean' /
+        'running_var' / 'bn_inv' / 'bn_shift' / 'pre_bn' of BN layer 0 .. 5 (bn1 .. bn6), 'pool_winner' 0 / 1, 'gmax_row',
+        'hidden' 0 .. 3, 'picks', 'cols', 'cov', 'code', 'mid', 'recon', 'chamfer_idx' 0 / 1, 'slot1', 'slot2'.  device=True
+        returns a view of the handle's memory instead: drop it before the trainer."""
+        p, cnt = C.c_void_p(), C.c_size_t()
+        _lib.check(_lib.lib().geoadv_fold_trainer_state(self._h, _STATE[what], int(layer), C.byref(p), C.byref(cnt)),
+                   "fold_trainer_state")
+        torch.cuda.synchronize(self.device)
+        if not cnt.value:
+            raise ValueError("state(%r) is empty before the first step" % what)
+        a = self._raw(p.value, cnt.value, "<i4" if what in _INT_STATES else "<f4")
+        B, n = self.batch_size, self.num_points
+        shapes = {"pre_bn": (-1, LAYERS[int(layer)][2]), "pool_winner": (B, n, -1), "gmax_row": (B, 1024), "hidden": (-1, 512),
+                  "picks": (2, B, n, K), "cols": (2, B, n, K), "cov": (B, n, 9), "code": (B, 512), "mid": (B, G2, 3),
+                  "recon": (B, G2, 3), "chamfer_idx": (B, -1)}
+        if not device:
+            a = a.cpu().numpy().copy()
+        return a.reshape(shapes[what]) if what in shapes else a
+
+    def counters(self):
+        """(optimizer steps taken, clouds seen)."""
+        s, o = C.c_longlong(), C.c_longlong()
+        _lib.check(_lib.lib().geoadv_fold_trainer_counters(self._h, C.byref(s), C.byref(o)), "fold_trainer_counters")
+        return int(s.value), int(o.value)
+
+    @property
+    def step(self):
+        return self.counters()[0]
+
+    def _unflatten(self, flat):
+        """{parameter key: array in torch's shape} from a flat parameter-layout buffer."""
+        out = {}
+        for l, (pre, fi, fo, conv, bn) in enumerate(LAYERS):
+            o = self._offsets[4 * l: 4 * l + 4]
+            w = flat[o[0]:o[0] + fi * fo].reshape(fi, fo).T
+            out[pre + ".weight"] = np.ascontiguousarray(w[:, :, None] if conv else w)
+            out[pre + ".bias"] = flat[o[1]:o[1] + fo].copy()
+            if bn:
+                out["encoder.bn%d.weight" % bn] = flat[o[2]:o[2] + fo].copy()
+                out["encoder.bn%d.bias" % bn] = flat[o[3]:o[3] + fo].copy()
+        return out
+
+    def _flatten(self, named):
+        flat = np.zeros(self._count, np.float32)
+        for l, (pre, fi, fo, conv, bn) in enumerate(LAYERS):
+            o = self._offsets[4 * l: 4 * l + 4]
+            flat[o[0]:o[0] + fi * fo] = np.asarray(named[pre + ".weight"], np.float32).reshape(fo, fi).T.reshape(-1)
+            flat[o[1]:o[1] + fo] = np.asarray(named[pre + ".bias"], np.float32).reshape(-1)
+            if bn:
+                flat[o[2]:o[2] + fo] = np.asarray(named["encoder.bn%d.weight" % bn], np.float32).reshape(-1)
+                flat[o[3]:o[3] + fo] = np.asarray(named["encoder.bn%d.bias" % bn], np.float32).reshape(-1)
+        return flat
+
+    def parameters(self):
+        """{parameter key: array} of the trainable tensors (host copies, torch's shapes)."""
+        torch.cuda.synchronize(self.device)
+        return self._unflatten(self._raw(self._params_ptr, self._count).cpu().numpy())
+
+    def gradients(self):
+        """{parameter key: d loss / d parameter} of the last step, without the weight-decay term."""
+        torch.cuda.synchronize(self.device)
+        return self._unflatten(self._raw(self._grads_ptr, self._count).cpu().numpy())
+
+    def slots(self):
+        """Adam's {'exp_avg': {key: array}, 'exp_avg_sq': {key: array}}."""
+        return {"exp_avg": self._unflatten(self.state("slot1")), "exp_avg_sq": self._unflatten(self.state("slot2"))}
+
+    # ---- the steps -----------------------------------------------------------------------------------------
+    def _dev(self, x):
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        return t.to(self.device, dtype=torch.float32).contiguous()
+
+    def degrees(self, x):
+        """(batch, n) int32 device tensor: the length of every point's adjacency row (what picks index into).  Through a
+        FoldingNetAE kept for its graph build alone -- the graph does not depend on the weights, so it is built once."""
+        if self._graph_model is None:
+            self._graph_model = FoldingNetAE(state=FW.initial_weights(0), seed=self.seed, sampling=self.sampling,
+                                             batch_size=self.batch_size, device=self.device)
+            self._graph_model._rs = self._rs           # 'reference' sampling: one RandomState for the trainer's lifetime
+        return self._graph_model.graph(self._dev(x))[0]
+
+    def eval_model(self):
+        """The FoldingNetAE of the current weights (eval mode: running statistics); rebuilt after every train_step."""
+        if self._eval is None:
+            self._eval = FoldingNetAE(state=self.export_state_dict(), seed=self.seed, sampling=self.sampling,
+                                      batch_size=self.batch_size, device=self.device)
+        return self._eval
+
+    def train_step(self, x, picks=None):
+        """One optimizer step on x (batch_size, num_points, 3): (loss, mid_loss) of the pre-update parameters.  picks:
+        (2, batch_size, num_points, 16) positions in each point's sorted adjacency row, else drawn as `sampling` says."""
+        x = self._dev(x)
+        B, n = self.batch_size, self.num_points
+        if tuple(x.shape) != (B, n, 3):
+            raise ValueError("train_step takes x (%d, %d, 3); got %s" % (B, n, tuple(x.shape)))
+        if picks is None and self.sampling == "reference":
+            deg = self.degrees(x).cpu().numpy()
+            picks = self._graph_model.reference_picks(deg)
+        mode = PICKS_DEVICE
+        if picks is not None:
+            pk = torch.as_tensor(picks)
+            if tuple(pk.shape) != (2, B, n, K):
+                raise ValueError("picks must be of shape %s; got %s" % ((2, B, n, K), tuple(pk.shape)))
+            pk = pk.to(self.device, dtype=torch.int32).contiguous()
+            deg = self.degrees(x)
+            if bool(((pk < 0) | (pk >= deg[None, :, :, None])).any()):
+                raise ValueError("picks must lie in [0, degree) of their point")
+            self._picks.copy_(pk)
+            mode = PICKS_GIVEN
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().geoadv_fold_trainer_step(self._h, _lib.ptr(x), mode, _lib.ptr(self._picks), _lib.ptr(self._loss),
+                                                           _lib.ptr(self._loss[1:]), _lib.stream_handle()), "fold_trainer_step")
+        self._eval = None
+        out = self._loss.cpu().numpy()
+        return float(out[0]), float(out[1])
+
+    def eval_step(self, x, picks=None, cloud_offset=0):
+        """Eval mode (running statistics) through FoldingNetAE on the exported weights: its forward's dict (code, recon,
+        picks, cols)."""
+        return self.eval_model().forward(self._dev(x), picks=picks, cloud_offset=cloud_offset)
+
+    # ---- what the reference's torch.save writes --------------------------------------------------------------
+    def export_state_dict(self):
+        """{state-dict key: array} of the model: parameters and running statistics (no num_batches_tracked)."""
+        out = self.parameters()
+        for i in range(6):
+            out["encoder.bn%d.running_mean" % (i + 1)] = self.state("running_mean", i)
+            out["encoder.bn%d.running_var" % (i + 1)] = self.state("running_var", i)
+        return out
+
+    def save(self, folder, epoch):
+        """checkpoint_<epoch>.pth: {'epoch', 'model', 'optimizer': a torch.optim.Adam state_dict, 'graph_ordinal'}."""
+        step, ordinal = self.counters()
+        opt = dict(self.slots(), step=step, lr=self.learning_rate, weight_decay=self.weight_decay)
+        FW.save(folder, epoch, self.export_state_dict(), optimizer=opt, extra={"graph_ordinal": ordinal})
+        return FW.checkpoint_path(folder, epoch)
+
+    @classmethod
+    def restore(cls, folder, epoch, **kwargs):
+        """A trainer continuing from a checkpoint `save` (or train_foldingnet) wrote: weights, running statistics, Adam's
+        slots and step count, and the sampler's cloud ordinal."""
+        state, opt, ck = FW.load_training(folder, epoch)
+        if opt is None:
+            return cls(weights=state, **kwargs)
+        return cls(weights=state, step=opt["step"], slots=opt, ordinal=int(ck.get("graph_ordinal", 0)), **kwargs)

@@ -102,17 +102,83 @@ def load(folder, epoch):
     return {k: np.asarray(v, np.float32) for k, v in state.items()}
 
 
-def save(folder, epoch, state, prefix=""):
-    """Writes checkpoint_<epoch>.pth as train_foldingnet.py:173-177 does (with an empty optimizer state)."""
+def parameter_names():
+    """The trainable tensors in FoldingNet_graph().parameters() order (the index torch's optimizer state uses): the state-dict
+    order without the running statistics and counters."""
+    return [k for k in key_names() if not k.endswith(BN_FIELDS[2:])]
+
+
+def optimizer_state_dict(optimizer):
+    """A real torch.optim.Adam state_dict from optimizer = {'step': int, 'exp_avg': {key: array}, 'exp_avg_sq': {key: array},
+    'lr', 'weight_decay'}: state[i] = {step, exp_avg, exp_avg_sq} in parameter_names() order, plus this torch's param_groups."""
+    import torch
+    shapes = key_shapes()
+    names = parameter_names()
+    params = [torch.zeros(shapes[k], dtype=torch.float32, requires_grad=True) for k in names]
+    opt = torch.optim.Adam(params, lr=float(optimizer.get("lr", 1e-4)), betas=(0.9, 0.999),
+                           weight_decay=float(optimizer.get("weight_decay", 1e-6)))
+    for k, p in zip(names, params):
+        opt.state[p] = {"step": torch.tensor(float(optimizer["step"])),
+                        "exp_avg": torch.from_numpy(np.ascontiguousarray(optimizer["exp_avg"][k], np.float32).reshape(shapes[k])),
+                        "exp_avg_sq": torch.from_numpy(np.ascontiguousarray(optimizer["exp_avg_sq"][k], np.float32).reshape(shapes[k]))}
+    return opt.state_dict()
+
+
+def save(folder, epoch, state, prefix="", optimizer=None, extra=None):
+    """Writes checkpoint_<epoch>.pth as train_foldingnet.py:173-177 does: {'epoch', 'model', 'optimizer'}.  Without
+    `optimizer` the optimizer entry is empty; with it (see optimizer_state_dict) it is a torch.optim.Adam state_dict and
+    every num_batches_tracked is the optimizer's step count.  extra: further top-level entries (the trainer's counters)."""
     import torch
     os.makedirs(folder, exist_ok=True)
+    tracked = 7 if optimizer is None else int(optimizer["step"])
     sd = {}
     for k in key_names(prefix):
         short = k[len(prefix):]
-        sd[k] = torch.tensor(7, dtype=torch.int64) if k.endswith("num_batches_tracked") else torch.from_numpy(
+        sd[k] = torch.tensor(tracked, dtype=torch.int64) if k.endswith("num_batches_tracked") else torch.from_numpy(
             np.ascontiguousarray(state[short], np.float32))
-    torch.save({"epoch": epoch, "model": sd, "optimizer": {"state": {}, "param_groups": []}},
-               checkpoint_path(folder, epoch))
+    ck = {"epoch": epoch, "model": sd,
+          "optimizer": {"state": {}, "param_groups": []} if optimizer is None else optimizer_state_dict(optimizer)}
+    ck.update(extra or {})
+    torch.save(ck, checkpoint_path(folder, epoch))
+
+
+def load_training(folder, epoch):
+    """(state, optimizer, checkpoint) of a checkpoint `save` wrote with an optimizer: optimizer = {'step', 'exp_avg',
+    'exp_avg_sq'} keyed by parameter_names(), or None where the checkpoint's optimizer entry is empty."""
+    import torch
+    ck = torch.load(checkpoint_path(folder, epoch), map_location="cpu", weights_only=False)
+    st = ck["optimizer"].get("state", {})
+    opt = None
+    if st:
+        names = parameter_names()
+        if sorted(st) != list(range(len(names))):
+            raise KeyError("checkpoint %s: the optimizer state has %d entries, the model %d parameters"
+                           % (checkpoint_path(folder, epoch), len(st), len(names)))
+        opt = {"step": int(float(st[0]["step"])), "exp_avg": {k: st[i]["exp_avg"].numpy() for i, k in enumerate(names)},
+               "exp_avg_sq": {k: st[i]["exp_avg_sq"].numpy() for i, k in enumerate(names)}}
+    return load(folder, epoch), opt, ck
+
+
+def initial_weights(seed=0):
+    """A fresh model as torch initialises FoldingNet_graph(): every Conv1d / Linear weight and bias U(-1 / sqrt(fan_in),
+    1 / sqrt(fan_in)) (kaiming_uniform_(a = sqrt(5)) on the weight and the matching bound on the bias both come to that),
+    every BatchNorm1d weight 1, bias 0, running_mean 0, running_var 1.  Drawn from np.random.default_rng(seed), layer by
+    layer in state-dict order -- the same distribution as torch's, not its random stream."""
+    rng = np.random.default_rng(seed)
+    s = {}
+    layers = [("encoder." + name, fi, fo, conv) for name, fi, fo, conv in ENC_LAYERS] + \
+             [("decoder." + name, fi, fo, True) for name, fi, fo in DEC_LAYERS]
+    for k, fi, fo, conv in layers:
+        bound = 1.0 / np.sqrt(fi)
+        s[k + ".weight"] = rng.uniform(-bound, bound, (fo, fi, 1) if conv else (fo, fi)).astype(np.float32)
+        s[k + ".bias"] = rng.uniform(-bound, bound, fo).astype(np.float32)
+    for i, (_, _, fo, _) in enumerate(ENC_LAYERS[:6]):
+        bn = "encoder.bn%d." % (i + 1)
+        s[bn + "weight"] = np.ones(fo, np.float32)
+        s[bn + "bias"] = np.zeros(fo, np.float32)
+        s[bn + "running_mean"] = np.zeros(fo, np.float32)
+        s[bn + "running_var"] = np.ones(fo, np.float32)
+    return s
 
 
 # ------------------------------------------------------------------------------------------------ canonical layout

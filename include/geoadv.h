@@ -505,6 +505,75 @@ int geoadv_fold_forward(const geoadv_fold *fold, int b, int n, const float *pc, 
                         void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FoldingNet training: one step of transfer/foldingnet/train_foldingnet.py:76-117 -- FoldingNet_graph in train mode (batch
+ * statistics, eps 1e-5, running statistics 0.9 / 0.1 with the unbiased variance), loss = ChamferLoss(points, recon) (batch
+ * mean of mean_j min_k d + mean_k min_j d, squared distances; its gradient reaches recon only), torch.optim.Adam with
+ * weight decay on every parameter.  csrc/fold_train.hip states the pool backward's rule and the optimizer exactly.  One
+ * handle = one model with a fixed batch and point count; no process-wide state; a step is bitwise reproducible.  A handle
+ * keeps about 12 KB of device memory per decoder row (batch * 2025) and 15 KB per point: 1.8 GB at 32 x 2048, and about
+ * 27 GB at batch 1024 (with 17 ... 128 points).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct geoadv_fold_trainer geoadv_fold_trainer;
+typedef struct geoadv_fold_train_config {
+    int   batch;            /* 2 ... 1024 (bn6 takes its statistics over the clouds of the batch), batch * n_points <= 2^17 */
+    int   n_points;         /* 17 ... 16384, as geoadv_fold_forward                               */
+    float learning_rate;    /* 1e-4                                                                */
+    float weight_decay;     /* 1e-6, added to the gradient of every parameter                      */
+    long long seed;         /* key of the device neighbour sampler (taken modulo 2^64)             */
+    long long initial_step; /* optimizer steps taken so far (0, or a restored value)               */
+    long long initial_ordinal; /* clouds seen so far: the device sampler's next cloud ordinal      */
+} geoadv_fold_train_config;
+/* init: HOST values of every parameter (mean / var = the running statistics), in geoadv_fold_weights' layout.  Adam's
+ * slots start at zero; geoadv_fold_trainer_set_slots restores exp_avg / exp_avg_sq (flat, in the parameter layout). */
+int  geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoadv_fold_weights *init, const geoadv_fold_train_config *cfg);
+void geoadv_fold_trainer_destroy(geoadv_fold_trainer *t);
+int  geoadv_fold_trainer_set_slots(geoadv_fold_trainer *t, const float *slot1, const float *slot2);
+/* x: device [batch][n][3].  sampling / picks (device int32 [2][batch][n][16]) as geoadv_fold_forward: read with
+ * GEOADV_FOLD_PICKS_GIVEN, written (may be NULL) with GEOADV_FOLD_PICKS_DEVICE, where cloud k draws with ordinal
+ * (clouds seen so far) + k.  loss / mid_loss (device floats, of the PRE-update parameters: ChamferLoss against recon and
+ * against fold1's output) may be NULL.  Updates the parameters, slots, running statistics, step and ordinal counters. */
+int geoadv_fold_trainer_step(geoadv_fold_trainer *t, const float *x, int sampling, int *picks, float *loss, float *mid_loss,
+                             void *stream);
+/* Device pointers of the flat parameter / gradient buffers (`count` floats each); offsets52[4 l + f] = where layer l's
+ * weights [in][out] (f 0), biases (1), BN weight (2), BN bias (3) sit ((size_t)-1: none), layers in the order conv1 .. conv5,
+ * fc1, fc2, fold1.conv1 .. 3, fold2.conv1 .. 3; moving_offsets13[l] = where its statistics sit in the BN arenas (may be NULL). */
+int geoadv_fold_trainer_buffers(geoadv_fold_trainer *t, float **params, float **grads, size_t *count);
+int geoadv_fold_trainer_layout(const geoadv_fold_trainer *t, size_t *offsets52, size_t *moving_offsets13);
+int geoadv_fold_trainer_counters(const geoadv_fold_trainer *t, long long *step, long long *ordinal);
+/* Read-only TEST / export view of what the last step kept: *ptr and its element count.
+ *   BN_MEAN / BN_VAR / RUNNING_MEAN / RUNNING_VAR / BN_INV / BN_SHIFT  float [C_layer], layer 0 .. 5 (bn1 .. bn6): the batch's
+ *                  mean and biased variance, the running statistics, the folded constants (the step's BN output is
+ *                  a * inv + shift, two fp32 roundings)
+ *   PRE_BN         float [rows][C_layer]   the stored pre-BN activation; rows = batch * n (layers 0 .. 4) or batch (5)
+ *   POOL_WINNER    int [batch * n][64 | 128]  pool 0 / 1: the row (in its cloud) whose value each (point, channel) took, -1
+ *                  where the maximum is not positive
+ *   GMAX_ROW       int [batch][1024]       the first maximal row of bn5's output
+ *   HIDDEN         float [batch * 2025][512]  the ReLU outputs of fold1.conv1, fold1.conv2, fold2.conv1, fold2.conv2 (0 .. 3)
+ *   PICKS / COLS   int [2][batch][n][16]; COV float [batch][n][9]; CODE [batch][512]; MID / RECON [batch][2025][3]
+ *   CHAMFER_IDX    int: 0 = nearest recon point of every input point [batch][n], 1 = nearest input point [batch][2025]
+ *   SLOT1 / SLOT2  float [count]           Adam's exp_avg / exp_avg_sq in the parameter layout */
+#define GEOADV_FOLD_STATE_BN_MEAN       0
+#define GEOADV_FOLD_STATE_BN_VAR        1
+#define GEOADV_FOLD_STATE_RUNNING_MEAN  2
+#define GEOADV_FOLD_STATE_RUNNING_VAR   3
+#define GEOADV_FOLD_STATE_BN_INV        4
+#define GEOADV_FOLD_STATE_BN_SHIFT      5
+#define GEOADV_FOLD_STATE_PRE_BN        6
+#define GEOADV_FOLD_STATE_POOL_WINNER   7
+#define GEOADV_FOLD_STATE_GMAX_ROW      8
+#define GEOADV_FOLD_STATE_HIDDEN        9
+#define GEOADV_FOLD_STATE_PICKS        10
+#define GEOADV_FOLD_STATE_COLS         11
+#define GEOADV_FOLD_STATE_COV          12
+#define GEOADV_FOLD_STATE_CODE         13
+#define GEOADV_FOLD_STATE_MID          14
+#define GEOADV_FOLD_STATE_RECON        15
+#define GEOADV_FOLD_STATE_CHAMFER_IDX  16
+#define GEOADV_FOLD_STATE_SLOT1        17
+#define GEOADV_FOLD_STATE_SLOT2        18
+int geoadv_fold_trainer_state(const geoadv_fold_trainer *t, int what, int layer, const void **ptr, size_t *count);
+
+/* ------------------------------------------------------------------------------------------
  * The attack loop: AdvAE (src/adv_ae.py:30-251) + Adversary (src/adversary.py:9-57).
  * One handle = one batch slot of `batch` clouds with device-resident state
  * (pert, Adam m/v/beta powers, best-so-far outputs).

@@ -1,0 +1,330 @@
+"""GPU: the FoldingNet training step (csrc/fold_train.hip) against the float64 model of tests/_fold_train_model64.py with
+every discrete decision of the step PINNED to the GPU's own (the method of test_gpu_cls_train_pinned.py): the ReLU masks
+of bn1..4 and bn6, rebuilt on the host as (a * inv + shift) > 0 in float32 from the step's stored pre-BN activation and
+folded constants; both pools' winners; the global maximum's rows; the decoder's four ReLU masks (stored output > 0);
+Chamfer's nearest indices.  The model takes cov and the neighbour columns of the step itself (the graph build has its own
+tests).  Each disagreeing pin must lie within PIN_MARGIN = PIN_ULPS fp32 ulps (of 1: activations and coordinates are O(1))
+of its boundary in fp64, and at most PIN_SHARE of the pins of a layer may disagree.
+
+Tolerances (PROFILES; the worst measured values are in MEASURED, and every run with -s prints its own): loss / mid loss
+(relative), code, mid and recon (of their largest magnitude), gradients ||g - g64|| <= tol ||g64|| per variable, Adam's
+slots (relative norm), the parameter update (param_error: over the elements whose gradient is not next to zero, beyond the fp32
+parameter's own half-ulp rounding), running
+statistics (of their largest magnitude).  The batch mean / variance of every BN layer equal the float64 moments of the
+step's OWN stored activation within 2^-22 / 2^-20 relative (the device adds fp32 values in double and rounds once).
+The biases of conv1..conv5 and fc1 feed a batch norm, and bn5's bias reaches bn6 as a per-channel constant through the
+maximum over points: their gradients are zero in exact arithmetic and rounding noise on both sides (Adam turns that noise
+into full-size updates), so they are compared as noise (the noise tolerance, of the layer's BN-weight gradient) and left out of the
+parameter and slot checks.  Every step is checked against the model started from the handle's own state before that step
+(its exported fp32 parameters, running statistics and slots), so three steps are three independent one-step checks.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import _fold_model64 as F64  # noqa: E402
+import _fold_train_model64 as M  # noqa: E402
+from geometric_adv_amd import fold_weights as FW  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+PIN_ULPS = 6000          # 3.6e-4; the farthest disagreeing pin measured lies 1e-4 (1700 ulps) from its boundary
+PIN_MARGIN = PIN_ULPS * 2.0 ** -24
+PIN_SHARE = 1e-3
+PARAM_SELECT = 1e-3
+STAT_TOL = (2.0 ** -22, 2.0 ** -20)
+# Each constant is at most 4 x the worst value measured on the MI355X over the cases below (MEASURED).
+MEASURED = {"well": dict(loss=6.9e-6, out=1.3e-5, grad=9.1e-5, noise=6.6e-7, param=6.7e-6, slot=1.4e-4, running=7.7e-7)}
+PROFILES = {"well": dict(loss=2.5e-5, out=5e-5, grad=1.1e-4, noise=2.5e-6, param=2.5e-5, slot=2e-4, running=1.4e-6)}
+GRAD_TOL, PARAM_TOL, RUNNING_TOL = (PROFILES["well"][k] for k in ("grad", "param", "running"))
+
+FED_BIASES = ["encoder.conv%d.bias" % i for i in range(1, 6)] + ["encoder.fc1.bias", "encoder.bn5.bias"]
+BN_OF_BIAS = {k: "encoder.bn%d.weight" % (i + 1) for i, k in enumerate(FED_BIASES[:6])}
+BN_OF_BIAS["encoder.bn5.bias"] = "encoder.bn5.weight"
+RELU_BN = (1, 2, 3, 4, 6)
+
+
+def _trainer(w, B, n, **kw):
+    from geometric_adv_amd.fold_trainer import FoldingNetTrainer
+    return FoldingNetTrainer(weights=w, num_points=n, batch_size=B, **kw)
+
+
+def _batch(B, n, seed):
+    return (np.random.default_rng(seed).random((B, n, 3)) - 0.5).astype(np.float32)
+
+
+def gpu_decisions(tr):
+    pins = {"relu": {}, "win": [tr.state("pool_winner", p).astype(np.int64) for p in (0, 1)],
+            "gmax": tr.state("gmax_row").astype(np.int64), "hidden": [tr.state("hidden", k) > 0 for k in range(4)],
+            "chamfer": (tr.state("chamfer_idx", 0).astype(np.int64), tr.state("chamfer_idx", 1).astype(np.int64))}
+    stats = [0.0, 0.0]
+    for i in range(1, 7):
+        a = tr.state("pre_bn", i - 1)
+        if i in RELU_BN:
+            pins["relu"][i] = (a * tr.state("bn_inv", i - 1) + tr.state("bn_shift", i - 1)) > 0
+        a64 = a.astype(np.float64)
+        m64, v64 = a64.mean(0), a64.var(0)
+        mg, vg = tr.state("bn_mean", i - 1).astype(np.float64), tr.state("bn_var", i - 1).astype(np.float64)
+        stats[0] = max(stats[0], float((np.abs(mg - m64) / (np.abs(m64) + np.sqrt(v64))).max()))
+        stats[1] = max(stats[1], float((np.abs(vg - v64) / (v64 + 1e-30)).max()))
+    return pins, stats
+
+
+def _rel(a, b):
+    return float(np.linalg.norm(np.asarray(a, np.float64).reshape(-1) - np.asarray(b).reshape(-1)) / max(np.linalg.norm(b), 1e-300))
+
+
+def param_error(new, new64, old64, g64):
+    """g64: the gradient Adam sees (d loss / d p + weight_decay * p).  Error of a variable's update over the elements whose fp64 gradient is at least PARAM_SELECT of the variable's largest
+    (Adam divides by |g| + eps: the first step is lr * sign(g), which rounding noise decides where g is next to zero), beyond
+    the stored fp32 parameter's own half-ulp rounding 2^-24 ||p||, relative to the fp64 update's norm."""
+    sel = np.abs(g64) >= PARAM_SELECT * np.abs(g64).max()
+    diff = np.linalg.norm((np.asarray(new, np.float64) - new64)[sel]) - 2.0 ** -24 * np.linalg.norm(old64[sel])
+    return max(0.0, float(diff)) / max(np.linalg.norm((new64 - old64)[sel]), 1e-300)
+
+
+def run_steps(w, x, steps=1, picks=None, seed=5, ordinal=0, weight_decay=1e-6, step0=0, slots0=None, keep=None):
+    """`steps` steps of one handle on x, each followed by the model pinned to that step's decisions and started from the
+    handle's own state before the step.  Returns the list of per-step error dicts."""
+    B, n = x.shape[:2]
+    tr = _trainer(w, B, n, seed=seed, ordinal=ordinal, weight_decay=weight_decay, step=step0, slots=slots0)
+    out = []
+    for s in range(steps):
+        before = tr.export_state_dict()
+        state64 = {k: v.astype(np.float64) for k, v in before.items()}
+        sl = tr.slots()
+        slots64 = {k: (sl["exp_avg"][k].astype(np.float64), sl["exp_avg_sq"][k].astype(np.float64)) for k in M.PARAM_KEYS}
+        loss, mid = tr.train_step(x, picks=picks)
+        pins, stats = gpu_decisions(tr)
+        ref = M.step(state64, x.astype(np.float64), tr.state("cov"), tr.state("cols"), steps_done=step0 + s, slots=slots64, pins=pins,
+                     weight_decay=weight_decay)
+        if keep is not None:
+            keep.append((state64, slots64, pins, tr.state("cov"), tr.state("cols"), tr.export_state_dict(), ref))
+        err = {"stats": stats, "loss": abs(loss - ref["loss"]) / ref["loss"], "mid": abs(mid - ref["mid_loss"]) / ref["mid_loss"],
+               "loss_gpu": loss, "loss64": ref["loss"]}
+        for k in ("code", "recon", "mid"):
+            err["out_" + k] = float(np.abs(tr.state(k) - ref[k]).max() / np.abs(ref[k]).max())
+        err["pins"] = {k: (c, c / float(t), d) for k, (c, t, d) in ref["disagree"].items()}
+        grads, new, slots = tr.gradients(), tr.export_state_dict(), tr.slots()
+        err["grad"] = {k: _rel(grads[k], g) for k, g in ref["grads"].items() if k not in FED_BIASES}
+        err["noise"] = {k: float(np.linalg.norm(grads[k]) / np.linalg.norm(ref["grads"][BN_OF_BIAS[k]])) for k in FED_BIASES}
+        err["param"], err["slot"] = {}, {}
+        for k in M.PARAM_KEYS:
+            if k in FED_BIASES:
+                continue
+            err["param"][k] = param_error(new[k], ref["new_state"][k], state64[k], ref["grads"][k] + weight_decay * state64[k])
+            err["slot"][k] = max(_rel(slots["exp_avg"][k], ref["slots"][k][0]), _rel(slots["exp_avg_sq"][k], ref["slots"][k][1]))
+        err["running"] = max(float(np.abs(new[k] - ref["new_state"][k]).max() / np.abs(ref["new_state"][k]).max())
+                             for k in ref["new_state"] if "running" in k)
+        out.append(err)
+    return out
+
+
+def report(name, errs):
+    for s, e in enumerate(errs):
+        wg = max(e["grad"].items(), key=lambda kv: kv[1])
+        print("\n%s step %d: loss %.3g mid %.3g | code %.3g recon %.3g mid %.3g | stats %.2g / %.2g | worst gradient %s %.3g | noise %.3g | "
+              "param %.3g | slot %.3g | running %.3g | pins differing %s" % (
+                  name, s + 1, e["loss"], e["mid"], e["out_code"], e["out_recon"], e["out_mid"], e["stats"][0], e["stats"][1], wg[0], wg[1],
+                  max(e["noise"].values()), max(e["param"].values()), max(e["slot"].values()), e["running"],
+                  {k: "%d (%.2g of the layer, %.2g away)" % v for k, v in e["pins"].items() if v[0]}))
+        for what in ("grad", "param", "slot"):
+            print("  worst %s:" % what, ", ".join("%s %.3g" % kv for kv in sorted(e[what].items(), key=lambda kv: -kv[1])[:4]))
+
+
+def check(errs, profile="well"):
+    T = PROFILES[profile]
+    for e in errs:
+        for k, (count, share, dist) in e["pins"].items():
+            assert dist <= PIN_MARGIN, (k, count, dist)
+            assert share <= PIN_SHARE, (k, count, share)
+        assert e["stats"][0] <= STAT_TOL[0] and e["stats"][1] <= STAT_TOL[1], e["stats"]
+        assert e["loss"] <= T["loss"] and e["mid"] <= T["loss"], (e["loss"], e["mid"])
+        assert max(e["out_code"], e["out_recon"], e["out_mid"]) <= T["out"], (e["out_code"], e["out_recon"], e["out_mid"])
+        for what in ("grad", "param", "slot"):
+            bad = {k: v for k, v in e[what].items() if not v <= T[what]}
+            assert not bad, (what, bad)
+        assert max(e["noise"].values()) <= T["noise"], e["noise"]
+        assert e["running"] <= T["running"], e["running"]
+
+
+def _two_shapes(n, seed):
+    """The two-cloud batch: a uniform cube and a flattened ellipsoid's surface.  bn6 normalises two values per channel, and
+    what its backward passes on is eps / (var + eps) of the gradient: two clouds of one distribution have pooled features
+    whose difference lies below sqrt(eps) in many channels (variance down to 2e-8 for two uniform cubes of 256 points), where
+    the fp32 rounding of fc1's output decides that factor.  Two different shapes keep the variance above eps."""
+    r = np.random.default_rng(seed)
+    v = r.standard_normal((n, 3))
+    return np.stack([r.random((n, 3)) - 0.5, 0.4 * v / np.linalg.norm(v, axis=1, keepdims=True) * np.array([1, 0.6, 0.3])]).astype(np.float32)
+
+
+def _given_picks(x, seed):
+    """Explicit positions drawn on the host from the float64 graph's degrees (the device graph's degrees equal them on
+    these batches: test_gpu_foldingnet.py)."""
+    _, rows = F64.graph_from_knn(x, F64.knn(x))
+    rng = np.random.default_rng(seed)
+    return np.stack([np.stack([np.stack([rng.choice(len(r), 16, replace=False) for r in rc]) for rc in rows])
+                     for _ in range(2)]).astype(np.int32)
+
+
+def test_reference_default_batch_three_steps():
+    """B = 8 x 2048, device sampling, 3 steps: every quantity after 1 and after 3 steps, and the loss falls as fp64's does."""
+    w, x = FW.synthetic_state(0), _batch(8, 2048, 1)
+    errs = run_steps(w, x, steps=3)
+    report("8 x 2048", errs)
+    check(errs)
+    # the training loss falls, as the fp64 model's own (unpinned) trajectory from the same start does
+    state, slots, own = {k: np.asarray(v, np.float64) for k, v in w.items()}, None, []
+    tr = _trainer(w, 8, 2048, seed=5)
+    tr.train_step(x)
+    cov, cols = tr.state("cov"), tr.state("cols")      # the first step's graph and columns, held for the model's three steps
+    for s in range(3):
+        r = M.step(state, x.astype(np.float64), cov, cols, steps_done=s, slots=slots)
+        state, slots = r["new_state"], r["slots"]
+        own.append(r["loss"])
+    print("losses gpu", [e["loss_gpu"] for e in errs], "fp64 own trajectory", own)
+    assert own[2] < own[0] and errs[2]["loss_gpu"] < errs[0]["loss_gpu"]
+
+
+def test_smallest_batch_with_explicit_picks():
+    w, x = FW.synthetic_state(1), _two_shapes(256, 2)
+    errs = run_steps(w, x, steps=1, picks=_given_picks(x, 3))
+    report("2 x 256 given picks", errs)
+    check(errs)
+
+
+def test_odd_point_count():
+    w, x = FW.synthetic_state(2), _batch(3, 1001, 4)
+    errs = run_steps(w, x, steps=1, ordinal=11)
+    report("3 x 1001", errs)
+    check(errs)
+
+
+def test_batch_32():
+    w, x = FW.synthetic_state(0), _batch(32, 2048, 6)
+    errs = run_steps(w, x, steps=1)
+    report("32 x 2048", errs)
+    check(errs)
+
+
+def test_two_steps_from_equal_state_are_bitwise_equal_and_picks_follow_the_ordinals():
+    w, x = FW.synthetic_state(0), _batch(4, 512, 7)
+    got = []
+    for _ in range(2):
+        tr = _trainer(w, 4, 512, seed=9, ordinal=3)
+        losses = [tr.train_step(x), tr.train_step(x)]
+        flat = np.concatenate([v.reshape(-1) for _, v in sorted(tr.export_state_dict().items())])
+        g = np.concatenate([v.reshape(-1) for _, v in sorted(tr.gradients().items())])
+        got.append((losses, flat, g, tr.state("picks"), tr.counters()))
+        deg = tr.degrees(x).cpu().numpy()
+        # second step: ordinals 3 + 4 .. 3 + 7
+        assert np.array_equal(tr.state("picks"), F64.device_picks(9, np.arange(7, 11), deg))
+        del tr
+    assert got[0][0] == got[1][0] and got[0][4] == got[1][4] == (2, 11)
+    for a, b in zip(got[0][1:4], got[1][1:4]):
+        assert np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def test_eval_step_is_the_inference_forward_on_the_exported_weights():
+    from geometric_adv_amd.foldingnet import FoldingNetAE
+    w, x = FW.synthetic_state(0), _batch(4, 512, 8)
+    tr = _trainer(w, 4, 512, seed=9)
+    tr.train_step(x)
+    got = tr.eval_step(x, cloud_offset=5)
+    ae = FoldingNetAE(state=tr.export_state_dict(), seed=9)
+    want = ae.forward(x, cloud_offset=5)
+    for k in ("code", "recon", "picks"):
+        assert np.array_equal(got[k].cpu().numpy(), want[k].cpu().numpy()), k
+    assert not np.array_equal(want["code"].cpu().numpy(), FoldingNetAE(state=w, seed=9).forward(x, cloud_offset=5)["code"].cpu().numpy())
+
+
+def test_refuses_one_cloud_on_the_device_side_too():
+    import ctypes as C
+    from geometric_adv_amd import _lib
+    from geometric_adv_amd.fold_trainer import _FoldTrainConfig
+    from geometric_adv_amd.foldingnet import _FoldWeights
+    canon = FW.canonical(FW.synthetic_state(0))
+    hw = _FoldWeights()
+    for key, arrays in canon.items():
+        for i, a in enumerate(arrays):
+            getattr(hw, key)[i] = a.ctypes.data if a is not None else None
+    h = C.c_void_p()
+    cfg = _FoldTrainConfig(1, 256, 1e-4, 1e-6, 0, 0, 0)
+    assert _lib.lib().geoadv_fold_trainer_create(C.byref(h), C.byref(hw), C.byref(cfg)) != 0
+    _lib.lib().geoadv_last_error.restype = C.c_char_p
+    assert b"bn6" in _lib.lib().geoadv_last_error()
+
+
+def test_train_foldingnet_checkpoints_resume_and_load(tmp_path):
+    """train_foldingnet for 2 epochs on a small synthetic set (5 clouds at batch 2: batches of 2, 2 and a dropped 1), then
+    one more epoch from --checkpoint_num 2; FoldingNetAE reads the checkpoints and torch's Adam accepts the optimizer entry."""
+    import torch
+    from geometric_adv_amd import train_foldingnet
+    from geometric_adv_amd.foldingnet import FoldingNetAE
+    top = str(tmp_path)
+    np.save(os.path.join(top, "train.npy"), _batch(5, 256, 10))
+    np.save(os.path.join(top, "val.npy"), _batch(2, 256, 11))
+    args = ["--top_dir", top, "--training_set", "train.npy", "--validation_set", "val.npy", "--batchSize", "2", "--num_points", "256",
+            "--outf", "fold", "--graph_seed", "3"]
+    assert train_foldingnet.main(args + ["--nepoch", "2"]) == 0
+    assert train_foldingnet.main(args + ["--nepoch", "3", "--checkpoint_num", "2"]) == 0
+    for epoch, steps in ((1, 2), (2, 4), (3, 6)):
+        ck = torch.load(os.path.join(top, "fold", "checkpoint_%d.pth" % epoch), map_location="cpu", weights_only=False)
+        assert ck["epoch"] == epoch and ck["graph_ordinal"] == 2 * steps
+        assert int(ck["optimizer"]["state"][0]["step"]) == steps
+    ae = FoldingNetAE(os.path.join(top, "fold"), 3, seed=3)
+    assert np.isfinite(ae.get_reconstructions(_batch(2, 256, 12))).all()
+    # run_transfer reads the epoch-2 checkpoint through its own flags and lookup, as the README's pipeline does
+    from test_gpu_atlasnet import _eval_folder
+    from geometric_adv_amd import run_transfer
+    adv = _eval_folder(tmp_path, 256)
+    run_transfer.main(["--top_dir", top, "--ae_folder", "log/ae", "--attack_pc_idx", "log/ae/eval/sel_idx.npy", "--transfer_ae_type",
+                       "FoldingNet", "--transfer_ae_folder", "fold", "--transfer_ae_restore_epoch", "2", "--graph_seed", "17"])
+    out = tmp_path / "fold" / "eval" / "attack_res_transfer"
+    ae2 = FoldingNetAE(os.path.join(top, "fold"), 2, seed=17)
+    for name in ("chair", "car"):
+        if name in adv:
+            rec = np.load(out / name / "transferred_pc_recon.npy")
+            assert rec.shape == (1, len(adv[name][0]), 2025, 3)
+            assert np.array_equal(rec[0], ae2.get_reconstructions(adv[name][0]))
+
+
+def test_large_weight_decay_from_restored_slots_and_step():
+    """weight_decay 1e-2 (where the decay term is 1e-3 ... 1 of the gradients, not below every tolerance as at the default
+    1e-6), continuing from restored Adam slots at step 7, small enough that sqrt(v) is within reach of epsilon: set_slots, the bias corrections at t > 1 and the
+    m / sqrt(v) arithmetic on the device.  At this operating point the GPU's update must also lie at least 10 tolerances
+    from the fp64 model without weight decay and from the one with TF's epsilon placement."""
+    w, x = FW.synthetic_state(0), _batch(4, 512, 13)
+    rng = np.random.default_rng(14)
+    shapes = FW.key_shapes()
+    slots0 = {"exp_avg": {k: (1e-7 * rng.standard_normal(shapes[k])).astype(np.float32) for k in M.PARAM_KEYS},
+              "exp_avg_sq": {k: (1e-14 * (0.5 + rng.random(shapes[k]))).astype(np.float32) for k in M.PARAM_KEYS}}
+    keep = []
+    errs = run_steps(w, x, steps=2, weight_decay=1e-2, step0=7, slots0=slots0, keep=keep)
+    report("4 x 512 weight decay 1e-2 from step 7", errs)
+    check(errs)
+    state64, slots64, pins, cov, cols, new, ref = keep[0]
+    for switch in ("no_weight_decay", "tf_adam_eps"):
+        wrong = M.step(state64, x.astype(np.float64), cov, cols, steps_done=7, slots=slots64, pins=pins, weight_decay=1e-2,
+                       perturb={switch: True})
+        moved = max(param_error(new[k], wrong["new_state"][k], state64[k], ref["grads"][k] + 1e-2 * state64[k]) for k in M.PARAM_KEYS if k not in FED_BIASES)
+        print(switch, "moves the update by", moved)
+        assert moved >= 10 * PROFILES["well"]["param"], (switch, moved)
+
+
+def test_reference_sampling_draws_the_host_positions_in_the_references_order():
+    from geometric_adv_amd.foldingnet import FoldingNetAE
+    w, x = FW.synthetic_state(0), _batch(3, 128, 15)
+    tr = _trainer(w, 3, 128, seed=21, sampling="reference")
+    tr.train_step(x)
+    first = tr.state("picks")
+    tr.train_step(x)
+    ae = FoldingNetAE(state=w, seed=21, sampling="reference")
+    deg = ae.graph(x)[0].cpu().numpy()
+    assert np.array_equal(first, ae.reference_picks(deg))           # one RandomState(21) over the trainer's lifetime
+    assert np.array_equal(tr.state("picks"), ae.reference_picks(deg))
+    assert not np.array_equal(first, tr.state("picks"))
