@@ -184,19 +184,130 @@ def load(folder, overrides=None):
     return opt, {k: np.asarray(v, np.float32) for k, v in state.items()}
 
 
-def save(folder, opt, state):
+def parameter_names(nb_primitives, num_layers, decoder_bn=True):
+    """The trainable tensors in EncoderDecoder.parameters() order (the index torch's optimizer state uses): the state-dict
+    order without the running statistics and counters, no `module.` prefix."""
+    return [k for k in key_names(nb_primitives, num_layers, decoder_bn, prefix="") if not k.endswith(BN_FIELDS[2:])]
+
+
+def optimizer_state_dict(optimizer, nb_primitives, num_layers, decoder_bn=True):
+    """A real torch.optim.Adam state_dict from optimizer = {'step': int, 'lr': float, 'exp_avg': {key: array}, 'exp_avg_sq':
+    {key: array}}: state[i] = {step, exp_avg, exp_avg_sq} in parameter_names() order, plus this torch's param_groups."""
+    import torch
+    shapes = key_shapes(nb_primitives, num_layers, decoder_bn)
+    names = parameter_names(nb_primitives, num_layers, decoder_bn)
+    params = [torch.zeros(shapes[k], dtype=torch.float32, requires_grad=True) for k in names]
+    opt = torch.optim.Adam(params, lr=float(optimizer.get("lr", 1e-3)), betas=(0.9, 0.999))
+    for k, p in zip(names, params):
+        opt.state[p] = {"step": torch.tensor(float(optimizer["step"])),
+                        "exp_avg": torch.from_numpy(np.ascontiguousarray(optimizer["exp_avg"][k], np.float32).reshape(shapes[k])),
+                        "exp_avg_sq": torch.from_numpy(np.ascontiguousarray(optimizer["exp_avg_sq"][k], np.float32).reshape(shapes[k]))}
+    return opt.state_dict()
+
+
+def save(folder, opt, state, optimizer=None, tracked=None):
     """Writes network.pth (DataParallel prefix, num_batches_tracked included, as the reference's trainer does) and
-    options.json."""
+    options.json.  tracked: the value of every num_batches_tracked (the training steps taken; 7 where not given).
+    optimizer (see optimizer_state_dict): also writes optimizer.pth, a torch.optim.Adam state_dict, as
+    trainer_abstract.py:76-80 does."""
     import torch
     os.makedirs(folder, exist_ok=True)
     sd = {}
-    for k in key_names(int(opt["nb_primitives"]), int(opt["num_layers"]), has_decoder_bn(state)):
+    dbn = has_decoder_bn(state)
+    for k in key_names(int(opt["nb_primitives"]), int(opt["num_layers"]), dbn):
         short = k[len("module."):]
-        sd[k] = torch.tensor(7, dtype=torch.int64) if k.endswith("num_batches_tracked") else torch.from_numpy(
-            np.ascontiguousarray(state[short], np.float32))
+        sd[k] = torch.tensor(7 if tracked is None else int(tracked), dtype=torch.int64) if k.endswith("num_batches_tracked") \
+            else torch.from_numpy(np.ascontiguousarray(state[short], np.float32))
     torch.save(sd, os.path.join(folder, "network.pth"))
+    if optimizer is not None:
+        torch.save(optimizer_state_dict(optimizer, int(opt["nb_primitives"]), int(opt["num_layers"]), dbn),
+                   os.path.join(folder, "optimizer.pth"))
     with open(os.path.join(folder, "options.json"), "w") as f:
         json.dump(opt, f)
+
+
+def load_training(folder, overrides=None):
+    """(options, state, optimizer, tracked) of a folder `save` (or the reference's trainer) wrote: optimizer = {'step', 'lr',
+    'exp_avg', 'exp_avg_sq'} keyed by parameter_names(), or None where optimizer.pth is absent or holds no state; tracked =
+    the file's num_batches_tracked."""
+    import torch
+    opt, state = load(folder, overrides)
+    sd = torch.load(os.path.join(folder, "network.pth"), map_location="cpu", weights_only=True)
+    tracked = int(strip_prefix(sd)["encoder.bn1.num_batches_tracked"])
+    path = os.path.join(folder, "optimizer.pth")
+    optimizer = None
+    if os.path.exists(path):
+        osd = torch.load(path, map_location="cpu", weights_only=False)
+        st = osd.get("state", {})
+        if st:
+            names = parameter_names(int(opt["nb_primitives"]), int(opt["num_layers"]), has_decoder_bn(state))
+            if sorted(st) != list(range(len(names))):
+                raise KeyError("%s: the optimizer state has %d entries, the model %d parameters" % (path, len(st), len(names)))
+            optimizer = {"step": int(float(st[0]["step"])), "lr": float(osd["param_groups"][0]["lr"]),
+                         "exp_avg": {k: st[i]["exp_avg"].numpy() for i, k in enumerate(names)},
+                         "exp_avg_sq": {k: st[i]["exp_avg_sq"].numpy() for i, k in enumerate(names)}}
+    return opt, state, optimizer, tracked
+
+
+def initial_weights(seed=0, nb_primitives=25, num_layers=2, decoder_bn=True, number_points_eval=2500):
+    """(options, state) of a fresh model as the reference builds it: every Conv1d / Linear weight and bias U(-1 / sqrt(fan_in),
+    1 / sqrt(fan_in)) (torch's default), then weights_init (model.py:37-41): every BatchNorm1d weight N(1, 0.02), bias 0;
+    running_mean 0, running_var 1.  Drawn from np.random.default_rng(seed) in state-dict order -- the same distributions as
+    torch's, not its random stream."""
+    rng = np.random.default_rng(seed)
+    opt = dict(DEFAULT_OPTIONS, nb_primitives=nb_primitives, num_layers=num_layers, template_type="SQUARE",
+               remove_all_batchNorms=not decoder_bn, number_points_eval=number_points_eval)
+    s = {}
+
+    def layer(k, fi, fo, conv):
+        bound = 1.0 / np.sqrt(fi)
+        s[k + ".weight"] = rng.uniform(-bound, bound, (fo, fi, 1) if conv else (fo, fi)).astype(np.float32)
+        s[k + ".bias"] = rng.uniform(-bound, bound, fo).astype(np.float32)
+
+    def bn(k, fo):
+        s[k + ".weight"] = (1.0 + 0.02 * rng.standard_normal(fo)).astype(np.float32)
+        s[k + ".bias"] = np.zeros(fo, np.float32)
+        s[k + ".running_mean"] = np.zeros(fo, np.float32)
+        s[k + ".running_var"] = np.ones(fo, np.float32)
+
+    for name, fi, fo in ENC_LAYERS:
+        layer("encoder." + name, fi, fo, name.startswith("conv"))
+    for i, (_, _, fo) in enumerate(ENC_LAYERS):
+        bn("encoder.bn%d" % (i + 1), fo)
+    for p in range(nb_primitives):
+        d = "decoder.decoder.%d." % p
+        for name, fi, fo, _ in dec_layers(num_layers):
+            layer(d + name, fi, fo, True)
+        if decoder_bn:
+            for _, _, fo, b in dec_layers(num_layers)[:-1]:
+                bn(d + b, fo)
+    return opt, s
+
+
+# ------------------------------------------------------------------------------------------------ train-mode template
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9e3779b97f4a7c15
+
+
+def _mix64(z):
+    z = np.asarray(z, np.uint64)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
+    return z ^ (z >> np.uint64(31))
+
+
+def train_template(seed, tracked, nb_primitives, points):
+    """The template points the device draws at training step `tracked` (csrc/atlas_train.hip restated): float32
+    [nb_primitives, points, 2] in [0, 1), coordinate d of point j of primitive q from
+    key = mix(mix(mix(seed + G) ^ tracked) ^ (q << 32 | j)), r = mix(key + (d + 1) G), value = (r >> 40) * 2^-24."""
+    with np.errstate(over="ignore"):
+        base = _mix64(_mix64(np.uint64((int(seed) + _GOLDEN) & _M64)) ^ np.uint64(int(tracked) & _M64))
+        q = np.arange(nb_primitives, dtype=np.uint64)[:, None, None]
+        j = np.arange(points, dtype=np.uint64)[None, :, None]
+        d = np.arange(2, dtype=np.uint64)[None, None, :]
+        key = _mix64(base ^ ((q << np.uint64(32)) | j))
+        r = _mix64(key + (d + np.uint64(1)) * np.uint64(_GOLDEN))
+    return ((r >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ canonical layout

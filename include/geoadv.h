@@ -574,6 +574,79 @@ int geoadv_fold_trainer_counters(const geoadv_fold_trainer *t, long long *step, 
 int geoadv_fold_trainer_state(const geoadv_fold_trainer *t, int what, int layer, const void **ptr, size_t *count);
 
 /* ------------------------------------------------------------------------------------------
+ * AtlasNet training: one step of transfer/atlasnet/training/trainer.py's train_iteration for the point-cloud
+ * auto-encoder -- EncoderDecoder.forward(x, train=True) (batch statistics, eps 1e-5, running statistics 0.9 / 0.1 with the
+ * unbiased variance; template points uniform in [0, 1)^2, one draw per primitive shared by the batch), fuse_primitives,
+ * loss = mean(dist1) + mean(dist2) over the whole batch (squared distances; the gradient reaches the reconstruction only),
+ * torch.optim.Adam without weight decay.  csrc/atlas_train.hip states the template generator and the optimizer exactly.
+ * One handle = one model with a fixed batch, point count and template size; no process-wide state; a step is bitwise
+ * reproducible.  A handle keeps about (14 + 4 num_layers) KB of device memory per decoder row
+ * (nb_primitives * batch * points_per_primitive) and 6 KB per input point: 2.3 GB at 32 x 2048 with 25 x 100, num_layers 2.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct geoadv_atlas_trainer geoadv_atlas_trainer;
+typedef struct geoadv_atlas_train_config {
+    int   batch;                  /* 2 ... 1024 (bn4 / bn5 take their statistics over the clouds of the batch)            */
+    int   n_points;               /* 1 ... 16384, batch * n_points <= 2^17                                                */
+    int   points_per_primitive;   /* template points per primitive in TRAIN mode (number_points / nb_primitives), >= 1;
+                                     nb_primitives * batch * points_per_primitive <= 2^18 and
+                                     nb_primitives * points_per_primitive <= 16384                                        */
+    float learning_rate;          /* 1e-3                                                                                  */
+    long long seed;               /* key of the device template generator (taken modulo 2^64)                             */
+    long long initial_step;       /* Adam steps taken so far by the CURRENT optimizer (0, or a restored value)            */
+    long long initial_tracked;    /* training steps the model has taken in all (num_batches_tracked): the generator's counter */
+} geoadv_atlas_train_config;
+/* config: as geoadv_atlas_create (points_per_primitive there is ignored here: the train config's holds).  init: HOST values
+ * of every parameter (mean / var = the running statistics).  Adam's slots start at zero; set_slots restores exp_avg /
+ * exp_avg_sq (flat, in the parameter layout).  Sizes the handle cannot hold return GEOADV_EINVAL here, never later. */
+int  geoadv_atlas_trainer_create(geoadv_atlas_trainer **out, const geoadv_atlas_config *config, const geoadv_atlas_weights *init,
+                                 const geoadv_atlas_train_config *cfg);
+void geoadv_atlas_trainer_destroy(geoadv_atlas_trainer *t);
+int  geoadv_atlas_trainer_set_slots(geoadv_atlas_trainer *t, const float *slot1, const float *slot2);
+/* The reference builds a NEW Adam with lrate / 10 at its decay epochs: reset_optimizer != 0 zeroes both slots and the
+ * Adam step count as well (num_batches_tracked goes on). */
+int  geoadv_atlas_trainer_set_learning_rate(geoadv_atlas_trainer *t, float learning_rate, int reset_optimizer);
+/* x: device [batch][n_points][3].  template_points: device [nb_primitives][points_per_primitive][2], read if
+ * given_template != 0, else written with the step's draw (may then be NULL).  loss (a device float, of the PRE-update
+ * parameters) may be NULL.  Updates the parameters, slots, running statistics and both counters. */
+int geoadv_atlas_trainer_step(geoadv_atlas_trainer *t, const float *x, int given_template, float *template_points, float *loss,
+                              void *stream);
+/* Device pointers of the flat parameter / gradient buffers (`count` floats each); offsets[4 l + f] = where layer l's
+ * weights [in][out] (f 0), biases (1), BN weight (2), BN bias (3) sit ((size_t)-1: none); layers 0 .. 4 = the encoder's
+ * conv1, conv2, conv3, lin1, lin2, then the decoder's conv1, conv2, conv_list[0 .. num_layers), last_conv (8 + num_layers
+ * layers in all; offsets holds 4 * 12 entries).  A decoder entry is primitive 0's; primitive p follows at p * (size of one
+ * primitive's array).  moving_offsets[l] (12 entries, may be NULL) = where the layer's statistics sit in the BN arenas. */
+int geoadv_atlas_trainer_buffers(geoadv_atlas_trainer *t, float **params, float **grads, size_t *count);
+int geoadv_atlas_trainer_layout(const geoadv_atlas_trainer *t, size_t *offsets48, size_t *moving_offsets12);
+int geoadv_atlas_trainer_counters(const geoadv_atlas_trainer *t, long long *step, long long *tracked);
+/* Read-only TEST / export view of what the last step kept: *ptr and its element count.  A decoder layer's arrays hold all
+ * primitives, primitive-major; rows of a primitive are (cloud, template point), cloud-major.
+ *   BN_MEAN / BN_VAR / RUNNING_MEAN / RUNNING_VAR / BN_INV / BN_SHIFT  float [C] (encoder) or [nb][C] (decoder) of a layer
+ *                  with batch norm: the batch's mean and biased variance, the running statistics, the folded constants (the
+ *                  step's BN output is a * inv + shift, two fp32 roundings).  A decoder without batch norm has inv 1, shift 0.
+ *   PRE_BN         float: the stored pre-BN activation: [batch * n][C] (layers 0 .. 2), [batch][1024] (3, 4),
+ *                  [nb][batch * p][512] (6 ...).  Layer 5 (the decoder's conv1) returns t1 = conv1(template) [nb][p][1024]:
+ *                  its pre-BN activation is t1[j] + latent[b] and is never stored.
+ *   GMAX_ROW       int [batch][1024]   the first maximal row of bn3's output
+ *   TEMPLATE       float [nb][p][2]; LATENT [batch][1024]; RECON [batch][nb * p][3]
+ *   CHAMFER_IDX    int: 0 = nearest recon point of every input point [batch][n], 1 = nearest input point [batch][nb * p]
+ *   SLOT1 / SLOT2  float [count]       Adam's exp_avg / exp_avg_sq in the parameter layout */
+#define GEOADV_ATLAS_STATE_BN_MEAN       0
+#define GEOADV_ATLAS_STATE_BN_VAR        1
+#define GEOADV_ATLAS_STATE_RUNNING_MEAN  2
+#define GEOADV_ATLAS_STATE_RUNNING_VAR   3
+#define GEOADV_ATLAS_STATE_BN_INV        4
+#define GEOADV_ATLAS_STATE_BN_SHIFT      5
+#define GEOADV_ATLAS_STATE_PRE_BN        6
+#define GEOADV_ATLAS_STATE_GMAX_ROW      7
+#define GEOADV_ATLAS_STATE_TEMPLATE      8
+#define GEOADV_ATLAS_STATE_LATENT        9
+#define GEOADV_ATLAS_STATE_RECON        10
+#define GEOADV_ATLAS_STATE_CHAMFER_IDX  11
+#define GEOADV_ATLAS_STATE_SLOT1        12
+#define GEOADV_ATLAS_STATE_SLOT2        13
+int geoadv_atlas_trainer_state(const geoadv_atlas_trainer *t, int what, int layer, const void **ptr, size_t *count);
+
+/* ------------------------------------------------------------------------------------------
  * The attack loop: AdvAE (src/adv_ae.py:30-251) + Adversary (src/adversary.py:9-57).
  * One handle = one batch slot of `batch` clouds with device-resident state
  * (pert, Adam m/v/beta powers, best-so-far outputs).

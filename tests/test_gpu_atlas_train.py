@@ -1,0 +1,375 @@
+"""GPU: the AtlasNet training step (csrc/atlas_train.hip) against the float64 model of tests/_atlas_train_model64.py with every
+discrete decision of the step PINNED to the GPU's own (the method of test_gpu_fold_train.py): the ReLU masks, rebuilt on the
+host as (a * inv + shift) > 0 in float32 from the step's stored pre-BN activation and folded constants (the decoder's first
+layer from conv1(template) + latent, as the device forms it); the maximum's rows; Chamfer's nearest indices.  The model
+takes the template points of the step itself.  Each disagreeing pin must lie within PIN_MARGIN = PIN_ULPS fp32 ulps (of 1:
+activations and coordinates are O(1)) of its boundary in fp64, and at most PIN_SHARE of the pins of a layer may disagree.
+
+Tolerances (PROFILES; the worst measured values are in MEASURED, and every run with -s prints its own): loss (relative),
+latent and recon (of their largest magnitude), gradients ||g - g64|| <= tol ||g64|| per variable, Adam's slots (relative
+norm), the parameter update (param_error: over the elements whose gradient is not next to zero, beyond the fp32 parameter's
+own half-ulp rounding), running statistics (of their largest magnitude).  The batch mean / variance of every BN layer equal
+the float64 moments of the step's OWN stored activation within 2^-22 / 2^-20 relative (the device adds fp32 values in
+double and rounds once).  The biases that feed a batch norm -- every encoder conv / lin bias, with decoder batch norm every
+decoder bias but last_conv's -- and bn3's bias (it reaches bn4 as a per-channel constant through the maximum over points)
+have a gradient of zero in exact arithmetic and rounding noise on both sides (Adam turns that noise into full-size
+updates): they are compared as noise (of the following BN weight's gradient) and left out of the parameter and slot checks.
+Every step is checked against the model started from the handle's own state before that step (its exported fp32
+parameters, running statistics and slots), so three steps are three independent one-step checks.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import _atlas_train_model64 as M  # noqa: E402
+from geometric_adv_amd import atlas_weights as AW  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+PIN_ULPS = 6000          # 3.6e-4, as test_gpu_fold_train.py
+PIN_MARGIN = PIN_ULPS * 2.0 ** -24
+PIN_SHARE = 1e-3
+PARAM_SELECT = 1e-3
+STAT_TOL = (2.0 ** -22, 2.0 ** -20)
+# Each constant is at most 4 x the worst value measured on the MI355X over the cases below (MEASURED).
+# "two": the two-cloud batch, where bn4 and bn5 each normalise two values per channel and pass on eps / (var + eps) of the
+# gradient: in the channels whose two values differ by about sqrt(eps) the fp32 rounding of lin1's / lin2's output decides
+# xhat (forward: the latent) and that factor (backward: every encoder gradient), however the step is computed.
+MEASURED = {"well": dict(loss=1.65e-5, out=2.31e-4, grad=8.29e-4, noise=2.66e-6, param=3.2e-4, slot=1.88e-3, running=1.15e-5),
+            "two": dict(loss=1.64e-6, out=5.73e-4, grad=1.01e-2, noise=4.5e-7, param=0.25, slot=1.61e-2, running=1.89e-5)}
+PROFILES = {"well": dict(loss=5e-5, out=8e-4, grad=3e-3, noise=1e-5, param=1.2e-3, slot=7e-3, running=4e-5),
+            "two": dict(loss=6e-6, out=2e-3, grad=4e-2, noise=1.8e-6, param=1.0, slot=6e-2, running=7e-5)}
+GRAD_TOL, PARAM_TOL, RUNNING_TOL = (PROFILES["well"][k] for k in ("grad", "param", "running"))
+
+# the input batches of the pinned cases: name -> (weights seed, nb, num_layers, decoder_bn, B, n, p, batch seed; < 0 = two shapes)
+CASES = {"runner": (0, 25, 2, True, 32, 2048, 100, 1), "two": (1, 3, 2, True, 2, 256, 32, -2), "odd": (2, 3, 2, True, 3, 1001, 33, 4),
+         "layers0": (3, 2, 0, True, 4, 512, 50, 5), "layers4": (4, 2, 4, True, 4, 512, 50, 6), "nobn": (5, 3, 2, False, 4, 512, 40, 7),
+         "slots": (6, 2, 1, True, 4, 512, 50, 8)}
+
+
+def fed_biases(nb, num_layers, dbn):
+    """{zero-gradient bias: the BN weight whose gradient sets its noise scale}."""
+    out = {"encoder.%s.bias" % name: "encoder.bn%d.weight" % (i + 1) for i, (name, _, _) in enumerate(AW.ENC_LAYERS)}
+    out["encoder.bn3.bias"] = "encoder.bn3.weight"
+    if dbn:
+        for q in range(nb):
+            d = "decoder.decoder.%d." % q
+            for name, _, _, bn in AW.dec_layers(num_layers)[:-1]:
+                out[d + name + ".bias"] = d + bn + ".weight"
+    return out
+
+
+def case(name):
+    wseed, nb, nl, dbn, B, n, p, seed = CASES[name]
+    opt, w = AW.synthetic_state(nb, nl, dbn, seed=wseed, number_points_eval=max(4, min(100, p)) * nb)
+    opt["number_points"] = nb * p
+    x = _batch(B, n, seed) if seed >= 0 else _two_shapes(n, -seed)
+    tmpl = np.random.default_rng(100 + abs(seed)).random((nb, p, 2)).astype(np.float32)
+    return opt, w, x, tmpl
+
+
+def _trainer(w, opt, B, n, **kw):
+    from geometric_adv_amd.atlas_trainer import AtlasNetTrainer
+    return AtlasNetTrainer(weights=w, options=opt, num_points=n, batch_size=B, **kw)
+
+
+def _batch(B, n, seed):
+    return (np.random.default_rng(seed).random((B, n, 3)) - 0.5).astype(np.float32)
+
+
+def _two_shapes(n, seed):
+    """The two-cloud batch: a uniform cube and a flattened ellipsoid's surface (bn4 / bn5 normalise two values per channel;
+    two different shapes keep their variance above eps, see test_gpu_fold_train._two_shapes)."""
+    r = np.random.default_rng(seed)
+    v = r.standard_normal((n, 3))
+    return np.stack([r.random((n, 3)) - 0.5, 0.4 * v / np.linalg.norm(v, axis=1, keepdims=True) * np.array([1, 0.6, 0.3])]).astype(np.float32)
+
+
+ENC_RELU = {"enc1": 0, "enc2": 1, "enc4": 3, "enc5": 4}
+ENC_BN = {"enc1": 0, "enc2": 1, "enc3": 2, "enc4": 3, "enc5": 4}
+
+
+def gpu_decisions(tr):
+    """(pins, [worst mean error, worst variance error] of the device's batch statistics against its own stored activation)."""
+    nb, nl, B, p = tr.nb_primitives, tr.num_layers, tr.batch_size, tr.points_per_primitive
+    pins = {"relu": {}, "gmax": tr.state("gmax_row").astype(np.int64),
+            "chamfer": (tr.state("chamfer_idx", 0).astype(np.int64), tr.state("chamfer_idx", 1).astype(np.int64))}
+    stats = [0.0, 0.0]
+
+    def moments(a, l, group=None):
+        a64 = a.astype(np.float64)
+        m64, v64 = a64.mean(0), a64.var(0)
+        mg, vg = (tr.state(k, l, group).astype(np.float64) for k in ("bn_mean", "bn_var"))
+        stats[0] = max(stats[0], float((np.abs(mg - m64) / (np.abs(m64) + np.sqrt(v64))).max()))
+        stats[1] = max(stats[1], float((np.abs(vg - v64) / (v64 + 1e-30)).max()))
+
+    for name, l in ENC_BN.items():
+        a = tr.state("pre_bn", l)
+        if name in ENC_RELU:
+            pins["relu"][name] = (a * tr.state("bn_inv", l) + tr.state("bn_shift", l)) > 0
+        moments(a, l)
+    z = tr.state("latent")
+    for li in range(2 + nl):
+        l = 5 + li
+        inv, shift = tr.state("bn_inv", l), tr.state("bn_shift", l)
+        masks = []
+        for q in range(nb):
+            a = tr.state("pre_bn", l, q)
+            if li == 0:
+                a = (a[None, :, :] + z[:, None, :]).reshape(B * p, -1)          # fp32, as the device forms it
+            masks.append((a * inv[q] + shift[q]) > 0)
+            if tr.decoder_bn:
+                moments(a, l, q)
+        pins["relu"]["dec%d" % li] = np.stack(masks)
+    return pins, stats
+
+
+def _rel(a, b):
+    return float(np.linalg.norm(np.asarray(a, np.float64).reshape(-1) - np.asarray(b).reshape(-1)) / max(np.linalg.norm(b), 1e-300))
+
+
+def param_error(new, new64, old64, g64):
+    """Error of a variable's update over the elements whose fp64 gradient is at least PARAM_SELECT of the variable's largest
+    (Adam divides by |g| + eps: the first step is lr * sign(g), which rounding noise decides where g is next to zero), beyond
+    the stored fp32 parameter's own half-ulp rounding 2^-24 ||p||, relative to the fp64 update's norm."""
+    sel = np.abs(g64) >= PARAM_SELECT * np.abs(g64).max()
+    diff = np.linalg.norm((np.asarray(new, np.float64) - new64)[sel]) - 2.0 ** -24 * np.linalg.norm(old64[sel])
+    return max(0.0, float(diff)) / max(np.linalg.norm((new64 - old64)[sel]), 1e-300)
+
+
+def one_step(tr, x, template, lr, keep=None):
+    """One step of the handle, followed by the model pinned to that step's decisions and started from the handle's own state
+    before the step.  Returns the error dict."""
+    nb, nl = tr.nb_primitives, tr.num_layers
+    keys = tr.param_keys
+    fed = fed_biases(nb, nl, tr.decoder_bn)
+    before = tr.export_state_dict()
+    state64 = {k: v.astype(np.float64) for k, v in before.items()}
+    sl = tr.slots()
+    slots64 = {k: (sl["exp_avg"][k].astype(np.float64), sl["exp_avg_sq"][k].astype(np.float64)) for k in keys}
+    steps_done = tr.counters()[0]
+    loss = tr.train_step(x, template=template)
+    used = tr.state("template")
+    pins, stats = gpu_decisions(tr)
+    ref = M.step(state64, x.astype(np.float64), used.astype(np.float64), nl, lr=lr, steps_done=steps_done, slots=slots64, pins=pins)
+    if keep is not None:
+        keep.append((state64, slots64, pins, used, tr.export_state_dict(), ref))
+    err = {"stats": stats, "loss": abs(loss - ref["loss"]) / ref["loss"], "loss_gpu": loss, "loss64": ref["loss"]}
+    for k in ("latent", "recon"):
+        err["out_" + k] = float(np.abs(tr.state(k) - ref[k]).max() / np.abs(ref[k]).max())
+    err["pins"] = {k: (c, c / float(t), d) for k, (c, t, d) in ref["disagree"].items()}
+    grads, new, slots = tr.gradients(), tr.export_state_dict(), tr.slots()
+    err["grad"] = {k: _rel(grads[k], g) for k, g in ref["grads"].items() if k not in fed}
+    err["noise"] = {k: float(np.linalg.norm(grads[k]) / np.linalg.norm(ref["grads"][fed[k]])) for k in fed}
+    err["param"], err["slot"] = {}, {}
+    for k in keys:
+        if k in fed:
+            continue
+        err["param"][k] = param_error(new[k], ref["new_state"][k], state64[k], ref["grads"][k])
+        err["slot"][k] = max(_rel(slots["exp_avg"][k], ref["slots"][k][0]), _rel(slots["exp_avg_sq"][k], ref["slots"][k][1]))
+    err["running"] = max(float(np.abs(new[k] - ref["new_state"][k]).max() / np.abs(ref["new_state"][k]).max())
+                         for k in ref["new_state"] if "running" in k)
+    return err
+
+
+def report(name, errs):
+    for s, e in enumerate(errs):
+        wg = max(e["grad"].items(), key=lambda kv: kv[1])
+        print("\n%s step %d: loss %.3g (%.6f) | latent %.3g recon %.3g | stats %.2g / %.2g | worst gradient %s %.3g | noise %.3g | "
+              "param %.3g | slot %.3g | running %.3g | pins differing %s" % (
+                  name, s + 1, e["loss"], e["loss_gpu"], e["out_latent"], e["out_recon"], e["stats"][0], e["stats"][1], wg[0], wg[1],
+                  max(e["noise"].values()), max(e["param"].values()), max(e["slot"].values()), e["running"],
+                  {k: "%d (%.2g of the layer, %.2g away)" % v for k, v in e["pins"].items() if v[0]}))
+        for what in ("grad", "param", "slot", "noise"):
+            print("  worst %s:" % what, ", ".join("%s %.3g" % kv for kv in sorted(e[what].items(), key=lambda kv: -kv[1])[:4]))
+
+
+def check(errs, profile="well"):
+    T = PROFILES[profile]
+    for e in errs:
+        for k, (count, share, dist) in e["pins"].items():
+            assert dist <= PIN_MARGIN, (k, count, dist)
+            assert share <= PIN_SHARE, (k, count, share)
+        assert e["stats"][0] <= STAT_TOL[0] and e["stats"][1] <= STAT_TOL[1], e["stats"]
+        assert e["loss"] <= T["loss"], e["loss"]
+        assert max(e["out_latent"], e["out_recon"]) <= T["out"], (e["out_latent"], e["out_recon"])
+        for what in ("grad", "param", "slot"):
+            bad = {k: v for k, v in e[what].items() if not v <= T[what]}
+            assert not bad, (what, bad)
+        assert max(e["noise"].values()) <= T["noise"], e["noise"]
+        assert e["running"] <= T["running"], e["running"]
+
+
+def run_case(name, steps=1, given=True, **kw):
+    opt, w, x, tmpl = case(name)
+    tr = _trainer(w, opt, x.shape[0], x.shape[1], **kw)
+    errs = [one_step(tr, x, tmpl if given else None, tr.learning_rate) for _ in range(steps)]
+    report(name, errs)
+    return errs
+
+
+def test_two_clouds_of_different_shapes():
+    check(run_case("two"), "two")
+
+
+def test_odd_shape():
+    check(run_case("odd"))
+
+
+@pytest.mark.parametrize("name", ["layers0", "layers4"])
+def test_num_layers_0_and_4(name):
+    check(run_case(name))
+
+
+def test_decoder_without_batch_norm():
+    check(run_case("nobn"))
+
+
+def test_runner_shape_three_steps_with_device_drawn_templates():
+    """32 x 2048 with 25 x 100, device-drawn template points: every quantity after each of 3 steps; the templates are the numpy
+    generator's, bit for bit, keyed by the training step; the loss falls."""
+    opt, w, x, _ = case("runner")
+    tr = _trainer(w, opt, 32, 2048, seed=11, tracked=5)
+    errs = []
+    for s in range(3):
+        errs.append(one_step(tr, x, None, tr.learning_rate))
+        assert np.array_equal(tr.state("template").view(np.int32), AW.train_template(11, 5 + s, 25, 100).view(np.int32))
+    report("runner", errs)
+    check(errs)
+    assert tr.counters() == (3, 8)
+    assert errs[2]["loss_gpu"] < errs[0]["loss_gpu"]
+
+
+def test_device_template_is_the_numpy_generator_bit_for_bit():
+    opt, w, x, _ = case("odd")
+    tr = _trainer(w, opt, 3, 1001, seed=-3, tracked=2 ** 40)
+    tr.train_step(x)
+    t = tr.state("template")
+    assert np.array_equal(t.view(np.int32), AW.train_template(-3, 2 ** 40, 3, 33).view(np.int32))
+    assert t.min() >= 0 and t.max() < 1 and 0.4 < t.mean() < 0.6
+    tr.train_step(x)
+    assert np.array_equal(tr.state("template").view(np.int32), AW.train_template(-3, 2 ** 40 + 1, 3, 33).view(np.int32))
+    assert not np.array_equal(tr.state("template"), t)
+
+
+def test_a_step_from_restored_slots_after_set_learning_rate():
+    """Continuing from restored Adam slots at step 7 with the learning rate changed: set_slots, the bias corrections at t > 1 and
+    m / sqrt(v) on the device; then a NEW Adam (reset_optimizer): slots and step count start again, num_batches_tracked goes on.
+    (What the tolerances can tell apart is shown on the CPU: tests/test_atlas_train_host.py.)"""
+    opt, w, x, tmpl = case("slots")
+    from geometric_adv_amd.atlas_trainer import AtlasNetTrainer
+    keys = AW.parameter_names(2, 1, True)
+    shapes = AW.key_shapes(2, 1, True)
+    rng = np.random.default_rng(14)
+    slots0 = {"exp_avg": {k: (1e-7 * rng.standard_normal(shapes[k])).astype(np.float32) for k in keys},
+              "exp_avg_sq": {k: (1e-14 * (0.5 + rng.random(shapes[k]))).astype(np.float32) for k in keys}}
+    tr = AtlasNetTrainer(weights=w, options=opt, num_points=512, batch_size=4, step=7, slots=slots0, tracked=20)
+    tr.set_learning_rate(1e-4)
+    errs = [one_step(tr, x, tmpl, 1e-4)]
+    assert tr.counters() == (8, 21)
+    tr.set_learning_rate(1e-5, reset_optimizer=True)
+    assert tr.counters() == (0, 21)
+    assert not np.any(tr.state("slot1")) and not np.any(tr.state("slot2"))
+    errs.append(one_step(tr, x, tmpl, 1e-5))
+    assert tr.counters() == (1, 22)
+    report("slots", errs)
+    check(errs)
+
+
+def test_two_handles_from_one_state_are_bitwise_equal_after_three_steps():
+    opt, w, x, _ = case("layers0")
+    got = []
+    for _ in range(2):
+        tr = _trainer(w, opt, 4, 512, seed=9)
+        losses = [tr.train_step(x) for _ in range(3)]
+        flat = np.concatenate([v.reshape(-1) for _, v in sorted(tr.export_state_dict().items())])
+        g = np.concatenate([v.reshape(-1) for _, v in sorted(tr.gradients().items())])
+        got.append((losses, flat, g, tr.counters()))
+        del tr
+    assert got[0][0] == got[1][0] and got[0][3] == got[1][3] == (3, 3)
+    for a, b in zip(got[0][1:3], got[1][1:3]):
+        assert np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def test_eval_model_is_the_inference_forward_on_the_exported_weights():
+    from geometric_adv_amd.atlasnet import AtlasNetAE
+    opt, w, x, tmpl = case("layers0")
+    tr = _trainer(w, opt, 4, 512)
+    tr.train_step(x, template=tmpl)
+    got = tr.eval_model().get_reconstructions(x)
+    want = AtlasNetAE(state=tr.export_state_dict(), options=tr.options).get_reconstructions(x)
+    assert np.array_equal(got, want)
+    assert not np.array_equal(got, AtlasNetAE(state=w, options=tr.options).get_reconstructions(x))
+
+
+def test_refuses_one_cloud_and_sizes_it_cannot_hold():
+    from geometric_adv_amd.atlas_trainer import AtlasNetTrainer
+    opt, w, _, _ = case("layers0")
+    with pytest.raises(ValueError, match="bn4"):
+        AtlasNetTrainer(weights=w, options=opt, num_points=64, batch_size=1)
+    import ctypes as C
+    from geometric_adv_amd import _lib
+    from geometric_adv_amd.atlas_trainer import _AtlasTrainConfig
+    from geometric_adv_amd.atlasnet import _AtlasConfig, _AtlasWeights
+    canon = AW.canonical(w, 2, 0)
+    hw = _AtlasWeights()
+    for key, arrays in canon.items():
+        for i, a in enumerate(arrays):
+            getattr(hw, key)[i] = a.ctypes.data if a is not None else None
+    cfg = _AtlasConfig(2, 50, 2, 1024, 512, 0, 0, 1)
+    h = C.c_void_p()
+    assert _lib.lib().geoadv_atlas_trainer_create(C.byref(h), C.byref(cfg), C.byref(hw), C.byref(_AtlasTrainConfig(1, 256, 50, 1e-3, 0, 0, 0))) == 1
+    assert b"bn4" in _lib.lib().geoadv_last_error()
+    for bad in (_AtlasTrainConfig(1024, 256, 50, 1e-3, 0, 0, 0),      # batch * n_points
+                _AtlasTrainConfig(64, 64, 8192, 1e-3, 0, 0, 0),       # decoder rows
+                _AtlasTrainConfig(4, 64, 10000, 1e-3, 0, 0, 0)):      # reconstruction points
+        assert _lib.lib().geoadv_atlas_trainer_create(C.byref(h), C.byref(cfg), C.byref(hw), C.byref(bad)) == 1
+
+
+def test_train_atlasnet_writes_the_references_files_resumes_and_run_transfer_reads_them(tmp_path):
+    """train_atlasnet for 2 short epochs on synthetic clouds (5 clouds at batch 2: batches of 2, 2 and a dropped 1), with a
+    learning-rate decay at epoch 1; a rerun with --nepoch 3 resumes; run_transfer --transfer_ae_type AtlasNet reads the folder."""
+    import json
+    import torch
+    from geometric_adv_amd import train_atlasnet
+    from geometric_adv_amd.atlasnet import AtlasNetAE
+    top = str(tmp_path)
+    np.save(os.path.join(top, "train.npy"), _batch(5, 256, 10))
+    np.save(os.path.join(top, "val.npy"), _batch(3, 256, 11))
+    args = ["--top_dir", top, "--train_pc_path", "train.npy", "--eval_pc_path", "val.npy", "--batch_size", "2", "--batch_size_test", "2",
+            "--dir_name", "atlas", "--nb_primitives", "3", "--template_type", "SQUARE", "--num_layers", "1", "--number_points", "96",
+            "--number_points_eval", "75", "--custom_data", "--no_metro", "--lr_decay_1", "1", "--seed", "3"]
+    assert train_atlasnet.main(args + ["--nepoch", "2"]) == 0
+    folder = os.path.join(top, "atlas")
+    lines = [json.loads(l[len("json_stats: "):]) for l in open(os.path.join(folder, "log.txt"))]
+    assert [l["epoch"] for l in lines] == [1, 2] and lines[0]["lr"] == 1e-3 and abs(lines[1]["lr"] - 1e-4) < 1e-12
+    assert all(np.isfinite(l[k]) for l in lines for k in ("loss_train_total", "loss_val", "fscore"))
+    opts = json.load(open(os.path.join(folder, "options.json")))
+    assert opts["start_epoch"] == 2 and opts["nb_primitives"] == 3
+    sd = torch.load(os.path.join(folder, "network.pth"), map_location="cpu", weights_only=True)
+    assert int(sd["module.encoder.bn1.num_batches_tracked"]) == 4
+    osd = torch.load(os.path.join(folder, "optimizer.pth"), map_location="cpu", weights_only=False)
+    assert int(osd["state"][0]["step"]) == 2 and abs(osd["param_groups"][0]["lr"] - 1e-4) < 1e-12      # a new Adam at epoch 1
+    assert train_atlasnet.main(args + ["--nepoch", "3"]) == 0
+    lines = [json.loads(l[len("json_stats: "):]) for l in open(os.path.join(folder, "log.txt"))]
+    assert [l["epoch"] for l in lines] == [1, 2, 3]
+    osd = torch.load(os.path.join(folder, "optimizer.pth"), map_location="cpu", weights_only=False)
+    assert int(osd["state"][0]["step"]) == 4
+    sd = torch.load(os.path.join(folder, "network.pth"), map_location="cpu", weights_only=True)
+    assert int(sd["module.encoder.bn1.num_batches_tracked"]) == 6
+    ae = AtlasNetAE(folder)
+    assert np.isfinite(ae.get_reconstructions(_batch(2, 256, 12))).all()
+    from test_gpu_atlasnet import _eval_folder
+    from geometric_adv_amd import run_transfer
+    adv = _eval_folder(tmp_path, 256)
+    run_transfer.main(["--top_dir", top, "--ae_folder", "log/ae", "--attack_pc_idx", "log/ae/eval/sel_idx.npy", "--transfer_ae_type",
+                       "AtlasNet", "--transfer_ae_folder", "atlas"])
+    out = tmp_path / "atlas" / "eval" / "attack_res_transfer"
+    for name in ("chair", "car"):
+        if name in adv:
+            rec = np.load(out / name / "transferred_pc_recon.npy")
+            assert np.array_equal(rec[0], ae.get_reconstructions(adv[name][0]))
