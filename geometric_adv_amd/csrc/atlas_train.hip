@@ -131,6 +131,22 @@ __global__ __launch_bounds__(256) void at_gemm_kernel(BGemm g) {
         }
 }
 
+// The one launch of at_gemm_kernel: the step (Run::gemm) and geoadv_train_gemm both go through it.
+inline hipError_t at_launch_gemm(const BGemm &g, int batch, hipStream_t st) {
+    hipLaunchKernelGGL(at_gemm_kernel, dim3(cdiv(g.N, AG_T), cdiv(g.M, AG_T), batch), dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+
+// The same product on ct_launch_gemm (train_tile.h): its one bias serves every group, so g.sBiasZ is not read.
+inline hipError_t at_launch_splitk(const BGemm &b, int batch, float *partials, hipStream_t st) {
+    GemmArgs g{};
+    g.A = b.A; g.sAi = b.sAi; g.sAk = b.sAk; g.sAz = b.sAz;
+    g.B = b.B; g.sBk = b.sBk; g.sBj = b.sBj; g.sBz = b.sBz;
+    g.C = b.C; g.ldc = b.ldc; g.sCz = b.sCz; g.bias = b.bias;
+    g.alpha = 1.f; g.M = b.M; g.N = b.N; g.K = b.K; g.batch = batch;
+    return ct_launch_gemm(g, partials, st);
+}
+
 // ---- column statistics over groups ---------------------------------------------------------------------------
 // a [G][Rg][C]; part[(g * chunks + k) * C + c]: MODE 0 = (sum a, sum a^2), MODE 1 = (sum a, 0).  grid (ceil(C / 64), chunks, G).
 template <int MODE>
@@ -552,18 +568,9 @@ struct Run {
               float *Cm, long long ldc, long long sCz, const float *bias, long long sBiasZ, int M, int N, int K, int batch) {
         if (!ok()) return;
         const long long tiles = (long long)cdiv(M, AG_T) * cdiv(N, AG_T) * batch;
-        if ((bias && batch > 1) || (tiles >= kCUs && N >= 64)) {
-            BGemm g{A, sAi, sAk, sAz, Bm, sBk, sBj, sBz, Cm, ldc, sCz, bias, sBiasZ, M, N, K};
-            hipLaunchKernelGGL(at_gemm_kernel, dim3(cdiv(N, AG_T), cdiv(M, AG_T), batch), dim3(256), 0, st, g);
-            check();
-            return;
-        }
-        GemmArgs g{};
-        g.A = A; g.sAi = sAi; g.sAk = sAk; g.sAz = sAz;
-        g.B = Bm; g.sBk = sBk; g.sBj = sBj; g.sBz = sBz;
-        g.C = Cm; g.ldc = ldc; g.sCz = sCz; g.bias = bias;
-        g.alpha = 1.f; g.M = M; g.N = N; g.K = K; g.batch = batch;
-        err = ct_launch_gemm(g, t->partials, st);
+        const BGemm g{A, sAi, sAk, sAz, Bm, sBk, sBj, sBz, Cm, ldc, sCz, bias, sBiasZ, M, N, K};
+        const bool tile = (bias && batch > 1) || (tiles >= kCUs && N >= 64);
+        err = tile ? at_launch_gemm(g, batch, st) : at_launch_splitk(g, batch, t->partials, st);
     }
     // out[g] = in[g] @ W_l[g] + b_l[g]
     void linear_fwd(int l, const float *in, float *out) {
@@ -1007,4 +1014,30 @@ extern "C" int geoadv_atlas_trainer_state(const geoadv_atlas_trainer *t, int wha
     }
     set_error("atlas_trainer_state: unknown state %d", what);
     return GEOADV_EINVAL;
+}
+
+extern "C" size_t geoadv_train_gemm_partial_floats(void) { return CT_PARTIAL_FLOATS; }
+
+extern "C" int geoadv_train_gemm(int kernel, const float *A, long long sAi, long long sAk, long long sAz, const float *B, long long sBk,
+                                 long long sBj, long long sBz, float *C, long long ldc, long long sCz, const float *bias, long long sBiasZ,
+                                 int M, int N, int K, int batch, float *partials, size_t partial_floats, int *ksplit_out, void *stream) {
+    GA_REQUIRE(kernel == 0 || kernel == 1, "train_gemm: kernel %d must be 0 (split-K) or 1 (128-tile)", kernel);
+    GA_REQUIRE(A && B && C, "train_gemm: null operand");
+    GA_REQUIRE(M >= 1 && N >= 1 && K >= 1 && batch >= 1 && batch <= 1024 && M <= (1 << 20) && N <= (1 << 20),
+               "train_gemm: M, N in 1 ... 2^20, K >= 1 and batch in 1 ... 1024 (got %d x %d over %d, batch %d)", M, N, K, batch);
+    GA_REQUIRE(ldc >= N, "train_gemm: ldc %lld is below N = %d", ldc, N);
+    const BGemm g{A, sAi, sAk, sAz, B, sBk, sBj, sBz, C, ldc, sCz, bias, sBiasZ, M, N, K};
+    hipStream_t st = as_stream(stream);
+    if (kernel == 1) {
+        if (ksplit_out) *ksplit_out = 1;
+        GA_HIP(at_launch_gemm(g, batch, st));
+        return GEOADV_OK;
+    }
+    GA_REQUIRE(!(bias && batch > 1 && sBiasZ != 0), "train_gemm: the split-K kernel has one bias for all groups (bias stride %lld with batch %d)",
+               sBiasZ, batch);
+    GA_REQUIRE(partials && partial_floats >= CT_PARTIAL_FLOATS, "train_gemm: the split-K kernel needs %zu floats of partials (got %zu)",
+               (size_t)CT_PARTIAL_FLOATS, partial_floats);
+    if (ksplit_out) *ksplit_out = ct_ksplit(M, N, K, batch);
+    GA_HIP(at_launch_splitk(g, batch, partials, st));
+    return GEOADV_OK;
 }

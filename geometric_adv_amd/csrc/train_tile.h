@@ -85,16 +85,22 @@ static __global__ __launch_bounds__(256) void ct_splitk_reduce(GemmArgs g) {
     *c = g.accumulate ? *c + v : v;
 }
 
-// Launches the GEMM (and its split-K reduction over `partials`, CT_PARTIAL_FLOATS floats).  The K range is split only when
-// the tiles alone would leave most of the device idle; the split depends on the shape alone, so a step is reproducible.
+// The split of the K range ct_launch_gemm takes for a shape: more than 1 only when the tiles alone would leave most of the
+// device idle; it depends on the shape alone, so a step is reproducible.
+inline int ct_ksplit(int M, int N, int K, int batch) {
+    int ks = 1;
+    const long long blocks = (long long)cdiv(N, CT_TILE) * cdiv(M, CT_TILE) * batch;
+    if (blocks < 512 && K >= 4 * CT_KT) {
+        ks = (int)std::min<long long>(cdiv(K, 4 * CT_KT), 512 / blocks);
+        while (ks > 1 && (size_t)ks * batch * M * N > CT_PARTIAL_FLOATS) --ks;
+    }
+    return ks;
+}
+
+// Launches the GEMM (and its split-K reduction over `partials`, CT_PARTIAL_FLOATS floats) with the split of ct_ksplit.
 inline hipError_t ct_launch_gemm(GemmArgs g, float *partials, hipStream_t st) {
     const int gx = cdiv(g.N, CT_TILE), gy = cdiv(g.M, CT_TILE);
-    int ks = 1;
-    const long long blocks = (long long)gx * gy * g.batch;
-    if (blocks < 512 && g.K >= 4 * CT_KT) {
-        ks = (int)std::min<long long>(cdiv(g.K, 4 * CT_KT), 512 / blocks);
-        while (ks > 1 && (size_t)ks * g.batch * g.M * g.N > CT_PARTIAL_FLOATS) --ks;
-    }
+    const int ks = ct_ksplit(g.M, g.N, g.K, g.batch);
     g.ksplit = ks;
     g.P = partials;
     hipLaunchKernelGGL(ct_gemm_kernel, dim3(gx, gy, g.batch * ks), dim3(CT_THREADS), 0, st, g);

@@ -483,3 +483,33 @@ def chamfer_dist_matrix(pcs_a, pcs_b, max_workspace_bytes=2 << 30):
                                               C.c_size_t(nfl), _lib.stream_handle())
     _lib.check(st, "chamfer_matrix")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the training steps' GEMM kernels on their own (tests and tools)
+# ---------------------------------------------------------------------------------------------
+TRAIN_GEMM_SPLITK, TRAIN_GEMM_TILE = 0, 1       # include/geoadv.h geoadv_train_gemm's `kernel`
+
+
+def train_gemm(kernel, a, a_strides, b, b_strides, c, c_strides, bias, bias_stride, m, n, k, batch=1):
+    """geoadv_train_gemm: c[z][i * ldc + j] = sum_k a[z * sAz + i * sAi + k * sAk] * b[z * sBz + k * sBk + j * sBj] + bias[z * sBiasZ + j]
+    on float32 GPU tensors that are read and written from their first element on with the strides given (in floats): a_strides =
+    (sAi, sAk, sAz), b_strides = (sBk, sBj, sBz), c_strides = (ldc, sCz); bias may be None.  Nothing is reshaped or copied: the
+    caller owns the layout.  kernel: TRAIN_GEMM_SPLITK (csrc/train_tile.h) or TRAIN_GEMM_TILE (csrc/atlas_train.hip).
+    -> the split of the K range the launch took (1 for TRAIN_GEMM_TILE)."""
+    for t, name in ((a, "a"), (b, "b"), (c, "c")) + (((bias, "bias"),) if bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise ValueError("%s must be a float32 GPU tensor" % name)
+    ll = C.c_longlong
+    ks = C.c_int(0)
+    with torch.cuda.device(c.device):
+        part, nf = None, 0
+        if kernel == TRAIN_GEMM_SPLITK:
+            nf = int(_lib.lib().geoadv_train_gemm_partial_floats())
+            part = torch.empty(nf, dtype=torch.float32, device=c.device)      # caller-owned scratch (torch's caching allocator)
+        st = _lib.lib().geoadv_train_gemm(int(kernel), _lib.ptr(a), ll(a_strides[0]), ll(a_strides[1]), ll(a_strides[2]), _lib.ptr(b),
+                                          ll(b_strides[0]), ll(b_strides[1]), ll(b_strides[2]), _lib.ptr(c), ll(c_strides[0]),
+                                          ll(c_strides[1]), _lib.ptr(bias), ll(bias_stride), int(m), int(n), int(k), int(batch),
+                                          _lib.ptr(part), C.c_size_t(nf), C.byref(ks), _lib.stream_handle())
+    _lib.check(st, "train_gemm")
+    return ks.value

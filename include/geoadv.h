@@ -646,6 +646,19 @@ int geoadv_atlas_trainer_counters(const geoadv_atlas_trainer *t, long long *step
 #define GEOADV_ATLAS_STATE_SLOT2        13
 int geoadv_atlas_trainer_state(const geoadv_atlas_trainer *t, int what, int layer, const void **ptr, size_t *count);
 
+/* TESTS / TOOLS: one fp32 GEMM of the training steps on caller-supplied DEVICE buffers, through the launch the trainers use.
+ *   C[z][i * ldc + j] = sum_k A[z * sAz + i * sAi + k * sAk] * B[z * sBz + k * sBk + j * sBj] + bias[z * sBiasZ + j]
+ * for z < batch, i < M, j < N, k < K (strides in floats; bias may be NULL).
+ * kernel 0: the 64-tile kernel with its fixed-order split-K (csrc/train_tile.h); the split follows from the shape alone and is
+ *   written to *ksplit_out (may be NULL).  It has ONE bias for all groups: sBiasZ != 0 with batch > 1 returns GEOADV_EINVAL.
+ *   partials: device scratch of at least geoadv_train_gemm_partial_floats() floats (partial_floats = its size).
+ * kernel 1: the batched 128-tile kernel of the AtlasNet step (csrc/atlas_train.hip); partials is not used, *ksplit_out = 1.
+ * M, N in 1 ... 2^20, K >= 1, batch in 1 ... 1024, ldc >= N. */
+size_t geoadv_train_gemm_partial_floats(void);
+int geoadv_train_gemm(int kernel, const float *A, long long sAi, long long sAk, long long sAz, const float *B, long long sBk,
+                      long long sBj, long long sBz, float *C, long long ldc, long long sCz, const float *bias, long long sBiasZ,
+                      int M, int N, int K, int batch, float *partials, size_t partial_floats, int *ksplit_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * The attack loop: AdvAE (src/adv_ae.py:30-251) + Adversary (src/adversary.py:9-57).
  * One handle = one batch slot of `batch` clouds with device-resident state

@@ -39,7 +39,7 @@ STAT_TOL = (2.0 ** -22, 2.0 ** -20)
 # "two": the two-cloud batch, where bn4 and bn5 each normalise two values per channel and pass on eps / (var + eps) of the
 # gradient: in the channels whose two values differ by about sqrt(eps) the fp32 rounding of lin1's / lin2's output decides
 # xhat (forward: the latent) and that factor (backward: every encoder gradient), however the step is computed.
-MEASURED = {"well": dict(loss=1.65e-5, out=2.31e-4, grad=8.29e-4, noise=2.66e-6, param=3.2e-4, slot=1.88e-3, running=1.15e-5),
+MEASURED = {"well": dict(loss=1.65e-5, out=2.31e-4, grad=8.29e-4, noise=3.13e-6, param=3.2e-4, slot=1.88e-3, running=1.48e-5),
             "two": dict(loss=1.64e-6, out=5.73e-4, grad=1.01e-2, noise=4.5e-7, param=0.25, slot=1.61e-2, running=1.89e-5)}
 PROFILES = {"well": dict(loss=5e-5, out=8e-4, grad=3e-3, noise=1e-5, param=1.2e-3, slot=7e-3, running=4e-5),
             "two": dict(loss=6e-6, out=2e-3, grad=4e-2, noise=1.8e-6, param=1.0, slot=6e-2, running=7e-5)}
@@ -48,7 +48,13 @@ GRAD_TOL, PARAM_TOL, RUNNING_TOL = (PROFILES["well"][k] for k in ("grad", "param
 # the input batches of the pinned cases: name -> (weights seed, nb, num_layers, decoder_bn, B, n, p, batch seed; < 0 = two shapes)
 CASES = {"runner": (0, 25, 2, True, 32, 2048, 100, 1), "two": (1, 3, 2, True, 2, 256, 32, -2), "odd": (2, 3, 2, True, 3, 1001, 33, 4),
          "layers0": (3, 2, 0, True, 4, 512, 50, 5), "layers4": (4, 2, 4, True, 4, 512, 50, 6), "nobn": (5, 3, 2, False, 4, 512, 40, 7),
-         "slots": (6, 2, 1, True, 4, 512, 50, 8)}
+         "slots": (6, 2, 1, True, 4, 512, 50, 8),
+         # the GEMM paths of gemm_paths / PATHS below: rows per primitive off the 128- and 16-grids, the tile threshold, one group, 128 groups
+         "ragged16": (7, 16, 1, True, 3, 300, 131, 21), "ragged15": (8, 15, 1, True, 3, 300, 131, 22),
+         "encoder_tiles": (9, 2, 0, True, 5, 6561, 40, 23), "one_primitive": (10, 1, 2, True, 4, 512, 300, 24),
+         "one_primitive_tiles": (11, 1, 0, True, 8, 256, 1031, 25), "many_tiny": (12, 128, 1, True, 8, 3, 2, 26),
+         "repeated": (3, 2, 0, True, 4, 512, 50, 27)}
+REPEATED = ("repeated",)       # the second half of every cloud is a bit-exact copy of the first half
 
 
 def fed_biases(nb, num_layers, dbn):
@@ -68,6 +74,8 @@ def case(name):
     opt, w = AW.synthetic_state(nb, nl, dbn, seed=wseed, number_points_eval=max(4, min(100, p)) * nb)
     opt["number_points"] = nb * p
     x = _batch(B, n, seed) if seed >= 0 else _two_shapes(n, -seed)
+    if name in REPEATED:
+        x[:, n // 2:] = x[:, :n // 2]
     tmpl = np.random.default_rng(100 + abs(seed)).random((nb, p, 2)).astype(np.float32)
     return opt, w, x, tmpl
 
@@ -87,6 +95,49 @@ def _two_shapes(n, seed):
     r = np.random.default_rng(seed)
     v = r.standard_normal((n, 3))
     return np.stack([r.random((n, 3)) - 0.5, 0.4 * v / np.linalg.norm(v, axis=1, keepdims=True) * np.array([1, 0.6, 0.3])]).astype(np.float32)
+
+
+def gemm_paths(nb, num_layers, B, n, p):
+    """Which kernel each product of a step runs on: Run::gemm of csrc/atlas_train.hip restated.  A product of `batch` groups of
+    M x N over K goes to at_gemm_kernel ("tile") if it has a bias and more than one group, or if ceil(M / 128) * ceil(N / 128) *
+    batch >= 256 and N >= 64; otherwise to ct_launch_gemm ("split").  Keys: layer.fwd (out = in W + b), layer.w (dW = in^T da:
+    M = inputs, N = outputs, K = rows), layer.x (din = da W^T: M = rows, N = inputs, K = outputs); the encoder's first layer has
+    no .x; dec1 is the decoder's 1024 -> 512 layer, dec2 ... its 512 -> 512 layers (the decoder's conv1 and last_conv's forward have
+    kernels of their own)."""
+    def path(M, N, K, batch, bias):
+        tiles = -(-M // 128) * -(-N // 128) * batch
+        return "tile" if (bias and batch > 1) or (tiles >= 256 and N >= 64) else "split"
+
+    R, Rp = B * n, B * p
+    layers = [("enc%d" % (i + 1), rows, kin, kout, 1) for i, (rows, kin, kout) in
+              enumerate([(R, 3, 64), (R, 64, 128), (R, 128, 1024), (B, 1024, 1024), (B, 1024, 1024)])]
+    layers += [("dec%d" % (i + 1), Rp, kin, 512, nb) for i, kin in enumerate([1024] + [512] * num_layers)] + [("last", Rp, 512, 3, nb)]
+    out = {}
+    for name, rows, kin, kout, groups in layers:
+        if name != "last":
+            out[name + ".fwd"] = path(rows, kout, kin, groups, True)
+        out[name + ".w"] = path(kin, kout, rows, groups, False)
+        if name != "enc1":
+            out[name + ".x"] = path(rows, kin, kout, groups, False)
+    return out
+
+
+# what each case was written for: the products named here must take the path named here
+PATHS = {"ragged16": {"dec1.fwd": "tile", "dec2.fwd": "tile", "last.x": "tile", "dec2.w": "tile", "dec2.x": "tile", "dec1.w": "tile",
+                      "dec1.x": "tile", "last.w": "split"},
+         "ragged15": {"dec2.w": "split", "dec2.x": "split", "last.x": "split", "dec1.w": "tile", "dec1.x": "tile", "dec1.fwd": "tile"},
+         "encoder_tiles": {"enc1.fwd": "tile", "enc2.fwd": "tile", "enc3.fwd": "tile", "enc3.x": "tile", "enc2.x": "tile", "enc3.w": "split",
+                           "enc1.w": "split"},
+         "one_primitive": {"dec1.fwd": "split", "dec2.fwd": "split", "dec3.fwd": "split", "dec1.w": "split", "dec1.x": "split"},
+         "one_primitive_tiles": {"dec1.fwd": "tile", "dec1.x": "tile", "last.x": "tile", "dec1.w": "split"},
+         "many_tiny": {"dec1.fwd": "tile", "dec2.fwd": "tile", "dec1.w": "tile", "dec1.x": "tile", "dec2.w": "tile", "dec2.x": "tile",
+                       "last.x": "tile", "last.w": "split"}}
+
+
+def assert_paths(name):
+    _, nb, nl, _, B, n, p, _ = CASES[name]
+    got = gemm_paths(nb, nl, B, n, p)
+    assert {k: got[k] for k in PATHS[name]} == PATHS[name]
 
 
 ENC_RELU = {"enc1": 0, "enc2": 1, "enc4": 3, "enc5": 4}
@@ -227,6 +278,49 @@ def test_num_layers_0_and_4(name):
 
 def test_decoder_without_batch_norm():
     check(run_case("nobn"))
+
+
+@pytest.mark.parametrize("name", ["ragged16", "ragged15"])
+def test_ragged_rows_per_primitive_on_either_side_of_the_tile_threshold(name):
+    """393 = 3 x 128 + 9 = 24 x 16 + 9 rows per primitive.  16 primitives: every decoder backward product with N >= 64 runs on
+    at_gemm_kernel (256, 512, 256, 512 and 256 tiles) with M or K off the grid in both transposed layouts, K = 3 for last_conv.
+    15 primitives: the 512-wide products have 240 tiles and go to split-K, the 1024-wide ones stay: one step mixes both."""
+    assert_paths(name)
+    check(run_case(name))
+
+
+def test_encoder_on_the_tile_kernel_with_a_ragged_last_tile():
+    """32805 = 256 x 128 + 37 rows: 257 row tiles, batch 1; the forwards of conv1 (K = 3, N = 64), conv2, conv3 and the input
+    gradients of conv3 and conv2 run on at_gemm_kernel."""
+    assert_paths("encoder_tiles")
+    check(run_case("encoder_tiles"))
+
+
+@pytest.mark.parametrize("name", ["one_primitive", "one_primitive_tiles"])
+def test_one_primitive(name):
+    """One group: the biased forward goes through split-K with its bias (1200 rows), or, with 8248 rows = 65 tiles, the decoder
+    runs on at_gemm_kernel with batch 1 and a ragged last tile."""
+    assert_paths(name)
+    check(run_case(name))
+
+
+def test_128_primitives_of_16_rows():
+    """The most groups the step accepts, 16 rows per primitive, 3 points per cloud: fewer than at_gmax_kernel's four row phases."""
+    assert_paths("many_tiny")
+    check(run_case("many_tiny"))
+
+
+def test_repeated_points_the_first_of_equal_rows_wins():
+    """The second half of every cloud repeats the first bit for bit: every maximum is attained twice and the recorded row is the
+    first, as at_gmax_kernel promises; the step pinned to those rows still meets the profile."""
+    opt, w, x, tmpl = case("repeated")
+    assert np.array_equal(x[:, 256:].view(np.int32), x[:, :256].view(np.int32))
+    tr = _trainer(w, opt, 4, 512)
+    errs = [one_step(tr, x, tmpl, tr.learning_rate)]
+    rows = tr.state("gmax_row")
+    assert rows.min() >= 0 and rows.max() < 256, (rows.min(), rows.max())
+    report("repeated", errs)
+    check(errs)
 
 
 def test_runner_shape_three_steps_with_device_drawn_templates():
