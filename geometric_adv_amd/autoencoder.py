@@ -211,3 +211,23 @@ class PointNetAE(DeviceModel):
         gt = self._as_dev(feed_data if orig_data is None else orig_data)
         self.status()
         return self.loss_per_pc_tensor(recon, gt).cpu().numpy()
+
+    def evaluate(self, point_clouds, batch_size=50):
+        """What autoencoder/tst_ae.py takes from three passes over the set (get_latent_vectors, get_reconstructions,
+        get_loss_per_pc) from ONE forward per chunk of `batch_size` clouds -> (latent_vectors (N,bneck), reconstructions
+        (N,K,3), loss_per_pc (N,)) as numpy: bit for bit what transform, get_reconstructions and get_loss_per_pc return for
+        the same chunks."""
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        if len(point_clouds) == 0:
+            raise ValueError("evaluate needs at least one cloud")
+        latent, recons, loss = [], [], []
+        for s in range(0, len(point_clouds), batch_size):
+            x = self._as_dev(point_clouds[s:s + batch_size])
+            recon, z = self.forward(x)
+            per_pc = self.loss_per_pc_tensor(recon, x)
+            latent.append(z.cpu().numpy())
+            recons.append(recon.cpu().numpy())
+            loss.append(per_pc.cpu().numpy())
+        self.status()
+        return np.vstack(latent), np.vstack(recons), np.concatenate(loss)

@@ -356,6 +356,25 @@ def critical_split(point_clouds, max_val, max_idx):
 
 
 # ---------------------------------------------------------------------------------------------
+# the dataset stage (src/shift_rotate_util.py:22-62), device side
+# ---------------------------------------------------------------------------------------------
+def sort_axes(point_clouds, neg_rot=True):
+    """sort_axes(point_clouds, neg_rot) (shift_rotate_util.py:22-44) on a GPU tensor (b,n,3) -> (sorted clouds (b,n,3),
+    axes_idx (b,3) int32 = get_sort_axes_idx's indices).  The longer of the x and y extents becomes x, z stays; equal
+    extents are swapped as the reference swaps them ([1,0,2]); axis int(neg_rot) is negated only where x was strictly shorter.
+    Bit-equal to the reference (copies and sign flips).  1 <= n <= 16384 (include/geoadv.h)."""
+    pc = _f32(point_clouds, "point_clouds", 3)
+    if pc.shape[2] != 3:
+        raise ValueError("sort_axes only accepts 3d point sets")
+    b, n, _ = pc.shape
+    out = torch.empty_like(pc)
+    axes_idx = torch.empty((b, 3), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device):
+        _call("geoadv_sort_axes", b, n, _lib.ptr(pc), _lib.ptr(out), _lib.ptr(axes_idx), int(bool(neg_rot)))
+    return out, axes_idx
+
+
+# ---------------------------------------------------------------------------------------------
 # external/structural_losses/tf_approxmatch.py
 # ---------------------------------------------------------------------------------------------
 EMD_FAST, EMD_REFERENCE = 0, 1          # include/geoadv.h: how the pair weight expf(level * d2) is evaluated

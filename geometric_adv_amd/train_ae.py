@@ -1,6 +1,7 @@
 """autoencoder/train_ae.py on MI355X: trains the victim auto-encoder and writes `models.ckpt-<epoch>`
 (TF V2 checkpoint format, written without TensorFlow by tf_checkpoint.py; saver_step 50 plus the first and last epoch,
-autoencoder.py:213-215) and `train_stats.txt` (epoch, loss, minutes: autoencoder.py:206-209) into --train_folder.
+autoencoder.py:213-215), `train_stats.txt` (epoch, loss, minutes: autoencoder.py:206-209) and `configuration.json` (what
+tst_ae reads back: JSON where the reference pickles its Configuration) into --train_folder.
 
 Limitation of the checkpoint: the bundle holds the 36 `autoencoder/*` model variables (weights, biases, BN parameters and
 moving averages) -- exactly what the attack path restores (restore_ae_model filters the var_list by the 'autoencoder' prefix,
@@ -9,25 +10,43 @@ reference's own AutoEncoder.restore_model (neural_net.py:33-36, a Saver over ALL
 it is a victim for the attack, not a resumable training state.  The reader / writer pair is pinned to the published format
 and to its own round trip only; no TF-written bundle exists in this environment to test against.
 
-Differences forced by the environment: the ShapeNet folder reader (src/in_out.load_dataset, PLY files) is out of
-scope, so the training clouds come from one `.npy` of shape (n, 2048, 3) (--train_data; axes already sorted if
-wanted), shuffled once per epoch with numpy instead of PointCloudDataSet.next_batch's permutation.  Multi-GPU:
-launch with torchrun; every rank takes its shard of each batch and the flat gradient buffer is all-reduced (RCCL).
+Two sources of training clouds:
+  --data_dir   the ShapeNet PLY folder (<data_dir>/<synset id>/<model>.ply), as the reference: in_out.load_dataset of
+               --class_names for the train and the validation set, axes sorted on the device (--sort_axes 1), both sets
+               shuffled with seed 55 when there is more than one class, batches drawn through PointCloudDataSet.next_batch, and
+               every --held_out_step epochs the validation loss (mean of get_loss_per_pc over the whole batches; a set smaller
+               than one batch is taken whole) appended to train_stats.txt as `On Held_Out: <epoch>\t<loss>\t<minutes>`
+               (autoencoder.py:222-226).
+  --train_data one `.npy` of shape (n, n_points, 3) (axes already sorted if wanted), shuffled once per epoch with numpy.
+Multi-GPU: launch with torchrun; every rank takes its shard of each batch and the flat gradient buffer is all-reduced (RCCL).
 
+    python -m geometric_adv_amd.train_ae --data_dir data/shape_net_core_uniform_samples_2048 --train_folder log/autoencoder_victim
     python -m geometric_adv_amd.train_ae --train_data clouds.npy --train_folder log/autoencoder_victim --training_epochs 500
 """
 import argparse
+import json
 import os
 import os.path as osp
 
 import numpy as np
 
 
+CLASS_NAMES_13 = ['table', 'car', 'chair', 'airplane', 'sofa', 'rifle', 'lamp', 'watercraft', 'bench', 'loudspeaker', 'cabinet',
+                  'display', 'telephone']                          # autoencoder/train_ae.py:49
+CONFIGURATION_KEYS = ('n_input', 'loss', 'batch_size', 'learning_rate', 'training_epochs', 'saver_step', 'bneck_size',
+                      'object_class', 'class_names', 'sort_axes', 'experiment_name', 'held_out_step', 'data_source')
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument('--training_epochs', type=int, default=500, help='Number of training epochs [default: 500]')
     p.add_argument('--train_folder', type=str, default='log/autoencoder_victim')
-    p.add_argument('--train_data', type=str, required=True, help='.npy of shape (n, n_points, 3)')
+    p.add_argument('--train_data', type=str, default=None, help='.npy of shape (n, n_points, 3)')
+    p.add_argument('--data_dir', type=str, default=None, help='ShapeNet PLY folder (<synset id>/<model>.ply); not together with --train_data')
+    p.add_argument('--class_names', nargs='+', default=list(CLASS_NAMES_13), help='shape classes read from --data_dir [default: the 13 of the reference]')
+    p.add_argument('--sort_axes', type=int, default=1, help='1: Sort point cloud axes, 0: Do not sort axes [default: 1] (--data_dir input only)')
+    p.add_argument('--save_config_and_exit', type=int, default=0, help='1: Save autoencoder configuration and exit, 0: Do not exit [default: 0]')
+    p.add_argument('--held_out_step', type=int, default=5, help='epochs between two evaluations of the validation set (--data_dir only) [default: 5]')
     p.add_argument('--batch_size', type=int, default=50)            # default_train_params, ae_templates.py:43-51
     p.add_argument('--learning_rate', type=float, default=0.0005)
     p.add_argument('--saver_step', type=int, default=50)
@@ -35,34 +54,154 @@ def build_parser():
     return p
 
 
-def main(argv=None):
-    flags = build_parser().parse_args(argv)
+def parse_flags(argv=None):
+    p = build_parser()
+    flags = p.parse_args(argv)
+    if flags.train_data is None and flags.data_dir is None:
+        p.error('one of --data_dir (ShapeNet PLY folder) and --train_data (.npy of clouds) is required')
+    if flags.train_data is not None and flags.data_dir is not None:
+        p.error('--data_dir and --train_data are two sources of the training clouds: give one of them')
+    return flags
+
+
+def make_configuration(flags, n_points):
+    """The fields of the reference's Configuration (autoencoder/train_ae.py:58-78) that tst_ae and the later stages read, and
+    `data_source`: 'data_dir' or 'train_data'.  The classes, object_class and sort_axes describe a PLY folder; a run on a
+    `.npy` of clouds says nothing about where those came from, so they are recorded as empty / 0 and tst_ae, which would
+    have to read the classes' folders, refuses such a train folder."""
+    from_ply = flags.data_dir is not None
+    class_names = list(flags.class_names) if from_ply else []
+    return {'n_input': [int(n_points), 3], 'loss': 'chamfer', 'batch_size': flags.batch_size, 'learning_rate': flags.learning_rate,
+            'training_epochs': flags.training_epochs, 'saver_step': flags.saver_step, 'bneck_size': 128,
+            'object_class': ['%dl' % len(class_names)] if from_ply else [], 'class_names': class_names,
+            'sort_axes': int(flags.sort_axes) if from_ply else 0, 'experiment_name': 'autoencoder',
+            'held_out_step': flags.held_out_step, 'data_source': 'data_dir' if from_ply else 'train_data'}
+
+
+def save_configuration(train_dir, conf):
+    os.makedirs(train_dir, exist_ok=True)
+    with open(osp.join(train_dir, 'configuration.json'), 'w') as f:
+        json.dump(conf, f, indent=1, sort_keys=True)
+        f.write('\n')
+
+
+def load_configuration(train_dir):
+    with open(osp.join(train_dir, 'configuration.json')) as f:
+        conf = json.load(f)
+    missing = [k for k in CONFIGURATION_KEYS if k not in conf]
+    if missing:
+        raise ValueError('%s lacks %s' % (osp.join(train_dir, 'configuration.json'), missing))
+    return conf
+
+
+def _peek_n_points(flags):
+    """Points per cloud of the training data without loading them all."""
+    if flags.data_dir is not None:
+        from . import in_out
+        class_dir = osp.join(flags.data_dir, in_out.snc_category_to_synth_id()[flags.class_names[0]])
+        first = next(in_out.files_in_subdirs(class_dir, '.ply'), None)
+        if first is None:
+            raise FileNotFoundError('no .ply file under %s' % class_dir)
+        return in_out.load_ply(first).shape[0]
+    return np.load(flags.train_data, mmap_mode='r').shape[1]
+
+
+def sort_axes_on_device(point_clouds, device, chunk=8192):
+    """ops.sort_axes of host clouds (N, n, 3), `chunk` clouds at a time -> float32 numpy."""
     import torch
-    from . import dist as gdist, tf_checkpoint
+    from . import ops
+    out = np.empty(point_clouds.shape, np.float32)
+    for s in range(0, len(point_clouds), chunk):
+        x = torch.from_numpy(np.ascontiguousarray(point_clouds[s:s + chunk], dtype=np.float32)).to(device)
+        out[s:s + chunk] = ops.sort_axes(x)[0].cpu().numpy()
+    return out
+
+
+class _RankShard(object):
+    """next_batch of a PointCloudDataSet for one rank: every rank draws the same global batch and keeps its part.  The ranks'
+    copies of the set reshuffle through numpy's global generator; main() reseeds it on every rank at the start of each epoch
+    when there are several ranks, so a stray draw on one rank cannot leave them apart for longer than that epoch."""
+
+    def __init__(self, data_set, rank, world):
+        self.ds, self.rank, self.world = data_set, rank, world
+        self.num_examples = data_set.num_examples // world
+
+    def next_batch(self, local_bs):
+        batch, labels, noisy = self.ds.next_batch(local_bs * self.world)
+        return batch[self.rank * local_bs:(self.rank + 1) * local_bs], labels, noisy
+
+
+def held_out_loss(weights, n_points, val_data, batch_size, device):
+    """Mean of get_loss_per_pc over the whole batches of the validation set (taken whole if it is smaller than one batch)."""
+    from .autoencoder import PointNetAE
+    ae = PointNetAE(weights, n_points, device=device)
+    pcs = val_data.point_clouds
+    n_whole = (len(pcs) // batch_size) * batch_size or len(pcs)
+    per_pc = np.concatenate([ae.get_loss_per_pc(pcs[s:s + batch_size]) for s in range(0, n_whole, batch_size)])
+    return float(per_pc.mean())
+
+
+def main(argv=None):
+    flags = parse_flags(argv)
+    from . import dist as gdist
+    rank = gdist.env_rank()[0]
+    if rank == 0:
+        save_configuration(flags.train_folder, make_configuration(flags, _peek_n_points(flags)))
+    if flags.save_config_and_exit:
+        return []
+    import time
+    import torch
+    from . import tf_checkpoint
     from .trainer import PointNetAETrainer, initial_weights
     rank, world, local = gdist.init()
-    data = np.load(flags.train_data).astype(np.float32)
-    assert data.ndim == 3 and data.shape[2] == 3, 'train_data must be (n, n_points, 3)'
-    n_points = data.shape[1]
+    device = torch.device('cuda', local)
     assert flags.batch_size % world == 0, 'batch_size must divide over the ranks'
     local_bs = flags.batch_size // world
+    pc_data_train = pc_data_val = None
+    if flags.data_dir is not None:
+        from . import in_out
+        pc_data_train, _, _ = in_out.load_dataset(flags.class_names, 'train_set', flags.data_dir)
+        pc_data_val, _, _ = in_out.load_dataset(flags.class_names, 'val_set', flags.data_dir)
+        if flags.sort_axes:
+            pc_data_train.point_clouds = sort_axes_on_device(pc_data_train.point_clouds, device)
+            if pc_data_val.num_examples:
+                pc_data_val.point_clouds = sort_axes_on_device(pc_data_val.point_clouds, device)
+        if len(flags.class_names) > 1:                                         # autoencoder/train_ae.py:103-105
+            pc_data_train.shuffle_data(seed=55)
+            pc_data_val.shuffle_data(seed=55)
+        n_points = pc_data_train.n_points
+    else:
+        data = np.load(flags.train_data).astype(np.float32)
+        assert data.ndim == 3 and data.shape[2] == 3, 'train_data must be (n, n_points, 3)'
+        n_points = data.shape[1]
+        n_batches = len(data) // flags.batch_size
     tr = PointNetAETrainer(initial_weights(n_points, seed=flags.seed), n_points, batch_size=local_bs,
-                           learning_rate=flags.learning_rate, device=torch.device('cuda', local))
+                           learning_rate=flags.learning_rate, device=device)
     os.makedirs(flags.train_folder, exist_ok=True)
     fout = open(osp.join(flags.train_folder, 'train_stats.txt'), 'a', 1) if rank == 0 else None
     rng = np.random.default_rng(flags.seed)
-    n_batches = len(data) // flags.batch_size
     stats = []
     for epoch in range(1, flags.training_epochs + 1):
-        perm = rng.permutation(len(data))[:n_batches * flags.batch_size]       # same permutation on every rank
-        shard = data[perm].reshape(n_batches, world, local_bs, n_points, 3)[:, rank].reshape(-1, n_points, 3)
-        loss, duration = tr._single_epoch_train(shard)
+        if pc_data_train is not None:
+            if world > 1:
+                np.random.seed(flags.seed + epoch)                                 # the ranks must reshuffle alike
+            loss, duration = tr._single_epoch_train(_RankShard(pc_data_train, rank, world))
+        else:
+            perm = rng.permutation(len(data))[:n_batches * flags.batch_size]       # same permutation on every rank
+            shard = data[perm].reshape(n_batches, world, local_bs, n_points, 3)[:, rank].reshape(-1, n_points, 3)
+            loss, duration = tr._single_epoch_train(shard)
         stats.append((epoch, loss, duration))
         if rank == 0:
             print("Epoch:", '%04d' % epoch, 'training time (minutes)=', "{:.4f}".format(duration / 60.0), "loss=", "{:.9f}".format(loss))
             fout.write('%04d\t%.9f\t%.4f\n' % (epoch, loss, duration / 60.0))
             if epoch % flags.saver_step == 0 or epoch == 1 or epoch == flags.training_epochs:
                 tf_checkpoint.write_checkpoint(osp.join(flags.train_folder, 'models.ckpt-%d' % epoch), tr.export_weights())
+            if pc_data_val is not None and pc_data_val.num_examples and flags.held_out_step > 0 and epoch % flags.held_out_step == 0:
+                start = time.time()
+                val_loss = held_out_loss(tr.export_weights(), n_points, pc_data_val, flags.batch_size, device)
+                duration = time.time() - start
+                print('validation set after epoch %04d: loss %.9f (%.4f minutes)' % (epoch, val_loss, duration / 60.0))
+                fout.write('On Held_Out: %04d\t%.9f\t%.4f\n' % (epoch, val_loss, duration / 60.0))
     if fout:
         fout.close()
     return stats

@@ -219,6 +219,16 @@ int geoadv_critical_split(int b, int n, int c, const float *pc, const float *max
                           float *critical_points, short *critical_idx, short *critical_num, float *critical_pc,
                           float *non_critical_pc, void *stream);
 
+/* sort_axes (src/shift_rotate_util.py:22-62) on the device: per cloud of pc[b,n,3] the longer of the x and y extents
+ * (max - min, fp32) becomes x; z stays.  axes_idx[b,3] (may be NULL) is the reference's np.argsort([ex, ey, 0])[::-1]:
+ * {0,1,2} for ex > ey, {1,0,2} for ex < ey AND for ex == ey (the reference swaps on a tie).  Only where ex < ey strictly is
+ * axis (neg_rot ? 1 : 0) of the result negated (the swap becomes a rotation about z).  out[b,n,3] holds copies and sign
+ * flips of the input only: the reference's bits.  Where an x or y extent is exactly 0 the reference's own assertion fails;
+ * the rule above goes on holding here.  A NaN extent orders as the largest, as in numpy.  out must not be pc.
+ * 1 <= n <= 16384, b >= 1, else GEOADV_EINVAL. */
+int geoadv_sort_axes(int b, int n, const float *pc, float *out, int *axes_idx /* [b][3], may be NULL */, int neg_rot,
+                     void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Victim auto-encoder: src/encoders_decoders.py:19-147 with the architecture of
  * src/ae_templates.py:11-39 (5 x [conv1d k=1, BN(inference), ReLU], max over points,
