@@ -504,6 +504,32 @@ def chamfer_dist_matrix(pcs_a, pcs_b, max_workspace_bytes=2 << 30):
     return out
 
 
+LATENT_DIST_MAX_D = 128         # include/geoadv.h geoadv_latent_dist_matrix
+
+
+def latent_dist_matrix(a, b=None):
+    """All-pairs Euclidean distance of latent codes: out[i, j] = ||a[i] - b[j]||_2, the matrix of get_dist_mat
+    (src/general_utils.py:94-106) behind prepare_indices_for_attack.py:89-101, without its tiled (n, n, d) copies.
+    a (na,d), b (nb,d) float32 GPU tensors (b=None: b = a) -> (na, nb).  The bits of np.linalg.norm(s - t, axis=-1) (numpy's
+    summation order; csrc/latent_dist.hip); for b = a exactly symmetric with a +0 diagonal.  1 <= d <= 128."""
+    a = _f32(a, "a", 2)
+    b = a if b is None else _f32(b, "b", 2)
+    if b.device != a.device:
+        raise ValueError("a and b must live on the same device (got %s and %s)" % (a.device, b.device))
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("latent_dist_matrix expects a and b of the same width (got %d and %d)" % (a.shape[1], b.shape[1]))
+    d = a.shape[1]
+    if not 1 <= d <= LATENT_DIST_MAX_D:
+        raise ValueError("latent_dist_matrix supports 1 <= d <= %d (got %d)" % (LATENT_DIST_MAX_D, d))
+    na, nb = a.shape[0], b.shape[0]
+    out = torch.empty((na, nb), dtype=torch.float32, device=a.device)
+    if na == 0 or nb == 0:
+        return out
+    with torch.cuda.device(a.device):
+        _call("geoadv_latent_dist_matrix", na, nb, d, _lib.ptr(a), _lib.ptr(b), _lib.ptr(out))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # the training steps' GEMM kernels on their own (tests and tools)
 # ---------------------------------------------------------------------------------------------

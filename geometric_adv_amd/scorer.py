@@ -45,6 +45,27 @@ def sort_dist_mat(dist_mat, slice_idx):
     return nn_idx
 
 
+def get_latent_dist_mat(latent_vectors, device="cuda:0"):
+    """get_dist_mat (src/general_utils.py:94-106) of prepare_indices_for_attack.py:89-101 on the GPU: the (n, n) float32 matrix
+    of Euclidean distances between the latent codes (n, d <= 128), [i, j] = ||latent[j] - latent[i]||, the reference's bits
+    (ops.latent_dist_matrix) without its three (n, n, d) host arrays."""
+    x = torch.as_tensor(np.ascontiguousarray(latent_vectors, dtype=np.float32)).to(device)
+    return ops.latent_dist_matrix(x).cpu().numpy()
+
+
+def latent_dist_mat_host(latent_vectors, row_block=64):
+    """The same matrix in numpy, `row_block` rows at a time: the reference's own expression (source on axis 1, target on axis
+    0, np.linalg.norm over the last axis) on a (row_block, n, d) slab instead of the whole (n, n, d), so the reference's bits
+    at 1 / (n / row_block) of its memory.  The CLI's --device cpu path and the yardstick of the GPU kernel's tests."""
+    x = np.ascontiguousarray(latent_vectors, dtype=np.float32)
+    assert len(x.shape) == 2, 'The data is assumed to have 2 dimensions, got a shape of %s' % str(x.shape)
+    n = len(x)
+    out = np.empty((n, n), np.float32)
+    for r0 in range(0, n, row_block):
+        out[r0:r0 + row_block] = np.linalg.norm(x[None, :, :] - x[r0:r0 + row_block, None, :], axis=-1)
+    return out
+
+
 def get_chamfer_dist_mat_full(point_clouds, device="cuda:0", block=256, rank=0, world=1):
     """The complete (num_all, num_all) matrix of prepare_indices_for_attack.py:104-153 in one call, at half the work: the
     Chamfer distance of a pair is the same whichever cloud is called the source (mean of both directions, equal point counts),

@@ -229,6 +229,14 @@ int geoadv_critical_split(int b, int n, int c, const float *pc, const float *max
 int geoadv_sort_axes(int b, int n, const float *pc, float *out, int *axes_idx /* [b][3], may be NULL */, int neg_rot,
                      void *stream);
 
+/* get_dist_mat (src/general_utils.py:94-106) on the device: out[na,nb], out[i][j] = || a[i] - b[j] ||_2 of the fp32 row-major
+ * a[na,d] and b[nb,d] -- the latent distance matrix of attacker/prepare_indices_for_attack.py:89-101.  Bit for bit numpy's
+ * np.linalg.norm(s - t, axis=-1): fp32 differences, squares rounded on their own, numpy's pairwise summation order of a
+ * contiguous run of d <= 128 elements (eight accumulators, combined as a tree, the last d mod 8 elements added one by one),
+ * a correctly rounded square root, denormals kept.  With b == a the matrix is exactly symmetric and its diagonal is +0.
+ * 1 <= d <= 128 and na, nb >= 0, else GEOADV_EINVAL; na == 0 or nb == 0 is a no-op. */
+int geoadv_latent_dist_matrix(int na, int nb, int d, const float *a, const float *b, float *out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Victim auto-encoder: src/encoders_decoders.py:19-147 with the architecture of
  * src/ae_templates.py:11-39 (5 x [conv1d k=1, BN(inference), ReLU], max over points,
