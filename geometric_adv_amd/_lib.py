@@ -27,7 +27,7 @@ def lib():
         for name in ("geoadv_approx_match_temp_floats", "geoadv_ae_workspace_bytes", "geoadv_chamfer_matrix_workspace_floats",
                      "geoadv_emd_cost_grad1_temp_floats", "geoadv_nn_distance_sym_workspace_floats",
                      "geoadv_knn_workspace_bytes", "geoadv_group_point_grad_workspace_bytes", "geoadv_match_cost_workspace_floats",
-                     "geoadv_cls_workspace_bytes", "geoadv_atlas_workspace_bytes", "geoadv_fold_workspace_bytes",
+                     "geoadv_cls_workspace_bytes", "geoadv_cls_evaluate_workspace_bytes", "geoadv_atlas_workspace_bytes", "geoadv_fold_workspace_bytes",
                      "geoadv_train_gemm_partial_floats"):
             getattr(_lib, name).restype = C.c_size_t
     return _lib

@@ -375,6 +375,26 @@ def sort_axes(point_clouds, neg_rot=True):
 
 
 # ---------------------------------------------------------------------------------------------
+# classifier/provider.py, device side
+# ---------------------------------------------------------------------------------------------
+def rotate_point_cloud_by_angle(batch_data, rotation_angle):
+    """provider.rotate_point_cloud_by_angle on a GPU tensor (b,n,3): every point, as a row vector, times
+    [[c,0,s],[0,1,0],[-s,0,c]] with c, s = np.cos / np.sin of rotation_angle (float64, computed here on the host as the
+    reference computes them); the float32 coordinates are multiplied and summed in float64 on the device and rounded once, as
+    numpy's float32 @ float64 product stored into a float32 array."""
+    import numpy as np
+    pc = _f32(batch_data, "batch_data", 3)
+    if pc.shape[2] != 3:
+        raise ValueError("rotate_point_cloud_by_angle only accepts 3d point sets")
+    b, n, _ = pc.shape
+    out = torch.empty_like(pc)
+    with torch.cuda.device(pc.device):
+        _call("geoadv_rotate_y", b, n, _lib.ptr(pc), C.c_double(float(np.cos(rotation_angle))),
+              C.c_double(float(np.sin(rotation_angle))), _lib.ptr(out))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # external/structural_losses/tf_approxmatch.py
 # ---------------------------------------------------------------------------------------------
 EMD_FAST, EMD_REFERENCE = 0, 1          # include/geoadv.h: how the pair weight expf(level * d2) is evaluated

@@ -369,6 +369,30 @@ int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const float *pc, flo
                        float *transform_in, float *transform_feat, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Voted evaluation of the classifier (classifier/tst_classifier.py eval_one_epoch, one batch) and the rotation it votes
+ * over (classifier/provider.py rotate_point_cloud_by_angle).  csrc/cls_eval.hip.
+ * ---------------------------------------------------------------------------------------- */
+/* out[b,n,3] = pc[b,n,3] @ [[c,0,s],[0,1,0],[-s,0,c]] with c = cos_angle, s = sin_angle computed by the caller: float32
+ * points times the float64 matrix, products and sums in float64, rounded to float32 once.  out may be pc.  b == 0 or
+ * n == 0 is a no-op; negative shapes return GEOADV_EINVAL. */
+int geoadv_rotate_y(int b, int n, const float *pc, double cos_angle, double sin_angle, float *out, void *stream);
+/* Device scratch of geoadv_cls_evaluate for a batch of b clouds of n points (any number of votes). */
+size_t geoadv_cls_evaluate_workspace_bytes(const geoadv_cls *cls, int b, int n);
+/* For vote v = 0 .. num_votes - 1: pc rotated by v / num_votes * 2 pi (or by the HOST array cos_sin[num_votes][2] =
+ * (cos, sin) of every vote's angle when it is not NULL, read before the call returns), geoadv_cls_forward on it, and
+ *   loss[v]              float32: mean_b(softmax cross entropy against labels) + 0.001 * sum_b(0.5 ||T2 T2^T - I||_F^2),
+ *   pred_sum[b,C]        float64: the logits summed over the votes in vote order,
+ *   vote_counts[b,C]     int32: how many votes had their arg-max at each class,
+ *   pred[b]              int32: the first maximum of pred_sum after the last vote.
+ * labels[b] is a DEVICE int32 array; NULL (or loss NULL) computes no loss.  A label outside [0, C) makes every loss[v] of
+ * the call NaN and reads nothing out of bounds; the other outputs do not depend on the labels.  Any output may be NULL.
+ * All on `stream`, no host synchronisation; two calls on the same input give the same bits.  1 <= n <= 16384, b >= 1,
+ * 1 <= num_votes <= 64, else GEOADV_EINVAL. */
+int geoadv_cls_evaluate(const geoadv_cls *cls, int b, int n, const float *pc, const int *labels, int num_votes,
+                        const double *cos_sin, float *loss, int *pred, double *pred_sum, int *vote_counts,
+                        void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * PointNet classifier TRAINING step (classifier/train_classifier.py train_one_epoch: sess.run([train_op, loss, pred]) at
  * is_training = True): batch norm from the batch's moments, differentiated through; dropout keep 0.7 after fc1 and fc2;
  * loss = mean softmax cross entropy + 0.001 * l2_loss(T2 T2^T - I); AdamOptimizer or MomentumOptimizer with the
