@@ -220,6 +220,21 @@ class AdvAE:
             out["latent"] = out["latent"][:, :self.ae.bneck].contiguous()
         return out
 
+    def _test_loss_form(self, form):
+        """Tests only (geoadv_attack_test_loss_form): 0 = the default; bit 0: packed row minima only from 9 column slices on, bit 1:
+        the general gradient body and the packed words folded through LDS.  Same results, bit for bit."""
+        _lib.check(_lib.lib().geoadv_attack_test_loss_form(self._h, int(form)), "attack_test_loss_form")
+
+    def _test_loss_state(self):
+        """Tests only: what the cached forward's loss launch left -- g_recon, g_dist [B, n, 3], losses [8, B], dist_r1, dist_a1 [B, n]."""
+        B, n, dev = self.B, self.n, self.device
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        out = dict(g_recon=f(B, n, 3), g_dist=f(B, n, 3), losses=f(8, B), dist_r1=f(B, n), dist_a1=f(B, n))
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().geoadv_attack_test_loss_state(self._h, *[_lib.ptr(out[k]) for k in
+                       ("g_recon", "g_dist", "losses", "dist_r1", "dist_a1")], _lib.stream_handle()), "attack_test_loss_state")
+        return out
+
     def profile(self, classes, stride=1):
         """classes: True/False for all/none, or an iterable of PROF_NAMES to time; stride: time every stride-th launch."""
         _lib.check(_lib.lib().geoadv_attack_profile_stride(self._h, int(stride)), "attack_profile_stride")

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(CGA_THREADS) void chamfer_grad_attack_kernel(CGradA
 // grid = (clouds, problems * H)
 __global__ __launch_bounds__(CGA_THREADS) void chamfer_grad_attack_fx_kernel(CGradArgs a, int H) {
     extern __shared__ __attribute__((aligned(16))) unsigned fx_lds[];
-    cgrad_fx_body(a, blockIdx.y / H, blockIdx.x, blockIdx.y % H, H, fx_lds);
+    cgrad_fx(a, blockIdx.y / H, blockIdx.x, blockIdx.y % H, H, fx_lds);
 }
 
 // The per-cloud losses and the Chamfer gradients read the same NN results and do not depend on each other (unless the
@@ -228,7 +228,8 @@ struct geoadv_attack {
     float *best_err, *best_metrics, *best_adv, *best_recon;
     float *emd_temp, *emd_cost, *emd_g1;   // only when cfg.emd_weight > 0
     float *sym_ws;                   // row / column partials of the symmetric Chamfer kernel
-    unsigned long long *row64;       // [2][B][n] packed row minima of the symmetric scan's atomic form (small batches, chamfer_sym.h)
+    unsigned long long *row64;       // [2][B][n] packed row minima of the symmetric scan's atomic form (8 or more column slices, chamfer_sym.h)
+    int test_loss_form = 0;          // geoadv_attack_test_loss_form (tests only): how the row minima reach the loss launch and which bodies read them
     bool row64_filled;               // ... set to all ones by this forward's FC2 launch
     bool cgrad_done;                 // the cached forward's loss launch also produced the Chamfer gradients
     bool counted = false;            // this handle is counted in ae->attack_refs (geoadv_ae_set_encoder_arith refuses a switch under it)
@@ -353,9 +354,11 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
     const bool max_term = dist_chamfer && at->cfg.max_point_dist_weight > 0.f;   // the gradient needs the loss pass's arg-max first
     const bool loss_fused = (adv_chamfer || dist_chamfer) && !max_term && n <= CG_FX_MAX_N_PLANE;   // loss_cgrad_kernel below
     const bool merge_in_loss = loss_fused && adv_chamfer && dist_chamfer;
-    // narrow column slices (small batches): row minima folded into packed words by atomics; the FC2 launch fills them on its way
-    const bool use_row64 = merge_in_loss && at->chamfer_sym && at->row64 != nullptr && chamfer_sym_packs_rows((long)B * (pruned ? 1 : 2), n, n);
-    SymPartials part{nullptr, nullptr, 1, B, false, use_row64 ? at->row64 : nullptr};
+    // 8 or more column slices (up to 63 clouds of 2048 points): row minima folded into packed words by atomics; the FC2 launch
+    // fills them on its way
+    const int pack_from = (at->test_loss_form & 1) ? SYM_PACK_FROM + 1 : SYM_PACK_FROM;
+    const bool use_row64 = merge_in_loss && at->chamfer_sym && at->row64 != nullptr && chamfer_sym_packs_rows((long)B * (pruned ? 1 : 2), n, n, pack_from);
+    SymPartials part{nullptr, nullptr, 1, B, false, use_row64 ? at->row64 : nullptr, pack_from};
     {
         ProfScope ps(at, GEOADV_PROF_ENCODER_FWD, st, true);
         if (int rc = launch_encoder_fwd(A, B, at->x, at->pert, (at->adv_valid && !at->adam_pending) ? nullptr : at->adv, at->fs.pmax,
@@ -414,6 +417,7 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
         la.dz_latent = at->dz; la.hist = hist_slot; la.keep = keep; la.best_err = at->best_err;
         la.best_metrics = at->best_metrics; la.adv = at->adv; la.recon = at->recon;
         la.best_adv = at->best_adv; la.best_recon = at->best_recon;
+        la.fold_in_lds = (at->test_loss_form & 2) ? 1 : 0; ca.general = la.fold_in_lds;
         la.part = p; la.a1_need = pruned ? need_scan : nullptr; la.a1_all = pruned ? 0 : 1; la.r1_out = at->r1; la.a1_out = at->a1;
         // the Chamfer gradients the next step starts with ride in the same launch (see loss_cgrad_kernel)
         np = 0;
@@ -851,6 +855,28 @@ extern "C" int geoadv_attack_get_best(geoadv_attack *at, const float *target_ae_
 extern "C" int geoadv_attack_set_source_search(geoadv_attack *at, int on) {
     GA_REQUIRE(at, "attack_set_source_search: null handle");
     at->chamfer_prune = on != 0;           // read by every forward (do_forward); the verdict flags keep their state
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_attack_test_loss_form(geoadv_attack *at, int form) {
+    GA_REQUIRE(at && form >= 0 && form <= 3, "attack_test_loss_form: bad arguments");
+    at->test_loss_form = form;             // read by every forward (do_forward)
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_attack_test_loss_state(geoadv_attack *at, float *g_recon, float *g_dist, float *losses, float *dist_r1,
+                                             float *dist_a1, void *stream) {
+    GA_REQUIRE(at, "attack_test_loss_state: null handle");
+    hipStream_t st = as_stream(stream);
+    const size_t bn3 = 4 * (size_t)at->B * at->n * 3, bn = 4 * (size_t)at->B * at->n;
+    if (at->adam_pending || !at->fwd_valid)
+        if (int rc = do_forward(at, nullptr, 0, st)) return rc;
+    GA_REQUIRE(at->cgrad_done || !(g_recon || g_dist), "attack_test_loss_state: this configuration forms the Chamfer gradients in the step");
+    if (g_recon) GA_HIP(hipMemcpyAsync(g_recon, at->g_recon, bn3, hipMemcpyDeviceToDevice, st));
+    if (g_dist) GA_HIP(hipMemcpyAsync(g_dist, at->g_dist, bn3, hipMemcpyDeviceToDevice, st));
+    if (losses) GA_HIP(hipMemcpyAsync(losses, at->losses, 4 * 8 * (size_t)at->B, hipMemcpyDeviceToDevice, st));
+    if (dist_r1) GA_HIP(hipMemcpyAsync(dist_r1, at->r1, bn, hipMemcpyDeviceToDevice, st));
+    if (dist_a1) GA_HIP(hipMemcpyAsync(dist_a1, at->a1, bn, hipMemcpyDeviceToDevice, st));
     return GEOADV_OK;
 }
 

@@ -13,16 +13,18 @@ struct ChamferPair {
 // What launch_chamfer_sym_loop leaves to the caller's next launch when asked to (`defer`): the row minima as one
 // (distance, index) partial per column slice -- [pair][cloud][slice][n] -- whose lexicographic minimum is dist1 / idx1.
 // deferred == false: dist1 / idx1 are final in the pairs' own arrays (one slice, or the merge launch ran).
-// row64 (narrow column slices, i.e. small batches: more than 8 partials per row would cost a merge launch or a heavy consumer):
-// the scan instead folds every (row, slice) into ONE packed word per row -- (distance bits << 32) | index, 64-bit unsigned atomic
+// row64 (8 or more partials per row -- a merge launch or a heavy consumer, 8 loads per row at the least -- i.e. batches up to
+// 63 clouds of 2048 points): the scan instead folds every (row, slice) into ONE packed word per row -- (distance bits << 32) | index, 64-bit unsigned atomic
 // minimum: squared distances are >= +0, so the order of the words is the lexicographic order of (distance, index) -- in
 // row64[pair][cloud][n], which must hold all ones when the scan starts (the loop's FC2 launch fills it on its way).
+constexpr int SYM_PACK_FROM = 8;
 struct SymPartials {
     const float *rowpart_d;
     const int *rowpart_i;
     int slices, clouds;
     bool deferred;
     unsigned long long *row64;       // in: the caller's packed buffer (or null: never use the atomic form); out: null unless used
+    int pack_from = SYM_PACK_FROM;   // in: the fewest partials per row that are folded into the packed words
 };
 
 #ifdef __HIPCC__
@@ -91,7 +93,7 @@ int launch_nn_nonfinite_fix(int b, int n, const float *xyz1, int m, const float 
                             int *idx2, hipStream_t stream);
 
 size_t chamfer_sym_workspace_floats(int pairs, int b, int n, int m);
-bool chamfer_sym_packs_rows(long live_groups, int n, int m);
+bool chamfer_sym_packs_rows(long live_groups, int n, int m, int pack_from = SYM_PACK_FROM);
 int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, hipStream_t stream);
 struct GridArgs;
 struct JacRider;

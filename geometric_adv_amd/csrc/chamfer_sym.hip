@@ -496,9 +496,9 @@ size_t chamfer_sym_workspace_floats(int pairs, int b, int n, int m) {
 
 // Will launch_chamfer_sym_loop fold the row minima into the caller's packed words (SymPartials::row64) at this shape?  (The caller
 // fills them with all ones beforehand only then.)  live_groups: clouds x problems that are not gated off.
-bool chamfer_sym_packs_rows(long live_groups, int n, int m) {
+bool chamfer_sym_packs_rows(long live_groups, int n, int m, int pack_from) {
     const SymShape s = sym_shape(live_groups, n, m, true, mx_enabled());
-    return s.rtiles == 1 && s.cslices * s.cw > 8;
+    return s.rtiles == 1 && s.cslices * s.cw >= pack_from;
 }
 
 // pairs: up to 2 problems with identical (n, m).  Requires n >= 1, m >= 1.
@@ -525,6 +525,7 @@ int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m,
                           SymPartials *defer, bool loop, LossRider *loss) {
     if (loss) loss->blocks = 0;
     unsigned long long *row64 = defer ? defer->row64 : nullptr;
+    const int pack_from = defer ? defer->pack_from : SYM_PACK_FROM;
     if (defer) { defer->slices = 1; defer->rowpart_d = nullptr; defer->rowpart_i = nullptr; defer->clouds = b; defer->deferred = false; defer->row64 = nullptr; }
     if (b <= 0 || np <= 0) return GEOADV_OK;
     ChamferSymArgs a;
@@ -542,8 +543,9 @@ int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m,
     a.rowpart_i = reinterpret_cast<int *>(workspace + groups * rslices * n);
     a.colpart_d = workspace + 2 * groups * rslices * n;
     a.colpart_i = reinterpret_cast<int *>(a.colpart_d + groups * s.rtiles * m);
-    // more than 8 row partials per row (narrow slices: small batches) and a caller that reads packed words: atomic form
-    a.row64 = (defer && row64 && s.rtiles == 1 && rslices > 8) ? row64 : nullptr;
+    // 8 or more row partials per row (one 256-column slice each at 2048 points, or narrower ones) and a caller that reads packed
+    // words: atomic form
+    a.row64 = (defer && row64 && s.rtiles == 1 && rslices >= pack_from) ? row64 : nullptr;
     static DeviceOnce attr;
     if (int rc = attr.run([]() -> int {
             const int need = (int)std::max(std::max(std::max(CS_LDS_BYTES, MX_LDS_BYTES), chamfer_grid_lds_bytes(GR_MAX_N)), JAC_LDS_BYTES);

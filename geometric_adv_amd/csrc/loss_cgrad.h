@@ -42,6 +42,7 @@ struct LossArgs {
     SymPartials part;
     const int *a1_need; int a1_all;
     float *r1_out, *a1_out;
+    int fold_in_lds = 0;              // tests only: packed words go through loss_premerge's LDS arrays like the partials do
 };
 
 // One pass for everything: 5 sums and 2 (max, lowest index) pairs per thread, reduced across the
@@ -99,7 +100,7 @@ __device__ __forceinline__ void loss_premerge(const LossArgs &a, const int b, co
     const bool part3 = a.a1_all || (a.a1_need && sym_needed(a.a1_need, b));
     const size_t sl = (size_t)a.part.slices * n, o = (size_t)b * n;
     const float *p1 = a.part.rowpart_d + (size_t)b * sl, *p3 = a.part.rowpart_d + ((size_t)B + b) * sl;
-    const unsigned long long *w1 = a.part.row64 + o, *w3 = a.part.row64 + (size_t)B * n + o;      // packed form (small batches)
+    const unsigned long long *w1 = a.part.row64 + o, *w3 = a.part.row64 + (size_t)B * n + o;      // packed form (LossArgs::fold_in_lds)
     for (int j = threadIdx.x; j < n; j += nthreads) {
         float v1, v3 = 0.f;
         if (a.part.row64) {
@@ -115,7 +116,8 @@ __device__ __forceinline__ void loss_premerge(const LossArgs &a, const int b, co
 }
 
 // cloud b of B; executed by threads 0..255 of the workgroup (whole waves beyond that may have exited).  m1 / m3: loss_premerge's
-// LDS arrays when a.part.deferred (else unused)
+// LDS arrays when a.part.deferred (else unused); m1 == nullptr with a.part.deferred: the packed words (a.part.row64) are read here,
+// in the same round trip as everything else, and their distances left in r1 / a1
 __device__ __forceinline__ void loss_metrics_body(const LossArgs &a, const int b, const int B, const float *m1 = nullptr, const float *m3 = nullptr) {
     __shared__ float shf[4][8];
     __shared__ int shi[4][2];
@@ -129,16 +131,32 @@ __device__ __forceinline__ void loss_metrics_body(const LossArgs &a, const int b
     r.ja = r.jp = INT_MAX;
     const bool part1 = a.part.deferred;                                                  // (uniform)
     const bool part3 = part1 && (a.a1_all || (a.a1_need && sym_needed(a.a1_need, b)));
+    const bool words = part1 && m1 == nullptr;
+    const unsigned long long *w1 = a.part.row64 + o, *w3 = a.part.row64 + (size_t)B * n + o;
     constexpr int U = 4;                                  // points per thread and pass: all 7 * U loads requested first
     for (int j0 = t; j0 < n; j0 += U * 256) {             // (same order of accumulation as one point per pass)
         float v1[U], v2[U], v3[U], v4[U], vx[U], vy[U], vz[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u * 256 < n ? j0 + u * 256 : t;
-            v1[u] = part1 ? m1[j] : a.r1[o + j];
-            v3[u] = part3 ? m3[j] : a.a1[o + j];
+            if (words) {
+                v1[u] = __uint_as_float((unsigned)(w1[j] >> 32));
+                v3[u] = part3 ? __uint_as_float((unsigned)(w3[j] >> 32)) : a.a1[o + j];
+            } else {
+                v1[u] = part1 ? m1[j] : a.r1[o + j];
+                v3[u] = part3 ? m3[j] : a.a1[o + j];
+            }
             v2[u] = a.r2[o + j]; v4[u] = a.a2[o + j];
             vx[u] = a.pert[(o + j) * 3]; vy[u] = a.pert[(o + j) * 3 + 1]; vz[u] = a.pert[(o + j) * 3 + 2];
+        }
+        if (words) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + u * 256;
+                if (j >= n) continue;
+                a.r1_out[o + j] = v1[u];
+                if (part3) a.a1_out[o + j] = v3[u];
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -204,7 +222,7 @@ __device__ __forceinline__ void loss_metrics_body(const LossArgs &a, const int b
     }
 }
 
-struct CGradArgs { CGradProblem pr[2]; int n, P; };
+struct CGradArgs { CGradProblem pr[2]; int n, P; int general = 0; };   // general = 1 (tests only): cgrad_fx_body at every shape
 constexpr int CGA_THREADS = 512;
 
 // Fast variant for the loop (n*24 B of LDS must fit): instead of sorting, every scatter term is
@@ -342,21 +360,112 @@ __device__ __forceinline__ void cgrad_fx_body(const CGradArgs &a, const int pi, 
     }
 }
 
+// The same for H == 1 and n <= U * CGA_THREADS (the loop at up to 2048 points), where one pass covers the cloud: thread t owns the
+// points j = t + u * CGA_THREADS, which are also the scatter sources k it walks.  Two load round trips instead of the general
+// body's four to five (each one meets a cold L2 behind the kernel boundary): p_j, q_k, idx2[k] and the own match -- final, a packed
+// word, or the slice distances -- are requested together; then both dependent gathers, q[idx1[j]] and p[idx2[k]] (the slice form
+// takes the winner's index in a round trip between).  Same terms, same fixed-point sums: the same bits as cgrad_fx_body.
+constexpr int CG_FX_U = 4;
+__device__ __forceinline__ void cgrad_fx_body_1pass(const CGradArgs &a, const int pi, const int b, unsigned *lds) {
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(lds);     // [n][3]
+    const CGradProblem pr = a.pr[pi];
+    const int n = a.n;
+    const float wb = pr.w ? pr.w[b] : 1.0f;
+    const float gd = wb * (1.0f / (float)n);
+    const float g2 = gd * 2;
+    const float *p = pr.p + (size_t)b * n * 3, *q = pr.q + (size_t)b * n * 3;
+    const int *i1 = pr.idx1 + (size_t)b * n, *i2 = pr.idx2 + (size_t)b * n;
+    const bool part = (pr.part_d || pr.part_w) && (!pr.part_need || sym_needed(pr.part_need, b));          // (uniform)
+    const float *pd = pr.part_d + (size_t)b * pr.part_slices * n;
+    const int *pi_ = pr.part_i + (size_t)b * pr.part_slices * n;
+    const unsigned long long *pw = pr.part_w + (size_t)b * n;
+    const int js = (pr.jstar && pr.extra_w > 0.f) ? pr.jstar[b] : -1;
+    constexpr int U = CG_FX_U;
+    int jc[U], jj[U], mj[U];
+    float po[U][3], qo[U][3];                    // p_j and q_k (k == j): no index needed
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int j = threadIdx.x + u * CGA_THREADS;
+        jc[u] = j < n ? j : 0;
+        jj[u] = i2[jc[u]];                       // other point k matched our point jj
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { po[u][c] = p[3 * jc[u] + c]; qo[u][c] = q[3 * jc[u] + c]; }
+    }
+    if (part && pr.part_w) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) mj[u] = (int)(unsigned)pw[jc[u]];
+    } else if (part) {
+        int sl[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) (void)sym_merge_pick(pd + jc[u], pr.part_slices, n, sl[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) mj[u] = pi_[(size_t)sl[u] * n + jc[u]];
+    } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) mj[u] = i1[jc[u]];
+    }
+    for (int e = threadIdx.x; e < 3 * n; e += CGA_THREADS) acc[e] = 0ull;
+    float qm[U][3], ps[U][3];                    // q[idx1[j]] and p[idx2[k]]
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { qm[u][c] = q[3 * mj[u] + c]; ps[u][c] = p[3 * jj[u] + c]; }
+    }
+    if (part) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (threadIdx.x + u * CGA_THREADS < n) pr.idx1_out[(size_t)b * n + jc[u]] = mj[u];
+    }
+    __syncthreads();
+    LC_STAMP(1, 1);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (threadIdx.x + u * CGA_THREADS >= n) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = g2 * (qo[u][c] - ps[u][c]);
+            const long long f = __double2ll_rn((double)t * CG_FX);
+            atomicAdd(&acc[3 * jj[u] + c], (unsigned long long)f);
+        }
+    }
+    __syncthreads();
+    LC_STAMP(1, 2);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int j = threadIdx.x + u * CGA_THREADS;
+        if (j >= n) continue;
+        const float gown = (j == js ? gd + wb * pr.extra_w : gd) * 2;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float own = gown * (po[u][c] - qm[u][c]);
+            const float sc = (float)((double)(long long)acc[3 * j + c] * (1.0 / CG_FX));
+            pr.g[((size_t)b * n + j) * 3 + c] = own - sc;
+        }
+    }
+}
+__device__ __forceinline__ void cgrad_fx(const CGradArgs &a, const int pi, const int b, const int h, const int H, unsigned *lds) {
+    if (H == 1 && a.n <= CG_FX_U * CGA_THREADS && !a.general) cgrad_fx_body_1pass(a, pi, b, lds);     // (uniform)
+    else cgrad_fx_body(a, pi, b, h, H, lds);
+}
+
 // One workgroup (CGA_THREADS) of the fused pass for cloud b of B: row 0 = losses / metrics / keep-best (its four upper waves leave
-// after folding the row partials), rows 1.. = gradients (problem (row - 1) / H, part (row - 1) % H).  dyn: the workgroup's dynamic
+// after folding the row partials -- at once when the row minima come as packed words), rows 1.. = gradients (problem (row - 1) / H,
+// part (row - 1) % H).  dyn: the workgroup's dynamic
 // LDS, loss_cgrad_lds_bytes(n) at least.
 inline size_t loss_cgrad_lds_bytes(int n) { return std::max(cgrad_fx_lds_bytes(n), sizeof(float) * 2 * (size_t)LOSS_PRE_MAX_N); }
 __device__ __forceinline__ void loss_cgrad_block(const LossArgs &la, const CGradArgs &ca, const int H, const int b, const int B, const int row, unsigned *dyn) {
     if (row == 0) {
         float *m1 = reinterpret_cast<float *>(dyn), *m3 = m1 + LOSS_PRE_MAX_N;
-        if (la.part.deferred) {                            // (uniform) all eight waves fold the row partials, four sum them
+        // (uniform) all eight waves fold the row partials, four sum them; packed words need no folding: the four read them directly
+        const bool fold = la.part.deferred && (la.part.row64 == nullptr || la.fold_in_lds);
+        if (fold) {
             loss_premerge(la, b, B, CGA_THREADS, m1, m3);
             __syncthreads();
         }
-        if (threadIdx.x < 256) loss_metrics_body(la, b, B, m1, m3);
+        if (threadIdx.x < 256) loss_metrics_body(la, b, B, fold ? m1 : nullptr, m3);
     } else {
         LC_STAMP(1, 0);
-        cgrad_fx_body(ca, (row - 1) / H, b, (row - 1) % H, H, dyn);
+        cgrad_fx(ca, (row - 1) / H, b, (row - 1) % H, H, dyn);
         LC_STAMP(1, 7);
     }
 }

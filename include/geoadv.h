@@ -807,6 +807,17 @@ int geoadv_attack_status(geoadv_attack *at, void *stream);
 int geoadv_attack_peek(geoadv_attack *at, float *pert, float *adv, float *recon, float *latent,
                        float *grad, int *idx_r1, int *idx_r2, int *idx_a1, int *idx_a2, void *stream);
 
+/* TESTS ONLY.  The loss / Chamfer-gradient launch of the loop reads the symmetric scan's row minima in the cheapest form the shape
+ * admits; `form` selects, from the next forward on, the forms it replaced -- bit 0: packed (distance, index) words only from 9
+ * column slices on (8 slices leave as one partial per slice), bit 1: the general multi-pass gradient body at every size and the
+ * packed words folded through LDS.  0 = the default.  Same results, bit for bit. */
+int geoadv_attack_test_loss_form(geoadv_attack *at, int form);
+/* TESTS ONLY.  Copies of what the cached forward's loss launch left (any pointer may be NULL): the Chamfer gradients g_recon / g_dist
+ * [B,N,3] w.r.t. the reconstruction and the adversarial cloud, losses [8,B] (loss_adv, loss_dist, loss_pert, loss_max | max_dist,
+ * input_dist, loss_ae, loss_max(pert), max_dist), and the row minima dist_r1 / dist_a1 [B,N] of nn_distance(recon, gt) / (adv, x). */
+int geoadv_attack_test_loss_state(geoadv_attack *at, float *g_recon, float *g_dist, float *losses, float *dist_r1, float *dist_a1,
+                                  void *stream);
+
 /* How nn_distance(adv, x) is being answered: *searched = 1 if the paired grid search is in use for this handle (0: all-pairs
  * kernel, by configuration or batch size), *handed_back = number of clouds of the batch whose pairing the search currently
  * judges too poor (they go through the all-pairs kernel; verdicts of the last forward).  Synchronises the stream. */
