@@ -235,6 +235,20 @@ class AdvAE:
                        ("g_recon", "g_dist", "losses", "dist_r1", "dist_a1")], _lib.stream_handle()), "attack_test_loss_state")
         return out
 
+    def _test_plan(self):
+        """Tests only (geoadv_attack_test_plan): what the cached forward launched, as the library recorded it -- symmetric, screened
+        (bool), rtiles, rslices, H, range (int: parts of the fixed-point gradient body and receiving points per part), rows ('final' | 'partials' | 'packed' | 'merge_launch'), loss ('metrics' | 'fused' |
+        'riders'), grad ('none' | 'fused_1pass' | 'fused_general' | 'step_fx_1pass' | 'step_fx_general' | 'step_sorted') -- and
+        jstar [2, B] (GPU tensor): the arg-max points its loss row found for the max-point terms (distance, perturbation)."""
+        plan = (C.c_int * 9)()                     # GEOADV_PLAN_COUNT
+        jstar = torch.empty((2, self.B), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().geoadv_attack_test_plan(self._h, plan, _lib.ptr(jstar), _lib.stream_handle()), "attack_test_plan")
+        return dict(symmetric=bool(plan[0]), screened=bool(plan[1]), rtiles=plan[2], rslices=plan[3],
+                    rows=("final", "partials", "packed", "merge_launch")[plan[4]], loss=("metrics", "fused", "riders")[plan[5]],
+                    grad=("none", "fused_1pass", "fused_general", "step_fx_1pass", "step_fx_general", "step_sorted")[plan[6]],
+                    H=plan[7], range=plan[8], jstar=jstar)
+
     def profile(self, classes, stride=1):
         """classes: True/False for all/none, or an iterable of PROF_NAMES to time; stride: time every stride-th launch."""
         _lib.check(_lib.lib().geoadv_attack_profile_stride(self._h, int(stride)), "attack_profile_stride")

@@ -230,6 +230,7 @@ struct geoadv_attack {
     float *sym_ws;                   // row / column partials of the symmetric Chamfer kernel
     unsigned long long *row64;       // [2][B][n] packed row minima of the symmetric scan's atomic form (8 or more column slices, chamfer_sym.h)
     int test_loss_form = 0;          // geoadv_attack_test_loss_form (tests only): how the row minima reach the loss launch and which bodies read them
+    int plan[GEOADV_PLAN_COUNT] = {};         // geoadv_attack_test_plan (tests only): what the last forward launched, GEOADV_PLAN_* (host bookkeeping)
     bool row64_filled;               // ... set to all ones by this forward's FC2 launch
     bool cgrad_done;                 // the cached forward's loss launch also produced the Chamfer gradients
     bool counted = false;            // this handle is counted in ae->attack_refs (geoadv_ae_set_encoder_arith refuses a switch under it)
@@ -339,6 +340,8 @@ struct ProfScope {
 };
 
 
+bool cgrad_step_sorted(int n) { return n > CG_FX_MAX_N_PLANE; }   // launch_cgrad below: the sorted kernel instead of the fixed-point bodies
+
 // forward(pert): encoder -> latent/decoder -> both Chamfer problems -> per-cloud losses (+ metrics / keep-best).
 int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
     const DeviceAE &A = at->ae->d;
@@ -446,6 +449,7 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
     LossRider lr;
     lr.blocks = 0; lr.patch = nullptr; lr.ctx = nullptr; lr.force = false;
     bool want_host = false, hosted = false;
+    SymLaunchInfo info{0, 0, 0, GEOADV_PLAN_ROWS_FINAL};           // (two-scan kernel: final rows, nothing else to report)
     {
         ProfScope ps(at, GEOADV_PROF_CHAMFER_FWD, st);
         if (at->chamfer_sym) {   // one distance evaluation per pair serves both directions
@@ -470,7 +474,7 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
             // the row minima leave the scan as one (distance, index) partial per column slice; when the loss launch below is the
             // fused one with both Chamfer gradients inside, it merges them on its way in (no second Chamfer launch)
             if (int rc = launch_chamfer_sym_loop(pairs, 2, B, n, n, at->sym_ws, pruned ? need_scan : nullptr, rides_scan ? &rider : nullptr,
-                                                 jac_rides ? &jr : nullptr, merge_in_loss ? &part : nullptr, st, want_host ? &lr : nullptr)) return rc;
+                                                 jac_rides ? &jr : nullptr, merge_in_loss ? &part : nullptr, st, want_host ? &lr : nullptr, &info)) return rc;
             hosted = want_host && lr.blocks > 0;
             if (hosted) { at->loss_target = lr.target; at->cgrad_done = true; }
         } else {
@@ -499,6 +503,21 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
         }
         GA_LAUNCH_CHECK();
     }
+    {   // the tests' read-out: what this forward launched, and the gradient launch it leaves to the step
+        const int np = (adv_chamfer ? 1 : 0) + (dist_chamfer ? 1 : 0), H = cgrad_fx_parts(n);
+        const int general = (at->test_loss_form & 2) ? 1 : 0;
+        int *pl = at->plan;
+        pl[GEOADV_PLAN_SYMMETRIC] = at->chamfer_sym ? 1 : 0; pl[GEOADV_PLAN_SCREENED] = info.mx;
+        pl[GEOADV_PLAN_RTILES] = info.rtiles; pl[GEOADV_PLAN_RSLICES] = info.rslices; pl[GEOADV_PLAN_ROWS] = info.rows;
+        pl[GEOADV_PLAN_LOSS] = hosted ? GEOADV_PLAN_LOSS_RIDERS : loss_fused ? GEOADV_PLAN_LOSS_FUSED : GEOADV_PLAN_LOSS_METRICS;
+        if (at->cgrad_done) pl[GEOADV_PLAN_GRAD] = cgrad_fx_one_pass(n, H, general) ? GEOADV_PLAN_GRAD_FUSED_1PASS : GEOADV_PLAN_GRAD_FUSED_GENERAL;
+        else if (np == 0) pl[GEOADV_PLAN_GRAD] = GEOADV_PLAN_GRAD_NONE;
+        else if (cgrad_step_sorted(n)) pl[GEOADV_PLAN_GRAD] = GEOADV_PLAN_GRAD_STEP_SORTED;
+        else pl[GEOADV_PLAN_GRAD] = cgrad_fx_one_pass(n, H, 0) ? GEOADV_PLAN_GRAD_STEP_FX_1PASS : GEOADV_PLAN_GRAD_STEP_FX_GENERAL;   // (launch_cgrad: never `general`)
+        const int g = pl[GEOADV_PLAN_GRAD];
+        const bool fx = !(g == GEOADV_PLAN_GRAD_NONE || g == GEOADV_PLAN_GRAD_STEP_SORTED);
+        pl[GEOADV_PLAN_H] = fx ? H : 0; pl[GEOADV_PLAN_RANGE] = fx ? cgrad_fx_range(n) : 0;
+    }
     at->fwd_valid = true;
     return GEOADV_OK;
 }
@@ -509,7 +528,7 @@ int launch_cgrad(const CGradProblem *pr, int np, int B, int n, hipStream_t st) {
     CGradArgs ca;
     for (int i = 0; i < np; ++i) ca.pr[i] = pr[i];
     ca.n = n; ca.P = pow2_ge(n);
-    if (n <= CG_FX_MAX_N_PLANE) {
+    if (!cgrad_step_sorted(n)) {
         const int H = cgrad_fx_parts(n);
         chamfer_grad_attack_fx_kernel<<<dim3(B, np * H), CGA_THREADS, cgrad_fx_lds_bytes(n), st>>>(ca, H);
         GA_LAUNCH_CHECK();
@@ -877,6 +896,16 @@ extern "C" int geoadv_attack_test_loss_state(geoadv_attack *at, float *g_recon, 
     if (losses) GA_HIP(hipMemcpyAsync(losses, at->losses, 4 * 8 * (size_t)at->B, hipMemcpyDeviceToDevice, st));
     if (dist_r1) GA_HIP(hipMemcpyAsync(dist_r1, at->r1, bn, hipMemcpyDeviceToDevice, st));
     if (dist_a1) GA_HIP(hipMemcpyAsync(dist_a1, at->a1, bn, hipMemcpyDeviceToDevice, st));
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_attack_test_plan(geoadv_attack *at, int plan[GEOADV_PLAN_COUNT], int *jstar, void *stream) {
+    GA_REQUIRE(at && plan, "attack_test_plan: null argument");
+    hipStream_t st = as_stream(stream);
+    if (at->adam_pending || !at->fwd_valid)
+        if (int rc = do_forward(at, nullptr, 0, st)) return rc;
+    for (int i = 0; i < GEOADV_PLAN_COUNT; ++i) plan[i] = at->plan[i];
+    if (jstar) GA_HIP(hipMemcpyAsync(jstar, at->jstar, sizeof(int) * 2 * (size_t)at->B, hipMemcpyDeviceToDevice, st));
     return GEOADV_OK;
 }
 

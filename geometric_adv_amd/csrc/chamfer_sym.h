@@ -98,10 +98,15 @@ int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, fl
 struct GridArgs;
 struct JacRider;
 struct LossRider;
+// What a launch_chamfer_sym_loop call launched (host bookkeeping for the tests' read-out, geoadv_attack_test_plan): the screened
+// kernel or the plain one, the row super-tiles and row partials per row of its shape, and how the row minima left it
+// (GEOADV_PLAN_ROWS_*, include/geoadv.h).
+struct SymLaunchInfo { int mx, rtiles, rslices, rows; };
 // loss (or null): the loop's loss + gradient workgroups as the LAST riders of the launch (loss_cgrad.h; first_block / blocks /
 // target are set here).  Returns with loss->blocks == 0 when the launch could not host them (the caller then launches them itself).
 int launch_chamfer_sym_loop(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, const int *need1,
-                            const GridArgs *rider, const JacRider *jac, SymPartials *defer, hipStream_t stream, LossRider *loss = nullptr);
+                            const GridArgs *rider, const JacRider *jac, SymPartials *defer, hipStream_t stream, LossRider *loss = nullptr,
+                            SymLaunchInfo *info = nullptr);
 // can the symmetric scan's launch of this shape host the loss riders?  (the unscreened kernel, one row super-tile, whole groups of 8 clouds)
 bool chamfer_sym_hosts_loss(long live_groups, int b, int n, int m);
 

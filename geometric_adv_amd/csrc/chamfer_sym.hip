@@ -504,7 +504,8 @@ bool chamfer_sym_packs_rows(long live_groups, int n, int m, int pack_from) {
 // pairs: up to 2 problems with identical (n, m).  Requires n >= 1, m >= 1.
 int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, int pair_base,
                           int q_clouds, const int *need1, hipStream_t stream, const GridArgs *rider = nullptr,
-                          const JacRider *jac = nullptr, SymPartials *defer = nullptr, bool loop = false, LossRider *loss = nullptr);
+                          const JacRider *jac = nullptr, SymPartials *defer = nullptr, bool loop = false, LossRider *loss = nullptr,
+                          SymLaunchInfo *info = nullptr);
 int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, hipStream_t stream) {
     return launch_chamfer_sym_ex(pairs, np, b, n, m, workspace, 0, 0, nullptr, stream);
 }
@@ -512,8 +513,9 @@ int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, fl
 // rider (rider->n <= GR_MAX_N): the paired grid search as 8 * b extra workgroups of the scan launch; jac (or null): the pool
 // Jacobian's 8 * b workgroups as well (jac->first_block / blocks are set here); defer (or null): see SymPartials
 int launch_chamfer_sym_loop(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, const int *need1,
-                            const GridArgs *rider, const JacRider *jac, SymPartials *defer, hipStream_t stream, LossRider *loss) {
-    return launch_chamfer_sym_ex(pairs, np, b, n, m, workspace, 0, 0, need1, stream, rider, jac, defer, true, loss);
+                            const GridArgs *rider, const JacRider *jac, SymPartials *defer, hipStream_t stream, LossRider *loss,
+                            SymLaunchInfo *info) {
+    return launch_chamfer_sym_ex(pairs, np, b, n, m, workspace, 0, 0, need1, stream, rider, jac, defer, true, loss, info);
 }
 bool chamfer_sym_hosts_loss(long live_groups, int b, int n, int m) {
     const SymShape s = sym_shape(live_groups, n, m, true, mx_enabled());
@@ -522,7 +524,7 @@ bool chamfer_sym_hosts_loss(long live_groups, int b, int n, int m) {
 
 int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, int pair_base,
                           int q_clouds, const int *need1, hipStream_t stream, const GridArgs *rider, const JacRider *jac,
-                          SymPartials *defer, bool loop, LossRider *loss) {
+                          SymPartials *defer, bool loop, LossRider *loss, SymLaunchInfo *info) {
     if (loss) loss->blocks = 0;
     unsigned long long *row64 = defer ? defer->row64 : nullptr;
     const int pack_from = defer ? defer->pack_from : SYM_PACK_FROM;
@@ -596,6 +598,10 @@ int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m,
     else if (a.row64) { plan.deferred = true; plan.slices = 0; plan.row64 = a.row64; }
     else if (defer && s.rtiles == 1 && rslices <= 8) { plan.deferred = true; plan.slices = rslices; plan.rowpart_d = a.rowpart_d; plan.rowpart_i = a.rowpart_i; }
     else merge_launch = true;
+    if (info) {
+        info->mx = s.mx ? 1 : 0; info->rtiles = s.rtiles; info->rslices = rslices;
+        info->rows = merge_launch ? GEOADV_PLAN_ROWS_MERGE_LAUNCH : !plan.deferred ? GEOADV_PLAN_ROWS_FINAL : plan.row64 ? GEOADV_PLAN_ROWS_PACKED : GEOADV_PLAN_ROWS_PARTIALS;
+    }
     if (host_loss && !merge_launch) {
         // behind everything else: a cloud's riders can only start once its scan and search workgroups are done.  Every workgroup
         // of the scan (np problems, gated off or not) and of the search counts itself into done[cloud] once per call.

@@ -443,10 +443,15 @@ __device__ __forceinline__ void cgrad_fx_body_1pass(const CGradArgs &a, const in
         }
     }
 }
+// the one definition of which body runs: the device's choice below and what the host reports in the tests' read-out of the plan
+// (geoadv_attack_test_plan)
+#define CGRAD_FX_ONE_PASS(H, n, general) ((H) == 1 && (n) <= CG_FX_U * CGA_THREADS && !(general))
 __device__ __forceinline__ void cgrad_fx(const CGradArgs &a, const int pi, const int b, const int h, const int H, unsigned *lds) {
-    if (H == 1 && a.n <= CG_FX_U * CGA_THREADS && !a.general) cgrad_fx_body_1pass(a, pi, b, lds);     // (uniform)
+    if (CGRAD_FX_ONE_PASS(H, a.n, a.general)) cgrad_fx_body_1pass(a, pi, b, lds);     // (uniform)
     else cgrad_fx_body(a, pi, b, h, H, lds);
 }
+
+inline bool cgrad_fx_one_pass(int n, int H, int general) { return CGRAD_FX_ONE_PASS(H, n, general); }   // (host)
 
 // One workgroup (CGA_THREADS) of the fused pass for cloud b of B: row 0 = losses / metrics / keep-best (its four upper waves leave
 // after folding the row partials -- at once when the row minima come as packed words), rows 1.. = gradients (problem (row - 1) / H,

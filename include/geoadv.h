@@ -817,6 +817,26 @@ int geoadv_attack_test_loss_form(geoadv_attack *at, int form);
  * input_dist, loss_ae, loss_max(pert), max_dist), and the row minima dist_r1 / dist_a1 [B,N] of nn_distance(recon, gt) / (adv, x). */
 int geoadv_attack_test_loss_state(geoadv_attack *at, float *g_recon, float *g_dist, float *losses, float *dist_r1, float *dist_a1,
                                   void *stream);
+/* TESTS ONLY.  What the cached forward launched (it is run first if there is none), so that a test can assert the form it was written
+ * for; plan[GEOADV_PLAN_*] (host memory, GEOADV_PLAN_COUNT entries).  jstar (device, [2,B], or NULL): the arg-max points that forward's loss row found -- first
+ * arg-max of the (adv -> source) distances, first arg-max of |pert|^2 -- which the max-point terms of the step use. */
+enum {
+    GEOADV_PLAN_SYMMETRIC = 0,   /* 1: the symmetric scan, 0: the two-scan kernel (rows always final, the next four entries 0) */
+    GEOADV_PLAN_SCREENED = 1,    /* 1: the matrix-pipe-screened scan kernel, 0: the plain one */
+    GEOADV_PLAN_RTILES = 2,      /* row super-tiles of the scan's launch shape */
+    GEOADV_PLAN_RSLICES = 3,     /* row partials per row (column slices x column waves) */
+    GEOADV_PLAN_ROWS = 4,        /* how the row minima left the scan: GEOADV_PLAN_ROWS_* */
+    GEOADV_PLAN_LOSS = 5,        /* which loss row ran: GEOADV_PLAN_LOSS_* */
+    GEOADV_PLAN_GRAD = 6,        /* which Chamfer gradient ran or is left to the step: GEOADV_PLAN_GRAD_* */
+    GEOADV_PLAN_H = 7,           /* parts per (cloud, problem) of the fixed-point gradient body (0 where none runs) */
+    GEOADV_PLAN_RANGE = 8,       /* receiving points per part: part h owns the points [h * range, (h + 1) * range) (0 where none runs) */
+    GEOADV_PLAN_COUNT = 9
+};
+enum { GEOADV_PLAN_ROWS_FINAL = 0, GEOADV_PLAN_ROWS_PARTIALS = 1, GEOADV_PLAN_ROWS_PACKED = 2, GEOADV_PLAN_ROWS_MERGE_LAUNCH = 3 };
+enum { GEOADV_PLAN_LOSS_METRICS = 0, GEOADV_PLAN_LOSS_FUSED = 1, GEOADV_PLAN_LOSS_RIDERS = 2 };
+enum { GEOADV_PLAN_GRAD_NONE = 0, GEOADV_PLAN_GRAD_FUSED_1PASS = 1, GEOADV_PLAN_GRAD_FUSED_GENERAL = 2, GEOADV_PLAN_GRAD_STEP_FX_1PASS = 3,
+       GEOADV_PLAN_GRAD_STEP_FX_GENERAL = 4, GEOADV_PLAN_GRAD_STEP_SORTED = 5 };
+int geoadv_attack_test_plan(geoadv_attack *at, int plan[GEOADV_PLAN_COUNT], int *jstar, void *stream);
 
 /* How nn_distance(adv, x) is being answered: *searched = 1 if the paired grid search is in use for this handle (0: all-pairs
  * kernel, by configuration or batch size), *handed_back = number of clouds of the batch whose pairing the search currently

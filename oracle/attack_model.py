@@ -127,10 +127,11 @@ class AttackModel:
         z, hs = M.encode(adv, keep=True)
         recon, d1, d2 = M.decode(z, keep=True)
         recon32 = recon.astype(np.float32)
-        R1, iR1, R2, iR2 = _o().nn_distance(recon32, self.gt)
-        A1, iA1, A2, iA2 = _o().nn_distance(adv32, self.x)
-        if idx_override is not None:
+        if idx_override is not None:                       # (the all-pairs searches are the model's cost at large clouds: skipped)
             iR1, iR2, iA1, iA2 = idx_override
+        else:
+            _, iR1, _, iR2 = _o().nn_distance(recon32, self.gt)
+            _, iA1, _, iA2 = _o().nn_distance(adv32, self.x)
         B = self.x.shape[0]
         ar = np.arange(B)[:, None]
         # distances in the model's dtype from the (possibly pinned) matches
