@@ -152,13 +152,13 @@ class FoldingNetAE(DeviceModel):
     def restore_model(self, *_args, **_kwargs):
         """foldingnet_ae.py:36-38: the weights are loaded when the object is built."""
 
-    def get_reconstructions(self, pc_input, flags=None):
-        """foldingnet_ae.py:40-66: float32 (n, 2025, 3) reconstructions of any number of clouds, batch_size at a time."""
-        x = self._as_dev(pc_input)
+    def _forward_batches(self, x, p1=False):
+        """Yields (s, e, forward(x[s:e])) over the device clouds x, batch_size at a time, with the object's sampling: device
+        draws at ordinals that run on from the clouds seen so far, or reference_picks of all of x drawn first.  Advances
+        the sampling state by len(x) once the last batch has been taken."""
         total = int(x.shape[0])
-        out = np.zeros((total, G2, 3), dtype=np.float32)
         if total == 0:
-            return out
+            return
         picks = None
         if self.sampling == "reference":
             deg = np.concatenate([self.graph(x[s:s + self.batch_size])[0].cpu().numpy()
@@ -167,13 +167,49 @@ class FoldingNetAE(DeviceModel):
         for s in range(0, total, self.batch_size):
             e = min(total, s + self.batch_size)
             if picks is None:
-                r = self.forward(x[s:e], cloud_offset=self._ordinal + s)
+                r = self.forward(x[s:e], cloud_offset=self._ordinal + s, p1=p1)
             else:
-                r = self.forward(x[s:e], picks=picks[:, s:e])
-            out[s:e] = r["recon"].cpu().numpy()
+                r = self.forward(x[s:e], picks=picks[:, s:e], p1=p1)
+            yield s, e, r
         if picks is None:
             self._ordinal += total
+
+    def get_reconstructions(self, pc_input, flags=None):
+        """foldingnet_ae.py:40-66: float32 (n, 2025, 3) reconstructions of any number of clouds, batch_size at a time."""
+        x = self._as_dev(pc_input)
+        out = np.zeros((int(x.shape[0]), G2, 3), dtype=np.float32)
+        for s, e, r in self._forward_batches(x):
+            out[s:e] = r["recon"].cpu().numpy()
         return out
+
+    def evaluate(self, clouds, progress=None):
+        """tst_foldingnet.py:75-94 per cloud: {'loss_per_pc', 'mid_loss_per_pc'}, float32 (n,) -- the Chamfer distance
+        (get_loss_per_pc) between every cloud and its reconstruction, and between it and fold1's output.  The clouds go
+        through forward(..., p1=True) batch_size at a time with the sampling and ordinals of get_reconstructions, so a
+        fresh object with the same seed reconstructs the same clouds.  The nearest-neighbour distances of all batches are
+        kept on the device and averaged per cloud in one step, the one get_loss_per_pc takes over the same clouds, so the
+        result equals get_loss_per_pc(get_reconstructions(clouds), clouds) bit for bit and does not depend on batch_size.
+        progress(batch index, seconds), if given, is called after every batch, once the GPU has finished it."""
+        import time
+        x = self._as_dev(clouds)
+        total, n = int(x.shape[0]), int(x.shape[1])
+        if total == 0:
+            return {"loss_per_pc": np.zeros(0, np.float32), "mid_loss_per_pc": np.zeros(0, np.float32)}
+        dists = {k: (torch.empty((total, G2), dtype=torch.float32, device=self.device),
+                     torch.empty((total, n), dtype=torch.float32, device=self.device)) for k in ("recon", "p1")}
+        start = time.time()
+        for j, (s, e, r) in enumerate(self._forward_batches(x, p1=True)):
+            for k, (to_cloud, to_output) in dists.items():
+                to_cloud[s:e], _, to_output[s:e], _ = ops.nn_distance(r[k], x[s:e])
+            if progress is not None:
+                torch.cuda.synchronize(self.device)
+                progress(j, time.time() - start)
+                start = time.time()
+        return {"loss_per_pc": self._chamfer_per_pc(*dists["recon"]), "mid_loss_per_pc": self._chamfer_per_pc(*dists["p1"])}
+
+    @staticmethod
+    def _chamfer_per_pc(d1, d2):
+        return (d1.mean(1) + d2.mean(1)).cpu().numpy()
 
     def get_loss_per_pc(self, pc_recon, target_pc):
         """foldingnet_ae.py:68-87 (ChamferDistance :209-238): per cloud mean(dist1) + mean(dist2) of
@@ -182,4 +218,4 @@ class FoldingNetAE(DeviceModel):
         assert len(target_pc.shape) == 3, 'The target_pc should have 3 dimensions'
         assert pc_recon.shape[0] == target_pc.shape[0], 'Number of point clouds must match'
         d1, _, d2, _ = ops.nn_distance(self._as_dev(pc_recon), self._as_dev(target_pc))
-        return (d1.mean(1) + d2.mean(1)).cpu().numpy()
+        return self._chamfer_per_pc(d1, d2)
