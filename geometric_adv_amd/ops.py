@@ -374,6 +374,77 @@ def sort_axes(point_clouds, neg_rot=True):
     return out, axes_idx
 
 
+class BatchAugment(C.Structure):
+    """geoadv_batch_augment (include/geoadv.h): the noise generator's key (seed, counter, slot_offset), the noise (mu, sigma,
+    clip; sigma 0 = none, clip <= 0 = unclamped) and the order of noise and rotation.  rot_count is filled in by batch_gather."""
+    _fields_ = [("seed", C.c_ulonglong), ("counter", C.c_ulonglong), ("slot_offset", C.c_int), ("noise_mu", C.c_float),
+                ("noise_sigma", C.c_float), ("noise_clip", C.c_float), ("rot_count", C.c_int), ("rotate_first", C.c_int)]
+
+
+def batch_gather(data, index=None, augment=None, rot=None, want_clean=False):
+    """One training batch out of resident clouds in one launch (csrc/dataset.hip, geoadv_batch_gather).
+    data: GPU float32 (num_clouds, n, 3).  index: the source cloud of every output cloud -- a host sequence / numpy array
+    (range-checked here: ValueError before any launch) or a device integer tensor (not checked on the host: the kernel never
+    reads outside data and leaves the slot of a bad index unwritten); None = every cloud of data in order.
+    augment: None, a BatchAugment or a dict of its fields (seed, counter, slot_offset, noise_mu, noise_sigma, noise_clip,
+    rotate_first).  rot: None, or rotation matrices (3, 3) for the whole batch / (b, 3, 3) one per cloud, numpy or a float64
+    GPU tensor; a point is a row vector times its matrix, in float64.
+    -> feed (b, n, 3), or (clean, feed) with want_clean: clean holds the bits of data[index]."""
+    import numpy as np
+    data = _f32(data, "data", 3)
+    if data.shape[2] != 3:
+        raise ValueError("batch_gather only accepts 3d point sets")
+    num_clouds, n, _ = data.shape
+    dev = data.device
+    if index is None:
+        b, idx = num_clouds, None
+    elif isinstance(index, torch.Tensor) and index.is_cuda:
+        if index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
+            raise ValueError("index must be a one-dimensional int32 or int64 tensor (got %s of shape %s)" % (index.dtype, tuple(index.shape)))
+        idx = index.to(device=dev, dtype=torch.int32).contiguous()
+        b = int(idx.numel())
+    else:
+        host = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+        if host.ndim != 1 or host.dtype.kind not in "iu":
+            raise ValueError("index must be a one-dimensional integer array")
+        if host.size and (int(host.min()) < 0 or int(host.max()) >= num_clouds):
+            raise ValueError("index out of range: values %d .. %d for %d clouds" % (int(host.min()), int(host.max()), num_clouds))
+        b = int(host.size)
+        idx = torch.from_numpy(host.astype(np.int32)).to(dev)
+    if b < 1 or n < 1:
+        raise ValueError("batch_gather needs at least one cloud and one point (b=%d, n=%d)" % (b, n))
+    aug = None
+    if isinstance(augment, BatchAugment):
+        aug = BatchAugment.from_buffer_copy(augment)
+    elif augment is not None:
+        unknown = set(augment) - {f for f, _ in BatchAugment._fields_ if f != "rot_count"}
+        if unknown:
+            raise ValueError("unknown augment fields %s" % sorted(unknown))
+        aug = BatchAugment(**augment)
+    rot_dev = None
+    if rot is not None:
+        if aug is None:
+            aug = BatchAugment()
+        if isinstance(rot, torch.Tensor):
+            rot_dev = rot.to(device=dev, dtype=torch.float64)
+        else:
+            rot_dev = torch.from_numpy(np.ascontiguousarray(rot, dtype=np.float64)).to(dev)
+        if rot_dev.dim() == 2:
+            rot_dev = rot_dev[None]
+        if rot_dev.dim() != 3 or tuple(rot_dev.shape[1:]) != (3, 3) or rot_dev.shape[0] not in (1, b):
+            raise ValueError("rot must be (3, 3) or (%d, 3, 3); got %s" % (b, tuple(rot_dev.shape)))
+        rot_dev = rot_dev.contiguous()
+        aug.rot_count = int(rot_dev.shape[0])
+    elif aug is not None:
+        aug.rot_count = 0
+    feed = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    clean = torch.empty_like(feed) if want_clean else None
+    with torch.cuda.device(dev):
+        _call("geoadv_batch_gather", b, n, _lib.ptr(data), C.c_longlong(num_clouds), _lib.ptr(idx),
+              C.byref(aug) if aug is not None else None, _lib.ptr(rot_dev), _lib.ptr(clean), _lib.ptr(feed))
+    return (clean, feed) if want_clean else feed
+
+
 # ---------------------------------------------------------------------------------------------
 # classifier/provider.py, device side
 # ---------------------------------------------------------------------------------------------

@@ -18,6 +18,17 @@ Two sources of training clouds:
                than one batch is taken whole) appended to train_stats.txt as `On Held_Out: <epoch>\t<loss>\t<minutes>`
                (autoencoder.py:222-226).
   --train_data one `.npy` of shape (n, n_points, 3) (axes already sorted if wanted), shuffled once per epoch with numpy.
+Data side (all off by default; with the defaults every path, file and bit is what it was):
+  --device_data 1          the training clouds are uploaded once (device_data.DevicePointCloudDataSet) and every batch is one
+                           gather launch by index; shuffles reorder a host index array.  The --train_data path replaces
+                           data[perm] by that index gather.
+  --gauss_augment_sigma S [--gauss_augment_mu M], --z_rotate 1, --denoising 1
+                           the reference's Configuration.gauss_augment / z_rotate / denoising (src/general_utils.py:124-144,
+                           src/pointnet_ae.py:116-128), applied on the device in the batch's launch.  z_rotate draws its matrix
+                           from numpy's global stream as the reference does; the Gaussian noise is the device generator's
+                           (csrc/dataset.hip) keyed by --seed and the batch count, so a run with noise does not advance numpy's
+                           stream by the reference's np.random.normal draws and its later shuffles differ from the reference's.
+                           configuration.json gains `denoising`, `z_rotate` and `gauss_augment` only when one of them is set.
 Multi-GPU: launch with torchrun; every rank takes its shard of each batch and the flat gradient buffer is all-reduced (RCCL).
 
     python -m geometric_adv_amd.train_ae --data_dir data/shape_net_core_uniform_samples_2048 --train_folder log/autoencoder_victim
@@ -51,6 +62,11 @@ def build_parser():
     p.add_argument('--learning_rate', type=float, default=0.0005)
     p.add_argument('--saver_step', type=int, default=50)
     p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--device_data', type=int, default=0, help='1: keep the training clouds on the GPU and gather every batch there, 0: host batches [default: 0]')
+    p.add_argument('--denoising', type=int, default=0, help='1: feed the augmented batch and take the loss against the clean one [default: 0]')
+    p.add_argument('--z_rotate', type=int, default=0, help='1: one random rotation about z per batch [default: 0]')
+    p.add_argument('--gauss_augment_mu', type=float, default=0.0, help='mean of the Gaussian noise added to every coordinate [default: 0]')
+    p.add_argument('--gauss_augment_sigma', type=float, default=0.0, help='its standard deviation; 0: no noise [default: 0]')
     return p
 
 
@@ -61,6 +77,8 @@ def parse_flags(argv=None):
         p.error('one of --data_dir (ShapeNet PLY folder) and --train_data (.npy of clouds) is required')
     if flags.train_data is not None and flags.data_dir is not None:
         p.error('--data_dir and --train_data are two sources of the training clouds: give one of them')
+    if flags.gauss_augment_sigma < 0:
+        p.error('--gauss_augment_sigma must be >= 0')
     return flags
 
 
@@ -71,11 +89,16 @@ def make_configuration(flags, n_points):
     have to read the classes' folders, refuses such a train folder."""
     from_ply = flags.data_dir is not None
     class_names = list(flags.class_names) if from_ply else []
-    return {'n_input': [int(n_points), 3], 'loss': 'chamfer', 'batch_size': flags.batch_size, 'learning_rate': flags.learning_rate,
+    conf = {'n_input': [int(n_points), 3], 'loss': 'chamfer', 'batch_size': flags.batch_size, 'learning_rate': flags.learning_rate,
             'training_epochs': flags.training_epochs, 'saver_step': flags.saver_step, 'bneck_size': 128,
             'object_class': ['%dl' % len(class_names)] if from_ply else [], 'class_names': class_names,
             'sort_axes': int(flags.sort_axes) if from_ply else 0, 'experiment_name': 'autoencoder',
             'held_out_step': flags.held_out_step, 'data_source': 'data_dir' if from_ply else 'train_data'}
+    gauss = flags.gauss_augment_sigma > 0
+    if gauss or flags.z_rotate or flags.denoising:     # only then: the default dictionary stays as it was
+        conf.update({'denoising': bool(flags.denoising), 'z_rotate': bool(flags.z_rotate),
+                     'gauss_augment': {'mu': flags.gauss_augment_mu, 'sigma': flags.gauss_augment_sigma} if gauss else None})
+    return conf
 
 
 def save_configuration(train_dir, conf):
@@ -126,9 +149,14 @@ class _RankShard(object):
         self.ds, self.rank, self.world = data_set, rank, world
         self.num_examples = data_set.num_examples // world
 
-    def next_batch(self, local_bs):
+        self.device_resident = getattr(data_set, 'device_resident', False)
+
+    def next_batch(self, local_bs, **device_kw):
+        if self.device_resident:              # the global batch is drawn, this rank's slice of it gathered
+            return self.ds.next_batch(local_bs * self.world, rank_slice=(self.rank, self.world), **device_kw)
         batch, labels, noisy = self.ds.next_batch(local_bs * self.world)
-        return batch[self.rank * local_bs:(self.rank + 1) * local_bs], labels, noisy
+        window = slice(self.rank * local_bs, (self.rank + 1) * local_bs)
+        return batch[window], labels, None if noisy is None else noisy[window]
 
 
 def held_out_loss(weights, n_points, val_data, batch_size, device):
@@ -170,26 +198,43 @@ def main(argv=None):
             pc_data_train.shuffle_data(seed=55)
             pc_data_val.shuffle_data(seed=55)
         n_points = pc_data_train.n_points
+        if flags.device_data:                                                  # same order, same draws from here on
+            from .device_data import DevicePointCloudDataSet
+            pc_data_train = DevicePointCloudDataSet(pc_data_train.point_clouds, labels=pc_data_train.labels, device=device,
+                                                    init_shuffle=False)
     else:
         data = np.load(flags.train_data).astype(np.float32)
         assert data.ndim == 3 and data.shape[2] == 3, 'train_data must be (n, n_points, 3)'
         n_points = data.shape[1]
         n_batches = len(data) // flags.batch_size
+        if flags.device_data:
+            from .device_data import DevicePointCloudDataSet
+            resident = DevicePointCloudDataSet(data, device=device, init_shuffle=False)
     tr = PointNetAETrainer(initial_weights(n_points, seed=flags.seed), n_points, batch_size=local_bs,
                            learning_rate=flags.learning_rate, device=device)
     os.makedirs(flags.train_folder, exist_ok=True)
     fout = open(osp.join(flags.train_folder, 'train_stats.txt'), 'a', 1) if rank == 0 else None
     rng = np.random.default_rng(flags.seed)
+    augment = None
+    if flags.gauss_augment_sigma > 0 or flags.z_rotate:
+        from .device_data import Augmentation
+        augment = Augmentation(flags.gauss_augment_mu, flags.gauss_augment_sigma, z_rotate=bool(flags.z_rotate), seed=flags.seed)
+        if flags.z_rotate and pc_data_train is None:
+            np.random.seed(flags.seed)                                             # the rotations' stream (the ranks draw alike)
+    how = dict(augment=augment, denoising=bool(flags.denoising))
     stats = []
     for epoch in range(1, flags.training_epochs + 1):
         if pc_data_train is not None:
             if world > 1:
                 np.random.seed(flags.seed + epoch)                                 # the ranks must reshuffle alike
-            loss, duration = tr._single_epoch_train(_RankShard(pc_data_train, rank, world))
+            loss, duration = tr._single_epoch_train(_RankShard(pc_data_train, rank, world), **how)
         else:
             perm = rng.permutation(len(data))[:n_batches * flags.batch_size]       # same permutation on every rank
-            shard = data[perm].reshape(n_batches, world, local_bs, n_points, 3)[:, rank].reshape(-1, n_points, 3)
-            loss, duration = tr._single_epoch_train(shard)
+            if flags.device_data:
+                shard = resident.set_order(perm.reshape(n_batches, world, local_bs)[:, rank].reshape(-1))
+            else:
+                shard = data[perm].reshape(n_batches, world, local_bs, n_points, 3)[:, rank].reshape(-1, n_points, 3)
+            loss, duration = tr._single_epoch_train(shard, **how)
         stats.append((epoch, loss, duration))
         if rank == 0:
             print("Epoch:", '%04d' % epoch, 'training time (minutes)=', "{:.4f}".format(duration / 60.0), "loss=", "{:.9f}".format(loss))

@@ -8,6 +8,11 @@ epochs, the five statistics .npy files and log_train.txt.  Paths are relative to
 
 Host randomness (shuffle, jitter) is numpy's global generator seeded by --seed; dropout uses the device generator of
 csrc/cls_train.hip keyed by --seed and the step counter.  Rotation augmentation stays off, as in the reference.
+
+--jitter_on_device 1 keeps the training clouds on the GPU: the epoch order is the same np.random.shuffle(idx) draw, and every
+batch is one ops.batch_gather launch (gather by index, jitter sigma 0.01 clipped at 0.05) with the device generator of
+csrc/dataset.hip keyed by --seed and the global step (epoch * batches per epoch + batch).  The host's np.random.randn draws are
+then not made, so numpy's stream -- and the shuffle order of every epoch after the first -- differs from the default mode's.
 """
 import argparse
 import os
@@ -38,6 +43,7 @@ def build_parser():
     p.add_argument('--model_path', default=None, help='checkpoint prefix to continue training from')
     p.add_argument('--restore_epoch', type=int, default=0)
     p.add_argument('--seed', type=int, default=0, help='numpy seed (shuffle, jitter, initial weights) and dropout key')
+    p.add_argument('--jitter_on_device', type=int, default=0, help='1: resident training clouds, batches gathered and jittered on the GPU [default: 0]')
     p.add_argument('--top_dir', type=str, default='.', help='root that the path flags are relative to')
     return p
 
@@ -93,17 +99,30 @@ def main(argv=None):
 
     slots = int(flags.max_epoch / flags.save_model_interval)
     stats = {k: np.zeros(slots) for k in ('mean_loss', 'accuracy', 'eval_mean_loss', 'eval_accuracy', 'eval_avg_class_acc')}
+    if flags.jitter_on_device:
+        import torch
+        from . import ops
+        train_dev = torch.from_numpy(np.ascontiguousarray(train_data, dtype=np.float32)).to(tr.device)
     for epoch in range(flags.restore_epoch, flags.max_epoch):
         log_string('**** EPOCH %03d ****' % epoch)
         sys.stdout.flush()
         # train_one_epoch
-        data, label, _ = shuffle_data(train_data, train_label)
-        num_batches = data.shape[0] // B
+        if flags.jitter_on_device:
+            idx = np.arange(len(train_label))
+            np.random.shuffle(idx)                                     # shuffle_data's draw; the clouds stay where they are
+            label = train_label[idx]
+        else:
+            data, label, _ = shuffle_data(train_data, train_label)
+        num_batches = len(label) // B
         total_correct = total_seen = 0
         loss_sum = 0.0
         for bi in range(num_batches):
             s, e = bi * B, (bi + 1) * B
-            jittered = jitter_point_cloud(data[s:e]).astype(np.float32)
+            if flags.jitter_on_device:
+                jittered = ops.batch_gather(train_dev, idx[s:e], dict(seed=flags.seed % (1 << 64), counter=epoch * num_batches + bi,
+                                                                      noise_sigma=0.01, noise_clip=0.05))
+            else:
+                jittered = jitter_point_cloud(data[s:e]).astype(np.float32)
             loss_val, pred = tr.train_step(jittered, label[s:e])
             total_correct += int(np.sum(pred == label[s:e]))
             total_seen += B

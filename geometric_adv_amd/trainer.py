@@ -101,6 +101,7 @@ class PointNetAETrainer:
         self._params_ptr, self._grads_ptr = pp.value, gp.value
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.epoch = 0
+        self._batches_served = 0                                # the noise generator's counter (_single_epoch_train)
         self.sync_bn = bool(sync_bn)
         self._world_set = 1
 
@@ -255,29 +256,63 @@ class PointNetAETrainer:
             self.apply(1.0)
         return recon, (float(loss.item()) if sync else loss)
 
-    def _single_epoch_train(self, train_data, batch_size=None):
-        """pointnet_ae.py:101-139 without augmentation / denoising: train_data is an array (n, N, 3) or an object with
-        next_batch(batch_size) -> (batch, labels, noisy) and num_examples."""
+    def _augmented_step(self, source, clean_source, augment, denoising):
+        """One step on host or GPU clouds `source` (batch_size, n, 3) fed through ops.batch_gather under `augment`;
+        denoising: the loss is taken against clean_source (pointnet_ae.py:125-128)."""
+        from .device_data import gather_augmented
+        world = torch.distributed.get_world_size() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
+        rank = torch.distributed.get_rank() if world > 1 else 0
+        feed = gather_augmented(self._dev(source), None, augment, self._batches_served, rank * self.batch_size)
+        self._batches_served += 1
+        gt = self._dev(clean_source) if denoising else None
+        return self.partial_fit(feed, gt, want_recon=False, sync=False)[1].clone()
+
+    def _single_epoch_train(self, train_data, batch_size=None, augment=None, denoising=False):
+        """pointnet_ae.py:101-139: train_data is an array (n, N, 3), an object with next_batch(batch_size) -> (batch, labels,
+        noisy) and num_examples (in_out.PointCloudDataSet), or a device_data.DevicePointCloudDataSet, whose batches are
+        gathered and augmented on the device in one launch.  augment: a device_data.Augmentation (Configuration.gauss_augment /
+        z_rotate; None = none).  denoising (Configuration.denoising): the set's noisy copy, or the clean batch where it has
+        none, is augmented and fed, and the loss is taken against the clean batch: partial_fit(feed, clean).  The noise
+        generator's counter is this trainer's count of batches served.  With both left at their defaults a host set or array
+        goes the way it always did: no launch is added."""
         bs = self.batch_size
         start = time.time()
         losses = []
-        if hasattr(train_data, "next_batch"):
+        plain = (augment is None or not augment.active) and not denoising
+        if getattr(train_data, "device_resident", False):
+            world = torch.distributed.get_world_size() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
+            rank = torch.distributed.get_rank() if world > 1 else 0
             n_batches = int(train_data.num_examples / bs)
             for _ in range(n_batches):
-                batch_i, _, _ = train_data.next_batch(bs)
-                losses.append(self.partial_fit(batch_i, want_recon=False, sync=False)[1].clone())
+                clean, _, feed = train_data.next_batch(bs, augment=augment, counter=self._batches_served, slot_offset=rank * bs,
+                                                       from_noisy=denoising)
+                self._batches_served += 1
+                losses.append(self.partial_fit(feed, clean if denoising else None, want_recon=False, sync=False)[1].clone())
+        elif hasattr(train_data, "next_batch"):
+            n_batches = int(train_data.num_examples / bs)
+            for _ in range(n_batches):
+                batch_i, _, noisy = train_data.next_batch(bs)
+                if plain:
+                    losses.append(self.partial_fit(batch_i, want_recon=False, sync=False)[1].clone())
+                else:
+                    source = noisy if (denoising and noisy is not None) else batch_i
+                    losses.append(self._augmented_step(source, batch_i, augment, denoising))
         else:
             n_batches = len(train_data) // bs
             for i in range(n_batches):
-                losses.append(self.partial_fit(train_data[i * bs:(i + 1) * bs], want_recon=False, sync=False)[1].clone())
+                batch_i = train_data[i * bs:(i + 1) * bs]
+                if plain:
+                    losses.append(self.partial_fit(batch_i, want_recon=False, sync=False)[1].clone())
+                else:
+                    losses.append(self._augmented_step(batch_i, batch_i, augment, denoising))
         epoch_loss = float(torch.stack(losses).mean().item()) if losses else 0.0
         return epoch_loss, time.time() - start
 
-    def train(self, train_data, training_epochs, log_file=None, loss_display_step=1):
+    def train(self, train_data, training_epochs, log_file=None, loss_display_step=1, augment=None, denoising=False):
         """AutoEncoder.train (autoencoder.py:196-227): -> [(epoch, loss, duration)]."""
         stats = []
         for _ in range(training_epochs):
-            loss, duration = self._single_epoch_train(train_data)
+            loss, duration = self._single_epoch_train(train_data, augment=augment, denoising=denoising)
             self.epoch += 1
             stats.append((self.epoch, loss, duration))
             if self.epoch % loss_display_step == 0 and log_file is not None:

@@ -229,6 +229,29 @@ int geoadv_critical_split(int b, int n, int c, const float *pc, const float *max
 int geoadv_sort_axes(int b, int n, const float *pc, float *out, int *axes_idx /* [b][3], may be NULL */, int neg_rot,
                      void *stream);
 
+/* One training batch built on the device in one launch: clean[i] = the bits of data[index[i]] (data[num_clouds,n,3] resident,
+ * index device [b] or NULL = 0..b-1), feed[i] = that cloud with Gaussian noise and / or a rotation.  aug == NULL: feed holds the
+ * gathered bits.  Rotation: every point as a row vector times R (the reference's batch.dot(R), src/general_utils.py:142),
+ * float64 products and sums rounded once to fp32.  Noise of output slot s = slot_offset + i, point p, coordinate c (mix =
+ * splitmix64's finaliser, G = 0x9e3779b97f4a7c15, 64-bit wrap-around):
+ *   key = mix(mix(mix(seed + G) ^ counter) ^ (s << 32 | p));  r = mix(key + (c + 1) * G)
+ *   u1 = ((r >> 40) + 1) * 2^-24;  u2 = ((r >> 16) & 0xFFFFFF) * 2^-24;  g = sqrt(-2 ln u1) * cos(2 pi u2)   (fp32)
+ *   value = x + (mu + clamp(sigma * g, -clip, clip))   (three fp32 roundings)
+ * so it depends on (seed, counter, s, p, c) alone.  GEOADV_EINVAL: b, n or num_clouds < 1, rot_count not in {0, 1, b},
+ * rot == NULL with rot_count > 0, data or feed NULL, feed or clean overlapping data or each other, slot_offset < 0, sigma < 0.
+ * An index outside [0, num_clouds) is never dereferenced: that slot of clean and feed is left unwritten. */
+typedef struct geoadv_batch_augment {
+    unsigned long long seed, counter;  /* generator key; counter = the caller's global step ordinal */
+    int   slot_offset;                 /* slot of output cloud 0 (data-parallel ranks: rank * local batch) */
+    float noise_mu, noise_sigma;       /* sigma == 0: no noise is generated and mu is ignored */
+    float noise_clip;                  /* > 0: sigma * g is clamped to [-clip, clip]; <= 0: no clamp */
+    int   rot_count;                   /* 0: none; 1: one matrix for the batch; b: one per cloud */
+    int   rotate_first;                /* 0: noise then rotation (AE order); 1: rotation then noise (classifier order) */
+} geoadv_batch_augment;
+int geoadv_batch_gather(int b, int n, const float *data, long long num_clouds, const int *index /* device [b] or NULL = 0..b-1 */,
+                        const geoadv_batch_augment *aug /* NULL = plain gather */, const double *rot /* device [rot_count][9], row-major */,
+                        float *clean /* device [b,n,3] or NULL */, float *feed /* device [b,n,3] */, void *stream);
+
 /* get_dist_mat (src/general_utils.py:94-106) on the device: out[na,nb], out[i][j] = || a[i] - b[j] ||_2 of the fp32 row-major
  * a[na,d] and b[nb,d] -- the latent distance matrix of attacker/prepare_indices_for_attack.py:89-101.  Bit for bit numpy's
  * np.linalg.norm(s - t, axis=-1): fp32 differences, squares rounded on their own, numpy's pairwise summation order of a
