@@ -28,6 +28,7 @@ __device__ __forceinline__ void wave_selection_sort(float *val, int *idx, int n,
         // => lexicographic min of (value, position)
         float bv = INFINITY;
         int bp = 0x7fffffff;
+        const float head = val[s];                // (wave-uniform; the load travels with the scan's own, it is only needed after them)
         {   // four independent streams per lane (a single chain pays the LDS latency once per entry: 32 times per pass at n = 2048),
             // merged lexicographically -- the minimum of (value, position) does not depend on the order it is taken in
             float sv[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
@@ -52,8 +53,11 @@ __device__ __forceinline__ void wave_selection_sort(float *val, int *idx, int n,
         // a lane whose values are all NaN / that saw nothing keeps (inf, maxint)
         wave_lexmin(bv, bp);                      // (DPP + readlane: six ds_bpermute round trips per pass were half of a pass)
         // (bv, bp) = the first position of [s, n) attaining the minimum, exactly what the reference's
-        // scan "min = s; if (p[t] < p[min]) min = t" finds; nothing comparable (all NaN) keeps s.
-        const int mn = bp == 0x7fffffff ? s : bp;
+        // scan "min = s; if (p[t] < p[min]) min = t" finds -- as long as p[s] itself compares.  Nothing comparable (only NaN
+        // and +inf) keeps s; and so does a NaN IN SLOT s, whatever follows it: no p[t] is ever '<' a NaN, the reference's min
+        // never leaves s, and the NaN stays in column s of the result (the lexicographic minimum alone would skip it and pull
+        // the smallest later value forward).  Decided for the whole wave from the one value.
+        const int mn = (bp == 0x7fffffff || head != head) ? s : bp;
         if (mn != s) {
             if (lane == 0) {
                 const float tv = val[mn]; val[mn] = val[s]; val[s] = tv;

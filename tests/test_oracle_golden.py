@@ -100,6 +100,23 @@ def test_selection_sort_known_answer_and_ties(oracle, golden_grouping):
     assert list(g["swap_idx"][0, 1, :4]) == [5, 1, 3, 4]
 
 
+def test_selection_sort_nonfinite_rows_match_reference(oracle):
+    """NaN / +-inf rows (oracle/make_golden_nonfinite.py; test/selection_sort.cpp:40-58: every pass starts with min = s and
+    moves on `p[t] < p[min]`): a NaN in slot s is never beaten and stays in column s, a NaN elsewhere is never chosen.
+    Indices exact, values equal with NaN == NaN (the payload of a NaN is not pinned)."""
+    import os
+    from conftest import GOLDEN
+    g = np.load(os.path.join(GOLDEN, "grouping_nonfinite.npz"))
+    k = int(g["k"])
+    idx, val = oracle.selection_sort(k, g["dist"])
+    assert np.array_equal(idx, g["idx"])
+    assert np.array_equal(val, g["val"], equal_nan=True)
+    # not vacuous: every row keeps a NaN inside the first k columns, where the lexicographic minimum alone would not
+    assert np.isnan(g["val"][0, :, :k]).any(axis=1).all()
+    assert g["idx"][0, 0, 2] == 2 and np.isnan(g["val"][0, 0, 2])
+    assert np.array_equal(g["idx"][0, 3], np.arange(40))                  # all NaN: nothing moves
+
+
 def test_query_ball_and_group_point(oracle, golden_grouping):
     g = golden_grouping
     idx, cnt = oracle.query_ball_point(float(g["qb_radius"]), int(g["qb_nsample"]), g["qb_xyz1"], g["qb_xyz2"])
