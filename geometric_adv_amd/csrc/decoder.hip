@@ -16,6 +16,7 @@ namespace geoadv {
 int encoder_tiles(const DeviceAE &A, int b);
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int acc_row16(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // ------------------------------------------------------------------------------------------
@@ -42,6 +43,12 @@ __device__ __forceinline__ void latent_decode_block(const DeviceAE &A, int tiles
     const int t = threadIdx.x;
     GA_STAMP(0, 0);
     if (t == 0) tie = 0;
+    // the biases are constants: requested HERE, with the first batch of pool partials, not after the barrier that ends their FC
+    // (a lazy load there is one more global round trip on the chain, 0.4-0.6 us each).  Every thread asks (t & 255: the copies
+    // meet the same 1 KB), also where d1 is null and the block returns before it uses them: no branch in front of the loads.
+    constexpr int NC1 = 256 / PARTS;
+    const float bias0 = A.c0[t & 255];
+    const float bias1 = A.c1[part_id * NC1 + (PARTS == 1 ? (t & 255) : t % NC1)];
     // 8 contiguous tile groups x 128 channels; ascending tiles inside a group, groups merged in order.  Every merge is
     // BRANCH-FREE: with `if (pm > m) { a = pa; k = pk; }` the compiler makes the arg / count loads lazy -- one dependent
     // global round trip per tile and array, 8-16 in a row (4.4 us of this kernel's 9.8 at B = 4, in-kernel stamps) -- where
@@ -61,6 +68,10 @@ __device__ __forceinline__ void latent_decode_block(const DeviceAE &A, int tiles
                 const size_t o = ((size_t)b * tiles + tl) * 128 + c;
                 pm[u] = pmax[o]; pa[u] = parg[o]; pk[u] = pcnt[o];
             }
+            // (Selects alone did not do it: the compiler still moved the first compare up between the requests -- a wait for two
+            // loads with sixteen not yet issued -- and left one count behind a branch.  Every value passes through here first.)
+#pragma unroll
+            for (int u = 0; u < U; ++u) asm volatile("" : "+v"(pm[u]), "+v"(pa[u]), "+v"(pk[u]));
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const bool live = t0 + u < te;
@@ -103,7 +114,7 @@ __device__ __forceinline__ void latent_decode_block(const DeviceAE &A, int tiles
     {   // FC0 + ReLU: 128 -> 256
         const float s = fc256_split4<128, THREADS>(zs, A.v0, part);
         if (t < 256) {
-            const float v = fmaxf(s + A.c0[t], 0.f);
+            const float v = fmaxf(s + bias0, 0.f);
             hs[t] = v;
             if (part_id == 0) d1[(size_t)b * 256 + t] = v;
         }
@@ -112,12 +123,12 @@ __device__ __forceinline__ void latent_decode_block(const DeviceAE &A, int tiles
     GA_STAMP(0, 3);
     if (PARTS == 1) {   // FC1 + ReLU: 256 -> 256
         const float s = fc256_split4<256, THREADS>(hs, A.v1, part);
-        if (t < 256) d2[(size_t)b * 256 + t] = fmaxf(s + A.c1[t], 0.f);
+        if (t < 256) d2[(size_t)b * 256 + t] = fmaxf(s + bias1, 0.f);
     } else {            // ... this workgroup's 256 / PARTS columns of it
-        constexpr int NC = 256 / PARTS;
+        constexpr int NC = NC1;
         const int col0 = part_id * NC;
         const float s = fc256_split4_cols<256, NC>(hs, A.v1, part, col0);
-        if (t < NC) d2[(size_t)b * 256 + col0 + t] = fmaxf(s + A.c1[col0 + t], 0.f);
+        if (t < NC) d2[(size_t)b * 256 + col0 + t] = fmaxf(s + bias1, 0.f);
     }
     GA_STAMP(0, 7);
 }
@@ -129,16 +140,17 @@ __global__ __launch_bounds__(LD_THREADS) void latent_fc_kernel(DeviceAE A, const
     __shared__ float hs[256];
     __shared__ float part[4][256];
     const int t = threadIdx.x, b = blockIdx.x;
+    const float bias0 = A.c0[t & 255], bias1 = A.c1[t & 255];     // constants: requested with z (latent_decode_block)
     if (t < 128) zs[t] = z[(size_t)b * 128 + t];
     __syncthreads();
     {
         const float s = fc256_split4<128, LD_THREADS>(zs, A.v0, part);
-        if (t < 256) hs[t] = fmaxf(s + A.c0[t], 0.f);
+        if (t < 256) hs[t] = fmaxf(s + bias0, 0.f);
     }
     __syncthreads();
     {
         const float s = fc256_split4<256, LD_THREADS>(hs, A.v1, part);
-        if (t < 256) d2[(size_t)b * 256 + t] = fmaxf(s + A.c1[t], 0.f);
+        if (t < 256) d2[(size_t)b * 256 + t] = fmaxf(s + bias1, 0.f);
     }
 }
 
@@ -175,8 +187,10 @@ __global__ __launch_bounds__(THREADS) void latent_decode_and_grid_kernel(DeviceA
 // FC2 forward: out[b][3N] = d2[b][256] @ V2 + c2.  grid = (column blocks of 32, row blocks of 32),
 // 256 threads = 4 waves splitting K = 256 four ways; partials are summed in a fixed order.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void decoder_fc2_block(const DeviceAE &A, int batch, const float *d2, float *out, const int cb, const int rb) {
-    __shared__ float part[3][16][64];
+// fill / fill_count: decoder_fc2_kernel
+__device__ __forceinline__ void decoder_fc2_block(const DeviceAE &A, int batch, const float *d2, float *out, const int cb, const int rb,
+                                                  unsigned long long *fill = nullptr, size_t fill_count = 0) {
+    __shared__ float part[4][16][64];
     GA_STAMP(2, 0);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int h = lane >> 5, i = lane & 31;
@@ -196,6 +210,11 @@ __device__ __forceinline__ void decoder_fc2_block(const DeviceAE &A, int batch, 
         av[u] = *reinterpret_cast<const float4 *>(ap + 8 * t);
         wv[u] = bp[(size_t)t * 64];
     }
+    // the bias is a constant: requested behind the operands (the load counter runs in order: the MFMAs do not wait for it), not
+    // after the barrier
+    const int ncols = A.dec_dims[GEOADV_DEC_LAYERS];
+    const int col = cb * 32 + i;
+    const float bias_ld = A.c2[col < ncols ? col : ncols - 1];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         if (u < per) {
@@ -205,20 +224,31 @@ __device__ __forceinline__ void decoder_fc2_block(const DeviceAE &A, int batch, 
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].w, wv[u].w, acc, 0, 0, 0);
         }
     }
-    if (wave > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) part[wave - 1][r][lane] = acc[r];
+    // the rider stores go out BEHIND the operand loads and the MFMAs that wait for them (issued first, as they were, every wait
+    // for an operand was also a wait for these stores to be acknowledged)
+    if (fill) {
+        const size_t stride = (size_t)gridDim.x * gridDim.y * 256;
+        for (size_t e = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; e < fill_count; e += stride) fill[e] = ~0ull;
     }
-    __syncthreads();
-    if (wave == 0) {
-        const int ncols = A.dec_dims[GEOADV_DEC_LAYERS];
-        const int col = cb * 32 + i;
-        const float bias = col < ncols ? A.c2[col] : 0.f;
+    // Every wave leaves its accumulators in LDS and finishes four of the sixteen registers: (((w0 + w1) + w2) + w3) + bias, the
+    // sum wave 0 alone used to form for all sixteen (same order, same bits) -- four stores per wave on four SIMDs instead of
+    // sixteen store blocks in a row on one, every LDS read requested before the first add.
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float v = ((acc[r] + part[0][r][lane]) + part[1][r][lane]) + part[2][r][lane] + bias;
-            const int row = rb * 32 + acc_row16(r, h);
-            if (row < batch && col < ncols) out[(size_t)row * ncols + col] = v;
+    for (int r = 0; r < 16; ++r) part[wave][r][lane] = acc[r];
+    __syncthreads();
+    {
+        float p[4][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) p[j][q] = part[q][4 * wave + j][lane];
+        const float bias = col < ncols ? bias_ld : 0.f;
+        const int row0 = rb * 32 + 8 * wave + 4 * h;            // acc_row16(4 * wave + j, h) = 8 * wave + 4 * h + j
+        float *op = out + (size_t)row0 * ncols + col;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v = ((p[j][0] + p[j][1]) + p[j][2]) + p[j][3] + bias;
+            if (row0 + j < batch && col < ncols) op[(size_t)j * ncols] = v;
         }
     }
     GA_STAMP(2, 7);
@@ -228,11 +258,7 @@ __device__ __forceinline__ void decoder_fc2_block(const DeviceAE &A, int batch, 
 // scan of the SAME forward folds into with 64-bit atomic minima: chamfer_sym.hip) -- no launch of their own
 __global__ __launch_bounds__(256) void decoder_fc2_kernel(DeviceAE A, int batch, const float *d2, float *out, unsigned long long *fill,
                                                          size_t fill_count) {
-    if (fill) {
-        const size_t stride = (size_t)gridDim.x * gridDim.y * 256;
-        for (size_t e = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; e < fill_count; e += stride) fill[e] = ~0ull;
-    }
-    decoder_fc2_block(A, batch, d2, out, blockIdx.x, blockIdx.y);
+    decoder_fc2_block(A, batch, d2, out, blockIdx.x, blockIdx.y, fill, fill_count);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -255,14 +281,39 @@ __global__ __launch_bounds__(512) void decoder_fc2_bwd_kernel(DeviceAE A, int ba
     const int t0 = k0 >> 3;
     const int nt = min(DB_KC >> 3, kg_total - t0);
     const float4 *bp = reinterpret_cast<const float4 *>(L.w) + ((size_t)cb * kg_total + t0) * 64 + lane;
-    constexpr int NT = DB_KC >> 3;              // 8 k-groups: all B fragments requested up front, BEFORE the A tile is
-    float4 wv[NT];                              // staged (they do not depend on it: one global round trip instead of two)
+    constexpr int NT = DB_KC >> 3;              // 8 k-groups
+    float4 wv[NT];
+    // The 32 x 64 A tile: thread e takes the four consecutive k of row e / 16 -- ONE request per thread (a dwordx4 where every row
+    // base is 16-byte aligned, else four dwords issued together), made BEFORE the eight weight fragments: the counter of
+    // outstanding loads runs in order, so the tile is waited for with the weights still in flight, and the weights are met again
+    // only at the MFMAs.  Addresses are clamped and the zero fill is a select, so no load hides behind a branch.  (The loop this
+    // replaces compiled to four serial load -> wait -> LDS-write round trips, the first of which also drained the weights.)
+    float4 a4;
+    {
+        const int r = threadIdx.x >> 4, k = (threadIdx.x & 15) * 4;
+        const int row = rb * 32 + r, kk = k0 + k;
+        const float *gp = g_out + (size_t)(row < batch ? row : batch - 1) * ncols;
+        if ((ncols & 3) == 0 && (reinterpret_cast<size_t>(g_out) & 15) == 0) {      // (uniform)
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(gp + (kk < ncols ? kk : ncols - 4));
+            a4 = make_float4(v.x, v.y, v.z, v.w);
+        } else {
+            a4.x = gp[kk     < ncols ? kk     : ncols - 1];
+            a4.y = gp[kk + 1 < ncols ? kk + 1 : ncols - 1];
+            a4.z = gp[kk + 2 < ncols ? kk + 2 : ncols - 1];
+            a4.w = gp[kk + 3 < ncols ? kk + 3 : ncols - 1];
+        }
+    }
 #pragma unroll
     for (int t = 0; t < NT; ++t) wv[t] = bp[(size_t)(t < nt ? t : nt - 1) * 64];
-    for (int e = threadIdx.x; e < 32 * DB_KC; e += 512) {
-        const int r = e / DB_KC, k = e % DB_KC;
+    {
+        const int r = threadIdx.x >> 4, k = (threadIdx.x & 15) * 4;
         const int row = rb * 32 + r, kk = k0 + k;
-        as[r * (DB_KC + 4) + k] = (row < batch && kk < ncols) ? g_out[(size_t)row * ncols + kk] : 0.f;
+        const bool live = row < batch;
+        a4.x = live && kk     < ncols ? a4.x : 0.f;
+        a4.y = live && kk + 1 < ncols ? a4.y : 0.f;
+        a4.z = live && kk + 2 < ncols ? a4.z : 0.f;
+        a4.w = live && kk + 3 < ncols ? a4.w : 0.f;
+        *reinterpret_cast<float4 *>(as + r * (DB_KC + 4) + k) = a4;
     }
     __syncthreads();
     const float *ap = as + i * (DB_KC + 4) + 4 * h;

@@ -68,42 +68,61 @@ __device__ __forceinline__ void decoder_bwd_tail_body(const DeviceAE &A, int bat
     __shared__ float g2[256];
     __shared__ float g1[256];
     __shared__ float part[8][256];
+    __shared__ float partz[8][128];
     __shared__ __attribute__((aligned(16))) float dzs[128], jxs[128], jys[128], jzs[128];
     __shared__ __attribute__((aligned(16))) int crs[128];
     const int t = threadIdx.x, o = t & 255, ks = t >> 8;
     GA_STAMP(4, 0);
-    // the Jacobian rows and critical points of this cloud do not depend on anything computed here: requested first
     float jx = 0.f, jy = 0.f, jz = 0.f;
     int my_crit = -1, is_dense = 0;
-    if (ja.jac && t < 128) {
-        const float *jp = ja.jac + ((size_t)b * 128 + t) * 3;
-        jx = jp[0]; jy = jp[1]; jz = jp[2];
-        my_crit = ja.crit[(size_t)b * 128 + t];
-        is_dense = ja.dense[b];
-    }
-    {   // split-K partials: 4 contiguous chunk groups, ascending inside, merged in order
+    // Nothing the chain's head reads is computed here, so all of it is requested before the first wait: the two ReLU masks (the
+    // forward wrote d2 / d1 launches ago; loaded after the barriers that end their layers, each was one more global round trip)
+    // and the split-K partials.  (Every thread asks for the masks, though only t < 256 use them: the four copies of a request
+    // meet the same 1 KB, and a guard would put the loads behind a branch again.)
+    const float d2v = d2[(size_t)b * 256 + o], d1v = d1[(size_t)b * 256 + o];
+    {   // split-K partials: 4 contiguous chunk groups, ascending inside, merged in order.  All of a thread's loads are in flight
+        // together (24 at N = 2048; batches of 24 beyond that); the last chunk repeats where a batch is not full and a select
+        // keeps it out, so no load hides behind a branch.  The sum is the same ascending chain from 0.f.
         const int cb = chunks * ks / 4, ce = chunks * (ks + 1) / 4;
         float s = 0.f;
-#pragma unroll 8
-        for (int ch = cb; ch < ce; ++ch) s += partial[((size_t)ch * batch + b) * 256 + o];
+        constexpr int U = 24;
+        for (int c0 = cb; c0 < ce; c0 += U) {
+            float v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) v[u] = partial[((size_t)(c0 + u < ce ? c0 + u : ce - 1) * batch + b) * 256 + o];
+#pragma unroll
+            for (int u = 0; u < U; ++u) s = c0 + u < ce ? s + v[u] : s;
+        }
         part[ks][o] = s;
     }
     __syncthreads();
     if (t < 256) {
         const float s = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-        g2[t] = d2[(size_t)b * 256 + t] > 0.f ? s : 0.f;
+        g2[t] = d2v > 0.f ? s : 0.f;
     }
     __syncthreads();
     GA_STAMP(4, 1);
     {
         const float s = fc256_split4<256>(g2, A.v1t, part);
         __syncthreads();
-        if (t < 256) g1[t] = d1[(size_t)b * 256 + t] > 0.f ? s : 0.f;
+        if (t < 256) g1[t] = d1v > 0.f ? s : 0.f;
     }
     __syncthreads();
     GA_STAMP(4, 2);
     {   // dz: 128 outputs x 8 K-slices of 32
         const int c = t & 127, k8 = t >> 7;
+        // The cloud's Jacobian rows, critical points and tie flag are needed after this product and depend on nothing computed
+        // here: requested in front of V0^T's 32 loads.  (Requested first of all, as they were, the flag was compared on arrival
+        // -- a round trip that held back every later load; requested behind the partials, the wait for d2 took them in; in
+        // front of V1^T's 64 loads they were copied, and waited for, between the requests.  Here one wait is left as well: the
+        // compiler reuses jz's register for the flag and copies jz out first, so waves 0-1 wait for their row before they
+        // request V0^T -- DESIGN section 4 records the emitted skeleton.)
+        if (ja.jac && t < 128) {
+            const float *jp = ja.jac + ((size_t)b * 128 + t) * 3;
+            jx = jp[0]; jy = jp[1]; jz = jp[2];
+            my_crit = ja.crit[(size_t)b * 128 + t];
+        }
+        if (ja.dense) is_dense = ja.dense[b];                      // (every lane: the flag is uniform)
         float w[32];
 #pragma unroll
         for (int k = 0; k < 32; ++k) w[k] = A.v0t[(size_t)(k8 * 32 + k) * 128 + c];
@@ -121,7 +140,11 @@ __device__ __forceinline__ void decoder_bwd_tail_body(const DeviceAE &A, int bat
         }
         // (The fences are not decoration: the dense blocks may run on another XCD, whose L2 is not coherent with this one inside a
         // launch -- tools/handoff_probe.py: plain loads across XCDs returned stale data in 32 736 of 32 768 reads.)
-        if (ready && is_dense_all(ja, b)) {   // rare: a tied cloud -- publish dz for the dense blocks of this launch (agent scope)
+        // the flag is looked at HERE: without this its compare, and the wait for its load, move up to where it was requested
+        asm volatile("" : "+v"(is_dense));
+        is_dense = __builtin_amdgcn_readfirstlane(is_dense);
+        const bool tied = is_dense != 0;
+        if (ready && tied) {   // rare: a tied cloud -- publish dz for the dense blocks of this launch (agent scope)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its stores ...
             __syncthreads();                                       // ... before ONE lane releases and raises the flag
             if (t == 0) {
@@ -157,21 +180,14 @@ __device__ __forceinline__ void decoder_bwd_tail_body(const DeviceAE &A, int bat
                         gx = fmaf(d, xi[u], gx); gy = fmaf(d, yi[u], gy); gz = fmaf(d, zi[u], gz);
                     }
                 }
-                __syncthreads();                                   // (part[][] is free: the dz partials were consumed above)
-                part[pq][ch] = gx; part[pq][128 + ch] = gy;
-                __syncthreads();
-                float sx = 0.f, sy = 0.f;
-                if (t < 128) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) { sx += part[q][t]; sy += part[q][128 + t]; }
-                }
-                __syncthreads();
-                part[pq][ch] = gz;
+                // part[][] is free (its dz partials were read before the barrier above): the three partial planes go out in ONE
+                // pass, gz into a plane of its own -- two barriers for the apply where there were five
+                part[pq][ch] = gx; part[pq][128 + ch] = gy; partz[pq][ch] = gz;
                 __syncthreads();
                 if (t < 128 && !is_dense) {
-                    float sz = 0.f;
+                    float sx = 0.f, sy = 0.f, sz = 0.f;
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) sz += part[q][t];
+                    for (int q = 0; q < 8; ++q) { sx += part[q][t]; sy += part[q][128 + t]; sz += partz[q][t]; }
                     float *g = ja.g_enc + ((size_t)b * ja.n + my_crit) * 3;
                     g[0] = sx; g[1] = sy; g[2] = sz;
                 }
