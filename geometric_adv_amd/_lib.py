@@ -46,6 +46,19 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def device_view(ptr, count, typestr, device):
+    """1-D torch tensor over `count` elements of device memory at `ptr` (typestr '<f4', '<i4', '<f8'): a view, not a copy --
+    it aliases the owner's memory and dangles once the owner frees it."""
+    import torch
+
+    class _Arr:
+        pass
+    a = _Arr()
+    a.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+    with torch.cuda.device(device):
+        return torch.as_tensor(a, device=device)
+
+
 def stream_handle():
     """hipStream_t of torch's current stream, as void*."""
     import torch

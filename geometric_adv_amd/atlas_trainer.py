@@ -119,14 +119,6 @@ class AtlasNetTrainer:
             pass
 
     # ---- device views --------------------------------------------------------------------------------------
-    def _raw(self, ptr, count, typestr="<f4"):
-        class _Arr:
-            pass
-        a = _Arr()
-        a.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-        with torch.cuda.device(self.device):
-            return torch.as_tensor(a, device=self.device)
-
     def state(self, what, layer=0, primitive=None):
         """Host copy of what the last step kept (geoadv_atlas_trainer_state).  Layers: 0 .. 4 the encoder's conv1, conv2,
         conv3, lin1, lin2; 5 the decoder's conv1, 6 conv2, 7 ... conv_list.  'bn_mean' / 'bn_var' / 'running_mean' /
@@ -137,7 +129,7 @@ class AtlasNetTrainer:
         p, cnt = C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().geoadv_atlas_trainer_state(self._h, _STATE[what], int(layer), C.byref(p), C.byref(cnt)), "atlas_trainer_state")
         torch.cuda.synchronize(self.device)
-        a = self._raw(p.value, cnt.value, "<i4" if what in _INT_STATES else "<f4").cpu().numpy().copy()
+        a = _lib.device_view(p.value, cnt.value, "<i4" if what in _INT_STATES else "<f4", self.device).cpu().numpy().copy()
         B, nb, pp = self.batch_size, self.nb_primitives, self.points_per_primitive
         if what in _PER_LAYER:
             C_l = self.layers[int(layer)][2]
@@ -189,12 +181,12 @@ class AtlasNetTrainer:
     def parameters(self):
         """{parameter key: array} of the trainable tensors (host copies, torch's shapes)."""
         torch.cuda.synchronize(self.device)
-        return self._unflatten(self._raw(self._params_ptr, self._count).cpu().numpy())
+        return self._unflatten(_lib.device_view(self._params_ptr, self._count, "<f4", self.device).cpu().numpy())
 
     def gradients(self):
         """{parameter key: d loss / d parameter} of the last step."""
         torch.cuda.synchronize(self.device)
-        return self._unflatten(self._raw(self._grads_ptr, self._count).cpu().numpy())
+        return self._unflatten(_lib.device_view(self._grads_ptr, self._count, "<f4", self.device).cpu().numpy())
 
     def slots(self):
         """Adam's {'exp_avg': {key: array}, 'exp_avg_sq': {key: array}}."""

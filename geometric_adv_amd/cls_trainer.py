@@ -107,14 +107,6 @@ class PointNetClassifierTrainer:
         return cls(weights=weights, step=int(got.pop(CW.STEP_NAME)), slots=got, **kwargs)
 
     # ---- device views --------------------------------------------------------------------------------------
-    def _raw(self, ptr, count, typestr="<f4"):
-        class _Arr:
-            pass
-        a = _Arr()
-        a.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-        with torch.cuda.device(self.device):
-            return torch.as_tensor(a, device=self.device)
-
     def state(self, what, layer=0, device=False):
         """Host copy of what the last step kept (geoadv_cls_trainer_state): 'bn_mean' / 'bn_var' / 'moving_mean' /
         'moving_var' / 'bn_inv' / 'bn_shift' of a BN layer (GEOADV_CLS_* index), 'pre_bn' of a BN layer ([rows][C]: B * N
@@ -125,7 +117,7 @@ class PointNetClassifierTrainer:
         _lib.check(_lib.lib().geoadv_cls_trainer_state(self._h, _STATE[what], int(layer), C.byref(p), C.byref(cnt)),
                    "cls_trainer_state")
         torch.cuda.synchronize(self.device)
-        a = self._raw(p.value, cnt.value, "<i4" if what == "pool_argmax" else "<f4")
+        a = _lib.device_view(p.value, cnt.value, "<i4" if what == "pool_argmax" else "<f4", self.device)
         B = self.batch_size
         shapes = {"dropout_mask": (B, -1), "pool_argmax": (B, 1024), "t1": (B, 3, 3), "t2": (B, 64, 64), "logits": (B, -1)}
         if what == "pre_bn":
@@ -190,12 +182,12 @@ class PointNetClassifierTrainer:
     def parameters(self):
         """Host copy of the flat parameter buffer."""
         torch.cuda.synchronize(self.device)
-        return self._raw(self._params_ptr, self._count).cpu().numpy().copy()
+        return _lib.device_view(self._params_ptr, self._count, "<f4", self.device).cpu().numpy().copy()
 
     def gradients(self):
         """{trainable name: d loss / d variable} of the last step (host copies)."""
         torch.cuda.synchronize(self.device)
-        return self._unflatten(self._raw(self._grads_ptr, self._count).cpu().numpy())
+        return self._unflatten(_lib.device_view(self._grads_ptr, self._count, "<f4", self.device).cpu().numpy())
 
     # ---- the steps -----------------------------------------------------------------------------------------
     def _dev(self, x, dtype):

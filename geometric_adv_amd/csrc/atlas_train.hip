@@ -18,23 +18,22 @@
 // z ^= z >> 31), G = 0x9e3779b97f4a7c15, all in 64-bit wrap-around arithmetic.  r >> 40 has 24 bits, so the product is exact
 // in fp32 and lies in [0, 1): host and device agree to the bit.
 //
-// FORM: the direct one, as fold_train.hip.  STORED for the backward: the pre-BN activation and the post-ReLU output of every
-// BN layer but the decoder's first; the global maximum's rows.  RECOMPUTED: every ReLU mask (a * inv + shift > 0, the
-// forward's expression bit for bit) and xhat.  The decoder's first layer is never materialised before its BN: pre1 =
+// FORM: the direct one, as fold_train.hip, on the batch-norm, global-max, loss, Adam and running-statistics kernels of
+// train_bn.h (what is stored, what is recomputed and why lin1 / lin2's backward is in double: there).  STORED besides: the
+// post-ReLU output of every BN layer.  The decoder's first layer is never materialised before its BN: pre1 =
 // t1[q][j] + z[b] with t1 = conv1(template) [nb][p][1024]; over the product grid (b, j) its mean is mean_j t1 + mean_b z and
-// its variance var_j t1 + var_b z (the cross term vanishes), the backward rebuilds it from t1 and z, and its gradient
-// reduces to dz[b] = sum_q sum_j and dt1[q][j] = sum_b, each in ascending order.
+// its variance var_j t1 + var_b z (the cross term vanishes), the backward rebuilds it from t1 and z (train_bn.h: RB), and
+// its gradient reduces to dz[b] = sum_q sum_j and dt1[q][j] = sum_b, each in ascending order.
 //
 // GEMMs on v_mfma_f32_32x32x2_f32.  The decoder's products (batched over the primitives) run on at_gemm_kernel: a 128 x 128
 // tile per workgroup (each wave 64 x 64 = four accumulator blocks), operands double-buffered in LDS (the next K slice is
 // loaded into registers while the current one is multiplied), the per-primitive bias in the epilogue.  Products whose grid
 // of 128-tiles would leave most of the device idle, and all of the encoder's, go through ct_launch_gemm and its fixed-order
-// split-K (train_tile.h).  Batch statistics are per-chunk double partials added in a fixed order; no float atomics
-// anywhere: two steps from the same state are bitwise identical.
+// split-K (train_tile.h).  No float atomics anywhere: two steps from the same state are bitwise identical.
 //
 // Adam (torch.optim.Adam, lr, betas .9 / .999, eps 1e-8, no weight decay): m += (g - m) * 0.1; v = 0.999 v + 0.001 g g;
 // p -= lr / (1 - 0.9^t) * m / (sqrt(v) / sqrt(1 - 0.999^t) + eps), t = steps this optimizer has taken including this one.
-#include "train_tile.h"
+#include "train_bn.h"
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -44,15 +43,6 @@ namespace geoadv {
 constexpr float AT_EPS = 1e-5f;
 constexpr int AT_LAT = 1024, AT_HID = 512;
 constexpr long long AT_MAX_ROWS = 1ll << 17, AT_MAX_DEC_ROWS = 1ll << 18;
-
-__device__ __forceinline__ float at_pre(float a, float inv, float shift) { return a * inv + shift; }
-
-// The activation of group g, row r, column c.  RB: the decoder's first layer, rebuilt as t1[g][r % p][c] + z[r / p][c].
-template <bool RB>
-__device__ __forceinline__ float at_val(const float *a, const float *z, int g, int r, int c, int Rg, int C, int p) {
-    if (RB) return a[((size_t)g * p + r % p) * C + c] + z[(size_t)(r / p) * C + c];
-    return a[((size_t)g * Rg + r) * C + c];
-}
 
 // ---- the decoder's GEMM ------------------------------------------------------------------------------------
 constexpr int AG_T = 128, AG_KT = 16, AG_LDS = AG_T + 4;
@@ -147,45 +137,6 @@ inline hipError_t at_launch_splitk(const BGemm &b, int batch, float *partials, h
     return ct_launch_gemm(g, partials, st);
 }
 
-// ---- column statistics over groups ---------------------------------------------------------------------------
-// a [G][Rg][C]; part[(g * chunks + k) * C + c]: MODE 0 = (sum a, sum a^2), MODE 1 = (sum a, 0).  grid (ceil(C / 64), chunks, G).
-template <int MODE>
-__global__ __launch_bounds__(256) void at_colsum_kernel(const float *a, int Rg, int C, int rpc, double2 *part) {
-    __shared__ double2 red[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6, g = blockIdx.z;
-    const int r0 = blockIdx.y * rpc, r1 = min(Rg, r0 + rpc);
-    double s = 0.0, q = 0.0;
-    if (c < C)
-        for (int r = r0 + ph; r < r1; r += 4) {
-            const double v = (double)a[((size_t)g * Rg + r) * C + c];
-            s += v;
-            if (MODE == 0) q += v * v;
-        }
-    red[ph][threadIdx.x & 63] = make_double2(s, q);
-    __syncthreads();
-    if (ph == 0 && c < C) {
-        double2 o = red[0][threadIdx.x];
-        for (int p = 1; p < 4; ++p) { o.x += red[p][threadIdx.x].x; o.y += red[p][threadIdx.x].y; }
-        part[((size_t)g * gridDim.y + blockIdx.y) * C + c] = o;
-    }
-}
-
-// Batch statistics from the partials: mean, biased variance, folded constants.  One thread per (group, column).
-__global__ __launch_bounds__(256) void at_bn_stats_kernel(const double2 *part, int chunks, int C, int G, double inv_rows, const float *gamma,
-                                                          const float *beta, float *mean, float *var, float *inv, float *shift) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= G * C) return;
-    const int g = e / C, c = e - g * C;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < chunks; ++k) { const double2 v = part[((size_t)g * chunks + k) * C + c]; s += v.x; q += v.y; }
-    const double m = s * inv_rows;
-    double v = q * inv_rows - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mf = (float)m, vf = (float)v;
-    const float iv = gamma[e] * (1.0f / sqrtf(vf + AT_EPS));
-    mean[e] = mf; var[e] = vf; inv[e] = iv; shift[e] = beta[e] - mf * iv;
-}
-
 // The decoder's bn1: pre1 = t1[q][j] + z[b] over the grid (b, j): mean = mean_j t1 + mean_b z, var = var_j t1 + var_b z.
 __global__ __launch_bounds__(256) void at_bn1_stats_kernel(const float *t1, const float *z, int p, int B, int C, int G, const float *gamma,
                                                            const float *beta, float *mean, float *var, float *inv, float *shift) {
@@ -204,48 +155,6 @@ __global__ __launch_bounds__(256) void at_bn1_stats_kernel(const float *t1, cons
     const float mf = (float)(mt + mz), vf = (float)(vt + vz);
     const float iv = gamma[e] * (1.0f / sqrtf(vf + AT_EPS));
     mean[e] = mf; var[e] = vf; inv[e] = iv; shift[e] = beta[e] - mf * iv;
-}
-
-// y = relu(a * inv + shift), a [G][Rg][C], constants [G][C]
-template <bool RB>
-__global__ __launch_bounds__(256) void at_bn_relu_kernel(const float *a, const float *z, size_t total, int Rg, int C, int p, const float *inv,
-                                                         const float *shift, float *y) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c = (int)(e % C);
-    const size_t gr = e / C;
-    const int g = (int)(gr / Rg), r = (int)(gr % Rg);
-    y[e] = fmaxf(at_pre(at_val<RB>(a, z, g, r, c, Rg, C, p), inv[g * C + c], shift[g * C + c]), 0.f);
-}
-
-// Max over the n rows of each cloud of a * inv + shift (no ReLU): the maximum and its FIRST row.  grid (ceil(C / 64), B).
-__global__ __launch_bounds__(256) void at_gmax_kernel(const float *a, int n, int C, const float *inv, const float *shift, float *pooled,
-                                                      int *arg) {
-    __shared__ float mv[4][64];
-    __shared__ int mi[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6, b = blockIdx.y;
-    float best = -INFINITY;
-    int bi = 0;
-    if (c < C) {
-        const float iv = inv[c], sh = shift[c];
-        if (ph < n) best = at_pre(a[((size_t)b * n + ph) * C + c], iv, sh), bi = ph;
-        for (int r = ph + 4; r < n; r += 4) {
-            const float v = at_pre(a[((size_t)b * n + r) * C + c], iv, sh);
-            if (v > best) { best = v; bi = r; }
-        }
-    }
-    mv[ph][threadIdx.x & 63] = best;
-    mi[ph][threadIdx.x & 63] = bi;
-    __syncthreads();
-    if (ph == 0 && c < C) {
-        for (int p = 1; p < 4 && p < n; ++p) {
-            const float v = mv[p][threadIdx.x];
-            const int i = mi[p][threadIdx.x];
-            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-        }
-        pooled[(size_t)b * C + c] = best;
-        arg[(size_t)b * C + c] = bi;
-    }
 }
 
 // t1[q][j][c] = b1[q][c] + tmpl[q][j][0] * W1[q][0][c] + tmpl[q][j][1] * W1[q][1][c] (two fmas in that order)
@@ -301,150 +210,6 @@ __global__ __launch_bounds__(256) void at_fuse_kernel(float *prim, float *fused,
     if (FWD) fused[f] = prim[e]; else prim[e] = fused[f];
 }
 
-// out = sum d1 / c1 + sum d2 / c2: one block, strided double sums added in a fixed order
-__global__ __launch_bounds__(256) void at_loss_kernel(const float *d1, size_t c1, const float *d2, size_t c2, float *out) {
-    __shared__ double r1[256], r2[256];
-    double s = 0.0, q = 0.0;
-    for (size_t e = threadIdx.x; e < c1; e += 256) s += (double)d1[e];
-    for (size_t e = threadIdx.x; e < c2; e += 256) q += (double)d2[e];
-    r1[threadIdx.x] = s; r2[threadIdx.x] = q;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0;
-        for (int i = 0; i < 256; ++i) { a += r1[i]; b += r2[i]; }
-        out[0] = (float)(a / (double)c1 + b / (double)c2);
-    }
-}
-
-// ---- backward ----------------------------------------------------------------------------------------------
-// BN backward of a ReLU layer, dense dy:  g = dy * [a * inv + shift > 0].  Pass 1: (sum g, sum g * xhat) per chunk and group.
-template <bool RB>
-__global__ __launch_bounds__(256) void at_bn_bwd_part_kernel(const float *dy, const float *a, const float *z, int Rg, int C, int p, int rpc,
-                                                             const float *mean, const float *var, const float *inv, const float *shift,
-                                                             double2 *part) {
-    __shared__ double2 red[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6, g = blockIdx.z;
-    const int r0 = blockIdx.y * rpc, r1 = min(Rg, r0 + rpc);
-    double s = 0.0, q = 0.0;
-    if (c < C) {
-        const int k = g * C + c;
-        const float rs = 1.0f / sqrtf(var[k] + AT_EPS), m = mean[k], iv = inv[k], sh = shift[k];
-        for (int r = r0 + ph; r < r1; r += 4) {
-            const float av = at_val<RB>(a, z, g, r, c, Rg, C, p);
-            const float gv = at_pre(av, iv, sh) > 0.f ? dy[((size_t)g * Rg + r) * C + c] : 0.f;
-            s += (double)gv;
-            q += (double)gv * (double)((av - m) * rs);
-        }
-    }
-    red[ph][threadIdx.x & 63] = make_double2(s, q);
-    __syncthreads();
-    if (ph == 0 && c < C) {
-        double2 o = red[0][threadIdx.x];
-        for (int pp = 1; pp < 4; ++pp) { o.x += red[pp][threadIdx.x].x; o.y += red[pp][threadIdx.x].y; }
-        part[((size_t)g * gridDim.y + blockIdx.y) * C + c] = o;
-    }
-}
-
-// Pass 1 of conv3's BN (no ReLU), whose g is dpool at the maximum's row of each (cloud, channel): clouds in ascending order.
-__global__ __launch_bounds__(256) void at_bn_bwd_gmax_part_kernel(const float *dpool, const int *arg, const float *a, int B, int n, int C,
-                                                                  const float *mean, const float *var, double2 *part) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const float rs = 1.0f / sqrtf(var[c] + AT_EPS), m = mean[c];
-    double s = 0.0, q = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const float av = a[((size_t)b * n + arg[(size_t)b * C + c]) * C + c];
-        const float gv = dpool[(size_t)b * C + c];
-        s += (double)gv;
-        q += (double)gv * (double)((av - m) * rs);
-    }
-    part[c] = make_double2(s, q);
-}
-
-// Pass 2: dbeta, dgamma and the means m1 = dbeta / rows, m2 = dgamma / rows, per (group, column)
-__global__ __launch_bounds__(256) void at_bn_bwd_final_kernel(const double2 *part, int chunks, int C, int G, double inv_rows, float *dgamma,
-                                                              float *dbeta, float *m1, float *m2) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= G * C) return;
-    const int g = e / C, c = e - g * C;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < chunks; ++k) { const double2 v = part[((size_t)g * chunks + k) * C + c]; s += v.x; q += v.y; }
-    dbeta[e] = (float)s; dgamma[e] = (float)q;
-    m1[e] = (float)(s * inv_rows); m2[e] = (float)(q * inv_rows);
-}
-
-// out[g][c] = sum of the partials' .x (a bias gradient)
-__global__ __launch_bounds__(256) void at_colsum_final_kernel(const double2 *part, int chunks, int C, int G, float *out) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= G * C) return;
-    const int g = e / C, c = e - g * C;
-    double s = 0.0;
-    for (int k = 0; k < chunks; ++k) s += part[((size_t)g * chunks + k) * C + c].x;
-    out[e] = (float)s;
-}
-
-// Pass 3: da = gamma * rs * (g - m1 - xhat * m2), dense dy through the ReLU.  BN false (no batch norm): da = g.
-template <bool RB, bool BN>
-__global__ __launch_bounds__(256) void at_bn_bwd_apply_kernel(const float *dy, const float *a, const float *z, size_t total, int Rg, int C, int p,
-                                                              const float *mean, const float *var, const float *gamma, const float *inv,
-                                                              const float *shift, const float *m1, const float *m2, float *da) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c = (int)(e % C);
-    const size_t gr = e / C;
-    const int g = (int)(gr / Rg), r = (int)(gr % Rg), k = g * C + c;
-    const float av = at_val<RB>(a, z, g, r, c, Rg, C, p);
-    const float gv = at_pre(av, inv[k], shift[k]) > 0.f ? dy[e] : 0.f;
-    if (!BN) { da[e] = gv; return; }
-    const float rs = 1.0f / sqrtf(var[k] + AT_EPS);
-    const float xh = (av - mean[k]) * rs;
-    da[e] = gamma[k] * rs * (gv - m1[k] - xh * m2[k]);
-}
-
-// conv3's BN: da = gamma * rs * ([row is the maximum's] dpool - m1 - xhat * m2)
-__global__ __launch_bounds__(256) void at_bn_bwd_gmax_apply_kernel(const float *dpool, const int *arg, const float *a, size_t total, int n, int C,
-                                                                   const float *mean, const float *var, const float *gamma, const float *m1,
-                                                                   const float *m2, float *da) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c = (int)(e % C);
-    const size_t r = e / C, b = r / n;
-    const float gv = arg[b * C + c] == (int)(r - b * n) ? dpool[b * C + c] : 0.f;
-    const float rs = 1.0f / sqrtf(var[c] + AT_EPS);
-    const float xh = (a[e] - mean[c]) * rs;
-    da[e] = gamma[c] * rs * (gv - m1[c] - xh * m2[c]);
-}
-
-// BN backward of lin1 / lin2 (rows = the batch's clouds), one thread per column, all in double from the stored activation:
-// with few rows g - mean(g) - xhat mean(g xhat) cancels almost completely, and xhat rounded to fp32 would decide what is left.
-__global__ __launch_bounds__(256) void at_bn_bwd_fc_kernel(const float *dy, const float *a, int R, int C, const float *gamma,
-                                                           const float *inv, const float *shift, float *dgamma, float *dbeta,
-                                                           float *da) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double m = 0.0, v = 0.0;
-    for (int r = 0; r < R; ++r) m += (double)a[(size_t)r * C + c];
-    m /= R;
-    for (int r = 0; r < R; ++r) { const double d = (double)a[(size_t)r * C + c] - m; v += d * d; }
-    v /= R;
-    const double rs = 1.0 / sqrt(v + (double)AT_EPS);
-    const float iv = inv[c], sh = shift[c];
-    double s = 0.0, q = 0.0;
-    for (int r = 0; r < R; ++r) {
-        const size_t e = (size_t)r * C + c;
-        const double gv = at_pre(a[e], iv, sh) > 0.f ? (double)dy[e] : 0.0;
-        s += gv;
-        q += gv * (((double)a[e] - m) * rs);
-    }
-    dbeta[c] = (float)s; dgamma[c] = (float)q;
-    const double m1 = s / R, m2 = q / R, gr = (double)gamma[c] * rs;
-    for (int r = 0; r < R; ++r) {
-        const size_t e = (size_t)r * C + c;
-        const double gv = at_pre(a[e], iv, sh) > 0.f ? (double)dy[e] : 0.0;
-        da[e] = (float)(gr * (gv - m1 - ((double)a[e] - m) * rs * m2));
-    }
-}
-
 // d pre1 [nb][B * p][1024] -> dt1[q][j][c] = sum_b (ascending)
 __global__ __launch_bounds__(256) void at_dt1_kernel(const float *d, int B, int p, size_t total, float *dt1) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -493,26 +258,6 @@ __global__ __launch_bounds__(256) void at_conv1_grad_kernel(const float *dt1, co
     dw[(q * 2 + 1) * AT_LAT + c] = (float)w1;
 }
 
-// torch.optim.Adam; bc1 = 1 - beta1^t, bc2s = sqrt(1 - beta2^t)
-__global__ __launch_bounds__(256) void at_adam_kernel(float *p, float *m, float *v, const float *g, size_t count, float lr, float bc1, float bc2s) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= count) return;
-    const float gv = g[e];
-    const float mn = m[e] + (gv - m[e]) * (1.f - 0.9f);
-    const float vn = v[e] * 0.999f + (gv * gv) * (1.f - 0.999f);
-    m[e] = mn; v[e] = vn;
-    const float denom = sqrtf(vn) / bc2s + 1e-8f;
-    p[e] = p[e] - (lr / bc1) * (mn / denom);
-}
-
-// running = 0.9 running + 0.1 stat * scale (scale = rows / (rows - 1) for the variance, 1 for the mean)
-__global__ __launch_bounds__(256) void at_running_kernel(float *running, const float *stat, const float *scale, size_t count) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= count) return;
-    const float s = scale ? stat[e] * scale[e] : stat[e];
-    running[e] = running[e] * (1.f - 0.1f) + 0.1f * s;
-}
-
 }  // namespace geoadv
 
 using namespace geoadv;
@@ -542,23 +287,9 @@ struct geoadv_atlas_trainer {
 };
 
 namespace {
-template <class T> T *dev_alloc(geoadv_atlas_trainer *t, size_t count, hipError_t &err) {
-    void *p = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T) + 16);
-    if (err == hipSuccess) { t->allocs.push_back(p); err = hipMemset(p, 0, count * sizeof(T) + 16); }
-    return static_cast<T *>(p);
-}
-
-inline unsigned blocks_of(size_t total) { return (unsigned)((total + 255) / 256); }
-inline int rpc_of(int R) { return std::max(1, std::min(R, 256)); }
-
-struct Run {
+struct Run : Launch {
     geoadv_atlas_trainer *t;
-    hipStream_t st;
-    hipError_t err = hipSuccess;
 
-    void check() { if (err == hipSuccess) err = hipGetLastError(); }
-    bool ok() const { return err == hipSuccess; }
     float *W(int l) { return t->params + t->o_w[l]; }
     int rows(int l) const { return l <= E3 ? t->R : l <= L2 ? t->B : t->Rp; }      // per group
 
@@ -577,31 +308,18 @@ struct Run {
         const int M = rows(l), K = t->kin[l], N = t->kout[l], G = t->grp[l];
         gemm(in, K, 1, (long long)M * K, W(l), N, 1, (long long)K * N, out, N, (long long)M * N, t->params + t->o_b[l], N, M, N, K, G);
     }
-    template <int MODE> void colsum(const float *a, int Rg, int C, int G, int rpc) {
-        if (!ok()) return;
-        hipLaunchKernelGGL(at_colsum_kernel<MODE>, dim3(cdiv(C, 64), cdiv(Rg, rpc), G), dim3(256), 0, st, a, Rg, C, rpc, t->part);
-        check();
-    }
     void batch_stats(int l) {
-        const int Rg = rows(l), C = t->kout[l], G = t->grp[l], rpc = rpc_of(Rg);
-        colsum<0>(t->a[l], Rg, C, G, rpc);
-        if (!ok()) return;
         const size_t o = t->o_mv[l];
-        hipLaunchKernelGGL(at_bn_stats_kernel, dim3(cdiv(G * C, 256)), dim3(256), 0, st, t->part, cdiv(Rg, rpc), C, G, 1.0 / Rg,
-                           t->params + t->o_g[l], t->params + t->o_be[l], t->bat_mean + o, t->bat_var + o, t->inv + o, t->shift + o);
-        check();
+        bn_batch_stats(t->a[l], rows(l), t->kout[l], t->grp[l], t->part, t->params + t->o_g[l], t->params + t->o_be[l], AT_EPS, t->bat_mean + o,
+                       t->bat_var + o, t->inv + o, t->shift + o);
     }
     void bn_relu(int l, float *y) {
-        if (!ok()) return;
         const int Rg = rows(l), C = t->kout[l], G = t->grp[l];
         const size_t total = (size_t)G * Rg * C, o = t->o_mv[l];
         if (l == D0)
-            hipLaunchKernelGGL(at_bn_relu_kernel<true>, dim3(blocks_of(total)), dim3(256), 0, st, t->t1, t->h[L2], total, Rg, C, t->p, t->inv + o,
-                               t->shift + o, y);
+            launch(tb_bn_relu_kernel<true>, dim3(blocks_of(total)), dim3(256), t->t1, t->h[L2], total, Rg, C, t->p, t->inv + o, t->shift + o, y);
         else
-            hipLaunchKernelGGL(at_bn_relu_kernel<false>, dim3(blocks_of(total)), dim3(256), 0, st, t->a[l], (const float *)nullptr, total, Rg, C,
-                               t->p, t->inv + o, t->shift + o, y);
-        check();
+            launch(tb_bn_relu_kernel<false>, dim3(blocks_of(total)), dim3(256), t->a[l], nullptr, total, Rg, C, t->p, t->inv + o, t->shift + o, y);
     }
     void bn_layer(int l, const float *in, float *y) {
         linear_fwd(l, in, t->a[l]);
@@ -615,13 +333,7 @@ struct Run {
         const int M = rows(l), K = t->kin[l], N = t->kout[l], G = t->grp[l];
         gemm(in, 1, K, (long long)M * K, da, N, 1, (long long)M * N, t->grads + t->o_w[l], N, (long long)K * N, nullptr, 0, K, N, M, G);
     }
-    void bias_grad(int l, const float *da) {
-        const int Rg = rows(l), C = t->kout[l], G = t->grp[l], rpc = rpc_of(Rg);
-        colsum<1>(da, Rg, C, G, rpc);
-        if (!ok()) return;
-        hipLaunchKernelGGL(at_colsum_final_kernel, dim3(cdiv(G * C, 256)), dim3(256), 0, st, t->part, cdiv(Rg, rpc), C, G, t->grads + t->o_b[l]);
-        check();
-    }
+    void bias_grad(int l, const float *da) { bias_colsum(da, rows(l), t->kout[l], t->grp[l], t->part, t->grads + t->o_b[l]); }
     // din[g] = da[g] W_l[g]^T
     void input_grad(int l, const float *da, float *din) {
         const int M = rows(l), K = t->kin[l], N = t->kout[l], G = t->grp[l];
@@ -634,114 +346,72 @@ struct Run {
     }
     // BN + ReLU backward of layer l, dense dy -> da (may alias dy).  The decoder's first layer rebuilds its activation.
     void bn_bwd(int l, const float *dy, float *da) {
-        if (!ok()) return;
-        const int Rg = rows(l), C = t->kout[l], G = t->grp[l];
+        const int Rg = rows(l), C = t->kout[l], G = t->grp[l], p = t->p;
         const size_t o = t->o_mv[l], total = (size_t)G * Rg * C;
-        const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o;
+        const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o, *gam = t->params + t->o_g[l];
+        float *dgam = t->grads + t->o_g[l], *dbeta = t->grads + t->o_be[l];
         const bool rb = l == D0;
         const float *a = rb ? t->t1 : t->a[l], *z = rb ? t->h[L2] : nullptr;
+        const dim3 flat(blocks_of(total));
         if (!t->bn_of(l)) {
-            if (rb) hipLaunchKernelGGL((at_bn_bwd_apply_kernel<true, false>), dim3(blocks_of(total)), dim3(256), 0, st, dy, a, z, total, Rg, C, t->p,
-                                       mean, var, mean, iv, sh, mean, mean, da);
-            else hipLaunchKernelGGL((at_bn_bwd_apply_kernel<false, false>), dim3(blocks_of(total)), dim3(256), 0, st, dy, a, z, total, Rg, C, t->p,
-                                    mean, var, mean, iv, sh, mean, mean, da);
-            check();
+            launch(rb ? tb_bn_bwd_apply_kernel<true, false> : tb_bn_bwd_apply_kernel<false, false>, flat, dim3(256), dy, a, z, total, Rg, C, p, mean,
+                   var, mean, iv, sh, mean, mean, AT_EPS, da);
             return;
         }
         if (l == L1 || l == L2) {
-            hipLaunchKernelGGL(at_bn_bwd_fc_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, dy, t->a[l], Rg, C, t->params + t->o_g[l], iv, sh,
-                               t->grads + t->o_g[l], t->grads + t->o_be[l], da);
-            check();
+            launch(tb_bn_bwd_fc_kernel, dim3(cdiv(C, 256)), dim3(256), dy, t->a[l], Rg, C, gam, iv, sh, AT_EPS, dgam, dbeta, da);
             return;
         }
         const int rpc = rpc_of(Rg), chunks = cdiv(Rg, rpc);
-        const dim3 grid(cdiv(C, 64), chunks, G);
-        if (rb) hipLaunchKernelGGL(at_bn_bwd_part_kernel<true>, grid, dim3(256), 0, st, dy, a, z, Rg, C, t->p, rpc, mean, var, iv, sh, t->part);
-        else hipLaunchKernelGGL(at_bn_bwd_part_kernel<false>, grid, dim3(256), 0, st, dy, a, z, Rg, C, t->p, rpc, mean, var, iv, sh, t->part);
-        check();
-        if (!ok()) return;
-        hipLaunchKernelGGL(at_bn_bwd_final_kernel, dim3(cdiv(G * C, 256)), dim3(256), 0, st, t->part, chunks, C, G, 1.0 / Rg, t->grads + t->o_g[l],
-                           t->grads + t->o_be[l], t->m1 + o, t->m2 + o);
-        check();
-        if (!ok()) return;
-        const float *gam = t->params + t->o_g[l];
-        if (rb) hipLaunchKernelGGL((at_bn_bwd_apply_kernel<true, true>), dim3(blocks_of(total)), dim3(256), 0, st, dy, a, z, total, Rg, C, t->p, mean,
-                                   var, gam, iv, sh, t->m1 + o, t->m2 + o, da);
-        else hipLaunchKernelGGL((at_bn_bwd_apply_kernel<false, true>), dim3(blocks_of(total)), dim3(256), 0, st, dy, a, z, total, Rg, C, t->p, mean,
-                                var, gam, iv, sh, t->m1 + o, t->m2 + o, da);
-        check();
+        launch(rb ? tb_bn_bwd_part_kernel<true> : tb_bn_bwd_part_kernel<false>, dim3(cdiv(C, 64), chunks, G), dim3(256), dy, a, z, Rg, C, p, rpc,
+               mean, var, iv, sh, AT_EPS, t->part);
+        launch(tb_bn_bwd_final_kernel, dim3(cdiv(G * C, 256)), dim3(256), t->part, chunks, C, G, 1.0 / Rg, dgam, dbeta, t->m1 + o, t->m2 + o);
+        launch(rb ? tb_bn_bwd_apply_kernel<true, true> : tb_bn_bwd_apply_kernel<false, true>, flat, dim3(256), dy, a, z, total, Rg, C, p, mean, var,
+               gam, iv, sh, t->m1 + o, t->m2 + o, AT_EPS, da);
     }
     // conv3's BN: dpool [B][1024] at the maximum's rows -> da [R][1024]
     void bn_bwd_gmax(const float *dpool, float *da) {
-        if (!ok()) return;
         const int l = E3, C = AT_LAT;
         const size_t o = t->o_mv[l], total = (size_t)t->R * C;
         const float *mean = t->bat_mean + o, *var = t->bat_var + o;
-        hipLaunchKernelGGL(at_bn_bwd_gmax_part_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, dpool, t->arg, t->a[l], t->B, t->n, C, mean, var,
-                           t->part);
-        check();
-        if (!ok()) return;
-        hipLaunchKernelGGL(at_bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, 1, C, 1, 1.0 / t->R, t->grads + t->o_g[l],
-                           t->grads + t->o_be[l], t->m1 + o, t->m2 + o);
-        check();
-        if (!ok()) return;
-        hipLaunchKernelGGL(at_bn_bwd_gmax_apply_kernel, dim3(blocks_of(total)), dim3(256), 0, st, dpool, t->arg, t->a[l], total, t->n, C, mean, var,
-                           t->params + t->o_g[l], t->m1 + o, t->m2 + o, da);
-        check();
+        launch(tb_bn_bwd_gmax_part_kernel, dim3(cdiv(C, 256)), dim3(256), dpool, t->arg, t->a[l], t->B, t->n, C, mean, var, AT_EPS, t->part);
+        launch(tb_bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), t->part, 1, C, 1, 1.0 / t->R, t->grads + t->o_g[l], t->grads + t->o_be[l],
+               t->m1 + o, t->m2 + o);
+        launch(tb_bn_bwd_gmax_apply_kernel, dim3(blocks_of(total)), dim3(256), dpool, t->arg, t->a[l], total, t->n, C, mean, var,
+               t->params + t->o_g[l], t->m1 + o, t->m2 + o, AT_EPS, da);
     }
 };
 
 int run_step(geoadv_atlas_trainer *t, const float *x, hipStream_t st) {
-    Run q{t, st};
+    Run q{{st}, t};
     const int B = t->B, nb = t->nb, p = t->p, NL = t->NL, LAST = NL - 1;
+    const dim3 blk(256);
     // ---- forward: encoder ----
     q.bn_layer(E1, x, t->h[E1]);
     q.bn_layer(E2, t->h[E1], t->h[E2]);
     q.bn_layer(E3, t->h[E2], nullptr);
-    if (q.ok()) {
-        const size_t o = t->o_mv[E3];
-        hipLaunchKernelGGL(at_gmax_kernel, dim3(AT_LAT / 64, B), dim3(256), 0, st, t->a[E3], t->n, AT_LAT, t->inv + o, t->shift + o, t->pooled,
-                           t->arg);
-        q.check();
-    }
+    q.launch(tb_gmax_kernel, dim3(AT_LAT / 64, B), blk, t->a[E3], t->n, AT_LAT, t->inv + t->o_mv[E3], t->shift + t->o_mv[E3], t->pooled, t->arg);
     q.bn_layer(L1, t->pooled, t->h[L1]);
     q.bn_layer(L2, t->h[L1], t->h[L2]);                                   // the latent
     // ---- forward: decoder ----
-    if (q.ok()) {
-        const int total = nb * p * AT_LAT;
-        hipLaunchKernelGGL(at_t1_kernel, dim3(blocks_of(total)), dim3(256), 0, st, t->tmpl, q.W(D0), t->params + t->o_b[D0], p, total, t->t1);
-        q.check();
-    }
-    if (q.ok() && t->dbn) {
+    q.launch(at_t1_kernel, dim3(blocks_of(nb * p * AT_LAT)), blk, t->tmpl, q.W(D0), t->params + t->o_b[D0], p, nb * p * AT_LAT, t->t1);
+    if (t->dbn) {
         const size_t o = t->o_mv[D0];
-        hipLaunchKernelGGL(at_bn1_stats_kernel, dim3(cdiv(nb * AT_LAT, 256)), dim3(256), 0, st, t->t1, t->h[L2], p, B, AT_LAT, nb,
-                           t->params + t->o_g[D0], t->params + t->o_be[D0], t->bat_mean + o, t->bat_var + o, t->inv + o, t->shift + o);
-        q.check();
+        q.launch(at_bn1_stats_kernel, dim3(cdiv(nb * AT_LAT, 256)), blk, t->t1, t->h[L2], p, B, AT_LAT, nb, t->params + t->o_g[D0],
+                 t->params + t->o_be[D0], t->bat_mean + o, t->bat_var + o, t->inv + o, t->shift + o);
     }
     q.bn_relu(D0, t->h[D0]);
     for (int l = D1; l < LAST; ++l) q.bn_layer(l, t->h[l - 1], t->h[l]);
-    if (q.ok()) {
-        hipLaunchKernelGGL(at_last_fwd_kernel, dim3(cdiv(t->rows, 4)), dim3(256), 0, st, t->h[LAST - 1], q.W(LAST), t->params + t->o_b[LAST], t->Rp,
-                           t->rows, t->prim);
-        q.check();
-    }
+    q.launch(at_last_fwd_kernel, dim3(cdiv(t->rows, 4)), blk, t->h[LAST - 1], q.W(LAST), t->params + t->o_b[LAST], t->Rp, t->rows, t->prim);
     const size_t r3 = (size_t)t->rows * 3;
-    if (q.ok()) {
-        hipLaunchKernelGGL(at_fuse_kernel<true>, dim3(blocks_of(r3)), dim3(256), 0, st, t->prim, t->recon, B, nb, p, r3);
-        q.check();
-    }
+    q.launch(at_fuse_kernel<true>, dim3(blocks_of(r3)), blk, t->prim, t->recon, B, nb, p, r3);
     // ---- loss and its gradient ----
-    if (q.ok()) {
+    if (q.ok())
         if (int rc = geoadv_nn_distance(B, t->n, x, t->m, t->recon, t->d1, t->i1, t->d2, t->i2, st)) return rc;
-        hipLaunchKernelGGL(at_loss_kernel, dim3(1), dim3(256), 0, st, t->d1, (size_t)t->R, t->d2, (size_t)t->rows, t->loss);
-        q.check();
-    }
+    q.launch(tb_loss_kernel, dim3(1), blk, t->d1, (size_t)t->R, t->d2, (size_t)t->rows, t->loss);
     if (q.ok())
         if (int rc = geoadv_nn_distance_grad(B, t->n, x, t->m, t->recon, t->gd1, t->i1, t->gd2, t->i2, t->dx, t->drecon, st)) return rc;
-    if (q.ok()) {
-        hipLaunchKernelGGL(at_fuse_kernel<false>, dim3(blocks_of(r3)), dim3(256), 0, st, t->dprim, t->drecon, B, nb, p, r3);
-        q.check();
-    }
+    q.launch(at_fuse_kernel<false>, dim3(blocks_of(r3)), blk, t->dprim, t->drecon, B, nb, p, r3);
     // ---- backward: decoder ----
     q.linear_bwd(LAST, t->h[LAST - 1], t->dprim, t->Y);                   // d h of the last hidden layer [nb][Rp][512]
     for (int l = LAST - 1; l >= D1; --l) {
@@ -749,15 +419,11 @@ int run_step(geoadv_atlas_trainer *t, const float *x, hipStream_t st) {
         q.linear_bwd(l, t->h[l - 1], t->Z, t->Y);                         // d h_{l-1} (l = D1: [nb][Rp][1024])
     }
     q.bn_bwd(D0, t->Y, t->Y);                                             // d pre1, in place
-    if (q.ok()) {
-        const size_t tt = (size_t)nb * p * AT_LAT, tz = (size_t)nb * B * AT_LAT;
-        hipLaunchKernelGGL(at_dt1_kernel, dim3(blocks_of(tt)), dim3(256), 0, st, t->Y, B, p, tt, t->dt1);
-        hipLaunchKernelGGL(at_dzq_kernel, dim3(blocks_of(tz)), dim3(256), 0, st, t->Y, p, tz, t->dzq);
-        hipLaunchKernelGGL(at_dz_kernel, dim3(cdiv(B * AT_LAT, 256)), dim3(256), 0, st, t->dzq, nb, B * AT_LAT, t->dz);
-        hipLaunchKernelGGL(at_conv1_grad_kernel, dim3(cdiv(nb * AT_LAT, 256)), dim3(256), 0, st, t->dt1, t->tmpl, p, nb, t->grads + t->o_w[D0],
-                           t->grads + t->o_b[D0]);
-        q.check();
-    }
+    const size_t tt = (size_t)nb * p * AT_LAT, tz = (size_t)nb * B * AT_LAT;
+    q.launch(at_dt1_kernel, dim3(blocks_of(tt)), blk, t->Y, B, p, tt, t->dt1);
+    q.launch(at_dzq_kernel, dim3(blocks_of(tz)), blk, t->Y, p, tz, t->dzq);
+    q.launch(at_dz_kernel, dim3(cdiv(B * AT_LAT, 256)), blk, t->dzq, nb, B * AT_LAT, t->dz);
+    q.launch(at_conv1_grad_kernel, dim3(cdiv(nb * AT_LAT, 256)), blk, t->dt1, t->tmpl, p, nb, t->grads + t->o_w[D0], t->grads + t->o_b[D0]);
     // ---- backward: encoder ----
     q.bn_bwd(L2, t->dz, t->dsm1);
     q.linear_bwd(L2, t->h[L1], t->dsm1, t->dsm2);                         // d h4 [B][1024]
@@ -774,13 +440,14 @@ int run_step(geoadv_atlas_trainer *t, const float *x, hipStream_t st) {
         return GEOADV_EHIP;
     }
     // ---- optimizer, running statistics, counters ----
-    const double tt = (double)(t->step + 1);
-    const float bc1 = (float)(1.0 - pow(0.9, tt)), bc2s = (float)sqrt(1.0 - pow(0.999, tt));
-    hipLaunchKernelGGL(at_adam_kernel, dim3(blocks_of(t->P)), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, t->lr, bc1, bc2s);
+    const double ts = (double)(t->step + 1);
+    const float bc1 = (float)(1.0 - pow(0.9, ts)), bc2s = (float)sqrt(1.0 - pow(0.999, ts));
+    hipLaunchKernelGGL(tb_adam_kernel<false>, dim3(blocks_of(t->P)), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, t->lr, 0.f, bc1,
+                       bc2s);
     GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(at_running_kernel, dim3(blocks_of(t->MVbn)), dim3(256), 0, st, t->run_mean, t->bat_mean, (const float *)nullptr, t->MVbn);
+    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MVbn)), dim3(256), 0, st, t->run_mean, t->bat_mean, (const float *)nullptr, t->MVbn);
     GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(at_running_kernel, dim3(blocks_of(t->MVbn)), dim3(256), 0, st, t->run_var, t->bat_var, t->unbias, t->MVbn);
+    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MVbn)), dim3(256), 0, st, t->run_var, t->bat_var, t->unbias, t->MVbn);
     GA_LAUNCH_CHECK();
     t->step += 1;
     t->tracked += 1;
@@ -852,30 +519,31 @@ extern "C" int geoadv_atlas_trainer_create(geoadv_atlas_trainer **out, const geo
     t->P = P; t->MV = MV;
     const size_t R = t->R, B = t->B, rows = t->rows, nb = t->nb, p = t->p;
     hipError_t e = hipSuccess;
-    t->params = dev_alloc<float>(t, P, e); t->grads = dev_alloc<float>(t, P, e);
-    t->slot1 = dev_alloc<float>(t, P, e); t->slot2 = dev_alloc<float>(t, P, e);
+    std::vector<void *> &mem = t->allocs;
+    t->params = dev_alloc<float>(mem, P, e); t->grads = dev_alloc<float>(mem, P, e);
+    t->slot1 = dev_alloc<float>(mem, P, e); t->slot2 = dev_alloc<float>(mem, P, e);
     for (float **pp : {&t->run_mean, &t->run_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2, &t->unbias})
-        *pp = dev_alloc<float>(t, MV, e);
+        *pp = dev_alloc<float>(mem, MV, e);
     for (int l = 0; l < NL - 1; ++l) {
         const size_t count = (l <= E3 ? R : l <= L2 ? B : rows) * t->kout[l];
-        t->a[l] = l == D0 ? nullptr : dev_alloc<float>(t, count, e);
-        t->h[l] = l == E3 ? nullptr : dev_alloc<float>(t, count, e);
+        t->a[l] = l == D0 ? nullptr : dev_alloc<float>(mem, count, e);
+        t->h[l] = l == E3 ? nullptr : dev_alloc<float>(mem, count, e);
     }
-    t->pooled = dev_alloc<float>(t, B * AT_LAT, e); t->arg = dev_alloc<int>(t, B * AT_LAT, e);
-    t->t1 = dev_alloc<float>(t, nb * p * AT_LAT, e); t->dt1 = dev_alloc<float>(t, nb * p * AT_LAT, e);
-    t->tmpl = dev_alloc<float>(t, nb * p * 2, e);
-    t->prim = dev_alloc<float>(t, rows * 3, e); t->recon = dev_alloc<float>(t, rows * 3, e);
-    t->dprim = dev_alloc<float>(t, rows * 3, e); t->drecon = dev_alloc<float>(t, rows * 3, e); t->dx = dev_alloc<float>(t, R * 3, e);
-    t->d1 = dev_alloc<float>(t, R, e); t->i1 = dev_alloc<int>(t, R, e); t->gd1 = dev_alloc<float>(t, R, e);
-    t->d2 = dev_alloc<float>(t, rows, e); t->i2 = dev_alloc<int>(t, rows, e); t->gd2 = dev_alloc<float>(t, rows, e);
-    t->loss = dev_alloc<float>(t, 1, e);
-    t->Y = dev_alloc<float>(t, std::max(R, rows) * AT_LAT, e);
-    t->Z = dev_alloc<float>(t, std::max(R * 128, rows * AT_HID), e);
-    t->T = dev_alloc<float>(t, R * 128, e);
-    t->dz = dev_alloc<float>(t, B * AT_LAT, e); t->dsm1 = dev_alloc<float>(t, B * AT_LAT, e); t->dsm2 = dev_alloc<float>(t, B * AT_LAT, e);
-    t->dzq = dev_alloc<double>(t, nb * B * AT_LAT, e);
-    t->partials = dev_alloc<float>(t, CT_PARTIAL_FLOATS, e);
-    t->part = dev_alloc<double2>(t, std::max((size_t)cdiv((int)R, 256), nb * cdiv(t->Rp, 256)) * AT_LAT + 1024, e);
+    t->pooled = dev_alloc<float>(mem, B * AT_LAT, e); t->arg = dev_alloc<int>(mem, B * AT_LAT, e);
+    t->t1 = dev_alloc<float>(mem, nb * p * AT_LAT, e); t->dt1 = dev_alloc<float>(mem, nb * p * AT_LAT, e);
+    t->tmpl = dev_alloc<float>(mem, nb * p * 2, e);
+    t->prim = dev_alloc<float>(mem, rows * 3, e); t->recon = dev_alloc<float>(mem, rows * 3, e);
+    t->dprim = dev_alloc<float>(mem, rows * 3, e); t->drecon = dev_alloc<float>(mem, rows * 3, e); t->dx = dev_alloc<float>(mem, R * 3, e);
+    t->d1 = dev_alloc<float>(mem, R, e); t->i1 = dev_alloc<int>(mem, R, e); t->gd1 = dev_alloc<float>(mem, R, e);
+    t->d2 = dev_alloc<float>(mem, rows, e); t->i2 = dev_alloc<int>(mem, rows, e); t->gd2 = dev_alloc<float>(mem, rows, e);
+    t->loss = dev_alloc<float>(mem, 1, e);
+    t->Y = dev_alloc<float>(mem, std::max(R, rows) * AT_LAT, e);
+    t->Z = dev_alloc<float>(mem, std::max(R * 128, rows * AT_HID), e);
+    t->T = dev_alloc<float>(mem, R * 128, e);
+    t->dz = dev_alloc<float>(mem, B * AT_LAT, e); t->dsm1 = dev_alloc<float>(mem, B * AT_LAT, e); t->dsm2 = dev_alloc<float>(mem, B * AT_LAT, e);
+    t->dzq = dev_alloc<double>(mem, nb * B * AT_LAT, e);
+    t->partials = dev_alloc<float>(mem, CT_PARTIAL_FLOATS, e);
+    t->part = dev_alloc<double2>(mem, std::max((size_t)cdiv((int)R, 256), nb * cdiv(t->Rp, 256)) * AT_LAT + 1024, e);
     if (e == hipSuccess) {
         std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f), hu(MV, 1.f), hi(MV, 1.f), g1(R, 1.f / (float)R), g2(rows, 1.f / (float)rows);
         for (int l = 0; l < NL; ++l) {
@@ -898,7 +566,7 @@ extern "C" int geoadv_atlas_trainer_create(geoadv_atlas_trainer **out, const geo
         up(t->params, hp); up(t->run_mean, hm); up(t->run_var, hv); up(t->unbias, hu); up(t->inv, hi); up(t->gd1, g1); up(t->gd2, g2);
     }
     if (e != hipSuccess) {
-        for (void *pp : t->allocs) (void)hipFree(pp);
+        dev_free_all(t->allocs);
         delete t;
         set_error("atlas_trainer_create: %s", hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
@@ -909,7 +577,7 @@ extern "C" int geoadv_atlas_trainer_create(geoadv_atlas_trainer **out, const geo
 
 extern "C" void geoadv_atlas_trainer_destroy(geoadv_atlas_trainer *t) {
     if (!t) return;
-    for (void *p : t->allocs) (void)hipFree(p);
+    dev_free_all(t->allocs);
     delete t;
 }
 

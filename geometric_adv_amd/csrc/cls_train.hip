@@ -29,7 +29,7 @@
 // lr = max(base * decay_rate^floor(k B / decay_step), 1e-5), bn_decay = min(0.99, 1 - 0.5 * 0.5^floor(k B / decay_step)).
 // Moving statistics: ExponentialMovingAverage(bn_decay) of the moments tensors (zero slots, zero_debias = False):
 // shadow -= (shadow - batch_stat) * (1 - bn_decay).
-#include "train_tile.h"
+#include "train_bn.h"
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -38,26 +38,6 @@ namespace geoadv {
 
 constexpr float CT_KEEP = 0.7f, CT_EPS = 1e-3f;
 constexpr unsigned CT_KEEP_BELOW = 11744051u;
-
-// ---- batch norm -----------------------------------------------------------------------------------------------------------
-// The folded constants: inv = gamma / sqrt(var + eps), shift = beta - mean * inv; y = relu(a * inv + shift).  The backward
-// recomputes the same expression, so its ReLU mask is the forward's bit for bit.
-__device__ __forceinline__ float ct_pre(float a, float inv, float shift) { return a * inv + shift; }
-
-// Batch statistics from the partials: mean, population variance, folded constants.  One thread per column.
-__global__ __launch_bounds__(256) void ct_bn_stats_kernel(const double2 *part, int chunks, int C, double inv_rows, const float *gamma,
-                                                          const float *beta, float *mean, float *var, float *inv, float *shift) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < chunks; ++k) { s += part[(size_t)k * C + c].x; q += part[(size_t)k * C + c].y; }
-    const double m = s * inv_rows;
-    double v = q * inv_rows - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mf = (float)m, vf = (float)v;
-    const float iv = gamma[c] * (1.0f / sqrtf(vf + CT_EPS));
-    mean[c] = mf; var[c] = vf; inv[c] = iv; shift[c] = beta[c] - mf * iv;
-}
 
 __device__ __forceinline__ float ct_keep(unsigned long long seed, long long step, int layer, int cloud, int ch) {
     const unsigned long long h = mix64(mix64(seed + kGolden64 * (unsigned long long)(step + 1)) ^
@@ -71,7 +51,7 @@ __global__ __launch_bounds__(256) void ct_bn_fwd_kernel(const float *a, int R, i
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)R * C) return;
     const int c = (int)(e % C), r = (int)(e / C);
-    float v = fmaxf(ct_pre(a[e], inv[c], shift[c]), 0.f);
+    float v = fmaxf(tb_pre(a[e], inv[c], shift[c]), 0.f);
     if (dropout_layer >= 0) {
         const float m = ct_keep(seed, step, dropout_layer, r, c);
         mask[e] = m;
@@ -91,7 +71,7 @@ __global__ __launch_bounds__(256) void ct_pool_kernel(const float *a, int n, int
     if (c < C) {
         const float iv = inv[c], sh = shift[c];
         for (int r = ph; r < n; r += 4) {
-            const float v = fmaxf(ct_pre(a[((size_t)b * n + r) * C + c], iv, sh), 0.f);
+            const float v = fmaxf(tb_pre(a[((size_t)b * n + r) * C + c], iv, sh), 0.f);
             if (v > best) { best = v; bi = r; }
         }
     }
@@ -124,7 +104,7 @@ __global__ __launch_bounds__(256) void ct_bn_bwd_part_kernel(const float *dy, co
         for (int r = r0 + ph; r < r1; r += 4) {
             const size_t e = (size_t)r * C + c;
             const float av = a[e];
-            float gv = ct_pre(av, iv, sh) > 0.f ? dy[e] : 0.f;
+            float gv = tb_pre(av, iv, sh) > 0.f ? dy[e] : 0.f;
             if (DROP) gv = gv * mask[e] / CT_KEEP;
             s += (double)gv;
             q += (double)gv * (double)((av - m) * rs);
@@ -150,7 +130,7 @@ __global__ __launch_bounds__(256) void ct_bn_bwd_pool_part_kernel(const float *d
     double s = 0.0, q = 0.0;
     for (int b = 0; b < B; ++b) {
         const float av = a[((size_t)b * n + arg[(size_t)b * C + c]) * C + c];
-        const float gv = ct_pre(av, iv, sh) > 0.f ? dpool[(size_t)b * C + c] : 0.f;
+        const float gv = tb_pre(av, iv, sh) > 0.f ? dpool[(size_t)b * C + c] : 0.f;
         s += (double)gv;
         q += (double)gv * (double)((av - m) * rs);
     }
@@ -168,7 +148,7 @@ __global__ __launch_bounds__(256) void ct_bn_bwd_apply_kernel(const float *dy, c
     const int c = (int)(e % C), r = (int)(e / C);
     const float av = a[e];
     float gv = 0.f;
-    if (ct_pre(av, inv[c], shift[c]) > 0.f) {
+    if (tb_pre(av, inv[c], shift[c]) > 0.f) {
         if (MODE == 2) {
             const int b = r / n;
             if (arg[(size_t)b * C + c] == r - b * n) gv = dy[(size_t)b * C + c];
@@ -298,24 +278,11 @@ struct geoadv_cls_trainer {
 };
 
 namespace {
-template <class T> T *dev_alloc(geoadv_cls_trainer *t, size_t count, hipError_t &err) {
-    void *p = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T) + 16);
-    if (err == hipSuccess) { t->allocs.push_back(p); err = hipMemset(p, 0, count * sizeof(T) + 16); }
-    return static_cast<T *>(p);
-}
-
-struct Run {
+struct Run : Launch {
     geoadv_cls_trainer *t;
-    hipStream_t st;
-    hipError_t err = hipSuccess;
-
-    void check() { if (err == hipSuccess) err = hipGetLastError(); }
 
     // C = alpha * A B (+ bias) (+ C)
-    void gemm(GemmArgs g) {
-        if (err == hipSuccess) err = ct_launch_gemm(g, t->partials, st);
-    }
+    void gemm(const GemmArgs &g) { Launch::gemm(g, t->partials); }
     static GemmArgs plain(const float *A, const float *B, float *C, int M, int N, int K) {
         GemmArgs g{};
         g.A = A; g.sAi = K; g.sAk = 1;
@@ -334,84 +301,50 @@ struct Run {
         gemm(g);
     }
     void batch_stats(int l) {
-        if (err != hipSuccess) return;
-        const int R = rows(l), C = t->out[l];
-        const int rpc = std::max(1, std::min(R, 256)), chunks = cdiv(R, rpc);
-        hipLaunchKernelGGL(ct_colsum_kernel<0>, dim3(cdiv(C, 64), chunks), dim3(256), 0, st, t->a[l], R, C, rpc, t->part);
-        check();
         const size_t o = t->o_mv[l];
-        hipLaunchKernelGGL(ct_bn_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, chunks, C, 1.0 / R,
-                           t->params + t->o_g[l], t->params + t->o_be[l], t->bat_mean + o, t->bat_var + o, t->inv + o, t->shift + o);
-        check();
+        bn_batch_stats(t->a[l], rows(l), t->out[l], 1, t->part, t->params + t->o_g[l], t->params + t->o_be[l], CT_EPS, t->bat_mean + o,
+                       t->bat_var + o, t->inv + o, t->shift + o);
     }
     // BN + ReLU (+ dropout) of a stored layer
     void bn_fwd(int l, int drop) {
-        if (err != hipSuccess) return;
         const int R = rows(l), C = t->out[l];
         const size_t o = t->o_mv[l];
-        const size_t total = (size_t)R * C;
-        hipLaunchKernelGGL(ct_bn_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, t->a[l], R, C, t->inv + o, t->shift + o,
-                           t->h[l], drop, t->seed, t->step, drop >= 0 ? t->mask[drop] : nullptr);
-        check();
+        launch(ct_bn_fwd_kernel, dim3(blocks_of((size_t)R * C)), dim3(256), t->a[l], R, C, t->inv + o, t->shift + o, t->h[l], drop, t->seed, t->step,
+               drop >= 0 ? t->mask[drop] : nullptr);
     }
     void pool(int l, int which) {
-        if (err != hipSuccess) return;
         const size_t o = t->o_mv[l];
-        hipLaunchKernelGGL(ct_pool_kernel, dim3(cdiv(t->out[l], 64), t->B), dim3(256), 0, st, t->a[l], t->n, t->out[l], t->inv + o,
-                           t->shift + o, t->pooled[which], t->arg[which]);
-        check();
+        launch(ct_pool_kernel, dim3(cdiv(t->out[l], 64), t->B), dim3(256), t->a[l], t->n, t->out[l], t->inv + o, t->shift + o, t->pooled[which],
+               t->arg[which]);
     }
     void layer(int l, const float *in) { linear_fwd(l, in, t->a[l]); batch_stats(l); bn_fwd(l, l == F1 ? 0 : l == F2 ? 1 : -1); }
 
     // d bias = column sums of da over the layer's rows
-    void bias_grad(int l, const float *da) {
-        if (err != hipSuccess) return;
-        const int R = rows(l), C = t->out[l];
-        const int rpc = std::max(1, std::min(R, 256)), chunks = cdiv(R, rpc);
-        hipLaunchKernelGGL(ct_colsum_kernel<1>, dim3(cdiv(C, 64), chunks), dim3(256), 0, st, da, R, C, rpc, t->part);
-        check();
-        hipLaunchKernelGGL(ct_colsum_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, chunks, C, t->grads + t->o_b[l]);
-        check();
-    }
+    void bias_grad(int l, const float *da) { bias_colsum(da, rows(l), t->out[l], 1, t->part, t->grads + t->o_b[l]); }
     // BN backward of layer l: mode 0 dense, 1 dense through dropout mask `drop`, 2 pool `which` (dy = dpool [B][C]).
     void bn_bwd(int l, int mode, const float *dy, int aux, float *da) {
-        if (err != hipSuccess) return;
         const int R = rows(l), C = t->out[l];
         const size_t o = t->o_mv[l];
-        const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o;
-        int chunks = 1;
-        if (mode == 2) {
-            hipLaunchKernelGGL(ct_bn_bwd_pool_part_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, dy, t->arg[aux], t->a[l], t->B, t->n, C,
-                               mean, var, iv, sh, t->part);
-        } else {
-            const int rpc = std::max(1, std::min(R, 256));
-            chunks = cdiv(R, rpc);
-            if (mode == 1)
-                hipLaunchKernelGGL(ct_bn_bwd_part_kernel<true>, dim3(cdiv(C, 64), chunks), dim3(256), 0, st, dy, t->mask[aux], t->a[l], R, C,
-                                   rpc, mean, var, iv, sh, t->part);
-            else
-                hipLaunchKernelGGL(ct_bn_bwd_part_kernel<false>, dim3(cdiv(C, 64), chunks), dim3(256), 0, st, dy, nullptr, t->a[l], R, C,
-                                   rpc, mean, var, iv, sh, t->part);
-        }
-        check();
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(ct_bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, chunks, C, 1.0 / R,
-                           t->grads + t->o_g[l], t->grads + t->o_be[l], t->m1 + o, t->m2 + o);
-        check();
-        if (err != hipSuccess) return;
-        const size_t total = (size_t)R * C;
-        const dim3 grid((unsigned)((total + 255) / 256));
-        const float *gam = t->params + t->o_g[l];
-        if (mode == 0)
-            hipLaunchKernelGGL(ct_bn_bwd_apply_kernel<0>, grid, dim3(256), 0, st, dy, nullptr, nullptr, t->a[l], R, t->n, C, mean, var, gam,
-                               iv, sh, t->m1 + o, t->m2 + o, da);
+        const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o, *gam = t->params + t->o_g[l];
+        const int rpc = rpc_of(R), chunks = mode == 2 ? 1 : cdiv(R, rpc);
+        const dim3 rows_grid(cdiv(C, 64), chunks), flat(blocks_of((size_t)R * C));
+        if (mode == 2)
+            launch(ct_bn_bwd_pool_part_kernel, dim3(cdiv(C, 256)), dim3(256), dy, t->arg[aux], t->a[l], t->B, t->n, C, mean, var, iv, sh, t->part);
         else if (mode == 1)
-            hipLaunchKernelGGL(ct_bn_bwd_apply_kernel<1>, grid, dim3(256), 0, st, dy, t->mask[aux], nullptr, t->a[l], R, t->n, C, mean, var,
-                               gam, iv, sh, t->m1 + o, t->m2 + o, da);
+            launch(ct_bn_bwd_part_kernel<true>, rows_grid, dim3(256), dy, t->mask[aux], t->a[l], R, C, rpc, mean, var, iv, sh, t->part);
         else
-            hipLaunchKernelGGL(ct_bn_bwd_apply_kernel<2>, grid, dim3(256), 0, st, dy, nullptr, t->arg[aux], t->a[l], R, t->n, C, mean, var,
-                               gam, iv, sh, t->m1 + o, t->m2 + o, da);
-        check();
+            launch(ct_bn_bwd_part_kernel<false>, rows_grid, dim3(256), dy, nullptr, t->a[l], R, C, rpc, mean, var, iv, sh, t->part);
+        launch(tb_bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), t->part, chunks, C, 1, 1.0 / R, t->grads + t->o_g[l], t->grads + t->o_be[l],
+               t->m1 + o, t->m2 + o);
+        if (mode == 0)
+            launch(ct_bn_bwd_apply_kernel<0>, flat, dim3(256), dy, nullptr, nullptr, t->a[l], R, t->n, C, mean, var, gam, iv, sh, t->m1 + o,
+                   t->m2 + o, da);
+        else if (mode == 1)
+            launch(ct_bn_bwd_apply_kernel<1>, flat, dim3(256), dy, t->mask[aux], nullptr, t->a[l], R, t->n, C, mean, var, gam, iv, sh, t->m1 + o,
+                   t->m2 + o, da);
+        else
+            launch(ct_bn_bwd_apply_kernel<2>, flat, dim3(256), dy, nullptr, t->arg[aux], t->a[l], R, t->n, C, mean, var, gam, iv, sh, t->m1 + o,
+                   t->m2 + o, da);
     }
     // dW_l = in^T da, db_l = sum da, din (=|+=) da W_l^T
     void linear_bwd(int l, const float *in, const float *da, float *din, int accumulate) {
@@ -432,15 +365,11 @@ struct Run {
             gemm(d);
         }
     }
-    void launch_1d(void (*k)(float *, int, int), float *p, int B, int kk) {
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(k, dim3(cdiv(B * kk, 256)), dim3(256), 0, st, p, B, kk);
-        check();
-    }
+    void add_eye(float *p, int kk) { launch(ct_add_eye_kernel, dim3(cdiv(t->B * kk, 256)), dim3(256), p, t->B, kk); }
 };
 
 int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipStream_t st) {
-    Run q{t, st};
+    Run q{{st}, t};
     const int B = t->B, n = t->n, R = t->R, NC = t->C;
     // ---- forward ----
     q.layer(T1C1, x);
@@ -449,7 +378,7 @@ int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipSt
     q.layer(T1F1, t->pooled[0]);
     q.layer(T1F2, t->h[T1F1]);
     q.linear_fwd(T1XYZ, t->h[T1F2], t->t1);
-    q.launch_1d(ct_add_eye_kernel, t->t1, B, 3);
+    q.add_eye(t->t1, 3);
     {   // u = x T1 per cloud
         GemmArgs g = Run::plain(x, t->t1, t->u, n, 3, 3);
         g.sAz = (long long)n * 3; g.sBz = 9; g.sCz = (long long)n * 3; g.batch = B;
@@ -463,7 +392,7 @@ int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipSt
     q.layer(T2F1, t->pooled[1]);
     q.layer(T2F2, t->h[T2F1]);
     q.linear_fwd(T2FEAT, t->h[T2F2], t->t2);
-    q.launch_1d(ct_add_eye_kernel, t->t2, B, 64);
+    q.add_eye(t->t2, 64);
     {   // v = h2 T2 per cloud
         GemmArgs g = Run::plain(t->h[C2], t->t2, t->v, n, 64, 64);
         g.sAz = (long long)n * 64; g.sBz = 4096; g.sCz = (long long)n * 64; g.batch = B;
@@ -483,12 +412,8 @@ int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipSt
         g.alpha = 1.f; g.M = 64; g.N = 64; g.K = 64; g.batch = B;
         q.gemm(g);
     }
-    if (q.err == hipSuccess) { hipLaunchKernelGGL(ct_reg_kernel, dim3(B), dim3(256), 0, st, t->E, B, t->reg_cloud); q.check(); }
-    if (q.err == hipSuccess) {
-        hipLaunchKernelGGL(ct_loss_kernel, dim3(1), dim3(1024), 0, st, t->logits, labels_dev, B, NC, t->reg_cloud, t->dlogits, t->pred,
-                           t->loss, t->ce_cloud);
-        q.check();
-    }
+    q.launch(ct_reg_kernel, dim3(B), dim3(256), t->E, B, t->reg_cloud);
+    q.launch(ct_loss_kernel, dim3(1), dim3(1024), t->logits, labels_dev, B, NC, t->reg_cloud, t->dlogits, t->pred, t->loss, t->ce_cloud);
     // ---- backward ----
     q.linear_bwd(F3, t->h[F2], t->dlogits, t->dsmall1, 0);                 // d h_F2 [B][256]
     q.bn_bwd(F2, 1, t->dsmall1, 1, t->dsmall2);
@@ -554,7 +479,7 @@ int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipSt
     q.bn_bwd(T1C1, 0, t->dB, 0, t->da);
     q.linear_bwd(T1C1, x, t->da, nullptr, 0);
     (void)R;
-    if (q.err != hipSuccess) {
+    if (!q.ok()) {
         set_error("cls_trainer_step: %s", hipGetErrorString(q.err));
         return GEOADV_EHIP;
     }
@@ -562,13 +487,13 @@ int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipSt
     const double e = floor((double)t->step * B / (double)t->decay_step);
     const float lr = (float)std::max((double)t->base_lr * pow((double)t->decay_rate, e), 1e-5);
     const float bn_decay = (float)std::min(0.99, 1.0 - 0.5 * pow(0.5, e));
-    const unsigned pg = (unsigned)((t->P + 255) / 256);
+    const unsigned pg = blocks_of(t->P);
     if (t->optimizer == GEOADV_CLS_OPT_ADAM)
         hipLaunchKernelGGL(ct_adam_kernel, dim3(pg), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, lr, t->b1p, t->b2p);
     else
         hipLaunchKernelGGL(ct_momentum_kernel, dim3(pg), dim3(256), 0, st, t->params, t->slot1, t->grads, t->P, lr, t->momentum);
     GA_LAUNCH_CHECK();
-    const unsigned mg = (unsigned)((t->MV + 255) / 256);
+    const unsigned mg = blocks_of(t->MV);
     hipLaunchKernelGGL(ct_ema_kernel, dim3(mg), dim3(256), 0, st, t->mov_mean, t->bat_mean, t->MV, 1.f - bn_decay);
     GA_LAUNCH_CHECK();
     hipLaunchKernelGGL(ct_ema_kernel, dim3(mg), dim3(256), 0, st, t->mov_var, t->bat_var, t->MV, 1.f - bn_decay);
@@ -616,29 +541,30 @@ extern "C" int geoadv_cls_trainer_create(geoadv_cls_trainer **out, const geoadv_
     t->P = P; t->MV = MV;
     const size_t R = t->R, B = t->B;
     hipError_t e = hipSuccess;
-    t->params = dev_alloc<float>(t, P, e); t->grads = dev_alloc<float>(t, P, e);
-    t->slot1 = dev_alloc<float>(t, P, e); t->slot2 = dev_alloc<float>(t, P, e);
-    for (float **p : {&t->mov_mean, &t->mov_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2}) *p = dev_alloc<float>(t, MV, e);
+    std::vector<void *> &mem = t->allocs;
+    t->params = dev_alloc<float>(mem, P, e); t->grads = dev_alloc<float>(mem, P, e);
+    t->slot1 = dev_alloc<float>(mem, P, e); t->slot2 = dev_alloc<float>(mem, P, e);
+    for (float **p : {&t->mov_mean, &t->mov_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2}) *p = dev_alloc<float>(mem, MV, e);
     for (int l = 0; l < NL; ++l) {
         t->a[l] = t->h[l] = nullptr;
         if (!bn_of(l)) continue;
-        t->a[l] = dev_alloc<float>(t, (per_point(l) ? R : B) * t->out[l], e);
-        if (!pooled_layer(l)) t->h[l] = dev_alloc<float>(t, (per_point(l) ? R : B) * t->out[l], e);
+        t->a[l] = dev_alloc<float>(mem, (per_point(l) ? R : B) * t->out[l], e);
+        if (!pooled_layer(l)) t->h[l] = dev_alloc<float>(mem, (per_point(l) ? R : B) * t->out[l], e);
     }
-    t->u = dev_alloc<float>(t, R * 3, e); t->v = dev_alloc<float>(t, R * 64, e);
-    t->t1 = dev_alloc<float>(t, B * 9, e); t->t2 = dev_alloc<float>(t, B * 4096, e); t->E = dev_alloc<float>(t, B * 4096, e);
-    for (int i = 0; i < 3; ++i) { t->pooled[i] = dev_alloc<float>(t, B * 1024, e); t->arg[i] = dev_alloc<int>(t, B * 1024, e); }
-    t->mask[0] = dev_alloc<float>(t, B * 512, e); t->mask[1] = dev_alloc<float>(t, B * 256, e);
-    t->logits = dev_alloc<float>(t, B * NC, e); t->dlogits = dev_alloc<float>(t, B * NC, e); t->loss = dev_alloc<float>(t, 1, e);
-    t->labels = dev_alloc<int>(t, B, e); t->pred = dev_alloc<int>(t, B, e);
-    t->da = dev_alloc<float>(t, R * 1024, e); t->dA = dev_alloc<float>(t, R * 128, e);
-    t->dB = dev_alloc<float>(t, R * 64, e); t->dC = dev_alloc<float>(t, R * 64, e);
-    t->dsmall1 = dev_alloc<float>(t, B * 4096, e); t->dsmall2 = dev_alloc<float>(t, B * 4096, e);
-    t->du = dev_alloc<float>(t, R * 3, e); t->dv = dev_alloc<float>(t, R * 64, e);
-    t->dT1 = dev_alloc<float>(t, B * 9, e); t->dT2 = dev_alloc<float>(t, B * 4096, e);
-    t->partials = dev_alloc<float>(t, CT_PARTIAL_FLOATS, e);
-    t->part = dev_alloc<double2>(t, std::max((size_t)cdiv((int)R, 256) * 1024, (size_t)cdiv((int)B, 256) * 4096) + 1024, e);
-    t->reg_cloud = dev_alloc<double>(t, B, e); t->ce_cloud = dev_alloc<double>(t, B, e);
+    t->u = dev_alloc<float>(mem, R * 3, e); t->v = dev_alloc<float>(mem, R * 64, e);
+    t->t1 = dev_alloc<float>(mem, B * 9, e); t->t2 = dev_alloc<float>(mem, B * 4096, e); t->E = dev_alloc<float>(mem, B * 4096, e);
+    for (int i = 0; i < 3; ++i) { t->pooled[i] = dev_alloc<float>(mem, B * 1024, e); t->arg[i] = dev_alloc<int>(mem, B * 1024, e); }
+    t->mask[0] = dev_alloc<float>(mem, B * 512, e); t->mask[1] = dev_alloc<float>(mem, B * 256, e);
+    t->logits = dev_alloc<float>(mem, B * NC, e); t->dlogits = dev_alloc<float>(mem, B * NC, e); t->loss = dev_alloc<float>(mem, 1, e);
+    t->labels = dev_alloc<int>(mem, B, e); t->pred = dev_alloc<int>(mem, B, e);
+    t->da = dev_alloc<float>(mem, R * 1024, e); t->dA = dev_alloc<float>(mem, R * 128, e);
+    t->dB = dev_alloc<float>(mem, R * 64, e); t->dC = dev_alloc<float>(mem, R * 64, e);
+    t->dsmall1 = dev_alloc<float>(mem, B * 4096, e); t->dsmall2 = dev_alloc<float>(mem, B * 4096, e);
+    t->du = dev_alloc<float>(mem, R * 3, e); t->dv = dev_alloc<float>(mem, R * 64, e);
+    t->dT1 = dev_alloc<float>(mem, B * 9, e); t->dT2 = dev_alloc<float>(mem, B * 4096, e);
+    t->partials = dev_alloc<float>(mem, CT_PARTIAL_FLOATS, e);
+    t->part = dev_alloc<double2>(mem, std::max((size_t)cdiv((int)R, 256) * 1024, (size_t)cdiv((int)B, 256) * 4096) + 1024, e);
+    t->reg_cloud = dev_alloc<double>(mem, B, e); t->ce_cloud = dev_alloc<double>(mem, B, e);
     if (e == hipSuccess) {
         std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f);
         for (int l = 0; l < NL; ++l) {
@@ -655,7 +581,7 @@ extern "C" int geoadv_cls_trainer_create(geoadv_cls_trainer **out, const geoadv_
         if (e == hipSuccess) e = hipMemcpy(t->mov_var, hv.data(), sizeof(float) * MV, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
-        for (void *p : t->allocs) (void)hipFree(p);
+        dev_free_all(t->allocs);
         delete t;
         set_error("cls_trainer_create: %s", hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
@@ -666,7 +592,7 @@ extern "C" int geoadv_cls_trainer_create(geoadv_cls_trainer **out, const geoadv_
 
 extern "C" void geoadv_cls_trainer_destroy(geoadv_cls_trainer *t) {
     if (!t) return;
-    for (void *p : t->allocs) (void)hipFree(p);
+    dev_free_all(t->allocs);
     delete t;
 }
 

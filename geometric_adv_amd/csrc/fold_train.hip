@@ -9,11 +9,10 @@
 // and the picks of both pools come from foldingnet.hip's kernels (fold_graph.h), the Chamfer scan and its gradient from
 // geoadv_nn_distance / geoadv_nn_distance_grad.
 //
-// FORM: the direct one, as cls_train.hip.  STORED for the backward: the pre-BN activation of every BN layer, the post-ReLU
-// outputs of conv1..conv4 and of the four hidden decoder layers, both pools' outputs and winners, the global maximum's rows.
-// RECOMPUTED: every ReLU mask of a BN layer (a * inv + shift > 0, the forward's expression bit for bit) and xhat.
-// GEMMs on v_mfma_f32_32x32x2_f32 with fixed-order split-K (train_tile.h), batch statistics as per-chunk double partials
-// added in a fixed order, no float atomics anywhere: two steps from the same state are bitwise identical.
+// FORM: the direct one, as cls_train.hip, on the GEMM of train_tile.h and the batch-norm, global-max, loss, Adam and
+// running-statistics kernels of train_bn.h (what is stored, what is recomputed and why the fc layer's backward is in double:
+// there).  STORED besides: the post-ReLU outputs of conv1..conv4 and of the four hidden decoder layers, both pools' outputs
+// and winners.  Two steps from the same state are bitwise identical.
 //
 // Decoder: the 512 code rows of each fold's first layer act once per cloud, s = code . W[0:512] + b; per grid point only the
 // 2 (grid) or 3 (mid) point rows are added.  Backward, d s = the column sums of d pre over the cloud's 2025 points, then
@@ -30,7 +29,7 @@
 //
 // Adam (torch.optim.Adam, lr, betas .9 / .999, eps 1e-8, weight_decay): g += wd * p on EVERY parameter; m += (g - m) * 0.1;
 // v = 0.999 v + 0.001 g g; p -= lr / (1 - 0.9^t) * m / (sqrt(v) / sqrt(1 - 0.999^t) + eps), t = steps taken including this.
-#include "train_tile.h"
+#include "train_bn.h"
 #include "fold_graph.h"
 #include <math.h>
 #include <string.h>
@@ -41,36 +40,12 @@ namespace geoadv {
 constexpr float FT_EPS = 1e-5f;
 constexpr int FT_NB = 16, FT_GRID = 45, FT_G2 = FT_GRID * FT_GRID, FT_CODE = 512, FT_LAT = 1024;
 
-__device__ __forceinline__ float ft_pre(float a, float inv, float shift) { return a * inv + shift; }
-
 // in[r][0:3] = xyz, in[r][3:12] = cov
 __global__ __launch_bounds__(256) void ft_input_kernel(const float *x, const float *cov, int R, float *in) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= R * 12) return;
     const int r = e / 12, k = e - 12 * r;
     in[e] = k < 3 ? x[(size_t)r * 3 + k] : cov[(size_t)r * 9 + k - 3];
-}
-
-// Batch statistics from the partials: mean, biased variance, folded constants.  One thread per column.
-__global__ __launch_bounds__(256) void ft_bn_stats_kernel(const double2 *part, int chunks, int C, double inv_rows, const float *gamma,
-                                                          const float *beta, float *mean, float *var, float *inv, float *shift) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < chunks; ++k) { s += part[(size_t)k * C + c].x; q += part[(size_t)k * C + c].y; }
-    const double m = s * inv_rows;
-    double v = q * inv_rows - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mf = (float)m, vf = (float)v;
-    const float iv = gamma[c] * (1.0f / sqrtf(vf + FT_EPS));
-    mean[c] = mf; var[c] = vf; inv[c] = iv; shift[c] = beta[c] - mf * iv;
-}
-
-__global__ __launch_bounds__(256) void ft_bn_relu_kernel(const float *a, size_t total, int C, const float *inv, const float *shift, float *y) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c = (int)(e % C);
-    y[e] = fmaxf(ft_pre(a[e], inv[c], shift[c]), 0.f);
 }
 
 // Graph pool + ReLU of h [B n][C]: g = relu(max(h_i, h over the 16 columns)); win = the row (in the cloud) that attained a
@@ -95,36 +70,6 @@ __global__ __launch_bounds__(256) void ft_graph_pool_kernel(const float *h, cons
     win[e] = pos ? w : -1;
 }
 
-// Max over the n rows of each cloud of a * inv + shift (no ReLU): the maximum and its FIRST row.  grid (ceil(C / 64), B).
-__global__ __launch_bounds__(256) void ft_gmax_kernel(const float *a, int n, int C, const float *inv, const float *shift, float *pooled,
-                                                      int *arg) {
-    __shared__ float mv[4][64];
-    __shared__ int mi[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6, b = blockIdx.y;
-    float best = -INFINITY;
-    int bi = 0;
-    if (c < C) {
-        const float iv = inv[c], sh = shift[c];
-        if (ph < n) best = ft_pre(a[((size_t)b * n + ph) * C + c], iv, sh), bi = ph;
-        for (int r = ph + 4; r < n; r += 4) {
-            const float v = ft_pre(a[((size_t)b * n + r) * C + c], iv, sh);
-            if (v > best) { best = v; bi = r; }
-        }
-    }
-    mv[ph][threadIdx.x & 63] = best;
-    mi[ph][threadIdx.x & 63] = bi;
-    __syncthreads();
-    if (ph == 0 && c < C) {
-        for (int p = 1; p < 4 && p < n; ++p) {
-            const float v = mv[p][threadIdx.x];
-            const int i = mi[p][threadIdx.x];
-            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-        }
-        pooled[(size_t)b * C + c] = best;
-        arg[(size_t)b * C + c] = bi;
-    }
-}
-
 // A fold's first layer: H[r][k] = relu(s[cloud(r)][k] + sum_d pts[r][d] * wp[d][k]), D = 2 (the grid) or 3 (mid)
 template <int D>
 __global__ __launch_bounds__(256) void ft_fold_l1_kernel(const float *s, const float *pts, const float *wp, size_t total, float *H) {
@@ -147,117 +92,6 @@ __global__ __launch_bounds__(256) void ft_relu_kernel(float *y, size_t total) {
 __global__ __launch_bounds__(256) void ft_mask_kernel(float *d, const float *H, size_t total) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e < total) d[e] = H[e] > 0.f ? d[e] : 0.f;
-}
-
-// out = sum d1 / (B n) + sum d2 / (B m): one block, strided double sums added in a fixed order
-__global__ __launch_bounds__(256) void ft_loss_kernel(const float *d1, size_t c1, const float *d2, size_t c2, float *out) {
-    __shared__ double r1[256], r2[256];
-    double s = 0.0, q = 0.0;
-    for (size_t e = threadIdx.x; e < c1; e += 256) s += (double)d1[e];
-    for (size_t e = threadIdx.x; e < c2; e += 256) q += (double)d2[e];
-    r1[threadIdx.x] = s; r2[threadIdx.x] = q;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0;
-        for (int i = 0; i < 256; ++i) { a += r1[i]; b += r2[i]; }
-        out[0] = (float)(a / (double)c1 + b / (double)c2);
-    }
-}
-
-// BN backward of a ReLU layer, dense dy:  g = dy * [a * inv + shift > 0].  Pass 1: (sum g, sum g * xhat) per chunk.
-__global__ __launch_bounds__(256) void ft_bn_bwd_part_kernel(const float *dy, const float *a, int R, int C, int rows_per_chunk,
-                                                             const float *mean, const float *var, const float *inv, const float *shift,
-                                                             double2 *part) {
-    __shared__ double2 red[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
-    const int r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    double s = 0.0, q = 0.0;
-    if (c < C) {
-        const float rs = 1.0f / sqrtf(var[c] + FT_EPS), m = mean[c], iv = inv[c], sh = shift[c];
-        for (int r = r0 + ph; r < r1; r += 4) {
-            const size_t e = (size_t)r * C + c;
-            const float av = a[e];
-            const float gv = ft_pre(av, iv, sh) > 0.f ? dy[e] : 0.f;
-            s += (double)gv;
-            q += (double)gv * (double)((av - m) * rs);
-        }
-    }
-    red[ph][threadIdx.x & 63] = make_double2(s, q);
-    __syncthreads();
-    if (ph == 0 && c < C) {
-        double2 o = red[0][threadIdx.x];
-        for (int p = 1; p < 4; ++p) { o.x += red[p][threadIdx.x].x; o.y += red[p][threadIdx.x].y; }
-        part[(size_t)blockIdx.y * C + c] = o;
-    }
-}
-
-// Pass 1 of conv5's BN (no ReLU), whose g is dpool at the maximum's row of each (cloud, channel): clouds in ascending order.
-__global__ __launch_bounds__(256) void ft_bn_bwd_gmax_part_kernel(const float *dpool, const int *arg, const float *a, int B, int n, int C,
-                                                                  const float *mean, const float *var, double2 *part) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const float rs = 1.0f / sqrtf(var[c] + FT_EPS), m = mean[c];
-    double s = 0.0, q = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const float av = a[((size_t)b * n + arg[(size_t)b * C + c]) * C + c];
-        const float gv = dpool[(size_t)b * C + c];
-        s += (double)gv;
-        q += (double)gv * (double)((av - m) * rs);
-    }
-    part[c] = make_double2(s, q);
-}
-
-// Pass 3: da = gamma * rs * (g - m1 - xhat * m2).  GMAX false: dense dy through the ReLU; true: dpool at the maximum's row.
-template <bool GMAX>
-__global__ __launch_bounds__(256) void ft_bn_bwd_apply_kernel(const float *dy, const int *arg, const float *a, size_t total, int n, int C,
-                                                              const float *mean, const float *var, const float *gamma, const float *inv,
-                                                              const float *shift, const float *m1, const float *m2, float *da) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c = (int)(e % C);
-    const size_t r = e / C;
-    const float av = a[e];
-    float gv = 0.f;
-    if (GMAX) {
-        const size_t b = r / n;
-        if (arg[b * C + c] == (int)(r - b * n)) gv = dy[b * C + c];
-    } else if (ft_pre(av, inv[c], shift[c]) > 0.f) {
-        gv = dy[e];
-    }
-    const float rs = 1.0f / sqrtf(var[c] + FT_EPS);
-    const float xh = (av - mean[c]) * rs;
-    da[e] = gamma[c] * rs * (gv - m1[c] - xh * m2[c]);
-}
-
-// BN backward of an fc layer (rows = the batch's clouds, a few to a few hundred), one thread per column, all in double
-// from the stored activation: with few rows g - mean(g) - xhat mean(g xhat) cancels almost completely (two rows: all but
-// eps / (var + eps) of it), and xhat rounded to fp32 would decide what is left.  The ReLU mask is the forward's fp32 test.
-__global__ __launch_bounds__(256) void ft_bn_bwd_fc_kernel(const float *dy, const float *a, int R, int C, const float *gamma,
-                                                           const float *inv, const float *shift, float *dgamma, float *dbeta,
-                                                           float *da) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double m = 0.0, v = 0.0;
-    for (int r = 0; r < R; ++r) m += (double)a[(size_t)r * C + c];
-    m /= R;
-    for (int r = 0; r < R; ++r) { const double d = (double)a[(size_t)r * C + c] - m; v += d * d; }
-    v /= R;
-    const double rs = 1.0 / sqrt(v + (double)FT_EPS);
-    const float iv = inv[c], sh = shift[c];
-    double s = 0.0, q = 0.0;
-    for (int r = 0; r < R; ++r) {
-        const size_t e = (size_t)r * C + c;
-        const double gv = ft_pre(a[e], iv, sh) > 0.f ? (double)dy[e] : 0.0;
-        s += gv;
-        q += gv * (((double)a[e] - m) * rs);
-    }
-    dbeta[c] = (float)s; dgamma[c] = (float)q;
-    const double m1 = s / R, m2 = q / R, gr = (double)gamma[c] * rs;
-    for (int r = 0; r < R; ++r) {
-        const size_t e = (size_t)r * C + c;
-        const double gv = ft_pre(a[e], iv, sh) > 0.f ? (double)dy[e] : 0.0;
-        da[e] = (float)(gr * (gv - m1 - ((double)a[e] - m) * rs * m2));
-    }
 }
 
 // Pool backward, gathered by destination: dh[j][c] = [win[j][c] == j] dg[j][c] + sum over i != j in j's sorted adjacency row,
@@ -286,26 +120,6 @@ __global__ __launch_bounds__(256) void ft_pool_bwd_kernel(const float *dg, const
 __global__ __launch_bounds__(256) void ft_part_rows_kernel(const double2 *part, int count, float *out) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < count) out[e] = (float)part[e].x;
-}
-
-// torch.optim.Adam with weight decay; bc1 = 1 - beta1^t, bc2s = sqrt(1 - beta2^t)
-__global__ __launch_bounds__(256) void ft_adam_kernel(float *p, float *m, float *v, const float *g, size_t count, float lr, float wd, float bc1, float bc2s) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= count) return;
-    const float gv = g[e] + wd * p[e];
-    const float mn = m[e] + (gv - m[e]) * (1.f - 0.9f);
-    const float vn = v[e] * 0.999f + (gv * gv) * (1.f - 0.999f);
-    m[e] = mn; v[e] = vn;
-    const float denom = sqrtf(vn) / bc2s + 1e-8f;
-    p[e] = p[e] - (lr / bc1) * (mn / denom);
-}
-
-// running = 0.9 running + 0.1 stat * scale (scale = rows / (rows - 1) for the variance, 1 for the mean)
-__global__ __launch_bounds__(256) void ft_running_kernel(float *running, const float *stat, const float *scale, size_t count) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= count) return;
-    const float s = scale ? stat[e] * scale[e] : stat[e];
-    running[e] = running[e] * (1.f - 0.1f) + 0.1f * s;
 }
 
 }  // namespace geoadv
@@ -340,22 +154,10 @@ struct geoadv_fold_trainer {
 };
 
 namespace {
-template <class T> T *dev_alloc(geoadv_fold_trainer *t, size_t count, hipError_t &err) {
-    void *p = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T) + 16);
-    if (err == hipSuccess) { t->allocs.push_back(p); err = hipMemset(p, 0, count * sizeof(T) + 16); }
-    return static_cast<T *>(p);
-}
-
-inline unsigned blocks_of(size_t total) { return (unsigned)((total + 255) / 256); }
-
-struct Run {
+struct Run : Launch {
     geoadv_fold_trainer *t;
-    hipStream_t st;
-    hipError_t err = hipSuccess;
 
-    void check() { if (err == hipSuccess) err = hipGetLastError(); }
-    void gemm(GemmArgs g) { if (err == hipSuccess) err = ct_launch_gemm(g, t->partials, st); }
+    void gemm(const GemmArgs &g) { Launch::gemm(g, t->partials); }
     float *W(int l) { return t->params + t->o_w[l]; }
     int rows(int l) const { return l <= E5 ? t->R : l <= F2 ? t->B : t->rows; }
 
@@ -370,28 +172,15 @@ struct Run {
         g.alpha = 1.f; g.M = M; g.N = N; g.K = K; g.batch = 1;
         gemm(g);
     }
-    void colsum(int mode, const float *a, int R, int C, int rpc) {
-        if (err != hipSuccess) return;
-        const dim3 grid(cdiv(C, 64), cdiv(R, rpc));
-        if (mode == 0) hipLaunchKernelGGL(ct_colsum_kernel<0>, grid, dim3(256), 0, st, a, R, C, rpc, t->part);
-        else hipLaunchKernelGGL(ct_colsum_kernel<1>, grid, dim3(256), 0, st, a, R, C, rpc, t->part);
-        check();
-    }
-    static int rpc_of(int R) { return std::max(1, std::min(R, 256)); }
     void batch_stats(int l) {
-        const int R = rows(l), C = kOut[l], rpc = rpc_of(R);
-        colsum(0, t->a[l], R, C, rpc);
-        if (err != hipSuccess) return;
         const size_t o = t->o_mv[l];
-        hipLaunchKernelGGL(ft_bn_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, cdiv(R, rpc), C, 1.0 / R,
-                           t->params + t->o_g[l], t->params + t->o_be[l], t->bat_mean + o, t->bat_var + o, t->inv + o, t->shift + o);
-        check();
+        bn_batch_stats(t->a[l], rows(l), kOut[l], 1, t->part, t->params + t->o_g[l], t->params + t->o_be[l], FT_EPS, t->bat_mean + o,
+                       t->bat_var + o, t->inv + o, t->shift + o);
     }
     void bn_relu(int l, float *y) {
-        if (err != hipSuccess) return;
         const size_t total = (size_t)rows(l) * kOut[l], o = t->o_mv[l];
-        hipLaunchKernelGGL(ft_bn_relu_kernel, dim3(blocks_of(total)), dim3(256), 0, st, t->a[l], total, kOut[l], t->inv + o, t->shift + o, y);
-        check();
+        launch(tb_bn_relu_kernel<false>, dim3(blocks_of(total)), dim3(256), t->a[l], nullptr, total, rows(l), kOut[l], 0, t->inv + o,
+               t->shift + o, y);
     }
     void bn_layer(int l, const float *in, float *y) {
         linear_fwd(l, in, t->a[l], rows(l), 0, kIn[l], true);
@@ -399,40 +188,25 @@ struct Run {
         if (y) bn_relu(l, y);
     }
     void graph_pool(const float *h, int which, int C, float *g, int *win) {
-        if (err != hipSuccess) return;
         const size_t total = (size_t)t->R * C;
-        hipLaunchKernelGGL(ft_graph_pool_kernel, dim3(blocks_of(total)), dim3(256), 0, st, h, t->graph.cols + (size_t)which * t->R * FT_NB,
-                           t->n, C, total, g, win);
-        check();
+        launch(ft_graph_pool_kernel, dim3(blocks_of(total)), dim3(256), h, t->graph.cols + (size_t)which * t->R * FT_NB, t->n, C, total, g, win);
     }
-    void relu(float *y, size_t total) {
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(ft_relu_kernel, dim3(blocks_of(total)), dim3(256), 0, st, y, total);
-        check();
-    }
-    void mask(float *d, const float *H, size_t total) {
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(ft_mask_kernel, dim3(blocks_of(total)), dim3(256), 0, st, d, H, total);
-        check();
-    }
+    void relu(float *y, size_t total) { launch(ft_relu_kernel, dim3(blocks_of(total)), dim3(256), y, total); }
+    void mask(float *d, const float *H, size_t total) { launch(ft_mask_kernel, dim3(blocks_of(total)), dim3(256), d, H, total); }
     // one fold forward: l0 = its first layer, pts [rows][D] the grid or mid, H1 / H2 its hidden outputs, out [rows][3]
     void fold_fwd(int l0, const float *pts, int D, float *H1, float *H2, float *out) {
         linear_fwd(l0, t->code, t->s, t->B, 0, FT_CODE, true);
-        if (err != hipSuccess) return;
         const size_t total = (size_t)t->rows * 512;
         const float *wp = W(l0) + (size_t)FT_CODE * 512;
-        if (D == 2) hipLaunchKernelGGL(ft_fold_l1_kernel<2>, dim3(blocks_of(total)), dim3(256), 0, st, t->s, pts, wp, total, H1);
-        else hipLaunchKernelGGL(ft_fold_l1_kernel<3>, dim3(blocks_of(total)), dim3(256), 0, st, t->s, pts, wp, total, H1);
-        check();
+        launch(D == 2 ? ft_fold_l1_kernel<2> : ft_fold_l1_kernel<3>, dim3(blocks_of(total)), dim3(256), t->s, pts, wp, total, H1);
         linear_fwd(l0 + 1, H1, H2, t->rows, 0, 512, true);
         relu(H2, total);
         linear_fwd(l0 + 2, H2, out, t->rows, 0, 512, true);
     }
     int chamfer(const float *x, const float *pc, float *out) {
-        if (err != hipSuccess) return GEOADV_EHIP;
+        if (!ok()) return GEOADV_EHIP;
         if (int rc = geoadv_nn_distance(t->B, t->n, x, FT_G2, pc, t->d1, t->i1, t->d2, t->i2, st)) return rc;
-        hipLaunchKernelGGL(ft_loss_kernel, dim3(1), dim3(256), 0, st, t->d1, (size_t)t->R, t->d2, (size_t)t->rows, out);
-        check();
+        launch(tb_loss_kernel, dim3(1), dim3(256), t->d1, (size_t)t->R, t->d2, (size_t)t->rows, out);
         return GEOADV_OK;
     }
 
@@ -447,13 +221,7 @@ struct Run {
         g.alpha = 1.f; g.M = K; g.N = N; g.K = M; g.batch = 1;
         gemm(g);
     }
-    void bias_grad(int l, const float *da, int M) {
-        const int C = kOut[l], rpc = rpc_of(M);
-        colsum(1, da, M, C, rpc);
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(ct_colsum_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, cdiv(M, rpc), C, t->grads + t->o_b[l]);
-        check();
-    }
+    void bias_grad(int l, const float *da, int M) { bias_colsum(da, M, kOut[l], 1, t->part, t->grads + t->o_b[l]); }
     // din (=|+=) da W_l[k0 : k0 + K]^T
     void input_grad(int l, const float *da, float *din, int M, int k0, int K, int accumulate) {
         const int N = kOut[l];
@@ -471,48 +239,31 @@ struct Run {
     }
     // BN backward of layer l; gmax: dy = dpool [B][C] at the maximum's rows (conv5), else dense dy through the ReLU
     void bn_bwd(int l, bool gmax, const float *dy, float *da) {
-        if (err != hipSuccess) return;
         const int R = rows(l), C = kOut[l];
-        const size_t o = t->o_mv[l];
-        const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o;
+        const size_t o = t->o_mv[l], total = (size_t)R * C;
+        const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o, *gam = t->params + t->o_g[l];
+        float *dgam = t->grads + t->o_g[l], *dbeta = t->grads + t->o_be[l];
         if (l == F1) {
-            hipLaunchKernelGGL(ft_bn_bwd_fc_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, dy, t->a[l], R, C, t->params + t->o_g[l], iv, sh,
-                               t->grads + t->o_g[l], t->grads + t->o_be[l], da);
-            check();
+            launch(tb_bn_bwd_fc_kernel, dim3(cdiv(C, 256)), dim3(256), dy, t->a[l], R, C, gam, iv, sh, FT_EPS, dgam, dbeta, da);
             return;
         }
-        int chunks = 1;
-        if (gmax) {
-            hipLaunchKernelGGL(ft_bn_bwd_gmax_part_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, dy, t->arg, t->a[l], t->B, t->n, C, mean, var,
-                               t->part);
-        } else {
-            const int rpc = rpc_of(R);
-            chunks = cdiv(R, rpc);
-            hipLaunchKernelGGL(ft_bn_bwd_part_kernel, dim3(cdiv(C, 64), chunks), dim3(256), 0, st, dy, t->a[l], R, C, rpc, mean, var, iv, sh,
-                               t->part);
-        }
-        check();
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(ct_bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, t->part, chunks, C, 1.0 / R, t->grads + t->o_g[l],
-                           t->grads + t->o_be[l], t->m1 + o, t->m2 + o);
-        check();
-        if (err != hipSuccess) return;
-        const size_t total = (size_t)R * C;
-        const float *gam = t->params + t->o_g[l];
+        const int rpc = rpc_of(R), chunks = gmax ? 1 : cdiv(R, rpc);
         if (gmax)
-            hipLaunchKernelGGL(ft_bn_bwd_apply_kernel<true>, dim3(blocks_of(total)), dim3(256), 0, st, dy, t->arg, t->a[l], total, t->n, C, mean,
-                               var, gam, iv, sh, t->m1 + o, t->m2 + o, da);
+            launch(tb_bn_bwd_gmax_part_kernel, dim3(cdiv(C, 256)), dim3(256), dy, t->arg, t->a[l], t->B, t->n, C, mean, var, FT_EPS, t->part);
         else
-            hipLaunchKernelGGL(ft_bn_bwd_apply_kernel<false>, dim3(blocks_of(total)), dim3(256), 0, st, dy, nullptr, t->a[l], total, t->n, C,
-                               mean, var, gam, iv, sh, t->m1 + o, t->m2 + o, da);
-        check();
+            launch(tb_bn_bwd_part_kernel<false>, dim3(cdiv(C, 64), chunks), dim3(256), dy, t->a[l], nullptr, R, C, 0, rpc, mean, var, iv, sh,
+                   FT_EPS, t->part);
+        launch(tb_bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), t->part, chunks, C, 1, 1.0 / R, dgam, dbeta, t->m1 + o, t->m2 + o);
+        if (gmax)
+            launch(tb_bn_bwd_gmax_apply_kernel, dim3(blocks_of(total)), dim3(256), dy, t->arg, t->a[l], total, t->n, C, mean, var, gam,
+                   t->m1 + o, t->m2 + o, FT_EPS, da);
+        else
+            launch(tb_bn_bwd_apply_kernel<false, true>, dim3(blocks_of(total)), dim3(256), dy, t->a[l], nullptr, total, R, C, 0, mean, var, gam,
+                   iv, sh, t->m1 + o, t->m2 + o, FT_EPS, da);
     }
     void pool_bwd(const float *dg, const int *win, int C, float *dh) {
-        if (err != hipSuccess) return;
         const size_t total = (size_t)t->R * C;
-        hipLaunchKernelGGL(ft_pool_bwd_kernel, dim3(blocks_of(total)), dim3(256), 0, st, dg, win, t->graph.off, t->graph.deg, t->graph.col,
-                           t->n, C, total, dh);
-        check();
+        launch(ft_pool_bwd_kernel, dim3(blocks_of(total)), dim3(256), dg, win, t->graph.off, t->graph.deg, t->graph.col, t->n, C, total, dh);
     }
     // one fold backward: dout [rows][3] -> every gradient of layers l0 .. l0 + 2, dcode (=|+=), dpts [rows][D] (or null)
     void fold_bwd(int l0, const float *pts, int D, const float *H1, const float *H2, const float *dout, float *dpts, int acc_code) {
@@ -528,24 +279,19 @@ struct Run {
         mask(t->Z, H1, total);                                           // d pre of the first layer
         weight_grad(l0, pts, t->Z, M, FT_CODE, D);                       // the point rows
         if (dpts) input_grad(l0, t->Z, dpts, M, FT_CODE, D, 0);
-        colsum(1, t->Z, M, 512, FT_G2);                                  // chunk = cloud: d s [B][512]
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(ft_part_rows_kernel, dim3(cdiv(t->B * 512, 256)), dim3(256), 0, st, t->part, t->B * 512, t->ds);
-        check();
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(ct_colsum_final_kernel, dim3(2), dim3(256), 0, st, t->part, t->B, 512, t->grads + t->o_b[l0]);
-        check();
+        colsum<1>(t->Z, M, 512, 1, FT_G2, t->part);                      // chunk = cloud: d s [B][512]
+        launch(ft_part_rows_kernel, dim3(cdiv(t->B * 512, 256)), dim3(256), t->part, t->B * 512, t->ds);
+        launch(tb_colsum_final_kernel, dim3(2), dim3(256), t->part, t->B, 512, 1, t->grads + t->o_b[l0]);
         weight_grad(l0, t->code, t->ds, t->B, 0, FT_CODE);               // the code rows
         input_grad(l0, t->ds, t->dcode, t->B, 0, FT_CODE, acc_code);
     }
 };
 
 int run_step(geoadv_fold_trainer *t, const float *x, hipStream_t st) {
-    Run q{t, st};
+    Run q{{st}, t};
     const int B = t->B, R = t->R;
     // ---- forward ----
-    hipLaunchKernelGGL(ft_input_kernel, dim3(cdiv(R * 12, 256)), dim3(256), 0, st, x, t->graph.cov, R, t->in0);
-    q.check();
+    q.launch(ft_input_kernel, dim3(cdiv(R * 12, 256)), dim3(256), x, t->graph.cov, R, t->in0);
     q.bn_layer(E1, t->in0, t->h[0]);
     q.bn_layer(E2, t->h[0], t->h[1]);
     q.bn_layer(E3, t->h[1], t->h[2]);
@@ -553,19 +299,15 @@ int run_step(geoadv_fold_trainer *t, const float *x, hipStream_t st) {
     q.bn_layer(E4, t->g1, t->h[3]);
     q.graph_pool(t->h[3], 1, 128, t->g2, t->win2);
     q.bn_layer(E5, t->g2, nullptr);
-    if (q.err == hipSuccess) {
-        const size_t o = t->o_mv[E5];
-        hipLaunchKernelGGL(ft_gmax_kernel, dim3(FT_LAT / 64, B), dim3(256), 0, st, t->a[E5], t->n, FT_LAT, t->inv + o, t->shift + o, t->pooled,
-                           t->arg);
-        q.check();
-    }
+    q.launch(tb_gmax_kernel, dim3(FT_LAT / 64, B), dim3(256), t->a[E5], t->n, FT_LAT, t->inv + t->o_mv[E5], t->shift + t->o_mv[E5], t->pooled,
+             t->arg);
     q.bn_layer(F1, t->pooled, t->h6);
     q.linear_fwd(F2, t->h6, t->code, B, 0, FT_CODE, true);
     q.fold_fwd(D0, t->grid, 2, t->H[0], t->H[1], t->mid);
     q.fold_fwd(D3, t->mid, 3, t->H[2], t->H[3], t->recon);
     if (int rc = q.chamfer(x, t->mid, t->mid_loss)) return rc;
     if (int rc = q.chamfer(x, t->recon, t->loss)) return rc;
-    if (q.err == hipSuccess)
+    if (q.ok())
         if (int rc = geoadv_nn_distance_grad(B, t->n, x, FT_G2, t->recon, t->gd1, t->i1, t->gd2, t->i2, t->dx, t->drecon, st)) return rc;
     // ---- backward ----
     q.fold_bwd(D3, t->mid, 3, t->H[2], t->H[3], t->drecon, t->dmid, 0);
@@ -585,19 +327,19 @@ int run_step(geoadv_fold_trainer *t, const float *x, hipStream_t st) {
     q.linear_bwd(E2, t->h[0], t->Z, t->Y);                                // d h1
     q.bn_bwd(E1, false, t->Y, t->Z);
     q.linear_bwd(E1, t->in0, t->Z, nullptr);
-    if (q.err != hipSuccess) {
+    if (!q.ok()) {
         set_error("fold_trainer_step: %s", hipGetErrorString(q.err));
         return GEOADV_EHIP;
     }
     // ---- optimizer, running statistics, counters ----
     const double tt = (double)(t->step + 1);
     const float bc1 = (float)(1.0 - pow(0.9, tt)), bc2s = (float)sqrt(1.0 - pow(0.999, tt));
-    hipLaunchKernelGGL(ft_adam_kernel, dim3(blocks_of(t->P)), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, t->lr, t->wd,
+    hipLaunchKernelGGL(tb_adam_kernel<true>, dim3(blocks_of(t->P)), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, t->lr, t->wd,
                        bc1, bc2s);
     GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ft_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_mean, t->bat_mean, (const float *)nullptr, t->MV);
+    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_mean, t->bat_mean, (const float *)nullptr, t->MV);
     GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ft_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_var, t->bat_var, t->unbias, t->MV);
+    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_var, t->bat_var, t->unbias, t->MV);
     GA_LAUNCH_CHECK();
     t->step += 1;
     return GEOADV_OK;
@@ -639,31 +381,32 @@ extern "C" int geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoad
     t->P = P; t->MV = MV;
     const size_t R = t->R, B = t->B, rows = t->rows;
     hipError_t e = hipSuccess;
-    t->params = dev_alloc<float>(t, P, e); t->grads = dev_alloc<float>(t, P, e);
-    t->slot1 = dev_alloc<float>(t, P, e); t->slot2 = dev_alloc<float>(t, P, e);
+    std::vector<void *> &mem = t->allocs;
+    t->params = dev_alloc<float>(mem, P, e); t->grads = dev_alloc<float>(mem, P, e);
+    t->slot1 = dev_alloc<float>(mem, P, e); t->slot2 = dev_alloc<float>(mem, P, e);
     for (float **p : {&t->run_mean, &t->run_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2, &t->unbias})
-        *p = dev_alloc<float>(t, MV, e);
-    t->in0 = dev_alloc<float>(t, R * 12, e);
-    for (int l = 0; l <= F1; ++l) t->a[l] = dev_alloc<float>(t, (l <= E5 ? R : B) * kOut[l], e);
-    for (int l = 0; l < 4; ++l) t->h[l] = dev_alloc<float>(t, R * kOut[l], e);
-    t->g1 = dev_alloc<float>(t, R * 64, e); t->g2 = dev_alloc<float>(t, R * 128, e);
-    t->win1 = dev_alloc<int>(t, R * 64, e); t->win2 = dev_alloc<int>(t, R * 128, e);
-    t->pooled = dev_alloc<float>(t, B * FT_LAT, e); t->arg = dev_alloc<int>(t, B * FT_LAT, e);
-    t->h6 = dev_alloc<float>(t, B * 512, e); t->code = dev_alloc<float>(t, B * 512, e); t->s = dev_alloc<float>(t, B * 512, e);
-    for (int i = 0; i < 4; ++i) t->H[i] = dev_alloc<float>(t, rows * 512, e);
-    t->mid = dev_alloc<float>(t, rows * 3, e); t->recon = dev_alloc<float>(t, rows * 3, e); t->grid = dev_alloc<float>(t, rows * 2, e);
-    t->picks = dev_alloc<int>(t, 2 * R * FT_NB, e);
-    t->d1 = dev_alloc<float>(t, R, e); t->i1 = dev_alloc<int>(t, R, e); t->gd1 = dev_alloc<float>(t, R, e);
-    t->d2 = dev_alloc<float>(t, rows, e); t->i2 = dev_alloc<int>(t, rows, e); t->gd2 = dev_alloc<float>(t, rows, e);
-    t->dx = dev_alloc<float>(t, R * 3, e); t->drecon = dev_alloc<float>(t, rows * 3, e); t->dmid = dev_alloc<float>(t, rows * 3, e);
-    t->loss = dev_alloc<float>(t, 1, e); t->mid_loss = dev_alloc<float>(t, 1, e);
-    t->X = dev_alloc<float>(t, R * FT_LAT, e);
-    t->Y = dev_alloc<float>(t, std::max(R * 128, rows * 512), e); t->Z = dev_alloc<float>(t, std::max(R * 128, rows * 512), e);
-    t->ds = dev_alloc<float>(t, B * 512, e); t->dcode = dev_alloc<float>(t, B * 512, e);
-    t->dsm1 = dev_alloc<float>(t, B * FT_LAT, e); t->dsm2 = dev_alloc<float>(t, B * FT_LAT, e);
-    t->partials = dev_alloc<float>(t, CT_PARTIAL_FLOATS, e);
-    t->part = dev_alloc<double2>(t, std::max((size_t)cdiv((int)R, 256) * FT_LAT, (size_t)cdiv((int)rows, 256) * 512) + 1024, e);
-    t->graph_ws = dev_alloc<char>(t, fold_train_graph_bytes(t->B, t->n), e);
+        *p = dev_alloc<float>(mem, MV, e);
+    t->in0 = dev_alloc<float>(mem, R * 12, e);
+    for (int l = 0; l <= F1; ++l) t->a[l] = dev_alloc<float>(mem, (l <= E5 ? R : B) * kOut[l], e);
+    for (int l = 0; l < 4; ++l) t->h[l] = dev_alloc<float>(mem, R * kOut[l], e);
+    t->g1 = dev_alloc<float>(mem, R * 64, e); t->g2 = dev_alloc<float>(mem, R * 128, e);
+    t->win1 = dev_alloc<int>(mem, R * 64, e); t->win2 = dev_alloc<int>(mem, R * 128, e);
+    t->pooled = dev_alloc<float>(mem, B * FT_LAT, e); t->arg = dev_alloc<int>(mem, B * FT_LAT, e);
+    t->h6 = dev_alloc<float>(mem, B * 512, e); t->code = dev_alloc<float>(mem, B * 512, e); t->s = dev_alloc<float>(mem, B * 512, e);
+    for (int i = 0; i < 4; ++i) t->H[i] = dev_alloc<float>(mem, rows * 512, e);
+    t->mid = dev_alloc<float>(mem, rows * 3, e); t->recon = dev_alloc<float>(mem, rows * 3, e); t->grid = dev_alloc<float>(mem, rows * 2, e);
+    t->picks = dev_alloc<int>(mem, 2 * R * FT_NB, e);
+    t->d1 = dev_alloc<float>(mem, R, e); t->i1 = dev_alloc<int>(mem, R, e); t->gd1 = dev_alloc<float>(mem, R, e);
+    t->d2 = dev_alloc<float>(mem, rows, e); t->i2 = dev_alloc<int>(mem, rows, e); t->gd2 = dev_alloc<float>(mem, rows, e);
+    t->dx = dev_alloc<float>(mem, R * 3, e); t->drecon = dev_alloc<float>(mem, rows * 3, e); t->dmid = dev_alloc<float>(mem, rows * 3, e);
+    t->loss = dev_alloc<float>(mem, 1, e); t->mid_loss = dev_alloc<float>(mem, 1, e);
+    t->X = dev_alloc<float>(mem, R * FT_LAT, e);
+    t->Y = dev_alloc<float>(mem, std::max(R * 128, rows * 512), e); t->Z = dev_alloc<float>(mem, std::max(R * 128, rows * 512), e);
+    t->ds = dev_alloc<float>(mem, B * 512, e); t->dcode = dev_alloc<float>(mem, B * 512, e);
+    t->dsm1 = dev_alloc<float>(mem, B * FT_LAT, e); t->dsm2 = dev_alloc<float>(mem, B * FT_LAT, e);
+    t->partials = dev_alloc<float>(mem, CT_PARTIAL_FLOATS, e);
+    t->part = dev_alloc<double2>(mem, std::max((size_t)cdiv((int)R, 256) * FT_LAT, (size_t)cdiv((int)rows, 256) * 512) + 1024, e);
+    t->graph_ws = dev_alloc<char>(mem, fold_train_graph_bytes(t->B, t->n), e);
     if (e == hipSuccess) {
         std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f), hu(MV, 1.f), hg(rows * 2), g1(R, 1.f / (float)R), g2(rows, 1.f / (float)rows);
         for (int l = 0; l < NL; ++l) {
@@ -689,7 +432,7 @@ extern "C" int geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoad
         up(t->params, hp); up(t->run_mean, hm); up(t->run_var, hv); up(t->unbias, hu); up(t->grid, hg); up(t->gd1, g1); up(t->gd2, g2);
     }
     if (e != hipSuccess) {
-        for (void *p : t->allocs) (void)hipFree(p);
+        dev_free_all(t->allocs);
         delete t;
         set_error("fold_trainer_create: %s", hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
@@ -700,7 +443,7 @@ extern "C" int geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoad
 
 extern "C" void geoadv_fold_trainer_destroy(geoadv_fold_trainer *t) {
     if (!t) return;
-    for (void *p : t->allocs) (void)hipFree(p);
+    dev_free_all(t->allocs);
     delete t;
 }
 

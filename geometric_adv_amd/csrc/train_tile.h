@@ -1,7 +1,7 @@
-// Kernels shared by the layer-by-layer training steps (cls_train.hip, fold_train.hip): the strided fp32 GEMM on
-// v_mfma_f32_32x32x2_f32 with its fixed-order split-K, the per-chunk column sums in double and the closing pass of the
-// batch-norm backward.  Nothing here depends on a model: the batch-norm kernels that carry an epsilon or a dropout mask
-// stay with their trainer.  Every kernel is `static`: each translation unit that includes this header gets its own copy.
+// The GEMM shared by the layer-by-layer training steps (cls_train.hip, fold_train.hip, atlas_train.hip): the strided fp32
+// product on v_mfma_f32_32x32x2_f32 with its fixed-order split-K, and its host launch.  The column-sum and batch-norm kernels
+// the three steps share are in train_bn.h.  Every kernel is `static`: each translation unit that includes this header gets
+// its own copy.
 #pragma once
 #include "mfma_tile.h"
 
@@ -111,49 +111,6 @@ inline hipError_t ct_launch_gemm(GemmArgs g, float *partials, hipStream_t st) {
         err = hipGetLastError();
     }
     return err;
-}
-
-// Column partials over a chunk of rows in double, fixed order: MODE 0 = (sum a, sum a^2), MODE 1 = (sum a, 0).
-// grid (ceil(C / 64), chunks), block 256 = 64 columns x 4 row phases.
-template <int MODE>
-static __global__ __launch_bounds__(256) void ct_colsum_kernel(const float *a, int R, int C, int rows_per_chunk, double2 *part) {
-    __shared__ double2 red[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
-    const int r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    double s = 0.0, q = 0.0;
-    if (c < C)
-        for (int r = r0 + ph; r < r1; r += 4) {
-            const double v = (double)a[(size_t)r * C + c];
-            s += v;
-            if (MODE == 0) q += v * v;
-        }
-    red[ph][threadIdx.x & 63] = make_double2(s, q);
-    __syncthreads();
-    if (ph == 0 && c < C) {
-        double2 o = red[0][threadIdx.x];
-        for (int p = 1; p < 4; ++p) { o.x += red[p][threadIdx.x].x; o.y += red[p][threadIdx.x].y; }
-        part[(size_t)blockIdx.y * C + c] = o;
-    }
-}
-
-// Column sums -> a gradient vector (conv / fc bias): out[c] = sum of the partials (the .x field), fixed order.
-static __global__ __launch_bounds__(256) void ct_colsum_final_kernel(const double2 *part, int chunks, int C, float *out) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0;
-    for (int k = 0; k < chunks; ++k) s += part[(size_t)k * C + c].x;
-    out[c] = (float)s;
-}
-
-// Batch-norm backward, pass 2: dbeta, dgamma (into the gradient arena) and the means m1 = dbeta / R, m2 = dgamma / R.
-static __global__ __launch_bounds__(256) void ct_bn_bwd_final_kernel(const double2 *part, int chunks, int C, double inv_rows, float *dgamma,
-                                                                     float *dbeta, float *m1, float *m2) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < chunks; ++k) { s += part[(size_t)k * C + c].x; q += part[(size_t)k * C + c].y; }
-    dbeta[c] = (float)s; dgamma[c] = (float)q;
-    m1[c] = (float)(s * inv_rows); m2[c] = (float)(q * inv_rows);
 }
 
 }  // namespace geoadv

@@ -96,14 +96,6 @@ class FoldingNetTrainer:
             pass
 
     # ---- device views --------------------------------------------------------------------------------------
-    def _raw(self, ptr, count, typestr="<f4"):
-        class _Arr:
-            pass
-        a = _Arr()
-        a.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-        with torch.cuda.device(self.device):
-            return torch.as_tensor(a, device=self.device)
-
     def state(self, what, layer=0, device=False):
         """Host copy of what the last step kept (geoadv_fold_trainer_state): 'bn_mean' / 'bn_var' / 'running_mean' /
         'running_var' / 'bn_inv' / 'bn_shift' / 'pre_bn' of BN layer 0 .. 5 (bn1 .. bn6), 'pool_winner' 0 / 1, 'gmax_row',
@@ -115,7 +107,7 @@ class FoldingNetTrainer:
         torch.cuda.synchronize(self.device)
         if not cnt.value:
             raise ValueError("state(%r) is empty before the first step" % what)
-        a = self._raw(p.value, cnt.value, "<i4" if what in _INT_STATES else "<f4")
+        a = _lib.device_view(p.value, cnt.value, "<i4" if what in _INT_STATES else "<f4", self.device)
         B, n = self.batch_size, self.num_points
         shapes = {"pre_bn": (-1, LAYERS[int(layer)][2]), "pool_winner": (B, n, -1), "gmax_row": (B, 1024), "hidden": (-1, 512),
                   "picks": (2, B, n, K), "cols": (2, B, n, K), "cov": (B, n, 9), "code": (B, 512), "mid": (B, G2, 3),
@@ -161,12 +153,12 @@ class FoldingNetTrainer:
     def parameters(self):
         """{parameter key: array} of the trainable tensors (host copies, torch's shapes)."""
         torch.cuda.synchronize(self.device)
-        return self._unflatten(self._raw(self._params_ptr, self._count).cpu().numpy())
+        return self._unflatten(_lib.device_view(self._params_ptr, self._count, "<f4", self.device).cpu().numpy())
 
     def gradients(self):
         """{parameter key: d loss / d parameter} of the last step, without the weight-decay term."""
         torch.cuda.synchronize(self.device)
-        return self._unflatten(self._raw(self._grads_ptr, self._count).cpu().numpy())
+        return self._unflatten(_lib.device_view(self._grads_ptr, self._count, "<f4", self.device).cpu().numpy())
 
     def slots(self):
         """Adam's {'exp_avg': {key: array}, 'exp_avg_sq': {key: array}}."""

@@ -116,20 +116,7 @@ class PointNetAETrainer:
     # ---- flat buffers -------------------------------------------------------------------------------------
     def _view(self, ptr):
         """The library-owned flat buffer as a torch tensor (no copy): what the gradient all-reduce runs on."""
-        class _Arr:
-            pass
-        a = _Arr()
-        a.__cuda_array_interface__ = {"shape": (self._count,), "typestr": "<f4", "data": (ptr, False), "version": 2}
-        with torch.cuda.device(self.device):
-            return torch.as_tensor(a, device=self.device)
-
-    def _view_f64(self, ptr, count):
-        class _Arr:
-            pass
-        a = _Arr()
-        a.__cuda_array_interface__ = {"shape": (count,), "typestr": "<f8", "data": (ptr, False), "version": 2}
-        with torch.cuda.device(self.device):
-            return torch.as_tensor(a, device=self.device)
+        return _lib.device_view(ptr, self._count, "<f4", self.device)
 
     _STATE = {"act": 0, "mean": 1, "inv_std": 2, "scale": 3, "shift": 4, "idx1": 5, "idx2": 6, "pool_max": 7, "pool_ties": 8,
                "d1": 9, "d2": 10}                           # GEOADV_TRAIN_STATE_*
@@ -140,13 +127,8 @@ class PointNetAETrainer:
         code's bit patterns and tie counts, the decoder's hidden activations."""
         p, cnt = C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().geoadv_trainer_state(self._h, self._STATE[what], int(layer), C.byref(p), C.byref(cnt)), "trainer_state")
-        class _Arr:
-            pass
-        a = _Arr()
         typestr = "<i4" if what in ("idx1", "idx2", "pool_max", "pool_ties") else "<f4"
-        a.__cuda_array_interface__ = {"shape": (int(cnt.value),), "typestr": typestr, "data": (p.value, False), "version": 2}
-        with torch.cuda.device(self.device):
-            return torch.as_tensor(a, device=self.device)
+        return _lib.device_view(p.value, cnt.value, typestr, self.device)
 
     def saved_state(self):
         """Host copies of everything _state_view exposes, shaped: {"act": [a_0..a_4], "mean"/"inv_std"/"scale"/"shift":
@@ -180,7 +162,7 @@ class PointNetAETrainer:
                 _lib.check(L.geoadv_trainer_run_phase(self._h, p, _lib.ptr(x), _lib.ptr(gt), _lib.stream_handle()), "trainer_run_phase")
                 _lib.check(L.geoadv_trainer_exchange(self._h, p, C.byref(buf), C.byref(cnt)), "trainer_exchange")
                 if cnt.value:
-                    all_reduce_sum_(self._view_f64(buf.value, int(cnt.value)))
+                    all_reduce_sum_(_lib.device_view(buf.value, cnt.value, "<f8", self.device))
             recon = torch.empty_like(x) if want_recon else None
             _lib.check(L.geoadv_trainer_fetch(self._h, _lib.ptr(self._loss), _lib.ptr(recon), _lib.stream_handle()), "trainer_fetch")
         all_reduce_sum_(self.gradient_buffer())
