@@ -15,6 +15,8 @@
 #include "decoder_tail.h"
 #define LC_STAMP(K, I) GA_STAMP(K, I)
 #include "loss_cgrad.h"
+#include "host_util.h"
+#include <assert.h>
 #include <dlfcn.h>
 #include <limits.h>
 #include <math.h>
@@ -231,13 +233,13 @@ struct geoadv_attack {
     unsigned long long *row64;       // [2][B][n] packed row minima of the symmetric scan's atomic form (8 or more column slices, chamfer_sym.h)
     int test_loss_form = 0;          // geoadv_attack_test_loss_form (tests only): how the row minima reach the loss launch and which bodies read them
     int plan[GEOADV_PLAN_COUNT] = {};         // geoadv_attack_test_plan (tests only): what the last forward launched, GEOADV_PLAN_* (host bookkeeping)
-    bool row64_filled;               // ... set to all ones by this forward's FC2 launch
     bool cgrad_done;                 // the cached forward's loss launch also produced the Chamfer gradients
     bool counted = false;            // this handle is counted in ae->attack_refs (geoadv_ae_set_encoder_arith refuses a switch under it)
     bool chamfer_prune;              // nn_distance(adv, x) through the paired grid search (cfg.all_pairs_source_dist = 0, the default)
     int *need_adv[2];                // [8 B] each: clouds the grid search handed back to the all-pairs kernel.  When the search
                                      // shares the all-pairs launch, call k reads [k & 1] (the verdicts of call k - 1) and
                                      // writes [(k + 1) & 1]; a search in its own launch (n > 4096) uses [0] in place
+    int *need_last;                  // ... the one the last searching forward wrote (geoadv_attack_search_state reads it)
     float *x_box;                    // [B][6] bounding boxes of the source clouds (the grid of the paired search)
     int grid_calls;                  // running number of grid-search launches (paces the retries of clouds that gave up)
     unsigned *masks;                 // [B][n][mask words] ReLU masks of the cached forward, or null (backward recomputes)
@@ -342,26 +344,59 @@ struct ProfScope {
 
 bool cgrad_step_sorted(int n) { return n > CG_FX_MAX_N_PLANE; }   // launch_cgrad below: the sorted kernel instead of the fixed-point bodies
 
+// The forward's own launch decisions, made once at its top (everything about the symmetric scan's launch is in its SymPlan):
+// pruned: nn_distance(adv, x) through the paired grid search -- adv = x + pert and most points barely move, so the exact search
+// seeded with the pairing (chamfer_grid.hip) answers it for a fraction of the all-pairs cost; clouds whose pairing has become poor
+// raise their `need` flag and are redone by the all-pairs launch (same results either way).
+// rides_scan / rides_latent: where the search runs.  It needs nothing the network produces and ~11-16 us per workgroup
+// (latency-bound: counting sort, cell walks).  With the symmetric scan (large batches) it shares the launch of the all-pairs scan of
+// (recon, target), which is longer and which it cannot slow down by much -- in the latent_decode launch, where it rode until round 2,
+// it was the longer half (in-kernel stamps: 16.1 against 11.5 us at B = 32).  The scans of (adv, source) in that same launch therefore
+// follow the verdicts of the PREVIOUS call (GridArgs::need_prev).  Small batches (two-scan kernel: 16-wave workgroups that fill a
+// CU's registers, so the search's workgroups would only start when the scans are done) keep it beside latent_decode (a second stream
+// for it, forked after the encoder and joined before the scans, was measured: + 25 us per iteration at B = 1 ... 16 -- each
+// cross-stream event costs more than the whole search); neither: clouds of more than GR_MAX_N points keep the search in a launch
+// of its own, ahead of the scans (it takes a CU's whole LDS).
+// loss_fused: loss_cgrad_kernel (losses + both Chamfer gradients); merge_in_loss: ... which also takes the scan's row minima as
+// partials or packed words (no second Chamfer launch).
+// jac_rides: the pool Jacobian of THIS forward (the next step's encoder backward, encoder_jac.h) beside the symmetric scan.  Where the
+// two-scan kernel runs instead (small batches) there is no launch long enough to hide it in, and as a launch of its own (8.2 us + the
+// 3.6 us look for tied clouds + two boundaries) it costs what the masked backward costs (11.6 us + one): those keep the masked backward.
+struct ForwardForm { bool pruned, rides_scan, rides_latent, loss_fused, merge_in_loss, jac_rides; };
+
 // forward(pert): encoder -> latent/decoder -> both Chamfer problems -> per-cloud losses (+ metrics / keep-best).
 int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
     const DeviceAE &A = at->ae->d;
-    const int B = at->B, n = at->n;
-    const ChamferScan sc_recon[2] = {{at->recon, at->gt, at->r1, at->ir1, n, n}, {at->gt, at->recon, at->r2, at->ir2, n, n}};
-    const ChamferScan sc_adv[2] = {{at->adv, at->x, at->a1, at->ia1, n, n}, {at->x, at->adv, at->a2, at->ia2, n, n}};
-    // nn_distance(adv, x): adv = x + pert and most points barely move, so the exact grid search seeded with the pairing
-    // (chamfer_grid.hip) answers it for a fraction of the all-pairs cost; clouds whose pairing has become poor raise
-    // their `need` flag and are redone by the all-pairs launch below (same results either way)
-    const bool pruned = at->chamfer_prune && chamfer_grid_supports(n, n);
+    const int B = at->B, n = at->n, H = cgrad_fx_parts(n);
     const bool adv_chamfer = at->cfg.loss_adv_type == GEOADV_LOSS_ADV_CHAMFER;
     const bool dist_chamfer = at->cfg.loss_dist_type == GEOADV_LOSS_DIST_CHAMFER;
     const bool max_term = dist_chamfer && at->cfg.max_point_dist_weight > 0.f;   // the gradient needs the loss pass's arg-max first
-    const bool loss_fused = (adv_chamfer || dist_chamfer) && !max_term && n <= CG_FX_MAX_N_PLANE;   // loss_cgrad_kernel below
-    const bool merge_in_loss = loss_fused && adv_chamfer && dist_chamfer;
-    // 8 or more column slices (up to 63 clouds of 2048 points): row minima folded into packed words by atomics; the FC2 launch
-    // fills them on its way
-    const int pack_from = (at->test_loss_form & 1) ? SYM_PACK_FROM + 1 : SYM_PACK_FROM;
-    const bool use_row64 = merge_in_loss && at->chamfer_sym && at->row64 != nullptr && chamfer_sym_packs_rows((long)B * (pruned ? 1 : 2), n, n, pack_from);
-    SymPartials part{nullptr, nullptr, 1, B, false, use_row64 ? at->row64 : nullptr, pack_from};
+    ForwardForm f;
+    f.pruned = at->chamfer_prune && chamfer_grid_supports(n, n);
+    f.rides_scan = f.pruned && chamfer_grid_rides(n) && at->chamfer_sym;
+    f.rides_latent = f.pruned && chamfer_grid_rides(n) && !at->chamfer_sym;
+    f.loss_fused = (adv_chamfer || dist_chamfer) && !max_term && n <= CG_FX_MAX_N_PLANE;
+    f.merge_in_loss = f.loss_fused && adv_chamfer && dist_chamfer;
+    f.jac_rides = at->jac && at->chamfer_sym;
+    // The scan's launch, planned before anything is launched: the FC2 launch fills the packed words only if the plan folds the rows
+    // into them, and the loss arguments depend on how the rows leave.  (Two-scan kernel: final rows, nothing else to report.)
+    SymPlan plan{};
+    if (at->chamfer_sym) {
+        SymRequest rq{2, B, n, n, true, f.pruned, f.rides_scan, f.jac_rides};
+        // the loss + gradient workgroups as the last riders of the launch (loss_cgrad.h) where it can host them: they wait for their
+        // cloud's workgroups through a counter instead of a kernel boundary.  (Not with the EMD term: its launch lies between.)
+        rq.loss = at->host_loss && f.merge_in_loss && !at->emd_temp; rq.loss_rows = 1 + 2 * H; rq.loss_force = at->host_loss_force;
+        rq.defer = f.merge_in_loss; rq.packed = f.merge_in_loss && at->row64 != nullptr;
+        rq.pack_from = (at->test_loss_form & 1) ? SYM_PACK_FROM + 1 : SYM_PACK_FROM;
+        rq.screen = chamfer_sym_screen_on();
+        plan = chamfer_sym_plan(rq);
+    }
+    const SymRows rows = chamfer_sym_rows(plan, at->sym_ws, at->row64);
+    const bool packed = plan.rows == GEOADV_PLAN_ROWS_PACKED, hosted = plan.loss.count > 0;
+    const int call = at->grid_calls;
+    int *need_new = at->need_adv[f.rides_scan ? (call + 1) & 1 : 0];
+    const int *need_scan = at->need_adv[f.rides_scan ? call & 1 : 0];      // what the all-pairs kernels act on in this call
+    if (f.pruned) { at->grid_calls++; at->need_last = need_new; }
     {
         ProfScope ps(at, GEOADV_PROF_ENCODER_FWD, st, true);
         if (int rc = launch_encoder_fwd(A, B, at->x, at->pert, (at->adv_valid && !at->adam_pending) ? nullptr : at->adv, at->fs.pmax,
@@ -370,86 +405,61 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
         at->adam_pending = false;
         at->adv_valid = true;
     }
-    // The paired search needs nothing the network produces and ~11-16 us per workgroup (latency-bound: counting sort, cell
-    // walks).  With the symmetric scan (large batches) it shares the launch of the all-pairs scan of (recon, target), which is
-    // longer and which it cannot slow down by much -- in the latent_decode launch, where it rode until round 2, it was the
-    // longer half (in-kernel stamps: 16.1 against 11.5 us at B = 32).  The scans of (adv, source) in that same launch therefore
-    // follow the verdicts of the PREVIOUS call (GridArgs::need_prev).  Small batches (two-scan kernel: 16-wave workgroups that
-    // fill a CU's registers, so the search's workgroups would only start when the scans are done) keep it beside
-    // latent_decode (a second stream for it, forked after the encoder and joined before the scans, was measured: + 25 us per
-    // iteration at B = 1 ... 16 -- each cross-stream event costs more than the whole search); clouds of more than GR_MAX_N
-    // points keep the search in a launch of its own, ahead of the scans.
-    const bool rides_scan = pruned && chamfer_grid_rides(n) && at->chamfer_sym;
-    const bool rides_latent = pruned && chamfer_grid_rides(n) && !at->chamfer_sym;
-    const int call = at->grid_calls;
-    int *need_new = at->need_adv[rides_scan ? (call + 1) & 1 : 0];
-    const int *need_scan = at->need_adv[rides_scan ? call & 1 : 0];      // what the all-pairs kernels act on in this call
-    if (pruned) at->grid_calls++;
     {
         ProfScope ps(at, GEOADV_PROF_DECODER_FWD, st);
-        if (pruned && !rides_scan && !rides_latent) {   // large clouds: the search takes a CU's whole LDS, so it gets its own launch
+        if (f.pruned && !f.rides_scan && !f.rides_latent) {
             if (int rc = launch_chamfer_grid(at->adv, at->x, at->a1, at->ia1, at->a2, at->ia2, B, n, need_new, call, at->x_box, st)) return rc;
         }
-        if (rides_latent) {
+        if (f.rides_latent) {
             if (int rc = launch_latent_decode_and_grid(A, B, at->fs.pmax, at->fs.parg, at->fs.pcnt, at->fs.z, at->fs.crit, at->fs.zcnt,
                                                        at->fs.dense, at->fs.d1, at->fs.d2, at->adv, at->x, at->a1, at->ia1, at->a2,
                                                        at->ia2, n, need_new, call, at->x_box, st)) return rc;
         } else if (int rc = launch_latent_decode(A, B, at->fs.pmax, at->fs.parg, at->fs.pcnt, at->fs.z, at->fs.crit, at->fs.zcnt,
                                                  at->fs.dense, at->fs.d1, at->fs.d2, st)) return rc;
-        if (int rc = launch_decoder_fc2(A, B, at->fs.d2, at->recon, st, use_row64 ? at->row64 : nullptr, use_row64 ? 2 * (size_t)B * n : 0)) return rc;
+        if (int rc = launch_decoder_fc2(A, B, at->fs.d2, at->recon, st, packed ? at->row64 : nullptr, packed ? 2 * (size_t)B * n : 0)) return rc;
     }
-    // The pool Jacobian of THIS forward (the next step's encoder backward, encoder_jac.h) beside the symmetric scan.  Where the
-    // two-scan kernel runs instead (small batches) there is no launch long enough to hide it in, and as a launch of its own
-    // (8.2 us + the 3.6 us look for tied clouds + two boundaries) it costs what the masked backward costs (11.6 us + one): those
-    // batches keep the masked backward.
     const JacArgs jargs{n, at->masks, at->fs.crit, at->fs.z, at->fs.dense, at->jac};
-    const bool jac_rides = at->jac && at->chamfer_sym;
-    at->jac_valid = jac_rides;
-    if (at->jac && !jac_rides && at->cfg.encoder_backward == GEOADV_ENC_BWD_JACOBIAN) {   // forced: a launch of its own
+    at->jac_valid = f.jac_rides;
+    if (at->jac && !f.jac_rides && at->cfg.encoder_backward == GEOADV_ENC_BWD_JACOBIAN) {   // forced: a launch of its own
         ProfScope ps(at, GEOADV_PROF_ENCODER_BWD, st);
         if (int rc = launch_encoder_jac(A, B, jargs, st)) return rc;
         at->jac_valid = true;
     }
-    // arguments of the loss / metrics / keep-best pass and of the two Chamfer gradients, for row minima that arrive as `p` says
-    auto fill_loss = [&](const SymPartials &p, LossArgs &la, CGradArgs &ca, int &np) {
-        la.n = n; la.loss_adv_type = at->cfg.loss_adv_type; la.loss_dist_type = at->cfg.loss_dist_type;
-        la.mp_pert_w = at->cfg.max_point_pert_weight; la.mp_dist_w = at->cfg.max_point_dist_weight;
-        la.r1 = at->r1; la.r2 = at->r2; la.a1 = at->a1; la.a2 = at->a2; la.pert = at->pert;
-        la.z = at->fs.z; la.tz = at->tz; la.w = at->w; la.losses = at->losses; la.jstar = at->jstar;
-        la.emd_cost = at->emd_temp ? at->emd_cost : nullptr; la.emd_weight = at->cfg.emd_weight;
-        la.dz_latent = at->dz; la.hist = hist_slot; la.keep = keep; la.best_err = at->best_err;
-        la.best_metrics = at->best_metrics; la.adv = at->adv; la.recon = at->recon;
-        la.best_adv = at->best_adv; la.best_recon = at->best_recon;
-        la.fold_in_lds = (at->test_loss_form & 2) ? 1 : 0; ca.general = la.fold_in_lds;
-        la.part = p; la.a1_need = pruned ? need_scan : nullptr; la.a1_all = pruned ? 0 : 1; la.r1_out = at->r1; la.a1_out = at->a1;
-        // the Chamfer gradients the next step starts with ride in the same launch (see loss_cgrad_kernel)
-        np = 0;
-        if (adv_chamfer) {
-            ca.pr[np] = CGradProblem{at->recon, at->gt, at->ir1, at->ir2, at->g_recon, nullptr, nullptr, 0.f};
-            if (p.deferred) {
-                ca.pr[np].part_d = p.rowpart_d; ca.pr[np].part_i = p.rowpart_i; ca.pr[np].part_slices = p.slices;
-                ca.pr[np].part_need = nullptr; ca.pr[np].idx1_out = at->ir1; ca.pr[np].part_w = p.row64;
-            }
-            ++np;
+    // arguments of the loss / metrics / keep-best pass and of the two Chamfer gradients, for row minima that arrive as `rows` says:
+    // they go to the riders of the scan's launch, or to loss_cgrad_kernel / loss_metrics_kernel below
+    LossArgs la;
+    CGradArgs ca;
+    int np = 0;
+    la.n = n; la.loss_adv_type = at->cfg.loss_adv_type; la.loss_dist_type = at->cfg.loss_dist_type;
+    la.mp_pert_w = at->cfg.max_point_pert_weight; la.mp_dist_w = at->cfg.max_point_dist_weight;
+    la.r1 = at->r1; la.r2 = at->r2; la.a1 = at->a1; la.a2 = at->a2; la.pert = at->pert;
+    la.z = at->fs.z; la.tz = at->tz; la.w = at->w; la.losses = at->losses; la.jstar = at->jstar;
+    la.emd_cost = at->emd_temp ? at->emd_cost : nullptr; la.emd_weight = at->cfg.emd_weight;
+    la.dz_latent = at->dz; la.hist = hist_slot; la.keep = keep; la.best_err = at->best_err;
+    la.best_metrics = at->best_metrics; la.adv = at->adv; la.recon = at->recon;
+    la.best_adv = at->best_adv; la.best_recon = at->best_recon;
+    la.fold_in_lds = (at->test_loss_form & 2) ? 1 : 0; ca.general = la.fold_in_lds;
+    la.part = rows; la.a1_need = f.pruned ? need_scan : nullptr; la.a1_all = f.pruned ? 0 : 1; la.r1_out = at->r1; la.a1_out = at->a1;
+    // the Chamfer gradients the next step starts with ride in the same launch (see loss_cgrad_kernel)
+    if (adv_chamfer) {
+        ca.pr[np] = CGradProblem{at->recon, at->gt, at->ir1, at->ir2, at->g_recon, nullptr, nullptr, 0.f};
+        if (rows.deferred) {
+            ca.pr[np].part_d = rows.rowpart_d; ca.pr[np].part_i = rows.rowpart_i; ca.pr[np].part_slices = rows.slices;
+            ca.pr[np].part_need = nullptr; ca.pr[np].idx1_out = at->ir1; ca.pr[np].part_w = rows.row64;
         }
-        if (dist_chamfer) {
-            ca.pr[np] = CGradProblem{at->adv, at->x, at->ia1, at->ia2, at->g_dist, at->w, at->jstar, 0.f};
-            if (p.deferred) {                             // pair 1's partials follow pair 0's B clouds
-                const size_t off = (size_t)B * p.slices * n;
-                ca.pr[np].part_d = p.rowpart_d + off; ca.pr[np].part_i = p.rowpart_i + off; ca.pr[np].part_slices = p.slices;
-                ca.pr[np].part_need = pruned ? need_scan : nullptr; ca.pr[np].idx1_out = at->ia1;
-                ca.pr[np].part_w = p.row64 ? p.row64 + (size_t)B * n : nullptr;
-            }
-            ++np;
+        ++np;
+    }
+    if (dist_chamfer) {
+        ca.pr[np] = CGradProblem{at->adv, at->x, at->ia1, at->ia2, at->g_dist, at->w, at->jstar, 0.f};
+        if (rows.deferred) {                             // pair 1's partials follow pair 0's B clouds
+            const size_t off = (size_t)B * rows.slices * n;
+            ca.pr[np].part_d = rows.rowpart_d + off; ca.pr[np].part_i = rows.rowpart_i + off; ca.pr[np].part_slices = rows.slices;
+            ca.pr[np].part_need = f.pruned ? need_scan : nullptr; ca.pr[np].idx1_out = at->ia1;
+            ca.pr[np].part_w = rows.row64 ? rows.row64 + (size_t)B * n : nullptr;
         }
-        ca.n = n; ca.P = 0;
-    };
-    struct LossCtx { void (*fill)(void *, const SymPartials &, LossArgs &, CGradArgs &, int &); void *self; };
-    LossCtx lctx{[](void *f, const SymPartials &p, LossArgs &la, CGradArgs &ca, int &np) { (*static_cast<decltype(fill_loss) *>(f))(p, la, ca, np); }, &fill_loss};
-    LossRider lr;
-    lr.blocks = 0; lr.patch = nullptr; lr.ctx = nullptr; lr.force = false;
-    bool want_host = false, hosted = false;
-    SymLaunchInfo info{0, 0, 0, GEOADV_PLAN_ROWS_FINAL};           // (two-scan kernel: final rows, nothing else to report)
+        ++np;
+    }
+    ca.n = n; ca.P = 0;
     {
         ProfScope ps(at, GEOADV_PROF_CHAMFER_FWD, st);
         if (at->chamfer_sym) {   // one distance evaluation per pair serves both directions
@@ -458,28 +468,17 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
             const GridArgs rider{at->adv, at->x, at->a1, at->ia1, at->a2, at->ia2, n, need_new, need_scan, call, at->x_box};
             JacRider jr;
             jr.j = jargs; jr.A = A; jr.first_block = 0; jr.blocks = 0; jr.raise_prio = 0;
-            // The loss + gradient workgroups as the last riders of this launch (loss_cgrad.h) where it can host them: they wait for
-            // their cloud's workgroups through a counter instead of a kernel boundary.  (Not with the EMD term: its launch lies between.)
-            if (at->host_loss && merge_in_loss && !at->emd_temp) {
-                lr.H = cgrad_fx_parts(n); lr.rows = 1 + 2 * lr.H; lr.done = at->loss_done; lr.target = at->loss_target;
-                lr.spin_timeout = reinterpret_cast<int *>(at->tail_ready + B);
-                lr.ctx = &lctx; lr.force = at->host_loss_force;
-                lr.patch = [](LossRider &r, const SymPartials &p, void *c) {
-                    LossCtx &x = *static_cast<LossCtx *>(c);
-                    int np_ = 0;
-                    x.fill(x.self, p, r.la, r.ca, np_);
-                };
-                want_host = true;
+            LossRider lr;
+            if (hosted) {
+                at->loss_target += plan.loss_arrivals;
+                lr = LossRider{la, ca, H, 1 + 2 * H, 0, 0, B, at->loss_done, at->loss_target, reinterpret_cast<int *>(at->tail_ready + B)};
             }
-            // the row minima leave the scan as one (distance, index) partial per column slice; when the loss launch below is the
-            // fused one with both Chamfer gradients inside, it merges them on its way in (no second Chamfer launch)
-            if (int rc = launch_chamfer_sym_loop(pairs, 2, B, n, n, at->sym_ws, pruned ? need_scan : nullptr, rides_scan ? &rider : nullptr,
-                                                 jac_rides ? &jr : nullptr, merge_in_loss ? &part : nullptr, st, want_host ? &lr : nullptr, &info)) return rc;
-            hosted = want_host && lr.blocks > 0;
-            if (hosted) { at->loss_target = lr.target; at->cgrad_done = true; }
+            if (int rc = launch_chamfer_sym(plan, pairs, at->sym_ws, f.pruned ? need_scan : nullptr, f.rides_scan ? &rider : nullptr,
+                                            f.jac_rides ? &jr : nullptr, hosted ? &lr : nullptr, at->row64, st)) return rc;
         } else {
-            ChamferScan all[4] = {sc_recon[0], sc_recon[1], sc_adv[0], sc_adv[1]};
-            if (pruned) all[2].need = all[3].need = need_scan;         // only the clouds the grid search handed back
+            ChamferScan all[4] = {{at->recon, at->gt, at->r1, at->ir1, n, n}, {at->gt, at->recon, at->r2, at->ir2, n, n},
+                                  {at->adv, at->x, at->a1, at->ia1, n, n}, {at->x, at->adv, at->a2, at->ia2, n, n}};
+            if (f.pruned) all[2].need = all[3].need = need_scan;         // only the clouds the grid search handed back
             if (int rc = launch_chamfer_scans(all, 4, B, st)) return rc;
         }
     }
@@ -487,29 +486,19 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
         ProfScope ps(at, GEOADV_PROF_CHAMFER_FWD, st);   // needs only its cost and d cost / d recon, so the plan itself is never stored
         if (int rc = geoadv_emd_cost_grad1_mode(at->cfg.emd_weight_mode, B, n, n, at->recon, at->gt, at->emd_cost, at->emd_g1, at->emd_temp, st)) return rc;
     }
+    at->cgrad_done = hosted || f.loss_fused;
     if (!hosted) {
         ProfScope ps(at, GEOADV_PROF_LOSS_GRAD, st);
-        LossArgs la;
-        CGradArgs ca;
-        int np = 0;
-        fill_loss(part, la, ca, np);
-        at->cgrad_done = false;
-        if (loss_fused) {
-            const int H = cgrad_fx_parts(n);
-            loss_cgrad_kernel<<<dim3(B, 1 + np * H), CGA_THREADS, loss_cgrad_lds_bytes(n), st>>>(la, ca, H);
-            at->cgrad_done = true;
-        } else {
-            loss_metrics_kernel<<<B, 256, 0, st>>>(la);
-        }
+        if (f.loss_fused) loss_cgrad_kernel<<<dim3(B, 1 + np * H), CGA_THREADS, loss_cgrad_lds_bytes(n), st>>>(la, ca, H);
+        else loss_metrics_kernel<<<B, 256, 0, st>>>(la);
         GA_LAUNCH_CHECK();
     }
-    {   // the tests' read-out: what this forward launched, and the gradient launch it leaves to the step
-        const int np = (adv_chamfer ? 1 : 0) + (dist_chamfer ? 1 : 0), H = cgrad_fx_parts(n);
+    {   // the tests' read-out: the scan's plan, and the two facts only the forward knows -- the loss launch and the gradient launch it leaves to the step
         const int general = (at->test_loss_form & 2) ? 1 : 0;
         int *pl = at->plan;
-        pl[GEOADV_PLAN_SYMMETRIC] = at->chamfer_sym ? 1 : 0; pl[GEOADV_PLAN_SCREENED] = info.mx;
-        pl[GEOADV_PLAN_RTILES] = info.rtiles; pl[GEOADV_PLAN_RSLICES] = info.rslices; pl[GEOADV_PLAN_ROWS] = info.rows;
-        pl[GEOADV_PLAN_LOSS] = hosted ? GEOADV_PLAN_LOSS_RIDERS : loss_fused ? GEOADV_PLAN_LOSS_FUSED : GEOADV_PLAN_LOSS_METRICS;
+        pl[GEOADV_PLAN_SYMMETRIC] = at->chamfer_sym ? 1 : 0; pl[GEOADV_PLAN_SCREENED] = plan.shape.mx ? 1 : 0;
+        pl[GEOADV_PLAN_RTILES] = plan.shape.rtiles; pl[GEOADV_PLAN_RSLICES] = plan.rslices; pl[GEOADV_PLAN_ROWS] = plan.rows;
+        pl[GEOADV_PLAN_LOSS] = hosted ? GEOADV_PLAN_LOSS_RIDERS : f.loss_fused ? GEOADV_PLAN_LOSS_FUSED : GEOADV_PLAN_LOSS_METRICS;
         if (at->cgrad_done) pl[GEOADV_PLAN_GRAD] = cgrad_fx_one_pass(n, H, general) ? GEOADV_PLAN_GRAD_FUSED_1PASS : GEOADV_PLAN_GRAD_FUSED_GENERAL;
         else if (np == 0) pl[GEOADV_PLAN_GRAD] = GEOADV_PLAN_GRAD_NONE;
         else if (cgrad_step_sorted(n)) pl[GEOADV_PLAN_GRAD] = GEOADV_PLAN_GRAD_STEP_SORTED;
@@ -621,6 +610,41 @@ int do_step(geoadv_attack *at, hipStream_t st) {
     return GEOADV_OK;
 }
 
+// Every device buffer of a handle, carved in one order from `base` at 256-byte alignment; returns the bytes taken.  Over a null
+// base it only measures (geoadv_attack_create runs it twice: to size the allocation, then over it).
+size_t carve_arena(geoadv_attack *at, void *base) {
+    const geoadv_attack_config &cfg = at->cfg;
+    const size_t B = at->B, n = at->n, bn3 = B * n * 3, bn = B * n;
+    Carver c(base);
+    auto F = [&](size_t count) { return c.take<float>(count); };
+    auto I = [&](size_t count) { return c.take<int>(count); };
+    at->x = F(bn3); at->gt = F(bn3); at->tz = F(B * 128); at->w = F(B);
+    at->pert = F(bn3); at->m = F(bn3); at->v = F(bn3);
+    at->adv = F(bn3); at->recon = F(bn3); at->g_recon = F(bn3); at->g_dist = F(bn3); at->g_enc = F(bn3); at->grad_last = F(bn3);
+    at->r1 = F(bn); at->r2 = F(bn); at->a1 = F(bn); at->a2 = F(bn);
+    at->ir1 = I(bn); at->ir2 = I(bn); at->ia1 = I(bn); at->ia2 = I(bn);
+    at->fs = carve_forward_scratch(c.take<char>(carve_forward_scratch(nullptr, at->B, at->n).bytes), at->B, at->n);
+    at->dz = F(B * 128); at->dec_partial = F((size_t)decoder_bwd_chunks(at->ae->d) * B * 256);
+    at->losses = F(8 * B); at->jstar = I(2 * B);
+    at->best_err = F(B); at->best_metrics = F(B * 4); at->best_adv = F(bn3); at->best_recon = F(bn3);
+    at->sym_ws = F(chamfer_sym_workspace_floats(2, at->B, at->n, at->n));
+    at->row64 = c.take<unsigned long long>(2 * bn);
+    const size_t mask_words = cfg.recompute_backward ? 0 : (size_t)encoder_mask_words() * bn;   // ReLU masks of the cached forward
+    at->masks = mask_words ? c.take<unsigned>(mask_words) : nullptr;
+    const bool use_jac = mask_words != 0 && cfg.loss_adv_type == GEOADV_LOSS_ADV_CHAMFER && cfg.encoder_backward != GEOADV_ENC_BWD_MASKED;
+    at->jac = use_jac ? F(B * 128 * 3) : nullptr;
+    at->tail_ready = c.take<unsigned>(B + 1);
+    at->loss_done = c.take<unsigned>(B);
+    at->need_adv[0] = I(8 * B); at->need_adv[1] = I(8 * B);
+    at->x_box = F(6 * B);
+    at->emd_temp = at->emd_cost = at->emd_g1 = nullptr;
+    if (cfg.emd_weight > 0.f) {
+        at->emd_temp = F(geoadv_emd_cost_grad1_temp_floats(at->B, at->n, at->n) + 2);
+        at->emd_cost = F(B); at->emd_g1 = F(bn3);
+    }
+    return c.bytes();
+}
+
 }  // namespace
 
 namespace geoadv {   // the same gradient for the training step (train.hip)
@@ -655,34 +679,7 @@ extern "C" int geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, co
                "attack_create: emd_weight needs the output-space attack (loss_adv_type chamfer)");
     geoadv_attack *at = new geoadv_attack();
     at->ae = ae; at->cfg = *cfg; at->B = cfg->batch; at->n = ae->d.n_points;
-    const size_t B = at->B, n = at->n, bn3 = B * n * 3, bn = B * n;
-    const int chunks = decoder_bwd_chunks(ae->d);
-    const size_t fs_bytes = carve_forward_scratch(nullptr, at->B, at->n).bytes;
-    size_t total = 0;
-    auto need = [&](size_t bytes) { total += rup(bytes, 256); };
-    for (int i = 0; i < 2; ++i) need(4 * bn3);            // x, gt
-    need(4 * B * 128); need(4 * B);                       // tz, w
-    for (int i = 0; i < 3; ++i) need(4 * bn3);            // pert, m, v
-    for (int i = 0; i < 6; ++i) need(4 * bn3);            // adv, recon, g_recon, g_dist, g_enc, grad_last
-    for (int i = 0; i < 8; ++i) need(4 * bn);             // r1 r2 a1 a2 + 4 idx
-    need(fs_bytes);
-    need(4 * B * 128); need(4 * (size_t)chunks * B * 256);
-    need(4 * 8 * B); need(4 * 2 * B);
-    need(4 * B); need(4 * B * 4); need(4 * bn3); need(4 * bn3);
-    const size_t sym_floats = chamfer_sym_workspace_floats(2, at->B, at->n, at->n);
-    need(4 * sym_floats);
-    need(8 * 2 * bn);                                     // row64
-    const size_t mask_words = cfg->recompute_backward ? 0 : (size_t)encoder_mask_words() * bn;   // ReLU masks of the cached forward
-    need(4 * mask_words);
-    const bool use_jac = mask_words != 0 && cfg->loss_adv_type == GEOADV_LOSS_ADV_CHAMFER && cfg->encoder_backward != GEOADV_ENC_BWD_MASKED;
-    need(use_jac ? 4 * B * 128 * 3 : 0);
-    need(4 * (B + 1));
-    need(4 * 8 * B); need(4 * 8 * B);                     // need_adv[2]
-    need(4 * 6 * B);                                      // x_box
-    const bool emd = cfg->emd_weight > 0.f;
-    const size_t emd_temp_f = emd ? geoadv_emd_cost_grad1_temp_floats(at->B, at->n, at->n) : 0;
-    if (emd) { need(4 * emd_temp_f + 8); need(4 * B); need(4 * bn3); }
-    at->arena_bytes = total;
+    const size_t total = at->arena_bytes = carve_arena(at, nullptr);      // over a null base: measured only
     if (hipMalloc(&at->arena, total) != hipSuccess) {
         delete at;
         set_error("attack_create: hipMalloc of %zu bytes failed", total);
@@ -697,37 +694,16 @@ extern "C" int geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, co
         set_error("attack_create: clearing %zu bytes failed", total);
         return GEOADV_EHIP;
     }
-    char *p = static_cast<char *>(at->arena);
-    auto take = [&](size_t bytes) { char *q = p; p += rup(bytes, 256); return q; };
-    auto F = [&](size_t bytes) { return reinterpret_cast<float *>(take(bytes)); };
-    auto I = [&](size_t bytes) { return reinterpret_cast<int *>(take(bytes)); };
-    at->x = F(4 * bn3); at->gt = F(4 * bn3); at->tz = F(4 * B * 128); at->w = F(4 * B);
-    at->pert = F(4 * bn3); at->m = F(4 * bn3); at->v = F(4 * bn3);
-    at->adv = F(4 * bn3); at->recon = F(4 * bn3); at->g_recon = F(4 * bn3); at->g_dist = F(4 * bn3);
-    at->g_enc = F(4 * bn3); at->grad_last = F(4 * bn3);
-    at->r1 = F(4 * bn); at->r2 = F(4 * bn); at->a1 = F(4 * bn); at->a2 = F(4 * bn);
-    at->ir1 = I(4 * bn); at->ir2 = I(4 * bn); at->ia1 = I(4 * bn); at->ia2 = I(4 * bn);
-    at->fs = carve_forward_scratch(take(fs_bytes), at->B, at->n);
-    at->dz = F(4 * B * 128); at->dec_partial = F(4 * (size_t)chunks * B * 256);
-    at->losses = F(4 * 8 * B); at->jstar = I(4 * 2 * B);
-    at->best_err = F(4 * B); at->best_metrics = F(4 * B * 4); at->best_adv = F(4 * bn3); at->best_recon = F(4 * bn3);
-    at->sym_ws = F(4 * sym_floats);
-    at->row64 = reinterpret_cast<unsigned long long *>(take(8 * 2 * bn));
-    at->masks = mask_words ? reinterpret_cast<unsigned *>(take(4 * mask_words)) : nullptr;
-    at->jac = use_jac ? F(4 * B * 128 * 3) : nullptr;
+    const size_t carved = carve_arena(at, at->arena);
+    assert(carved == at->arena_bytes); (void)carved;       // both passes agree
+    at->need_last = at->need_adv[0];
     at->jac_valid = false;
-    at->tail_ready = reinterpret_cast<unsigned *>(take(4 * (B + 1)));      // (the arena is zeroed above)
-    at->tail_epoch = 0;
-    at->loss_done = reinterpret_cast<unsigned *>(take(4 * (size_t)B));
-    at->loss_target = 0;
+    at->tail_epoch = 0; at->loss_target = 0; at->grid_calls = 0;      // (the arena is zeroed above: flags, counters)
     {
         int dev = 0, cus = 0;                               // unknown => 0: always the two plain launches
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) at->cus = cus;
         else at->cus = 0;
     }
-    at->need_adv[0] = I(4 * 8 * B); at->need_adv[1] = I(4 * 8 * B);
-    at->grid_calls = 0;
-    at->x_box = F(4 * 6 * B);
     // Tiny batches (< 10 K points: B <= 4 at N = 2048): the search's own latency (~11-14 us per workgroup beside a 6 us
     // latent_decode) costs what the two extra all-pairs scans cost on a mostly idle chip -- measured 0.0673 / 0.0725 ms at
     // B = 1 and 0.0758 / 0.0767 at B = 4 without / with it, 0.0977 / 0.0929 at B = 8 -- so it is only used above that
@@ -746,8 +722,6 @@ extern "C" int geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, co
         at->chamfer_sym = cfg->chamfer_kernel == GEOADV_CHAMFER_AUTO ? (long)at->B * at->n >= GEOADV_SYM_MIN_POINTS
                                                                      : cfg->chamfer_kernel == GEOADV_CHAMFER_SYMMETRIC;
     }
-    at->emd_temp = at->emd_cost = at->emd_g1 = nullptr;
-    if (emd) { at->emd_temp = F(4 * emd_temp_f + 8); at->emd_cost = F(4 * B); at->emd_g1 = F(4 * bn3); }
     at->cgrad_done = false;
     at->fuse_adam = cfg->separate_adam == 0;
     at->adam_pending = false;
@@ -952,10 +926,8 @@ extern "C" int geoadv_attack_search_state(geoadv_attack *at, int *searched, int 
     *handed_back = 0;
     if (!pruned) return GEOADV_OK;
     hipStream_t st = as_stream(stream);
-    const bool two = chamfer_grid_rides(at->n) && at->chamfer_sym;                 // (two flag arrays: the last call wrote this one)
-    const int *flags = at->need_adv[two ? at->grid_calls & 1 : 0];
     std::vector<int> h(8 * (size_t)at->B);
-    GA_HIP(hipMemcpyAsync(h.data(), flags, sizeof(int) * h.size(), hipMemcpyDeviceToHost, st));
+    GA_HIP(hipMemcpyAsync(h.data(), at->need_last, sizeof(int) * h.size(), hipMemcpyDeviceToHost, st));
     GA_HIP(hipStreamSynchronize(st));
     for (int c = 0; c < at->B; ++c) {
         int any = 0;

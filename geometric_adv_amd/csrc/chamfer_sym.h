@@ -10,22 +10,55 @@ struct ChamferPair {
     float *dist2; int *idx2;   // [b][m]  column minima (outputs 2,3)
 };
 
-// What launch_chamfer_sym_loop leaves to the caller's next launch when asked to (`defer`): the row minima as one
-// (distance, index) partial per column slice -- [pair][cloud][slice][n] -- whose lexicographic minimum is dist1 / idx1.
-// deferred == false: dist1 / idx1 are final in the pairs' own arrays (one slice, or the merge launch ran).
-// row64 (8 or more partials per row -- a merge launch or a heavy consumer, 8 loads per row at the least -- i.e. batches up to
-// 63 clouds of 2048 points): the scan instead folds every (row, slice) into ONE packed word per row -- (distance bits << 32) | index, 64-bit unsigned atomic
+// How the row minima leave a planned launch of the scan -- a read-only view for whoever reads them next (SymPlan::rows):
+// FINAL / MERGE_LAUNCH: dist1 / idx1 are final in the pairs' own arrays (one slice, or the merge launch ran): deferred == false.
+// PARTIALS: one (distance, index) partial per column slice -- [pair][cloud][slice][n] -- whose lexicographic minimum is dist1 / idx1.
+// PACKED (8 or more partials per row -- a merge launch or a heavy consumer, 8 loads per row at the least -- i.e. batches up to
+// 63 clouds of 2048 points): the scan folds every (row, slice) into ONE packed word per row -- (distance bits << 32) | index, 64-bit unsigned atomic
 // minimum: squared distances are >= +0, so the order of the words is the lexicographic order of (distance, index) -- in
-// row64[pair][cloud][n], which must hold all ones when the scan starts (the loop's FC2 launch fills it on its way).
+// row64[pair][cloud][n], which must hold all ones when the scan starts (the loop's FC2 launch fills it on its way); slices == 0.
 constexpr int SYM_PACK_FROM = 8;
-struct SymPartials {
-    const float *rowpart_d;
-    const int *rowpart_i;
-    int slices, clouds;
-    bool deferred;
-    unsigned long long *row64;       // in: the caller's packed buffer (or null: never use the atomic form); out: null unless used
-    int pack_from = SYM_PACK_FROM;   // in: the fewest partials per row that are folded into the packed words
+// (Kernel arguments carry this view: `clouds` and the trailing slot keep the arguments' offsets where they were before the launch was
+// planned on the host -- with the view shrunk to what is read, the loop measured 0.25 us per iteration slower, profiles/r11_sym_plan_ab.txt.)
+struct SymRows { const float *rowpart_d; const int *rowpart_i; int slices, clouds; bool deferred; const unsigned long long *row64; int unused_ = 0; };
+
+// What a caller asks of one launch of the scan.  Plain values only: chamfer_sym_plan() reads nothing else.
+struct SymRequest {
+    int np, b, n, m;                 // 1 or 2 problems of b clouds, n rows x m columns each
+    bool loop = false;               // the attack loop's launch rule (riders may share the launch)
+    bool need1 = false;              // the second pair is gated by per-cloud flags: it usually has no work and does not count as live
+    bool search = false, jac = false, loss = false;   // riders asked for: the paired grid search, the pool Jacobian, the loss + gradient workgroups
+    int loss_rows = 0;               // ... workgroups per cloud of the loss riders
+    bool loss_force = false;         // ... hosted wherever the launch CAN (the parity tests; the default hosts them where it pays)
+    bool defer = false;              // the caller's next launch takes the row minima as partials
+    bool packed = false;             // ... and has a packed buffer (SymRows::row64)
+    int pack_from = SYM_PACK_FROM;   // the fewest partials per row that are folded into the packed words
+    int q_clouds = 0, pair_base = 0; // q_clouds > 0: cloud c is the pair (P cloud (pair_base + c) / q_clouds, Q cloud (pair_base + c) % q_clouds)
+    bool screen = true;              // the process-wide screen switch (chamfer_sym_screen_on), read ONCE by whoever builds the request
 };
+// Launch shape of the symmetric scan: how the 8 waves of a workgroup are laid over rows and columns, and how many
+// columns a workgroup takes so that the grid fills the chip (256 / 128 / 64; `groups` = live (pair, cloud) groups).
+struct SymShape { int rw, cw, rtiles, C, S, cslices; bool mx; };
+struct SymBlocks { int first, count; };
+// Every decision of one launch, made once by chamfer_sym_plan() -- a pure host function: no device, no global -- read by the
+// caller (the loop's forward prepares its other launches from it) and executed by launch_chamfer_sym().
+struct SymPlan {
+    SymRequest req;
+    SymShape shape;
+    int kernel;                      // 0: the plain kernel; 2 / 4 / 8: the screened one at 64 / 128 / 256 columns per stage
+    int rslices;                     // row partials per row (column slices x column waves)
+    int rows;                        // how the row minima leave the launch: GEOADV_PLAN_ROWS_* (include/geoadv.h)
+    SymBlocks search, scan, jac, loss;   // block ranges in grid order (count 0: absent); grid = their sum
+    unsigned grid;
+    size_t lds_bytes;                // dynamic LDS of the launch
+    unsigned loss_arrivals;          // what every cloud's arrival counter gains in this launch (0 unless the loss riders are hosted)
+    int raise_prio;                  // JacRider::raise_prio
+    size_t group_floats;             // scratch floats per (pair, cloud) group
+    size_t part_off[4];              // offsets in the workspace, in floats: row distances, row indices, column distances, column indices
+};
+SymPlan chamfer_sym_plan(const SymRequest &r);
+bool chamfer_sym_screen_on();
+SymRows chamfer_sym_rows(const SymPlan &p, const float *workspace, const unsigned long long *row64);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ bool sym_needed(const int *need, int c) {
@@ -84,7 +117,7 @@ struct CGradProblem {
     // idx1 still as the symmetric scan's (distance, index) partials per column slice (null: idx1 is final); this kernel then
     // takes their lexicographic minimum on its way in and leaves it in idx1_out.  part_need: only the clouds flagged there.
     const float *part_d; const int *part_i; int part_slices; const int *part_need; int *idx1_out;
-    const unsigned long long *part_w;      // ... or as packed (distance, index) words [B][n] (SymPartials::row64): the index is the low half
+    const unsigned long long *part_w;      // ... or as packed (distance, index) words [B][n] (SymRows::row64): the index is the low half
 };
 int launch_chamfer_grad(const CGradProblem *pr, int np, int B, int n, hipStream_t st);
 
@@ -93,21 +126,15 @@ int launch_nn_nonfinite_fix(int b, int n, const float *xyz1, int m, const float 
                             int *idx2, hipStream_t stream);
 
 size_t chamfer_sym_workspace_floats(int pairs, int b, int n, int m);
-bool chamfer_sym_packs_rows(long live_groups, int n, int m, int pack_from = SYM_PACK_FROM);
-int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, hipStream_t stream);
 struct GridArgs;
 struct JacRider;
 struct LossRider;
-// What a launch_chamfer_sym_loop call launched (host bookkeeping for the tests' read-out, geoadv_attack_test_plan): the screened
-// kernel or the plain one, the row super-tiles and row partials per row of its shape, and how the row minima left it
-// (GEOADV_PLAN_ROWS_*, include/geoadv.h).
-struct SymLaunchInfo { int mx, rtiles, rslices, rows; };
-// loss (or null): the loop's loss + gradient workgroups as the LAST riders of the launch (loss_cgrad.h; first_block / blocks /
-// target are set here).  Returns with loss->blocks == 0 when the launch could not host them (the caller then launches them itself).
-int launch_chamfer_sym_loop(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, const int *need1,
-                            const GridArgs *rider, const JacRider *jac, SymPartials *defer, hipStream_t stream, LossRider *loss = nullptr,
-                            SymLaunchInfo *info = nullptr);
-// can the symmetric scan's launch of this shape host the loss riders?  (the unscreened kernel, one row super-tile, whole groups of 8 clouds)
-bool chamfer_sym_hosts_loss(long live_groups, int b, int n, int m);
+// Executes a plan.  need1: per-cloud flags (int[8 * b], 16-byte aligned) restricting the SECOND pair to the clouds that still need the
+// all-pairs kernel; rider / jac / loss: the riders the plan has block ranges for (their first_block / blocks / clouds / raise_prio
+// come from the plan; loss->target already counts plan.loss_arrivals); row64: the packed buffer when plan.rows is PACKED.
+int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *workspace, const int *need1, const GridArgs *rider,
+                       const JacRider *jac, const LossRider *loss, unsigned long long *row64, hipStream_t stream);
+// the operator form: every cloud live, no rider, rows final on return
+int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, hipStream_t stream);
 
 }  // namespace geoadv

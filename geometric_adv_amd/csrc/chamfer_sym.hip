@@ -414,13 +414,10 @@ __global__ __launch_bounds__(256) void chamfer_sym_merge_kernel(ChamferSymArgs a
     }
 }
 
-// Launch shape of the symmetric scan: how the 8 waves of a workgroup are laid over rows and columns, and how many
-// columns a workgroup takes so that the grid fills the chip (256 / 128 / 64; `groups` = live (pair, cloud) groups).
-struct SymShape { int rw, cw, rtiles, C, S, cslices; bool mx; };
 // process-wide switch (geoadv_set_chamfer_screen): 0 = the unscreened scan everywhere -- the parity tests' second opinion and the
 // A/B tools.  Scratch sizes never depend on it (they cover both kernels), so it may change between calls.
 static std::atomic<int> g_mx_on{1};
-static bool mx_enabled() { return g_mx_on.load() != 0; }
+bool chamfer_sym_screen_on() { return g_mx_on.load() != 0; }
 // loop: the attack loop's launch (riders may share it).  The screened kernel holds ONE workgroup per CU (256 registers a wave,
 // 100 KB of LDS): the loop's riders -- latency-bound workgroups that hide under the unscreened scan at two workgroups per CU --
 // would queue behind it, and its own serial phases (operands, column finish, uncertified queries: ~9 of ~24 us per 2048 x 256
@@ -479,75 +476,119 @@ static SymShape sym_shape(long groups, int n, int m, bool loop, bool screen) {
     s.cslices = cdiv(m, s.C * s.S);
     return s;
 }
-static size_t sym_group_floats(const SymShape &s, int n, int m) {
-    return 2 * (size_t)s.cslices * s.cw * n + (s.rtiles > 1 ? 2 * (size_t)s.rtiles * m : 0);
+// Every decision of one launch.  Requires n >= 1, m >= 1, np <= 2 (problems of identical (n, m)); b <= 0 or np <= 0: an empty plan.
+SymPlan chamfer_sym_plan(const SymRequest &r) {
+    SymPlan p{};
+    p.req = r;
+    p.rows = GEOADV_PLAN_ROWS_FINAL;
+    if (r.b <= 0 || r.np <= 0) return p;
+    // (a second pair gated by `need1` usually has no work at all -- the grid search answers it -- so it does not count)
+    const int np_live = r.need1 ? 1 : r.np;
+    const SymShape s = p.shape = sym_shape((long)r.b * np_live, r.n, r.m, r.loop, r.screen);
+    p.kernel = !s.mx ? 0 : s.C == 256 ? 8 : s.C == 128 ? 4 : 2;
+    p.rslices = s.cslices * s.cw;
+    p.group_floats = 2 * (size_t)p.rslices * r.n + (s.rtiles > 1 ? 2 * (size_t)s.rtiles * r.m : 0);
+    const size_t groups = (size_t)r.np * r.b;
+    p.part_off[0] = 0; p.part_off[1] = groups * p.rslices * r.n;
+    p.part_off[2] = 2 * groups * p.rslices * r.n; p.part_off[3] = p.part_off[2] + groups * s.rtiles * r.m;
+    // How the row minima leave: final with one slice; 8 or more row partials per row (one 256-column slice each at 2048 points, or
+    // narrower ones) and a caller that reads packed words: the atomic form; up to 8 slices: the caller's next launch merges the
+    // partials on its way in -- a cloud's partials are read by ONE workgroup there (64 KB of distances at 8 slices, ~100 GB/s per
+    // CU); the narrow slices of small batches, several row super-tiles and callers that defer nothing keep the merge launch
+    if (p.rslices == 1 && s.rtiles == 1) p.rows = GEOADV_PLAN_ROWS_FINAL;
+    else if (r.defer && r.packed && s.rtiles == 1 && p.rslices >= r.pack_from) p.rows = GEOADV_PLAN_ROWS_PACKED;
+    else if (r.defer && s.rtiles == 1 && p.rslices <= 8) p.rows = GEOADV_PLAN_ROWS_PARTIALS;
+    else p.rows = GEOADV_PLAN_ROWS_MERGE_LAUNCH;
+    // grid order: the search first (its latency-bound workgroups start at once), the scan, the Jacobian, the loss riders
+    p.lds_bytes = s.mx ? MX_LDS_BYTES : CS_LDS_BYTES;
+    if (r.search) {
+        p.search.count = grid_rider_blocks(r.b);
+        p.lds_bytes = std::max(p.lds_bytes, chamfer_grid_lds_bytes(r.n));
+    }
+    p.scan.first = p.search.count;
+    p.scan.count = s.rtiles * s.cslices * 8 * cdiv(r.b * r.np, 8);
+    p.grid = (unsigned)(p.search.count + p.scan.count);
+    if (r.jac) {
+        // LAST in the grid: every workgroup of the launch is charged the scan's 70 KB of LDS, so a CU holds two -- the search
+        // and the scan from the start; the Jacobian's workgroups take the search's places as those finish (~13 us into a 30 us
+        // scan).  Ahead of the scan they delayed it by their whole run time (51 instead of 33 us).
+        p.jac.first = (int)p.grid;
+        p.jac.count = r.b * (128 / JAC_ROWS);
+        p.raise_prio = p.jac.count * 2 <= kCUs ? 1 : 0;     // fewer riders than half the CUs (B <= 16): see JacRider
+        p.grid += (unsigned)p.jac.count;
+        p.lds_bytes = std::max(p.lds_bytes, JAC_LDS_BYTES);
+    }
+    // The loss riders (the unscreened kernel, one row super-tile, whole groups of 8 clouds, rows not left to a merge launch):
+    // riding pays in a narrow band only (tools/debug/loss_in_scan_ab.py, us per iteration riding / own launch, trajectories
+    // bit-identical everywhere): with the search's workgroups in the launch and two or more scan workgroups per CU, the riders of
+    // clouds whose slices ran first work under the later ones -- B = 64: 229.2 / 241.0, B = 96: 318.5 / 325.4 (B = 128: 428.2 /
+    // 427.2).  With one scan workgroup per CU every cloud's slowest slice ends with the launch: the riders start where a launch of
+    // their own would, and the producers' drained stores + the extra residents cost more than the boundary returns (B = 32: 134.1
+    // / 129.7, B = 16: 94.1 / 88.3; timeline in DESIGN 6); without the search (all-pairs) the scan's own workgroups hold every
+    // slot to the end (B = 32 ... 128: +- 0.6).
+    if (r.loss && !s.mx && s.rtiles == 1 && r.b % 8 == 0 && r.q_clouds == 0 && p.rows != GEOADV_PLAN_ROWS_MERGE_LAUNCH &&
+        (r.loss_force || (r.search && (long)s.rtiles * s.cslices * r.b * np_live >= 2 * (long)kCUs))) {
+        // behind everything else: a cloud's riders can only start once its scan and search workgroups are done.  Every workgroup
+        // of the scan (np problems, gated off or not) and of the search counts itself into done[cloud] once per call.
+        p.loss.first = (int)p.grid;
+        p.loss.count = loss_rider_blocks(r.b, r.loss_rows);
+        p.loss_arrivals = (unsigned)(r.np * s.rtiles * s.cslices + (r.search ? 2 * GR_QSPLIT : 0));
+        p.grid += (unsigned)p.loss.count;
+        p.lds_bytes = std::max(p.lds_bytes, loss_cgrad_lds_bytes(r.n));
+    }
+    return p;
 }
 
-// Scratch for `pairs` problems of `b` clouds each, in floats: an upper bound over the shapes the launcher may choose for
-// any number of live groups <= pairs * b (fewer live groups = narrower slices = more row partials per group).
+// Scratch floats per group of a launch of `groups` live groups: the plan's figure, the larger of the plain and the screened
+// kernel's (the switch may change between sizing and launching).
+static size_t sym_group_floats(long groups, int n, int m, bool loop) {
+    SymRequest plain{1, (int)groups, n, m, loop}, screened = plain;
+    plain.screen = false;
+    return std::max(chamfer_sym_plan(plain).group_floats, chamfer_sym_plan(screened).group_floats);
+}
+// Scratch for `pairs` problems of `b` clouds each, in floats: an upper bound over the shapes the plan may choose for
+// any number of live groups <= pairs * b (fewer live groups = narrower slices = more row partials per group), under either launch rule.
 size_t chamfer_sym_workspace_floats(int pairs, int b, int n, int m) {
     size_t per = 0;
-    for (int v = 0; v < 4; ++v) {                            // (either launch rule, screened or not: the switch may change later)
-        for (long g = 1; g <= (long)pairs * b; g *= 2) per = std::max(per, sym_group_floats(sym_shape(g, n, m, (v & 1) != 0, (v & 2) != 0), n, m));
-        per = std::max(per, sym_group_floats(sym_shape((long)pairs * b, n, m, (v & 1) != 0, (v & 2) != 0), n, m));
+    for (int loop = 0; loop < 2; ++loop) {
+        for (long g = 1; g <= (long)pairs * b; g *= 2) per = std::max(per, sym_group_floats(g, n, m, loop != 0));
+        per = std::max(per, sym_group_floats((long)pairs * b, n, m, loop != 0));
     }
     return (size_t)pairs * b * per + 64;
 }
 
-// Will launch_chamfer_sym_loop fold the row minima into the caller's packed words (SymPartials::row64) at this shape?  (The caller
-// fills them with all ones beforehand only then.)  live_groups: clouds x problems that are not gated off.
-bool chamfer_sym_packs_rows(long live_groups, int n, int m, int pack_from) {
-    const SymShape s = sym_shape(live_groups, n, m, true, mx_enabled());
-    return s.rtiles == 1 && s.cslices * s.cw >= pack_from;
+SymRows chamfer_sym_rows(const SymPlan &p, const float *workspace, const unsigned long long *row64) {
+    if (p.rows == GEOADV_PLAN_ROWS_PACKED) return SymRows{nullptr, nullptr, 0, p.req.b, true, row64};
+    if (p.rows == GEOADV_PLAN_ROWS_PARTIALS)
+        return SymRows{workspace + p.part_off[0], reinterpret_cast<const int *>(workspace + p.part_off[1]), p.rslices, p.req.b, true, nullptr};
+    return SymRows{nullptr, nullptr, 1, p.req.b, false, nullptr};
 }
 
-// pairs: up to 2 problems with identical (n, m).  Requires n >= 1, m >= 1.
-int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, int pair_base,
-                          int q_clouds, const int *need1, hipStream_t stream, const GridArgs *rider = nullptr,
-                          const JacRider *jac = nullptr, SymPartials *defer = nullptr, bool loop = false, LossRider *loss = nullptr,
-                          SymLaunchInfo *info = nullptr);
 int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, hipStream_t stream) {
-    return launch_chamfer_sym_ex(pairs, np, b, n, m, workspace, 0, 0, nullptr, stream);
-}
-// need1: per-cloud flags (int[8 * b], 16-byte aligned) restricting the SECOND pair to the clouds that still need the all-pairs kernel
-// rider (rider->n <= GR_MAX_N): the paired grid search as 8 * b extra workgroups of the scan launch; jac (or null): the pool
-// Jacobian's 8 * b workgroups as well (jac->first_block / blocks are set here); defer (or null): see SymPartials
-int launch_chamfer_sym_loop(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, const int *need1,
-                            const GridArgs *rider, const JacRider *jac, SymPartials *defer, hipStream_t stream, LossRider *loss,
-                            SymLaunchInfo *info) {
-    return launch_chamfer_sym_ex(pairs, np, b, n, m, workspace, 0, 0, need1, stream, rider, jac, defer, true, loss, info);
-}
-bool chamfer_sym_hosts_loss(long live_groups, int b, int n, int m) {
-    const SymShape s = sym_shape(live_groups, n, m, true, mx_enabled());
-    return !s.mx && s.rtiles == 1 && b % 8 == 0;
+    SymRequest r{np, b, n, m};
+    r.screen = chamfer_sym_screen_on();
+    return launch_chamfer_sym(chamfer_sym_plan(r), pairs, workspace, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
-int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, int pair_base,
-                          int q_clouds, const int *need1, hipStream_t stream, const GridArgs *rider, const JacRider *jac,
-                          SymPartials *defer, bool loop, LossRider *loss, SymLaunchInfo *info) {
-    if (loss) loss->blocks = 0;
-    unsigned long long *row64 = defer ? defer->row64 : nullptr;
-    const int pack_from = defer ? defer->pack_from : SYM_PACK_FROM;
-    if (defer) { defer->slices = 1; defer->rowpart_d = nullptr; defer->rowpart_i = nullptr; defer->clouds = b; defer->deferred = false; defer->row64 = nullptr; }
-    if (b <= 0 || np <= 0) return GEOADV_OK;
+int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *workspace, const int *need1, const GridArgs *rider,
+                       const JacRider *jac, const LossRider *loss, unsigned long long *row64, hipStream_t stream) {
+    const SymRequest &r = p.req;
+    if (p.grid == 0) return GEOADV_OK;
+    GA_REQUIRE((need1 != nullptr) == r.need1 && (rider != nullptr) == (p.search.count > 0) && (jac != nullptr) == (p.jac.count > 0) &&
+                   (p.loss.count == 0 || loss) && (p.rows != GEOADV_PLAN_ROWS_PACKED || row64),
+               "chamfer_sym: the launch's arguments are not the ones its plan was made for");
+    const SymShape &s = p.shape;
     ChamferSymArgs a;
     a.need[0] = nullptr; a.need[1] = need1;
-    a.pair_base = pair_base; a.q_clouds = q_clouds;
-    for (int i = 0; i < np; ++i) a.pr[i] = pairs[i];
-    a.n = n; a.m = m; a.clouds = b; a.pairs = np;
-    // (a second pair gated by `need1` usually has no work at all -- the grid search answers it -- so it does not count)
-    const int np_live = need1 ? 1 : np;
-    const SymShape s = sym_shape((long)b * np_live, n, m, loop, mx_enabled());
+    a.pair_base = r.pair_base; a.q_clouds = r.q_clouds;
+    for (int i = 0; i < r.np; ++i) a.pr[i] = pairs[i];
+    a.n = r.n; a.m = r.m; a.clouds = r.b; a.pairs = r.np;
     a.rw = s.rw; a.cw = s.cw; a.rtiles = s.rtiles; a.C = s.C; a.S = s.S; a.cslices = s.cslices;
-    const int rslices = s.cslices * s.cw;
-    const size_t groups = (size_t)np * b;
-    a.rowpart_d = workspace;
-    a.rowpart_i = reinterpret_cast<int *>(workspace + groups * rslices * n);
-    a.colpart_d = workspace + 2 * groups * rslices * n;
-    a.colpart_i = reinterpret_cast<int *>(a.colpart_d + groups * s.rtiles * m);
-    // 8 or more row partials per row (one 256-column slice each at 2048 points, or narrower ones) and a caller that reads packed
-    // words: atomic form
-    a.row64 = (defer && row64 && s.rtiles == 1 && rslices >= pack_from) ? row64 : nullptr;
+    a.rowpart_d = workspace + p.part_off[0];
+    a.rowpart_i = reinterpret_cast<int *>(workspace + p.part_off[1]);
+    a.colpart_d = workspace + p.part_off[2];
+    a.colpart_i = reinterpret_cast<int *>(workspace + p.part_off[3]);
+    a.row64 = p.rows == GEOADV_PLAN_ROWS_PACKED ? row64 : nullptr;
     static DeviceOnce attr;
     if (int rc = attr.run([]() -> int {
             const int need = (int)std::max(std::max(std::max(CS_LDS_BYTES, MX_LDS_BYTES), chamfer_grid_lds_bytes(GR_MAX_N)), JAC_LDS_BYTES);
@@ -557,84 +598,24 @@ int launch_chamfer_sym_ex(const ChamferPair *pairs, int np, int b, int n, int m,
             GA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_mx_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, need));
             return GEOADV_OK;
         })) return rc;
-    unsigned grid = (unsigned)(s.rtiles * s.cslices * 8 * cdiv(b * np, 8));
-    a.rider.blocks = 0; a.rider.first_block = 0; a.rider.clouds = 0; a.rider.done = nullptr;
-    a.loss.blocks = 0; a.loss.first_block = 0; a.loss.done = nullptr;
-    size_t scan_lds = s.mx ? MX_LDS_BYTES : CS_LDS_BYTES;
-    // ... which pays in a narrow band only (tools/debug/loss_in_scan_ab.py, us per iteration riding / own launch, trajectories
-    // bit-identical everywhere): with the search's workgroups in the launch and two or more scan workgroups per CU, the riders of
-    // clouds whose slices ran first work under the later ones -- B = 64: 229.2 / 241.0, B = 96: 318.5 / 325.4 (B = 128: 428.2 /
-    // 427.2).  With one scan workgroup per CU every cloud's slowest slice ends with the launch: the riders start where a launch of
-    // their own would, and the producers' drained stores + the extra residents cost more than the boundary returns (B = 32: 134.1
-    // / 129.7, B = 16: 94.1 / 88.3; timeline in DESIGN 6); without the search (all-pairs) the scan's own workgroups hold every
-    // slot to the end (B = 32 ... 128: +- 0.6).
-    const bool host_loss = loss && !s.mx && s.rtiles == 1 && b % 8 == 0 && q_clouds == 0 &&
-                           (loss->force || (rider != nullptr && (long)s.rtiles * s.cslices * b * np_live >= 2 * (long)kCUs));
-    if (rider) {
-        a.rider.g = *rider;
-        a.rider.first_block = 0;                           // dispatched first: its latency-bound workgroups start at once
-        a.rider.blocks = grid_rider_blocks(b);
-        a.rider.clouds = b;
-        if (host_loss) a.rider.done = loss->done;
-        grid += (unsigned)a.rider.blocks;
-        scan_lds = std::max(scan_lds, chamfer_grid_lds_bytes(rider->n));
-    }
-    a.jac.blocks = 0; a.jac.first_block = 0; a.jac.raise_prio = 0;
-    if (jac) {
-        // LAST in the grid: every workgroup of the launch is charged the scan's 70 KB of LDS, so a CU holds two -- the search
-        // and the scan from the start; the Jacobian's workgroups take the search's places as those finish (~13 us into a 30 us
-        // scan).  Ahead of the scan they delayed it by their whole run time (51 instead of 33 us).
-        a.jac = *jac;
-        a.jac.first_block = (int)grid;
-        a.jac.blocks = b * (128 / JAC_ROWS);
-        a.jac.raise_prio = a.jac.blocks * 2 <= kCUs ? 1 : 0;     // fewer riders than half the CUs (B <= 16): see JacRider
-        grid += (unsigned)a.jac.blocks;
-        scan_lds = std::max(scan_lds, JAC_LDS_BYTES);
-    }
-    // how the row minima will leave this launch (what `defer` reports below), known before the launch: the loss riders read them
-    SymPartials plan{nullptr, nullptr, 1, b, false, nullptr};
-    bool merge_launch = false;
-    if (rslices == 1 && s.rtiles == 1) {}                               // final in dist1 / idx1
-    else if (a.row64) { plan.deferred = true; plan.slices = 0; plan.row64 = a.row64; }
-    else if (defer && s.rtiles == 1 && rslices <= 8) { plan.deferred = true; plan.slices = rslices; plan.rowpart_d = a.rowpart_d; plan.rowpart_i = a.rowpart_i; }
-    else merge_launch = true;
-    if (info) {
-        info->mx = s.mx ? 1 : 0; info->rtiles = s.rtiles; info->rslices = rslices;
-        info->rows = merge_launch ? GEOADV_PLAN_ROWS_MERGE_LAUNCH : !plan.deferred ? GEOADV_PLAN_ROWS_FINAL : plan.row64 ? GEOADV_PLAN_ROWS_PACKED : GEOADV_PLAN_ROWS_PARTIALS;
-    }
-    if (host_loss && !merge_launch) {
-        // behind everything else: a cloud's riders can only start once its scan and search workgroups are done.  Every workgroup
-        // of the scan (np problems, gated off or not) and of the search counts itself into done[cloud] once per call.
-        loss->first_block = (int)grid;
-        loss->blocks = loss_rider_blocks(b, loss->rows);
-        loss->clouds = b;
-        loss->target += (unsigned)(np * s.rtiles * s.cslices + (rider ? 2 * GR_QSPLIT : 0));
-        if (loss->patch) loss->patch(*loss, plan, loss->ctx);
-        a.loss = *loss;
-        grid += (unsigned)a.loss.blocks;
-        scan_lds = std::max(scan_lds, loss_cgrad_lds_bytes(n));
-    } else if (a.rider.done) a.rider.done = nullptr;
-    if (!s.mx) chamfer_sym_kernel<<<grid, CS_THREADS, scan_lds, stream>>>(a);
-    else if (s.C == 256) chamfer_mx_kernel<8><<<grid, MX_THREADS, scan_lds, stream>>>(a);
-    else if (s.C == 128) chamfer_mx_kernel<4><<<grid, MX_THREADS, scan_lds, stream>>>(a);
-    else chamfer_mx_kernel<2><<<grid, MX_THREADS, scan_lds, stream>>>(a);
+    a.rider.first_block = p.search.first; a.rider.blocks = p.search.count; a.rider.clouds = rider ? r.b : 0;
+    a.rider.done = rider && p.loss.count ? loss->done : nullptr;      // the search's workgroups count in only when the loss riders wait for them
+    if (rider) a.rider.g = *rider;
+    if (jac) a.jac = *jac;
+    a.jac.first_block = p.jac.first; a.jac.blocks = p.jac.count; a.jac.raise_prio = p.raise_prio;
+    if (p.loss.count) a.loss = *loss;
+    else a.loss.done = nullptr;
+    a.loss.first_block = p.loss.first; a.loss.blocks = p.loss.count; a.loss.clouds = r.b;
+    if (p.kernel == 0) chamfer_sym_kernel<<<p.grid, CS_THREADS, p.lds_bytes, stream>>>(a);
+    else if (p.kernel == 8) chamfer_mx_kernel<8><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
+    else if (p.kernel == 4) chamfer_mx_kernel<4><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
+    else chamfer_mx_kernel<2><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
     GA_LAUNCH_CHECK();
-    if (rslices == 1 && s.rtiles == 1) return GEOADV_OK;  // both sides left the scan final
-    if (a.row64) {                                         // the caller's next launch unpacks the folded words on its way in
-        defer->deferred = true; defer->slices = 0; defer->row64 = a.row64;
-        return GEOADV_OK;
-    }
-    // the caller's next launch merges the row partials on its way in -- up to 8 slices: a cloud's partials are read by ONE
-    // workgroup there (64 KB of distances at 8 slices, ~100 GB/s per CU); the narrow slices of small batches keep the merge launch
-    if (defer && s.rtiles == 1 && rslices <= 8) {
-        defer->slices = rslices; defer->rowpart_d = a.rowpart_d; defer->rowpart_i = a.rowpart_i; defer->deferred = true;
-        return GEOADV_OK;
-    }
-    chamfer_sym_merge_kernel<<<dim3(cdiv(std::max(n, m), 256), b * np), 256, 0, stream>>>(a);
+    if (p.rows != GEOADV_PLAN_ROWS_MERGE_LAUNCH) return GEOADV_OK;   // final, or the caller's next launch reads partials / packed words
+    chamfer_sym_merge_kernel<<<dim3(cdiv(std::max(r.n, r.m), 256), r.b * r.np), 256, 0, stream>>>(a);
     GA_LAUNCH_CHECK();
     return GEOADV_OK;
 }
-
 
 // out[pair] = mean(dist1[pair]) + mean(dist2[pair])  (chamfer_dist of prepare_indices_for_attack.py:113-114)
 __global__ __launch_bounds__(256) void chamfer_pair_mean_kernel(int n, int m, const float *d1, const float *d2, float *out) {
@@ -660,8 +641,7 @@ using namespace geoadv;
 // Scratch of geoadv_chamfer_matrix for `cnt` pairs processed together, in floats: the four nn_distance outputs of every pair +
 // the symmetric scan's partials at the launch shape `cnt` groups get (fewer groups = narrower column slices = more row partials each).
 static size_t matrix_floats(size_t cnt, int n, int m) {
-    return cnt * 2 * ((size_t)n + m) + cnt * std::max(sym_group_floats(sym_shape((long)cnt, n, m, false, false), n, m),
-                                                      sym_group_floats(sym_shape((long)cnt, n, m, false, true), n, m)) + 64;
+    return cnt * 2 * ((size_t)n + m) + cnt * sym_group_floats((long)cnt, n, m, false) + 64;
 }
 
 extern "C" size_t geoadv_chamfer_matrix_workspace_floats(int na, int nb, int n, int m) {
@@ -690,7 +670,9 @@ extern "C" int geoadv_chamfer_matrix(int na, int nb, int n, int m, const float *
         float *ws = reinterpret_cast<float *>(i2 + (size_t)cnt * m);
         const ChamferPair pr{A, B, d1, i1, d2, i2};
         GA_REQUIRE(base <= 0x7fffffff, "chamfer_matrix: too many pairs");
-        if (int rc = launch_chamfer_sym_ex(&pr, 1, cnt, n, m, ws, (int)base, nb, nullptr, st)) return rc;
+        SymRequest rq{1, cnt, n, m};
+        rq.q_clouds = nb; rq.pair_base = (int)base; rq.screen = chamfer_sym_screen_on();
+        if (int rc = launch_chamfer_sym(chamfer_sym_plan(rq), &pr, ws, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return rc;
         chamfer_pair_mean_kernel<<<cnt, 256, 0, st>>>(n, m, d1, d2, out + base);
         GA_LAUNCH_CHECK();
         base += cnt_;
@@ -702,12 +684,12 @@ extern "C" int geoadv_chamfer_matrix(int na, int nb, int n, int m, const float *
 // The operator launches with exactly b live groups, so its scratch is the partials of THAT shape (the bound over every possible
 // live-group count, chamfer_sym_workspace_floats, is what an attack handle needs: its need flags change the count from call to call).
 static size_t nn_sym_floats(int b, int n, int m) {
-    return (size_t)b * std::max(sym_group_floats(sym_shape((long)b, n, m, false, false), n, m), sym_group_floats(sym_shape((long)b, n, m, false, true), n, m)) + 64;
+    return (size_t)b * sym_group_floats((long)b, n, m, false) + 64;
 }
 extern "C" int geoadv_set_chamfer_screen(int on) { return g_mx_on.exchange(on ? 1 : 0); }
 // 1 if geoadv_nn_distance_sym answers this shape with the matrix-pipe-screened kernel (chamfer_mx.h), 0 if with the unscreened scan
 extern "C" int geoadv_nn_distance_sym_is_screened(int b, int n, int m) {
-    return (b > 0 && n > 0 && m > 0 && sym_shape((long)b, n, m, false, mx_enabled()).mx) ? 1 : 0;
+    return (b > 0 && n > 0 && m > 0 && sym_shape((long)b, n, m, false, chamfer_sym_screen_on()).mx) ? 1 : 0;
 }
 extern "C" size_t geoadv_nn_distance_sym_workspace_floats(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 64;
@@ -723,5 +705,26 @@ extern "C" int geoadv_nn_distance_sym(int b, int n, const float *xyz1, int m, co
     const ChamferPair pr{xyz1, xyz2, dist1, idx1, dist2, idx2};
     if (int rc = launch_chamfer_sym(&pr, 1, b, n, m, workspace, as_stream(stream))) return rc;
     return launch_nn_nonfinite_fix(b, n, xyz1, m, xyz2, dist1, idx1, dist2, idx2, as_stream(stream));
+}
+// host only: the plan of a request, for the tests (include/geoadv.h: GEOADV_SYM_REQ_*, GEOADV_SYM_OUT_*)
+extern "C" int geoadv_debug_chamfer_sym_plan(const int *q, int *out) {
+    GA_REQUIRE(q && out, "debug_chamfer_sym_plan: null argument");
+    GA_REQUIRE(q[GEOADV_SYM_REQ_NP] >= 1 && q[GEOADV_SYM_REQ_NP] <= 2 && q[GEOADV_SYM_REQ_B] >= 1 && q[GEOADV_SYM_REQ_N] >= 1 && q[GEOADV_SYM_REQ_M] >= 1,
+               "debug_chamfer_sym_plan: bad dimensions");
+    SymRequest r{q[GEOADV_SYM_REQ_NP], q[GEOADV_SYM_REQ_B], q[GEOADV_SYM_REQ_N], q[GEOADV_SYM_REQ_M], q[GEOADV_SYM_REQ_LOOP] != 0,
+                 q[GEOADV_SYM_REQ_NEED1] != 0, q[GEOADV_SYM_REQ_SEARCH] != 0, q[GEOADV_SYM_REQ_JAC] != 0, q[GEOADV_SYM_REQ_LOSS] != 0,
+                 q[GEOADV_SYM_REQ_LOSS_ROWS], q[GEOADV_SYM_REQ_LOSS_FORCE] != 0, q[GEOADV_SYM_REQ_DEFER] != 0, q[GEOADV_SYM_REQ_PACKED] != 0,
+                 q[GEOADV_SYM_REQ_PACK_FROM], q[GEOADV_SYM_REQ_Q_CLOUDS], 0, q[GEOADV_SYM_REQ_SCREEN] != 0};
+    const SymPlan p = chamfer_sym_plan(r);
+    auto clip = [](size_t v) { return (int)std::min<size_t>(v, INT_MAX); };
+    const int o[GEOADV_SYM_OUT_COUNT] = {p.shape.mx ? 1 : 0, p.kernel, p.shape.rw, p.shape.cw, p.shape.rtiles, p.shape.C, p.shape.S, p.shape.cslices,
+                                         p.rslices, p.rows, p.search.first, p.search.count, p.scan.first, p.scan.count, p.jac.first, p.jac.count,
+                                         p.loss.first, p.loss.count, clip(p.grid), clip(p.lds_bytes), (int)p.loss_arrivals, p.raise_prio,
+                                         clip(p.group_floats), clip(p.part_off[0]), clip(p.part_off[1]), clip(p.part_off[2]), clip(p.part_off[3])};
+    for (int i = 0; i < GEOADV_SYM_OUT_COUNT; ++i) out[i] = o[i];
+    return GEOADV_OK;
+}
+extern "C" size_t geoadv_debug_chamfer_sym_workspace_floats(int pairs, int b, int n, int m) {
+    return (pairs <= 0 || b <= 0 || n <= 0 || m <= 0) ? 64 : chamfer_sym_workspace_floats(pairs, b, n, m);
 }
 GA_STAMPS_GETTER(geoadv_debug_stamps_chamfer_sym)

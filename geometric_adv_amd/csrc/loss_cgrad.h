@@ -39,7 +39,7 @@ struct LossArgs {
     // the symmetric scan's row minima still in one partial per column slice (chamfer_sym.h; slices <= 1: r1 / a1 are final):
     // r1 of every cloud, a1 of the clouds the all-pairs kernel computed (a1_all, or their `a1_need` flags).  This block forms
     // the minima on its way in and leaves them in r1 / a1 (mutable here for that reason).
-    SymPartials part;
+    SymRows part;
     const int *a1_need; int a1_all;
     float *r1_out, *a1_out;
     int fold_in_lds = 0;              // tests only: packed words go through loss_premerge's LDS arrays like the partials do
@@ -479,19 +479,16 @@ __device__ __forceinline__ void loss_cgrad_block(const LossArgs &la, const CGrad
 // dealt so that cloud b's sit on XCD b % 8 -- where that cloud's scan and search workgroups ran, whose plain stores are then visible
 // in the shared L2 (tools/handoff_probe.py: same-XCD hand-offs need no agent-scope data accesses; geoadv_attack verifies the
 // block -> XCD dealing once per device before it asks for this).  A rider waits until done[b] has reached `target` (every producer
-// of cloud b adds one on its way out, after draining its stores), bounded; then one L1 invalidate and the usual body.
+// of cloud b adds one on its way out, after draining its stores), bounded; then one L1 invalidate and the usual body.  Nothing here
+// decides: whether and where they ride is the plan's decision (chamfer_sym.h: SymPlan::loss), which the launcher copies in here.
 struct LossRider {
     LossArgs la; CGradArgs ca;
     int H, rows, first_block, blocks, clouds;
     unsigned *done;            // [clouds] arrival counters (never reset: `target` is cumulative over the calls)
     unsigned target;
     int *spin_timeout;
-    // host side only: the hosting launcher knows how the row minima will leave the scan (final / packed words / partials per slice)
-    // only once it has chosen its launch shape; it hands that to the caller's `patch`, which completes la / ca before the launch
-    void (*patch)(LossRider &, const SymPartials &, void *);
-    void *ctx;
-    bool force;                // host them wherever the launch CAN (the parity tests; the default hosts them where it pays)
-};
+    void *unused_[2] = {nullptr, nullptr}; bool unused_flag_ = false;   // (three former host-side slots, always zero: they keep the
+};                                                                      // kernel arguments' offsets, see SymRows in chamfer_sym.h)
 inline int loss_rider_blocks(int clouds, int rows) { return 8 * ((clouds + 7) / 8) * rows; }
 __device__ __forceinline__ bool loss_rider_block(const LossRider &r, unsigned *dyn) {
     if (r.blocks == 0 || (int)blockIdx.x < r.first_block || (int)blockIdx.x >= r.first_block + r.blocks) return false;

@@ -860,6 +860,28 @@ enum { GEOADV_PLAN_LOSS_METRICS = 0, GEOADV_PLAN_LOSS_FUSED = 1, GEOADV_PLAN_LOS
 enum { GEOADV_PLAN_GRAD_NONE = 0, GEOADV_PLAN_GRAD_FUSED_1PASS = 1, GEOADV_PLAN_GRAD_FUSED_GENERAL = 2, GEOADV_PLAN_GRAD_STEP_FX_1PASS = 3,
        GEOADV_PLAN_GRAD_STEP_FX_GENERAL = 4, GEOADV_PLAN_GRAD_STEP_SORTED = 5 };
 int geoadv_attack_test_plan(geoadv_attack *at, int plan[GEOADV_PLAN_COUNT], int *jstar, void *stream);
+/* TESTS ONLY, host only (no device is touched): every decision of one launch of the symmetric Chamfer scan, as the pure plan function
+ * behind geoadv_nn_distance_sym, geoadv_chamfer_matrix, the training step and the attack loop's forward makes it.
+ * request[GEOADV_SYM_REQ_COUNT]: problems (1 or 2), clouds, rows, columns; flags: the loop's launch rule, second pair gated, the
+ * search / Jacobian / loss riders asked for (+ workgroups per cloud of the loss riders, + hosted wherever possible), the caller takes
+ * deferred rows, has a packed buffer (+ the fewest partials per row that are packed); clouds of the second operand of an all-pairs
+ * matrix (0: cloud c against cloud c); the screen switch.  out[GEOADV_SYM_OUT_COUNT]: screened, kernel (0 plain, 2 / 4 / 8 screened),
+ * the launch shape, row partials per row, GEOADV_PLAN_ROWS_*, (first block, blocks) of the search, the scan, the Jacobian and the loss
+ * riders, the grid, dynamic LDS bytes, arrivals a cloud's loss counter gains, the Jacobian riders' priority flag, scratch floats per
+ * (pair, cloud) group and the offsets of the four partial arrays in floats (sizes saturate at INT_MAX). */
+enum { GEOADV_SYM_REQ_NP = 0, GEOADV_SYM_REQ_B, GEOADV_SYM_REQ_N, GEOADV_SYM_REQ_M, GEOADV_SYM_REQ_LOOP, GEOADV_SYM_REQ_NEED1,
+       GEOADV_SYM_REQ_SEARCH, GEOADV_SYM_REQ_JAC, GEOADV_SYM_REQ_LOSS, GEOADV_SYM_REQ_LOSS_ROWS, GEOADV_SYM_REQ_LOSS_FORCE,
+       GEOADV_SYM_REQ_DEFER, GEOADV_SYM_REQ_PACKED, GEOADV_SYM_REQ_PACK_FROM, GEOADV_SYM_REQ_Q_CLOUDS, GEOADV_SYM_REQ_SCREEN,
+       GEOADV_SYM_REQ_COUNT };
+enum { GEOADV_SYM_OUT_SCREENED = 0, GEOADV_SYM_OUT_KERNEL, GEOADV_SYM_OUT_RW, GEOADV_SYM_OUT_CW, GEOADV_SYM_OUT_RTILES, GEOADV_SYM_OUT_C,
+       GEOADV_SYM_OUT_S, GEOADV_SYM_OUT_CSLICES, GEOADV_SYM_OUT_RSLICES, GEOADV_SYM_OUT_ROWS, GEOADV_SYM_OUT_SEARCH_FIRST,
+       GEOADV_SYM_OUT_SEARCH_BLOCKS, GEOADV_SYM_OUT_SCAN_FIRST, GEOADV_SYM_OUT_SCAN_BLOCKS, GEOADV_SYM_OUT_JAC_FIRST, GEOADV_SYM_OUT_JAC_BLOCKS,
+       GEOADV_SYM_OUT_LOSS_FIRST, GEOADV_SYM_OUT_LOSS_BLOCKS, GEOADV_SYM_OUT_GRID, GEOADV_SYM_OUT_LDS_BYTES, GEOADV_SYM_OUT_LOSS_ARRIVALS,
+       GEOADV_SYM_OUT_RAISE_PRIO, GEOADV_SYM_OUT_GROUP_FLOATS, GEOADV_SYM_OUT_ROWPART_D, GEOADV_SYM_OUT_ROWPART_I, GEOADV_SYM_OUT_COLPART_D,
+       GEOADV_SYM_OUT_COLPART_I, GEOADV_SYM_OUT_COUNT };
+int geoadv_debug_chamfer_sym_plan(const int *request, int *out);
+/* ... and the scratch, in floats, that covers every plan of `pairs` problems of b clouds (what an attack handle reserves). */
+size_t geoadv_debug_chamfer_sym_workspace_floats(int pairs, int b, int n, int m);
 
 /* How nn_distance(adv, x) is being answered: *searched = 1 if the paired grid search is in use for this handle (0: all-pairs
  * kernel, by configuration or batch size), *handed_back = number of clouds of the batch whose pairing the search currently

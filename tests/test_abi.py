@@ -16,7 +16,7 @@ def test_header_declares_the_boundary():
     names = _declared()
     for must in ["geoadv_nn_distance", "geoadv_nn_distance_grad", "geoadv_approx_match", "geoadv_match_cost",
                  "geoadv_match_cost_grad", "geoadv_selection_sort", "geoadv_group_point", "geoadv_group_point_grad",
-                 "geoadv_query_ball_point", "geoadv_knn_point", "geoadv_attack_run"]:
+                 "geoadv_query_ball_point", "geoadv_knn_point", "geoadv_attack_run", "geoadv_debug_chamfer_sym_plan"]:
         assert must in names
 
 

@@ -1,0 +1,117 @@
+"""CPU: invariants of the symmetric Chamfer scan's launch plan (csrc/chamfer_sym.hip: chamfer_sym_plan), read through the
+host-only export geoadv_debug_chamfer_sym_plan -- no device is touched.  The sweep covers every cloud size at which the shape rule
+changes (wave layouts at 256 / 512 / 1024 rows, row super-tiles of 2048, the screened kernel above 1024, the search's limit at
+4096) and the sizes either side, for 1 ... 300 clouds, with the screen on and off, the second pair live or gated, and the loop's
+launch bare or with every rider and the deferred rows the attack's forward asks for."""
+import ctypes
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIZES = (1, 63, 64, 255, 256, 257, 511, 512, 513, 1000, 1024, 1025, 2047, 2048, 2049, 3000, 4096, 4097, 5000, 8192, 10001, 16385)
+BATCHES = range(1, 301)
+REQ = ("np", "b", "n", "m", "loop", "need1", "search", "jac", "loss", "loss_rows", "loss_force", "defer", "packed", "pack_from",
+       "q_clouds", "screen")                                                   # GEOADV_SYM_REQ_*
+OUT = ("screened", "kernel", "rw", "cw", "rtiles", "C", "S", "cslices", "rslices", "rows", "search_first", "search_blocks",
+       "scan_first", "scan_blocks", "jac_first", "jac_blocks", "loss_first", "loss_blocks", "grid", "lds_bytes", "loss_arrivals",
+       "raise_prio", "group_floats", "rowpart_d", "rowpart_i", "colpart_d", "colpart_i")   # GEOADV_SYM_OUT_*
+FINAL, PARTIALS, PACKED, MERGE_LAUNCH = range(4)                               # GEOADV_PLAN_ROWS_*
+PACK_FROM = 8
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import torch  # noqa: F401  -- before the library, so that both bind to one HIP runtime if GPU tests share the process
+    from geometric_adv_amd import _lib
+    import __graft_entry__
+    if not os.path.exists(_lib.LIB_PATH):
+        __graft_entry__.build()
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    so.geoadv_debug_chamfer_sym_workspace_floats.restype = ctypes.c_size_t
+    so.geoadv_nn_distance_sym_workspace_floats.restype = ctypes.c_size_t
+    return so
+
+
+def _plan(lib, **kw):
+    req = dict(np=2, b=1, n=1, m=1, loop=0, need1=0, search=0, jac=0, loss=0, loss_rows=0, loss_force=0, defer=0, packed=0,
+               pack_from=PACK_FROM, q_clouds=0, screen=1)
+    req.update(kw)
+    q = (ctypes.c_int * len(REQ))(*[int(req[k]) for k in REQ])
+    out = (ctypes.c_int * len(OUT))()
+    assert lib.geoadv_debug_chamfer_sym_plan(q, out) == 0
+    return dict(zip(OUT, out))
+
+
+def test_the_export_mirrors_the_header():
+    import re
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "geoadv.h")).read(), flags=re.S)
+    assert [s.lower() for s in re.findall(r"GEOADV_SYM_REQ_([A-Z0-9_]+)", text)] == list(REQ) + ["count"]
+    assert len(re.findall(r"GEOADV_SYM_OUT_([A-Z0-9_]+)", text)) == len(OUT) + 1
+
+
+def _check(p, b, n, np_, riders, where):
+    groups = np_ * b
+    # the four block ranges: disjoint, contiguous from 0, in the order search, scan, Jacobian, loss riders; absent ones are empty
+    at = 0
+    for k in ("search", "scan", "jac", "loss"):
+        if p[k + "_blocks"]:
+            assert p[k + "_first"] == at, where
+        assert p[k + "_blocks"] >= 0, where
+        at += p[k + "_blocks"]
+    assert at == p["grid"] and p["scan_blocks"] > 0, where
+    assert p["scan_blocks"] == p["rtiles"] * p["cslices"] * 8 * -(-groups // 8), where
+    assert (p["search_blocks"] > 0) == riders and (p["jac_blocks"] > 0) == riders, where
+    if p["loss_blocks"]:
+        assert riders and p["kernel"] == 0 and p["rtiles"] == 1 and b % 8 == 0 and p["rows"] != MERGE_LAUNCH, where
+        assert p["loss_arrivals"] > 0, where
+    else:
+        assert p["loss_arrivals"] == 0, where
+    assert (p["kernel"] != 0) == bool(p["screened"]) and p["kernel"] in (0, 2, 4, 8), where
+    assert p["rw"] * p["cw"] == 8 and p["rslices"] == p["cslices"] * p["cw"], where
+    # exactly one row exit, and each only where its reader can take it
+    assert p["rows"] in (FINAL, PARTIALS, PACKED, MERGE_LAUNCH), where
+    assert (p["rows"] == FINAL) == (p["rtiles"] == 1 and p["rslices"] == 1), where
+    if p["rows"] == PACKED:
+        assert riders and p["rtiles"] == 1 and p["rslices"] >= PACK_FROM, where
+    if p["rows"] == PARTIALS:
+        assert riders and p["rtiles"] == 1 and 2 <= p["rslices"] <= 8, where
+    # the partial arrays lie inside the scratch of `groups` groups
+    assert p["rowpart_d"] == 0 and p["rowpart_i"] == groups * p["rslices"] * n and p["colpart_d"] == 2 * p["rowpart_i"], where
+    assert p["colpart_d"] <= groups * p["group_floats"], where
+    if p["rtiles"] > 1:
+        assert p["colpart_i"] == p["colpart_d"] + groups * p["rtiles"] * n, where
+        assert p["colpart_i"] + groups * p["rtiles"] * n == groups * p["group_floats"], where
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_plan_invariants_and_scratch_bound(lib, n):
+    """Every combination must hold: nothing is skipped."""
+    checked = 0
+    for b in BATCHES:
+        arena = lib.geoadv_debug_chamfer_sym_workspace_floats(2, b, n, n)
+        operator = lib.geoadv_nn_distance_sym_workspace_floats(b, n, n)
+        for screen in (0, 1):
+            for need1 in (0, 1):
+                for riders in (False, True):
+                    where = "n=%d b=%d screen=%d need1=%d riders=%d" % (n, b, screen, need1, riders)
+                    kw = dict(search=1, jac=1, loss=1, loss_rows=3, loss_force=1, defer=1, packed=1) if riders else {}
+                    p = _plan(lib, np=2, b=b, n=n, m=n, loop=1, need1=need1, screen=screen, **kw)
+                    _check(p, b, n, 2, riders, where)
+                    assert 2 * b * p["group_floats"] + 64 <= arena, where
+                    checked += 1
+            p = _plan(lib, np=1, b=b, n=n, m=n, screen=screen)                 # the operator's launch: one pair, every cloud live
+            where = "operator n=%d b=%d screen=%d" % (n, b, screen)
+            _check(p, b, n, 1, False, where)
+            assert p["rows"] in (FINAL, MERGE_LAUNCH), where
+            assert b * p["group_floats"] + 64 <= operator, where
+    assert checked == len(BATCHES) * 8
+
+
+def test_riders_only_where_they_pay_unless_forced(lib):
+    """Without loss_force the loss riders need the search in the launch and two scan workgroups per CU (256 CUs)."""
+    kw = dict(np=2, n=2048, m=2048, loop=1, need1=1, search=1, jac=1, loss=1, loss_rows=3, defer=1, packed=1)
+    assert _plan(lib, b=32, **kw)["loss_blocks"] == 0 and _plan(lib, b=32, loss_force=1, **kw)["loss_blocks"] == 8 * 4 * 3
+    p = _plan(lib, b=64, **kw)
+    assert p["loss_blocks"] == 8 * 8 * 3 and p["rtiles"] * p["cslices"] * 64 >= 512
+    assert _plan(lib, b=64, **dict(kw, search=0))["loss_blocks"] == 0
