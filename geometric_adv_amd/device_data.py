@@ -154,3 +154,44 @@ class DevicePointCloudDataSet(object):
         else:
             clean, feed = gather_augmented(noisy, index, augment, counter, slot_offset, want_clean=True, clean_data=self.point_clouds)
         return clean, self.all_labels[index], feed
+
+
+class CloudAugmenter(object):
+    """The reference's AtlasNet Augmenter (transfer/atlasnet/dataset/augmenter.py) with its argument names, on resident clouds:
+    one ops.augment_batch launch per batch.  rotation_axis and flips are sequences of axes out of 0, 1, 2 (the axial rotations
+    are applied in ascending axis order); the operators come in the Augmenter's order and with its ranges.  The draws are the
+    device generator's (csrc/dataset.hip), keyed by (seed, the caller's batch counter, output slot): the reference's
+    distributions, not torch's numbers."""
+
+    def __init__(self, translation=False, rotation_axis=(), rotation_3D=False, anisotropic_scaling=False, flips=(), seed=0):
+        self.rotation_axis, self.flips = self._axes(rotation_axis, "rotation_axis"), self._axes(flips, "flips")
+        for name, v in (("translation", translation), ("rotation_3D", rotation_3D), ("anisotropic_scaling", anisotropic_scaling)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError("%s must be True or False, got %r" % (name, v))
+        self.translation, self.rotation_3D, self.anisotropic_scaling = bool(translation), bool(rotation_3D), bool(anisotropic_scaling)
+        self.seed = int(seed)
+
+    @staticmethod
+    def _axes(axes, name):
+        axes = list(axes)
+        if any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 0 <= a <= 2 for a in axes) or len(set(axes)) != len(axes):
+            raise ValueError("%s must hold distinct axes out of 0, 1, 2; got %r" % (name, axes))
+        return tuple(sorted(int(a) for a in axes))
+
+    @property
+    def active(self):
+        return bool(self.translation or self.rotation_axis or self.rotation_3D or self.anisotropic_scaling or self.flips)
+
+    def fields(self, counter=0, slot_offset=0):
+        """The fields of ops.CloudAugment for one batch (sample is left to ops.augment_batch)."""
+        return dict(seed=self.seed % (1 << 64), counter=int(counter) % (1 << 64), slot_offset=int(slot_offset),
+                    rot_axes=sum(1 << a for a in self.rotation_axis), rot_3d=int(self.rotation_3D), scale=int(self.anisotropic_scaling),
+                    flip_axes=sum(1 << a for a in self.flips), translate=int(self.translation))
+
+    def __call__(self, data, index, counter, slot_offset=0, sample_points=None):
+        """-> the batch (len(index), sample_points or data's points, 3) on the GPU: data[index], re-sampled with replacement
+        when sample_points is given, under this augmenter's operators."""
+        fields = self.fields(counter, slot_offset)
+        if sample_points:
+            fields["sample"] = 1
+        return ops.augment_batch(data, index, fields, n_out=sample_points or None)

@@ -374,6 +374,28 @@ def sort_axes(point_clouds, neg_rot=True):
     return out, axes_idx
 
 
+def _gather_index(index, num_clouds, dev):
+    """The source-cloud index of batch_gather / augment_batch -> (b, int32 device tensor or None for 0..num_clouds-1).  A host
+    index is range-checked here; a device index is not (the kernels never dereference a bad entry)."""
+    import numpy as np
+    if index is None:
+        return num_clouds, None
+    elif isinstance(index, torch.Tensor) and index.is_cuda:
+        if index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
+            raise ValueError("index must be a one-dimensional int32 or int64 tensor (got %s of shape %s)" % (index.dtype, tuple(index.shape)))
+        idx = index.to(device=dev, dtype=torch.int32).contiguous()
+        b = int(idx.numel())
+    else:
+        host = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+        if host.ndim != 1 or host.dtype.kind not in "iu":
+            raise ValueError("index must be a one-dimensional integer array")
+        if host.size and (int(host.min()) < 0 or int(host.max()) >= num_clouds):
+            raise ValueError("index out of range: values %d .. %d for %d clouds" % (int(host.min()), int(host.max()), num_clouds))
+        b = int(host.size)
+        idx = torch.from_numpy(host.astype(np.int32)).to(dev)
+    return b, idx
+
+
 class BatchAugment(C.Structure):
     """geoadv_batch_augment (include/geoadv.h): the noise generator's key (seed, counter, slot_offset), the noise (mu, sigma,
     clip; sigma 0 = none, clip <= 0 = unclamped) and the order of noise and rotation.  rot_count is filled in by batch_gather."""
@@ -396,21 +418,7 @@ def batch_gather(data, index=None, augment=None, rot=None, want_clean=False):
         raise ValueError("batch_gather only accepts 3d point sets")
     num_clouds, n, _ = data.shape
     dev = data.device
-    if index is None:
-        b, idx = num_clouds, None
-    elif isinstance(index, torch.Tensor) and index.is_cuda:
-        if index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
-            raise ValueError("index must be a one-dimensional int32 or int64 tensor (got %s of shape %s)" % (index.dtype, tuple(index.shape)))
-        idx = index.to(device=dev, dtype=torch.int32).contiguous()
-        b = int(idx.numel())
-    else:
-        host = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
-        if host.ndim != 1 or host.dtype.kind not in "iu":
-            raise ValueError("index must be a one-dimensional integer array")
-        if host.size and (int(host.min()) < 0 or int(host.max()) >= num_clouds):
-            raise ValueError("index out of range: values %d .. %d for %d clouds" % (int(host.min()), int(host.max()), num_clouds))
-        b = int(host.size)
-        idx = torch.from_numpy(host.astype(np.int32)).to(dev)
+    b, idx = _gather_index(index, num_clouds, dev)
     if b < 1 or n < 1:
         raise ValueError("batch_gather needs at least one cloud and one point (b=%d, n=%d)" % (b, n))
     aug = None
@@ -443,6 +451,87 @@ def batch_gather(data, index=None, augment=None, rot=None, want_clean=False):
         _call("geoadv_batch_gather", b, n, _lib.ptr(data), C.c_longlong(num_clouds), _lib.ptr(idx),
               C.byref(aug) if aug is not None else None, _lib.ptr(rot_dev), _lib.ptr(clean), _lib.ptr(feed))
     return (clean, feed) if want_clean else feed
+
+
+# ---------------------------------------------------------------------------------------------
+# AtlasNet's data side (transfer/atlasnet/dataset/pointcloud_processor.py, augmenter.py), device side
+# ---------------------------------------------------------------------------------------------
+NORMALIZATIONS = {"Identity": 0, "UnitBall": 1, "BoundingBox": 2}
+
+
+def normalize_clouds(point_clouds, normalization="UnitBall"):
+    """Normalization.normalize_unitL2ball_functional / normalize_bounding_box_functional / identity_functional
+    (pointcloud_processor.py:160-233) on a GPU tensor (b,n,3) -> a new tensor (b,n,3).  UnitBall: minus the cloud's mean, times
+    1 / sqrt(max ||p - mean||^2); BoundingBox: minus (min + max) / 2 per axis, times 1 / max_axis((max - min) / 2).  Centre and
+    factor are float64 and bitwise reproducible; (x - c) * s is rounded to fp32 once.  A cloud whose points all coincide, or
+    that holds a NaN, comes out all NaN, as in the reference.  1 <= n <= 2^20 (include/geoadv.h)."""
+    if normalization not in NORMALIZATIONS:
+        raise ValueError("normalization must be one of %s; got %r" % (sorted(NORMALIZATIONS), normalization))
+    pc = _f32(point_clouds, "point_clouds", 3)
+    if pc.shape[2] != 3:
+        raise ValueError("normalize_clouds only accepts 3d point sets")
+    b, n, _ = pc.shape
+    out = torch.empty_like(pc)
+    with torch.cuda.device(pc.device):
+        _call("geoadv_normalize_clouds", b, n, NORMALIZATIONS[normalization], _lib.ptr(pc), _lib.ptr(out))
+    return out
+
+
+AUGMENT_RECORD = 45     # GEOADV_AUGMENT_RECORD: 3 axial matrices, the 3-D matrix, scale, flip, translation
+
+
+class CloudAugment(C.Structure):
+    """geoadv_cloud_augment (include/geoadv.h): the generator's key (seed, counter, slot_offset), sample (points drawn with
+    replacement) and the Augmenter's operators: rot_axes / flip_axes are bit sets of the axes, rot_3d / scale / translate
+    switches.  The ranges default to the reference's: range_rot 360, scale 0.75 .. 1.25, translate_scale 0.03."""
+    _fields_ = [("seed", C.c_ulonglong), ("counter", C.c_ulonglong), ("slot_offset", C.c_int), ("sample", C.c_int),
+                ("rot_axes", C.c_int), ("range_rot", C.c_float), ("rot_3d", C.c_int), ("scale", C.c_int), ("scale_min", C.c_float),
+                ("scale_max", C.c_float), ("flip_axes", C.c_int), ("translate", C.c_int), ("translate_scale", C.c_float)]
+    DEFAULTS = dict(range_rot=360.0, scale_min=0.75, scale_max=1.25, translate_scale=0.03)
+
+
+def augment_batch(data, index=None, config=None, params=None, n_out=None, want_params=False):
+    """One AtlasNet training batch out of resident clouds in one launch (csrc/dataset.hip, geoadv_augment_batch): gather,
+    re-sampling, then the Augmenter's operators in its order (axial rotations, 3-D rotation, scale, flips, translation).
+    data: GPU float32 (num_clouds, n_src, 3).  index: as batch_gather's -- a host sequence (range-checked here), a device
+    integer tensor (a bad entry leaves its slot unwritten) or None = every cloud in order.
+    config: None (plain gather), a CloudAugment or a dict of its fields; fields left out of a dict take the reference's
+    defaults (CloudAugment.DEFAULTS), unknown keys are refused.  `sample` is set from n_out when the dict leaves it out.
+    n_out: points per output cloud; None = n_src.  Without sample it must equal n_src.
+    params: None, or explicit operators (b, 45) float32 (numpy or GPU): the enabled operators are taken from it, nothing is drawn.
+    -> out (b, n_out, 3), or (out, params (b, 45)) with want_params: the record that was applied (layout: include/geoadv.h)."""
+    import numpy as np
+    data = _f32(data, "data", 3)
+    if data.shape[2] != 3:
+        raise ValueError("augment_batch only accepts 3d point sets")
+    num_clouds, n_src, _ = data.shape
+    dev = data.device
+    b, idx = _gather_index(index, num_clouds, dev)
+    n_out = n_src if n_out is None else int(n_out)
+    if b < 1 or n_src < 1 or n_out < 1:
+        raise ValueError("augment_batch needs at least one cloud and one point (b=%d, n_src=%d, n_out=%d)" % (b, n_src, n_out))
+    cfg = None
+    if isinstance(config, CloudAugment):
+        cfg = CloudAugment.from_buffer_copy(config)
+    elif config is not None:
+        unknown = set(config) - {f for f, _ in CloudAugment._fields_}
+        if unknown:
+            raise ValueError("unknown config fields %s" % sorted(unknown))
+        fields = dict(CloudAugment.DEFAULTS, **config)
+        fields.setdefault("sample", int(n_out != n_src))
+        cfg = CloudAugment(**fields)
+    par = None
+    if params is not None:
+        par = params if isinstance(params, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32))
+        par = par.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(par.shape) != (b, AUGMENT_RECORD):
+            raise ValueError("params must be (%d, %d); got %s" % (b, AUGMENT_RECORD, tuple(par.shape)))
+    out = torch.empty((b, n_out, 3), dtype=torch.float32, device=dev)
+    par_out = torch.empty((b, AUGMENT_RECORD), dtype=torch.float32, device=dev) if want_params else None
+    with torch.cuda.device(dev):
+        _call("geoadv_augment_batch", b, n_out, _lib.ptr(data), C.c_longlong(num_clouds), n_src, _lib.ptr(idx),
+              C.byref(cfg) if cfg is not None else None, _lib.ptr(par), _lib.ptr(par_out), _lib.ptr(out))
+    return (out, par_out) if want_params else out
 
 
 # ---------------------------------------------------------------------------------------------

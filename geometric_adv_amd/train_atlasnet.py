@@ -8,8 +8,20 @@ which AtlasNetAE and run_transfer --transfer_ae_type AtlasNet read back.  Paths 
 
 A rerun in a folder that holds network.pth resumes from it (weights, running statistics, Adam's state, learning rate, epoch).
 At epochs --lr_decay_1/2/3 the learning rate is divided by 10 and a NEW Adam starts, as the reference does.  Left out:
-SPHERE, SVR, data augmentation, metro, visdom and the HTML report.  The epoch's shuffle is numpy's, seeded by --seed; the
+SPHERE, SVR, metro, visdom and the HTML report.  The epoch's shuffle is numpy's, seeded by --seed; the
 last, partial batch of an epoch is trained at its own size if it holds at least 2 clouds, else dropped.
+
+The data side (dataset/pointcloud_processor.py, dataset/augmenter.py, dataset_shapenet.py:213-215) runs on the GPU.  With
+--normalization UnitBall / BoundingBox, --sample_points K or any of the reference's augmentation flags (--random_rotation,
+--data_augmentation_axis_rotation, --data_augmentation_random_flips, --random_translation, --anisotropic_scaling) both sets are
+uploaded once and normalised once (ops.normalize_clouds), and every training batch is ONE ops.augment_batch launch: gather,
+K points drawn with replacement, the Augmenter's operators in its order.  The draws are keyed by (--seed, the number of
+training steps taken in all, the cloud's slot in the batch), so a resumed run continues the stream; they are the device
+generator's, with the reference's distributions and not torch's numbers.  The evaluation set is normalised and, with
+--sample_points, sampled once under a fixed key, and never augmented: loss_val is comparable across epochs.  The shuffle
+stream is the same with or without these flags, and with none of them the run is the host path, unchanged.
+--normalization defaults to Identity, not to the reference's UnitBall: the reference normalises only its ShapeNet cache,
+never the clouds of --custom_data (dataset_shapenet.py), and this command is always custom data.
 """
 import argparse
 import json
@@ -45,8 +57,30 @@ def build_parser():
     p.add_argument('--train_pc_path', type=str, required=True, help='.npy (clouds, points, 3)')
     p.add_argument('--eval_pc_path', type=str, required=True, help='.npy (clouds, points, 3)')
     p.add_argument('--top_dir', type=str, default='.', help='root that the path flags are relative to')
-    p.add_argument('--seed', type=int, default=0, help='initial weights, the shuffles and the template generator')
+    p.add_argument('--seed', type=int, default=0, help='initial weights, the shuffles, the template generator and the augmentation draws')
+    p.add_argument('--normalization', type=str, default='Identity', choices=['Identity', 'UnitBall', 'BoundingBox'],
+                   help='both sets are normalised once on the GPU.  [default: Identity -- the reference\'s UnitBall default only '
+                        'ever touches its ShapeNet cache, never --custom_data clouds, and this command is always custom data]')
+    p.add_argument('--sample_points', type=int, default=0,
+                   help='K > 0: every training cloud of a batch is K points drawn with replacement from the file\'s cloud (which may '
+                        'hold more, e.g. 30000), and the evaluation clouds are K points drawn once.  [default: 0 = off]')
+    p.add_argument('--random_rotation', action='store_true', help='apply data augmentation : random rotation')
+    p.add_argument('--data_augmentation_axis_rotation', action='store_true', help='apply data augmentation : random rotation about axis 1')
+    p.add_argument('--data_augmentation_random_flips', action='store_true', help='apply data augmentation : random flips of the axes 0 and 2')
+    p.add_argument('--random_translation', action='store_true', help='apply data augmentation : random translation')
+    p.add_argument('--anisotropic_scaling', action='store_true', help='apply data augmentation : anisotropic scaling')
     return p
+
+
+EVAL_SAMPLE_COUNTER = (1 << 64) - 1     # the fixed key of the evaluation set's sampling: no step counter reaches it
+
+
+def augmenter_of(flags):
+    """The device_data.CloudAugmenter of the reference's augmentation flags (training/trainer.py:60-62)."""
+    from .device_data import CloudAugmenter
+    return CloudAugmenter(translation=flags.random_translation, rotation_axis=(1,) if flags.data_augmentation_axis_rotation else (),
+                          rotation_3D=flags.random_rotation, anisotropic_scaling=flags.anisotropic_scaling,
+                          flips=(0, 2) if flags.data_augmentation_random_flips else (), seed=flags.seed)
 
 
 def fscore(dist1, dist2, threshold=FSCORE_THRESHOLD):
@@ -94,7 +128,20 @@ def main(argv=None):
         lrate, start_epoch = float(saved.get('lrate', lrate)), int(saved.get('start_epoch', 0))
         print('resuming from %s at epoch %d, learning rate %g' % (folder, start_epoch, lrate))
     B, n = flags.batch_size, train.shape[1]
-    trainers, current = {}, None      # one handle per batch size (the full one and the epoch's last, partial one)
+    if flags.sample_points < 0:
+        raise ValueError("--sample_points must be >= 0, got %d" % flags.sample_points)
+    augmenter, K = augmenter_of(flags), flags.sample_points
+    on_device = augmenter.active or K > 0 or flags.normalization != 'Identity'
+    if on_device:
+        import torch
+        from . import ops
+        device = torch.device("cuda:0")
+        train_dev = ops.normalize_clouds(torch.from_numpy(train).to(device), flags.normalization)
+        val = ops.normalize_clouds(torch.from_numpy(val).to(device), flags.normalization)
+        if K > 0:
+            val = ops.augment_batch(val, None, dict(seed=flags.seed % (1 << 64), counter=EVAL_SAMPLE_COUNTER, sample=1), n_out=K)
+            n = K
+    trainers, current = {}, None     # one handle per batch size (the full one and the epoch's last, partial one)
 
     def trainer(size):
         """The handle of this batch size, brought to the state of the one that stepped last."""
@@ -127,7 +174,12 @@ def main(argv=None):
                 idx = order[s:s + B]
                 if len(idx) < 2:
                     break
-                loss = trainer(len(idx)).train_step(train[idx])
+                if on_device:
+                    handle = trainer(len(idx))
+                    batch = augmenter(train_dev, idx, counter=handle.counters()[1], sample_points=K)
+                    loss = handle.train_step(batch)
+                else:
+                    loss = trainer(len(idx)).train_step(train[idx])
                 losses.append(loss)
                 print('[%d: %d/%d] chamfer train loss: %f' % (epoch, i, len(order) // B, loss))
         loss_val, fs = test_epoch(current, val, flags.batch_size_test)

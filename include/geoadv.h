@@ -252,6 +252,67 @@ int geoadv_batch_gather(int b, int n, const float *data, long long num_clouds, c
                         const geoadv_batch_augment *aug /* NULL = plain gather */, const double *rot /* device [rot_count][9], row-major */,
                         float *clean /* device [b,n,3] or NULL */, float *feed /* device [b,n,3] */, void *stream);
 
+/* Normalization (transfer/atlasnet/dataset/pointcloud_processor.py:160-233) on the device: out[b,n,3] = (pc - c) * s per cloud.
+ *   GEOADV_NORMALIZE_IDENTITY      the bits of pc
+ *   GEOADV_NORMALIZE_UNIT_BALL     c = the cloud's mean, s = 1 / sqrt(max_p ||p - c||^2)
+ *   GEOADV_NORMALIZE_BOUNDING_BOX  c = (min + max) / 2 per axis, s = 1 / max_axis((max - min) / 2)   (the reference's isotropic form)
+ * c and s are float64 (sums in a fixed order: bitwise reproducible, whatever the grid), (x - c) * s is evaluated in float64
+ * and rounded to fp32 once.  A NaN coordinate wins every extremum, so its cloud comes out all NaN; a cloud whose points all
+ * coincide (n = 1 included) comes out all NaN as well (0 * 1/0), as in the reference; other clouds are unaffected.
+ * out must not be pc.  b >= 1, 1 <= n <= 2^20, else GEOADV_EINVAL. */
+#define GEOADV_NORMALIZE_IDENTITY 0
+#define GEOADV_NORMALIZE_UNIT_BALL 1
+#define GEOADV_NORMALIZE_BOUNDING_BOX 2
+int geoadv_normalize_clouds(int b, int n, int kind, const float *pc, float *out, void *stream);
+
+/* One AtlasNet training batch in one launch: gather by index out of data[num_clouds,n_src,3], optional re-sampling of n_out
+ * points with replacement, then the Augmenter's operators (transfer/atlasnet/dataset/augmenter.py) in its order: axial
+ * rotations (ascending axis), 3-D rotation, anisotropic scale, flips, translation.  A point is a row vector times a matrix.
+ *
+ * The operators of an output cloud are one record of GEOADV_AUGMENT_RECORD fp32 values:
+ *   [0, 27)   the axial rotation about axis 0, 1, 2: three row-major 3x3 matrices (Operation.get_3D_rot_matrix)
+ *   [27, 36)  the 3-D rotation, row-major (DataAugmentation.get_random_rotation_matrix)
+ *   [36, 39)  scale per axis      [39, 42)  flip per axis (+1 / -1)      [42, 45)  translation per axis
+ * An operator that the configuration does not enable holds its identity (unit matrix, 1, 1, 0) and is not applied.
+ * params != NULL: device [b][GEOADV_AUGMENT_RECORD], the enabled operators are taken from it and nothing is drawn.
+ * params_out != NULL: device [b][GEOADV_AUGMENT_RECORD], receives the record that was applied, drawn or given.
+ * The fp32 operators are composed into one affine map in float64; every point is evaluated in float64 and rounded once.
+ * With no operator enabled the output holds the source points' bits.
+ *
+ * Draws of output slot s = slot_offset + i (mix = splitmix64's finaliser, G = 0x9e3779b97f4a7c15, 64-bit wrap-around):
+ *   r(q, k) = mix(mix(mix(mix(seed + G) ^ counter) ^ (s << 32 | q)) + k * G)       q = 0 for the operators, k the stream
+ *   u(k)  = (r >> 40) * 2^-24 in [0, 1);   normal g(k) = sqrt(-2 ln(((r >> 40) + 1) * 2^-24)) * cos(2 pi ((r >> 16) & 0xFFFFFF) * 2^-24)
+ *   axial, axis a      k = 16 + a   angle = u * 2K - K, K = pi * range_rot / 360 (float64); cos / sin in float64
+ *   3-D rotation       k = 19 + a   axis = (g(19), g(20), g(21)) / its norm;   k = 22   angle = u * 2 pi + pi (float64)
+ *   scale, axis a      k = 23 + a   u * (scale_max - scale_min) + scale_min           (fp32, every operation rounded)
+ *   flip, axis a       k = 26 + a   +1 where r >> 63 is set, else -1
+ *   translation, a     k = 29 + a   (u * 2) * translate_scale - translate_scale       (fp32, every operation rounded)
+ *   sample, point p    k = 32, q = p   source point j = ((r >> 32) * n_src) >> 32       (integers only)
+ * Matrix entries are computed in float64 and rounded to fp32 once.  The draws depend on (seed, counter, s, k, p) alone.
+ *
+ * GEOADV_EINVAL: a dimension < 1, out overlapping data (or params_out), n_out != n_src without sample, rot_axes or flip_axes
+ * outside [0, 7], range_rot outside (0, 360] with rot_axes, scale_min > scale_max or either not finite with scale, a
+ * translate_scale that is negative or not finite with translate, slot_offset < 0.  An index outside [0, num_clouds) is never
+ * dereferenced: that slot of out and params_out is left unwritten. */
+#define GEOADV_AUGMENT_RECORD 45
+typedef struct geoadv_cloud_augment {
+    unsigned long long seed, counter;  /* generator key; counter = the caller's global step ordinal */
+    int   slot_offset;                 /* slot of output cloud 0 (data-parallel ranks: rank * local batch) */
+    int   sample;                      /* 0: n_out == n_src, points in order; 1: n_out points drawn with replacement */
+    int   rot_axes;                    /* bit a: random rotation about axis a */
+    float range_rot;                   /* degrees, in (0, 360]; the reference's default is 360 */
+    int   rot_3d;                      /* 1: random 3-D rotation */
+    int   scale;                       /* 1: anisotropic scale in [scale_min, scale_max) */
+    float scale_min, scale_max;        /* the reference's defaults are 0.75 and 1.25 */
+    int   flip_axes;                   /* bit a: random flip of axis a */
+    int   translate;                   /* 1: translation in [-translate_scale, translate_scale) per axis */
+    float translate_scale;             /* the reference's default is 0.03 */
+} geoadv_cloud_augment;
+int geoadv_augment_batch(int b, int n_out, const float *data, long long num_clouds, int n_src,
+                         const int *index /* device [b] or NULL = 0..b-1 */, const geoadv_cloud_augment *cfg /* NULL = plain gather */,
+                         const float *params /* device [b][45] or NULL */, float *params_out /* device [b][45] or NULL */,
+                         float *out /* device [b,n_out,3] */, void *stream);
+
 /* get_dist_mat (src/general_utils.py:94-106) on the device: out[na,nb], out[i][j] = || a[i] - b[j] ||_2 of the fp32 row-major
  * a[na,d] and b[nb,d] -- the latent distance matrix of attacker/prepare_indices_for_attack.py:89-101.  Bit for bit numpy's
  * np.linalg.norm(s - t, axis=-1): fp32 differences, squares rounded on their own, numpy's pairwise summation order of a
