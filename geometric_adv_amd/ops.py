@@ -301,6 +301,77 @@ def knn_dists(pc, num_knn, kernel=None):
     return out
 
 
+FPS_MAX_POINTS = 16384                                      # include/geoadv.h geoadv_farthest_point_sample
+FPS_FORMS = {"auto": 0, "workgroup": 1, "wave": 2}          # GEOADV_FPS_*
+
+
+def _fps_form(form):
+    if form not in FPS_FORMS:
+        raise ValueError("form must be one of %s" % sorted(FPS_FORMS))
+    return FPS_FORMS[form]
+
+
+def farthest_point_sample_plan(n, form="auto"):
+    """The kernel instance that answers a cloud of n points (geoadv_farthest_point_sample_plan; no launch, no device) ->
+    (form "workgroup" or "wave", waves that share a cloud, points per thread).  ValueError where the op refuses (n, form)."""
+    f, w, p = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(_lib.lib().geoadv_farthest_point_sample_plan(int(n), _fps_form(form), C.byref(f), C.byref(w), C.byref(p)),
+               "farthest_point_sample_plan")
+    return {1: "workgroup", 2: "wave"}[f.value], w.value, p.value
+
+
+def _fps_start(start, b, n, dev):
+    """start of farthest_point_sample -> None or an int32 device tensor (b,) with every value outside [0, n) read as 0."""
+    import numpy as np
+    if start is None:
+        return None
+    if isinstance(start, torch.Tensor):
+        if start.dim() != 1 or start.shape[0] != b or start.dtype not in (torch.int32, torch.int64):
+            raise ValueError("start must be an int, or an int32 or int64 tensor of shape (%d,); got %s of shape %s" % (b, start.dtype, tuple(start.shape)))
+        s = start.to(dev)
+        return torch.where((s >= 0) & (s < n), s, torch.zeros_like(s)).to(torch.int32).contiguous()
+    if isinstance(start, (int, np.integer)) and not isinstance(start, bool):
+        host = np.full((b,), int(start), dtype=np.int64)
+    else:
+        host = np.asarray(start)
+        if host.shape != (b,) or host.dtype.kind not in "iu":
+            raise ValueError("start must be an int, or an integer array of shape (%d,)" % b)
+        host = host.astype(np.int64)
+    return torch.from_numpy(np.where((host >= 0) & (host < n), host, 0).astype(np.int32)).to(dev)
+
+
+def farthest_point_sample(xyz, npoint, start=None, return_points=False, return_mindist=False, form="auto"):
+    """Farthest point sampling (csrc/sampling.hip, the rule in include/geoadv.h): xyz (b,n,3) -> idx (b,npoint) int32, per cloud
+    the start index and then, npoint - 1 times, the point with the largest squared distance to those chosen so far (fp32, the
+    lowest index among equals).  npoint == n on distinct finite points is the cloud in farthest-point order.  A point with a NaN
+    or infinite coordinate is never chosen (except as the given start); 1 <= npoint <= n <= 16384.
+    start: None (index 0), an int for every cloud, or a (b,) int32 / int64 tensor or integer array; a value outside [0, n) reads as 0.
+    return_points: also sampled (b,npoint,3), the bits of xyz at idx.  return_mindist: also mindist (b,n), every point's final
+    squared distance to the chosen set (-1 for a non-finite point).
+    form: "auto" (by n), "workgroup" (a workgroup per cloud) or "wave" (a wave per cloud, n <= 1024): same bits.
+    -> idx, or (idx[, sampled][, mindist])."""
+    code = _fps_form(form)
+    xyz = _f32(xyz, "xyz", 3)
+    if xyz.shape[2] != 3:
+        raise ValueError("farthest_point_sample only accepts 3d point sets")
+    b, n, _ = xyz.shape
+    m = int(npoint)
+    if b < 1 or not 1 <= n <= FPS_MAX_POINTS:
+        raise ValueError("farthest_point_sample needs b >= 1 clouds of 1 <= n <= %d points (got b=%d, n=%d)" % (FPS_MAX_POINTS, b, n))
+    if not 1 <= m <= n:
+        raise ValueError("npoint must be in [1, n] (got npoint=%d for n=%d)" % (m, n))
+    farthest_point_sample_plan(n, form)                         # ValueError for "wave" beyond its size, before any launch
+    dev = xyz.device
+    st = _fps_start(start, b, n, dev)
+    idx = torch.empty((b, m), dtype=torch.int32, device=dev)
+    sampled = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if return_points else None
+    mindist = torch.empty((b, n), dtype=torch.float32, device=dev) if return_mindist else None
+    with torch.cuda.device(dev):
+        _call("geoadv_farthest_point_sample", b, n, _lib.ptr(xyz), m, _lib.ptr(st), code, _lib.ptr(idx), _lib.ptr(sampled), _lib.ptr(mindist))
+    out = (idx,) + ((sampled,) if return_points else ()) + ((mindist,) if return_mindist else ())
+    return out[0] if len(out) == 1 else out
+
+
 # ---------------------------------------------------------------------------------------------
 # the defenses' per-cloud bookkeeping (src/adversary_utils.py:149-178, src/ae_utils.py:12-80), device side
 # ---------------------------------------------------------------------------------------------

@@ -199,6 +199,36 @@ int geoadv_knn_dists_ws(int kernel, int b, int n, int k, const float *pc, float 
  * launch time, not meant to be flipped while other threads launch -- those pass `kernel` to the _ws forms. */
 int geoadv_knn_grid_mode(int mode);
 
+/* Farthest point sampling: per cloud of xyz[b,n,3], m indices into the cloud, each the point farthest from those chosen before
+ * it -- the sibling of the grouping operators above (PointNet++'s sampling layer; not part of the reference).  One launch for the
+ * batch, one workgroup or one wave per cloud, the cloud and its distances in registers throughout (csrc/sampling.hip).
+ * The rule, all fp32, every product and sum rounded on its own (no fused multiply-add):
+ *   t[i] = +inf where point i is finite, -1 where one of its coordinates is NaN or an infinity;   cur = start
+ *   for s = 0 .. m-1:   idx[s] = cur
+ *                       d[i] = ((x[i]-x[cur])^2 + (y[i]-y[cur])^2) + (z[i]-z[cur])^2;   t[i] = d[i] where d[i] < t[i]
+ *                       cur = the index of the largest t, the LOWEST index among equals
+ * so: t is never NaN (a NaN d replaces nothing); a non-finite point is never chosen, except as the given start, which is
+ * emitted as given; once every finite point has t = 0 (duplicates, or more picks than distinct points) the lowest such index
+ * repeats; with no finite point every pick after the first is 0; a start outside [0, n) reads as 0; m == n on distinct finite
+ * points yields a permutation, the cloud in farthest-point order.  There is no skip of points near the origin (the PointNet++
+ * CUDA kernel's |p|^2 <= 1e-3 test is not reproduced).
+ * start: device [b] or NULL = 0.  idx[b,m].  sampled (may be NULL) [b,m,3]: the bits of the chosen points.  mindist (may be
+ * NULL) [b,n]: the final t, the squared distance of every point to the chosen set (-1 for a non-finite point).
+ * form: which kernel answers the call, same bits -- GEOADV_FPS_AUTO (n <= 256: a wave per cloud, else a workgroup per cloud),
+ * GEOADV_FPS_WORKGROUP (every n), GEOADV_FPS_WAVE (n <= 1024).
+ * Enqueues on `stream` only.  GEOADV_EINVAL: b < 1, n < 1, n > 16384, m < 1, m > n, xyz or idx NULL, sampled or mindist
+ * overlapping xyz, an unknown form, GEOADV_FPS_WAVE with n > 1024. */
+#define GEOADV_FPS_AUTO      0
+#define GEOADV_FPS_WORKGROUP 1
+#define GEOADV_FPS_WAVE      2
+int geoadv_farthest_point_sample(int b, int n, const float *xyz /* [b,n,3] */, int m,
+                                 const int *start /* device [b] or NULL = 0 */, int form, int *idx /* [b,m] */,
+                                 float *sampled /* [b,m,3] or NULL */, float *mindist /* [b,n] or NULL: the final t */, void *stream);
+/* The kernel instance that answers a cloud of n points under `form`, without a launch (tests pin every boundary of the dispatch):
+ * *form_out = GEOADV_FPS_WORKGROUP or GEOADV_FPS_WAVE, *waves = the waves that share a cloud, *points_per_thread.  Any of the
+ * three may be NULL.  GEOADV_EINVAL where geoadv_farthest_point_sample refuses (n, form). */
+int geoadv_farthest_point_sample_plan(int n, int form, int *form_out, int *waves, int *points_per_thread);
+
 /* get_outlier_pc_inlier_pc (src/adversary_utils.py:149-178) on the device, fused with the score its caller forms
  * (defender/run_defense_surface.py:187-191: the mean of the first top_k kNN distances of a point): a point is an outlier if
  * mean(knn_dists[b,p,0:top_k]) > thresh, an inlier if <= thresh (a NaN score is neither, as with np.where).  knn_dists is
