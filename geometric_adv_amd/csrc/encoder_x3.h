@@ -110,12 +110,30 @@ __device__ __forceinline__ unsigned h2_cvt_pk(float lo, float hi) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo, hi}, f16x2));        // v_cvt_pk_f16_f32: RNE
 }
-// the same for the two fp16 pieces of two (already scaled) values; gmax: the running maximum of the range guard
-__device__ __forceinline__ void h2_split_pair(float a, float b, unsigned &w0, unsigned &w1, float &gmax) {
+// the same for the two fp16 pieces of two (already scaled) values; gmax: the running maximum of the range guard.
+// REFERENCE form, plain C++: v_cvt_pk, two v_cvt_f32_f16, two v_sub_f32, v_cvt_pk -- kept for geoadv_debug_h2_split only.
+__device__ __forceinline__ void h2_split_pair_ref(float a, float b, unsigned &w0, unsigned &w1, float &gmax) {
     gmax = fmaxf(gmax, fmaxf(a, b));                                                          // v_max3_f32
     w0 = h2_cvt_pk(a, b);
     const f16x2 h = __builtin_bit_cast(f16x2, w0);
     w1 = h2_cvt_pk(a - (float)h[0], b - (float)h[1]);
+}
+// The form every kernel uses: the second piece f16(a - f32(hi)) as ONE mixed-precision FMA per value, fma(f32(hi), -1, a)
+// rounded once to fp16 into a half of w1 (v_fma_mixlo_f16 / v_fma_mixhi_f16: three instructions a pair instead of six).  The
+// fp32 remainder a - f32(hi) is exact for every a (tests/test_h2_split_host.py), so one rounding gives the reference form's
+// bits (tests/test_gpu_h2_split_bits.py).  The compiler does not form the instruction from C++, hence the assembly; a and b
+// must be VALU results (every caller's are: max / mul outputs), never read straight from an MFMA's accumulator -- the compiler
+// pads no wait states for assembly it does not know.  For the same reason the guard's v_max3_f32 stands BEHIND the two in
+// the same statement: gfx940-class parts want one wait state between a VALU write of half a register and a VALU read of that
+// register, and whatever the scheduler puts next then never is that read.
+__device__ __forceinline__ void h2_split_pair(float a, float b, unsigned &w0, unsigned &w1, float &gmax) {
+    w0 = h2_cvt_pk(a, b);
+    unsigned r;
+    asm("v_fma_mixlo_f16 %0, %2, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %0, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_max3_f32 %1, %1, %3, %4"
+        : "=&v"(r), "+v"(gmax) : "v"(w0), "v"(a), "v"(b));
+    w1 = r;
 }
 // word `w` of every piece of a lane's fragment from two values
 __device__ __forceinline__ void xp_split_pair(float a, float b, X3 &out, int w, float &) {

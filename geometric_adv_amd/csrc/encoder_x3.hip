@@ -48,12 +48,13 @@ static_assert(X3_BIG_WG_PER_CU * x3_lds_bytes(3, true) <= 160 * 1024, "the workg
 // __builtin_amdgcn_global_load_lds: with the builtin the compiler knows the LDS is being written and puts an s_waitcnt vmcnt(0)
 // in front of the next ds_read that might alias -- every LDS read of this kernel -- which drains the ring at every slot; here the
 // counted vmcnt + barrier of slot_sync is the only ordering, as intended.  (M0 is compiler-reserved: saved and restored in the
-// same statement.)
-__device__ __forceinline__ void x3_glds16(const unsigned *gsrc, unsigned *lds_dst) {
+// same statement.)  The global address is a wave-uniform base in scalar registers plus the lane's constant 32-bit byte offset:
+// the base of every fetch is advanced on the scalar unit, where a 64-bit vector address cost a v_lshl_add_u64 per fetch.
+__device__ __forceinline__ void x3_glds16(const unsigned *gbase, unsigned lane_bytes, unsigned *lds_dst) {
     const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<uintptr_t>(lds_dst));
     unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(lane_bytes), "s"(gbase), "s"(dst) : "memory");
 }
 
 // (v > 0) of a non-negative-or-minus-zero float shifted into `m` from the right: bits + 0x7fffffff carries into bit 31 exactly
@@ -220,14 +221,16 @@ __global__ __launch_bounds__(X3_THREADS, X3_BIG_WG_PER_CU) void encoder_fwd3_ker
 
     // ---- the weight ring ----
     // fetch(t): this wave's fragments (the NP pieces of channel block `wave`, 1 KiB each, lane-linear) of the steps of slot t
+    const unsigned *wimg = img + wave * NP * X3_FRAG_WORDS;                    // wave-uniform: scalar registers
+    const unsigned lane_bytes = (unsigned)lane * 16u;
     auto fetch = [&](int t) {
 #pragma unroll
         for (int u = 0; u < X3_SLOT_STEPS; ++u) {
             const int s = t * X3_SLOT_STEPS + u;
-            const unsigned *src = img + (size_t)s * STEP_WORDS + wave * NP * X3_FRAG_WORDS + lane * 4;
+            const unsigned *src = wimg + (size_t)s * STEP_WORDS;
             unsigned *dst = ring + (t % X3_RING) * SLOT_WORDS + u * STEP_WORDS + wave * NP * X3_FRAG_WORDS;
 #pragma unroll
-            for (int q = 0; q < NP; ++q) x3_glds16(src + q * X3_FRAG_WORDS, dst + q * X3_FRAG_WORDS);
+            for (int q = 0; q < NP; ++q) x3_glds16(src + q * X3_FRAG_WORDS, lane_bytes, dst + q * X3_FRAG_WORDS);
         }
     };
 #pragma unroll
@@ -628,5 +631,26 @@ int launch_encoder_fwd_x3(const DeviceAE &A, int b, const float *x, const float 
     return launch_encoder_fwd_xp<3>(A, b, x, pert, adv_out, pmax, parg, pcnt, masks, stream, start, stop, fa);
 }
 
+// tests only: both forms of the f16x2 split over n pairs (in[2 i], in[2 i + 1]) -> word i of each piece
+__global__ void h2_split_debug_kernel(const float *in, int n, unsigned *w0, unsigned *w1, unsigned *w1_ref) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float a = in[2 * (size_t)i], b = in[2 * (size_t)i + 1];
+    float gmax = 0.f;
+    unsigned p0, p1, r0, r1;
+    h2_split_pair(a, b, p0, p1, gmax);
+    h2_split_pair_ref(a, b, r0, r1, gmax);
+    w0[i] = p0; w1[i] = p1; w1_ref[i] = r1;
+}
+
 }  // namespace geoadv
+extern "C" int geoadv_debug_h2_split(const float *in, int n, unsigned *w0, unsigned *w1, unsigned *w1_ref, void *stream) {
+    using namespace geoadv;
+    GA_REQUIRE(n >= 0 && n <= (1 << 30), "debug_h2_split: bad pair count (n=%d)", n);
+    if (n == 0) return GEOADV_OK;
+    GA_REQUIRE(in && w0 && w1 && w1_ref, "debug_h2_split: null pointer");
+    h2_split_debug_kernel<<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(in, n, w0, w1, w1_ref);
+    GA_LAUNCH_CHECK();
+    return GEOADV_OK;
+}
 GA_STAMPS_GETTER(geoadv_debug_stamps_encoder_x3)

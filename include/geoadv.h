@@ -973,6 +973,10 @@ enum { GEOADV_SYM_OUT_SCREENED = 0, GEOADV_SYM_OUT_KERNEL, GEOADV_SYM_OUT_RW, GE
 int geoadv_debug_chamfer_sym_plan(const int *request, int *out);
 /* ... and the scratch, in floats, that covers every plan of `pairs` problems of b clouds (what an attack handle reserves). */
 size_t geoadv_debug_chamfer_sym_workspace_floats(int pairs, int b, int n, int m);
+/* TESTS ONLY: the two fp16 pieces of the f16x2 encoder arithmetic for n pairs of values, in[2 i] and in[2 i + 1] (device memory,
+ * 2 n floats): w0[i] = the packed first pieces (low half: in[2 i]), w1[i] = the packed second pieces in the form the kernels use
+ * (one mixed-precision FMA per value), w1_ref[i] = the same in the plain convert-subtract-convert form (n words each, device). */
+int geoadv_debug_h2_split(const float *in, int n, unsigned *w0, unsigned *w1, unsigned *w1_ref, void *stream);
 
 /* How nn_distance(adv, x) is being answered: *searched = 1 if the paired grid search is in use for this handle (0: all-pairs
  * kernel, by configuration or batch size), *handed_back = number of clouds of the batch whose pairing the search currently
