@@ -138,6 +138,10 @@ __global__ void emd_init_kernel(int n, int m, double *temp) {
 // cells would not thin the pairs out enough -- a box of a few cells, points piled into a few cells, clouds of very different
 // extent -- a level keeps its dense sweeps: the choice is made per cloud pair and level on the device (SparseGrid::use,
 // emd_sparse_bin_kernel), both kinds of workgroups are in every such launch.
+// A cloud pair with a NaN or infinite coordinate in either cloud keeps the dense sweeps at every level (the binning kernel sees it
+// in its box pass), so what such a pair returns does not depend on the grid; the other pairs of the batch are not touched.
+// (What the CPU op returns there is an accident of the argument order of its std::min / std::max, not a rule -- measured: a
+// non-finite xyz1 point poisons its own row of the plan only, a non-finite xyz2 point all of it -- and is not reproduced.)
 // Measured (B = 32 / 128, N = 2048, uniform clouds; per launch under rocprofv3, profiles/r04_emd_trace_b32.txt / _b128.txt):
 // A8 8.2 / 23 us, B8 9.2 / 25, C8 + A7 11.2 / 35, B7 10.4 / 29, C7 + A6 32.9 / 107, B6 24.5 / 79 against 46 / 160 (passes A, B) and
 // 65 / 235 (C + A) dense, binning 32 / 57 us: approx_match 1.23 -> 1.08 ms and 4.40 -> 3.77 ms (reference weights: 4.21 -> 3.94 ms at
@@ -231,7 +235,7 @@ __global__ __launch_bounds__(SP_BIN_THREADS) void emd_sparse_bin_kernel(int n, i
     int *cntA = sp_lds, *cntB = cntA + SP_MAX_CELLS + 4, *cur = cntB + SP_MAX_CELLS + 4, *nbA = cur + SP_MAX_CELLS + 4, *nbB = nbA + SP_MAX_CELLS + 4;
     int *perm = nbB + SP_MAX_CELLS + 4;
     __shared__ float red[6][SP_BIN_THREADS / 64];
-    __shared__ int wsum[SP_BIN_THREADS / 64];
+    __shared__ int wsum[SP_BIN_THREADS / 64], oddw[SP_BIN_THREADS / 64];
     __shared__ unsigned long long work, work2;
     __shared__ int hcount;
     __shared__ SparseGrid g;
@@ -264,13 +268,25 @@ __global__ __launch_bounds__(SP_BIN_THREADS) void emd_sparse_bin_kernel(int n, i
     for (int off = 32; off > 0; off >>= 1)
 #pragma unroll
         for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], off)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off)); }
-    if ((t & 63) == 0)
+    // a coordinate that is NaN or infinite (fminf / fmaxf above pass a NaN by): such a pair keeps the dense sweeps, see `use` below
+    bool odd = false;
+#pragma unroll
+    for (int w = 0; w < 2; ++w)
+#pragma unroll
+        for (int u = 0; u < PER; ++u)
+            if (t + u * SP_BIN_THREADS < nn[w]) odd |= !(fabsf(px[w][u]) < INFINITY && fabsf(py[w][u]) < INFINITY && fabsf(pz[w][u]) < INFINITY);
+    const bool wave_odd = __ballot(odd) != 0ull;
+    if ((t & 63) == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { red[a][t >> 6] = lo[a]; red[3 + a][t >> 6] = hi[a]; }
+        oddw[t >> 6] = wave_odd ? 1 : 0;
+    }
     for (int i = t; i < 2 * (SP_MAX_CELLS + 4); i += SP_BIN_THREADS) cntA[i] = 0;       // (cntA and cntB are adjacent)
     if (t == 0) { work = 0ull; work2 = 0ull; }
     __syncthreads();
+    bool finite = true;                                     // (thread 0's: every coordinate of both clouds is a finite number)
     if (t == 0) {
+        for (int w = 0; w < SP_BIN_THREADS / 64; ++w) finite = finite && !oddw[w];
         const float reach = reach0 * (float)(1 << level) * 1.01f;       // the reach doubles from level to level (level = -4^j)
         for (int a = 0; a < 3; ++a) {
             float l = red[a][0], h = red[3 + a][0];
@@ -318,7 +334,10 @@ __global__ __launch_bounds__(SP_BIN_THREADS) void emd_sparse_bin_kernel(int n, i
     }
     __syncthreads();
     if (t == 0) {
-        g.use = (max(work, work2) <= (unsigned long long)n * (unsigned long long)m && max(n, m) <= SP_MAX_N) ? 1 : 0;
+        // (both sums EQUAL n * m where every own point of either cloud is heavy -- a box of two or three cells a side: a sparse launch
+        // would hand every point to the dense form's workgroups, so nothing thins out and the level stays dense)
+        const unsigned long long nm = (unsigned long long)n * (unsigned long long)m;
+        g.use = (finite && max(work, work2) <= nm && min(work, work2) < nm && max(n, m) <= SP_MAX_N) ? 1 : 0;
         reinterpret_cast<SparseGrid *>(base)[level] = g;
     }
     __syncthreads();
@@ -1032,6 +1051,16 @@ static int emd_check(const char *op, int b, int n, int m) {
     return GEOADV_OK;
 }
 
+// The pieces of a call's `temp`: the doubles of the levels from the first 8-byte boundary; behind them (and, in the fused form,
+// behind its cdiv(n, 64) cost partials per cloud) the sparse levels' scratch from the next 16-byte boundary, null where there
+// is none.  The two ops and geoadv_debug_emd_sparse_state all ask here.
+static double *emd_temp_doubles(const float *temp) { return reinterpret_cast<double *>((reinterpret_cast<size_t>(temp) + 7) & ~(size_t)7); }
+static char *emd_sparse_scratch(double *t, bool fused, int b, int n, int m) {
+    if (!emd_sparse_floats(b, n, m)) return nullptr;
+    const double *end = t + (size_t)b * emd_temp_doubles_per_cloud(n, m) + (fused ? (size_t)b * cdiv(n, 64) : 0);
+    return reinterpret_cast<char *>((reinterpret_cast<size_t>(end) + 15) & ~(size_t)15);
+}
+
 // the eleven levels: capacities and factors into temp (fp64), no plan yet
 static std::atomic<int> g_emd_sparse{1};   // geoadv_emd_sparse_levels: the process default of calls whose mode carries no GEOADV_EMD_DENSE_LEVELS
                                            // flag (0 = every sweep dense); tests and measurements only -- per call, use the flag
@@ -1101,7 +1130,7 @@ static int emd_mode_check(const char *op, int mode) {
 template <bool REF>
 static int approx_match_impl(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, double *t, bool dense_levels, hipStream_t st) {
     EmdLevels<REF> lv;
-    char *sparse = emd_sparse_floats(b, n, m) ? reinterpret_cast<char *>((reinterpret_cast<size_t>(t + (size_t)b * emd_temp_doubles_per_cloud(n, m)) + 15) & ~(size_t)15) : nullptr;
+    char *sparse = emd_sparse_scratch(t, false, b, n, m);
     if (int rc = emd_run_levels<REF>(b, n, m, xyz1, xyz2, t, sparse, lv, dense_levels, st)) return rc;
     emd_match_kernel<REF><<<dim3(cdiv(n, 256), cdiv(m, EMD_LT), b), 256, 0, st>>>(n, m, lv, xyz1, xyz2, t, match);
     GA_LAUNCH_CHECK();
@@ -1115,7 +1144,7 @@ extern "C" int geoadv_approx_match_mode(int mode, int b, int n, int m, const flo
     if (b == 0) return GEOADV_OK;
     GA_REQUIRE(xyz1 && xyz2 && match && temp, "approx_match: null pointer");
     hipStream_t st = as_stream(stream);
-    double *t = reinterpret_cast<double *>((reinterpret_cast<size_t>(temp) + 7) & ~(size_t)7);
+    double *t = emd_temp_doubles(temp);
     const bool dense = (mode & GEOADV_EMD_DENSE_LEVELS) != 0;
     return (mode & ~GEOADV_EMD_DENSE_LEVELS) == GEOADV_EMD_REFERENCE ? approx_match_impl<true>(b, n, m, xyz1, xyz2, match, t, dense, st)
                                                                     : approx_match_impl<false>(b, n, m, xyz1, xyz2, match, t, dense, st);
@@ -1136,7 +1165,7 @@ static int emd_cost_grad1_impl(int b, int n, int m, const float *xyz1, const flo
                                bool dense_levels, hipStream_t st) {
     double *partial = t + (size_t)b * emd_temp_doubles_per_cloud(n, m);
     EmdLevels<REF> lv;
-    char *sparse = emd_sparse_floats(b, n, m) ? reinterpret_cast<char *>((reinterpret_cast<size_t>(partial + (size_t)b * cdiv(n, 64)) + 15) & ~(size_t)15) : nullptr;
+    char *sparse = emd_sparse_scratch(t, true, b, n, m);
     if (int rc = emd_run_levels<REF>(b, n, m, xyz1, xyz2, t, sparse, lv, dense_levels, st)) return rc;
     const int parts = cdiv(n, 64);
     emd_plan_cost_grad1_kernel<REF><<<dim3(parts, b), SW_THREADS, 0, st>>>(n, m, lv, xyz1, xyz2, t, partial, grad1);
@@ -1153,7 +1182,7 @@ extern "C" int geoadv_emd_cost_grad1_mode(int mode, int b, int n, int m, const f
     if (b == 0) return GEOADV_OK;
     GA_REQUIRE(xyz1 && xyz2 && cost && grad1 && temp, "emd_cost_grad1: null pointer");
     hipStream_t st = as_stream(stream);
-    double *t = reinterpret_cast<double *>((reinterpret_cast<size_t>(temp) + 7) & ~(size_t)7);
+    double *t = emd_temp_doubles(temp);
     const bool dense = (mode & GEOADV_EMD_DENSE_LEVELS) != 0;
     return (mode & ~GEOADV_EMD_DENSE_LEVELS) == GEOADV_EMD_REFERENCE ? emd_cost_grad1_impl<true>(b, n, m, xyz1, xyz2, cost, grad1, t, dense, st)
                                                                     : emd_cost_grad1_impl<false>(b, n, m, xyz1, xyz2, cost, grad1, t, dense, st);
@@ -1162,6 +1191,31 @@ extern "C" int geoadv_emd_cost_grad1_mode(int mode, int b, int n, int m, const f
 extern "C" int geoadv_emd_cost_grad1(int b, int n, int m, const float *xyz1, const float *xyz2, float *cost, float *grad1,
                                      float *temp, void *stream) {
     return geoadv_emd_cost_grad1_mode(GEOADV_EMD_FAST, b, n, m, xyz1, xyz2, cost, grad1, temp, stream);
+}
+
+static_assert(SP_LEVELS <= GEOADV_EMD_SPARSE_LEVELS, "geoadv_debug_emd_sparse_state reports GEOADV_EMD_SPARSE_LEVELS levels");
+extern "C" int geoadv_debug_emd_sparse_state(int fused, int b, int n, int m, const float *temp, int *out, void *stream) {
+    if (int rc = emd_check("debug_emd_sparse_state", b, n, m)) return rc;
+    if (b == 0) return GEOADV_OK;
+    GA_REQUIRE(temp && out, "debug_emd_sparse_state: null pointer");
+    for (size_t i = 0; i < (size_t)b * GEOADV_EMD_SPARSE_LEVELS * 3; ++i) out[i] = 0;
+    const char *sparse = emd_sparse_scratch(emd_temp_doubles(temp), fused != 0, b, n, m);
+    if (!sparse) return GEOADV_OK;
+    GA_HIP(hipStreamSynchronize(as_stream(stream)));
+    for (int c = 0; c < b; ++c) {
+        char *base = const_cast<char *>(sparse) + (size_t)c * sp_bytes_per_pair(n, m);
+        SparseGrid g[SP_LEVELS];
+        GA_HIP(hipMemcpy(g, base, sizeof(g), hipMemcpyDeviceToHost));
+        for (int level = 0; level < SP_LEVELS; ++level) {
+            int *o = out + ((size_t)c * GEOADV_EMD_SPARSE_LEVELS + level) * 3;
+            o[0] = g[level].use;
+            if (!g[level].use) continue;                     // (a dense level's lists are not written)
+            const SparseView v = sp_view(base, n, m, level);
+            GA_HIP(hipMemcpy(o + 1, v.heavy[0], sizeof(int), hipMemcpyDeviceToHost));
+            GA_HIP(hipMemcpy(o + 2, v.heavy[1], sizeof(int), hipMemcpyDeviceToHost));
+        }
+    }
+    return GEOADV_OK;
 }
 
 extern "C" size_t geoadv_match_cost_workspace_floats(int b, int n, int m) {

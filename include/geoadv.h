@@ -977,6 +977,14 @@ size_t geoadv_debug_chamfer_sym_workspace_floats(int pairs, int b, int n, int m)
  * 2 n floats): w0[i] = the packed first pieces (low half: in[2 i]), w1[i] = the packed second pieces in the form the kernels use
  * (one mixed-precision FMA per value), w1_ref[i] = the same in the plain convert-subtract-convert form (n words each, device). */
 int geoadv_debug_h2_split(const float *in, int n, unsigned *w0, unsigned *w1, unsigned *w1_ref, void *stream);
+/* TESTS ONLY: which form the first EMD levels took (csrc/emd.hip, "Sparse levels" -- decided on the device per cloud pair and level).
+ * Reads the scratch a FINISHED geoadv_approx_match_mode (fused = 0) or geoadv_emd_cost_grad1_mode (fused != 0) call with the same
+ * (b, n, m) left in `temp` (device); the call must not have carried GEOADV_EMD_DENSE_LEVELS, which leaves that scratch unwritten.
+ * out[b][GEOADV_EMD_SPARSE_LEVELS][3] (host): use (1: the level's sweeps walked the cell grid), then the number of HEAVY own points
+ * of cloud 1 and of cloud 2 (they took the dense form inside the sparse launch; 0 where use is 0).  All zeros where the clouds are
+ * too large for any sparse scratch.  Synchronises the stream. */
+#define GEOADV_EMD_SPARSE_LEVELS 3
+int geoadv_debug_emd_sparse_state(int fused, int b, int n, int m, const float *temp, int *out, void *stream);
 
 /* How nn_distance(adv, x) is being answered: *searched = 1 if the paired grid search is in use for this handle (0: all-pairs
  * kernel, by configuration or batch size), *handed_back = number of clouds of the batch whose pairing the search currently

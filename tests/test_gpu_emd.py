@@ -197,6 +197,24 @@ def test_approx_match_deterministic_and_order_free():
     torch.testing.assert_close(c, a[:, p2][:, :, p1], rtol=1e-4, atol=2e-6)
 
 
+def _sparse_state(x1, x2, reference_weights):
+    """Which form the first levels of a default approx_match call take: [cloud pair][level] -> (use, heavy own points of cloud 1,
+    of cloud 2), read by geoadv_debug_emd_sparse_state from the temp of a call made here, with temp of our own."""
+    import ctypes as C
+    import torch
+    from geometric_adv_amd import _lib, ops
+    lib = _lib.lib()
+    b, n, m = x1.shape[0], x1.shape[1], x2.shape[1]
+    match = torch.empty((b, m, n), device="cuda:0")
+    temp = torch.empty(int(lib.geoadv_approx_match_temp_floats(b, n, m)), device="cuda:0")
+    rc = lib.geoadv_approx_match_mode(ops._emd_mode(reference_weights, False), b, n, m, _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(match), _lib.ptr(temp), None)
+    assert rc == 0, lib.geoadv_last_error()
+    out = (C.c_int * (b * 3 * 3))()
+    rc = lib.geoadv_debug_emd_sparse_state(0, b, n, m, _lib.ptr(temp), out, None)
+    assert rc == 0, lib.geoadv_last_error()
+    return np.ctypeslib.as_array(out).reshape(b, 3, 3).copy()
+
+
 @pytest.mark.parametrize("reference_weights", [False, True])
 @pytest.mark.parametrize("kind,b,n,m", [("uniform", 3, 2048, 2048), ("uniform", 2, 700, 1300), ("shell", 2, 1024, 2048),
                                          ("tiny_box", 2, 512, 512), ("flat", 2, 1024, 1024), ("far_apart", 2, 600, 600),
@@ -238,6 +256,16 @@ def test_sparse_levels_equal_dense_sweeps(kind, b, n, m, reference_weights):
             ops.emd_sparse_levels(True)
     md, cd, gd = out[False]
     ms, cs_, gs = out[True]
+    # the forms that ran (decided on the device): without this, a device that kept every level dense would compare dense with dense
+    state = _sparse_state(_t(x1), _t(x2), reference_weights)
+    if kind == "tiny_box":
+        assert (state[:, :, 0] == 0).all(), state.tolist()
+    elif kind in ("uniform", "shell", "flat"):
+        assert (state[:, :2, 0] == 1).all(), state.tolist()
+    elif kind == "blob_in_cube":
+        assert (state[:, 0, 0] == 1).all() and (state[:, 0, 2] > 0).all(), state.tolist()      # the cube (cloud 2) is the wide one
+    elif kind == "cube_in_blob":
+        assert (state[:, 0, 0] == 1).all() and (state[:, 0, 1] > 0).all(), state.tolist()      # ... cloud 1
     torch.testing.assert_close(ms, md, rtol=2e-6, atol=2e-8)
     torch.testing.assert_close(cs_, cd, rtol=1e-6, atol=0)
     torch.testing.assert_close(gs, gd, rtol=1e-5, atol=1e-7)
