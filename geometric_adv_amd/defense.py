@@ -7,6 +7,10 @@ Everything between the adversarial clouds and the defended reconstructions runs 
 the outlier / critical-point packing kernels (csrc/defense.hip, the reference does them with per-cloud numpy loops), the
 victim AE and the Chamfer score.  `*_device` functions take and return GPU tensors; the functions with the reference's names
 wrap them for numpy callers.
+
+defend_sor* and defend_srs* are the two baseline defenses of the wider point-cloud attack literature (statistical outlier
+removal as in DUP-Net / IF-Defense, simple random sampling); neither is in the reference.  Their rules are written out in
+include/geoadv.h, their kernels are csrc/stat_defense.hip, their commands run_defense_sor and run_defense_srs.
 """
 import numpy as np
 import torch
@@ -93,6 +97,34 @@ def defend_critical_device(ae, adversarial_pc, source_pc):
                 defended_pc=pc_defended, defended_recon=recon, recon_error_vs_source=err)
 
 
+def defend_sor_device(ae, adversarial_pc, source_pc, num_knn=2, alpha=1.1):
+    """Statistical outlier removal for one set of clouds, GPU tensors in and out (not in the reference: the scale-free form
+    of defend_surface_device): drop the points whose mean distance to their num_knn nearest neighbours exceeds the cloud's
+    mean + alpha * std of that score (ops.sor_filter), reconstruct the defended clouds with the victim AE, score them against
+    the sources."""
+    adv, src = ae._as_dev(adversarial_pc), ae._as_dev(source_pc)
+    knn = ops.knn_dists(adv, num_knn)
+    o_pts, o_idx, o_num, inlier, stats = ops.sor_filter(adv, knn, k=num_knn, alpha=alpha, return_stats=True)
+    recon, _ = ae.forward(inlier)
+    err = ae.loss_per_pc_tensor(recon, src)
+    return dict(knn_dists=knn, sor_stats=stats, outlier_points=o_pts, outlier_idx=o_idx, outlier_num=o_num, defended_pc=inlier,
+                defended_recon=recon, recon_error_vs_source=err)
+
+
+def defend_srs_device(ae, adversarial_pc, source_pc, drop_num=500, seed=0, counter=0, slot_offset=0):
+    """Simple random sampling for one set of clouds, GPU tensors in and out (not in the reference): drop drop_num points of
+    every cloud by the seeded draw of ops.random_drop (cloud i is slot slot_offset + i), reconstruct what is left and score
+    it against the source.  The keys are defend_sor_device's: outlier_* hold the dropped points (ascending indices, int32)."""
+    adv, src = ae._as_dev(adversarial_pc), ae._as_dev(source_pc)
+    kept, d_idx = ops.random_drop(adv, drop_num, seed, counter=counter, slot_offset=slot_offset, return_idx=True)
+    d_pts = torch.gather(adv, 1, d_idx.long().unsqueeze(-1).expand(-1, -1, 3))
+    d_num = torch.full((adv.shape[0],), int(drop_num), dtype=torch.int16, device=adv.device)
+    recon, _ = ae.forward(kept)
+    err = ae.loss_per_pc_tensor(recon, src)
+    return dict(outlier_points=d_pts, outlier_idx=d_idx, outlier_num=d_num, defended_pc=kept, defended_recon=recon,
+                recon_error_vs_source=err)
+
+
 def _to_numpy(d):
     return {k: v.cpu().numpy() for k, v in d.items()}
 
@@ -107,5 +139,19 @@ def defend_surface(ae, adversarial_pc, source_pc, num_knn=8, top_k=2, knn_dist_t
 def defend_critical(ae, adversarial_pc, source_pc):
     """defend_critical_device for numpy callers."""
     out = defend_critical_device(ae, adversarial_pc, source_pc)
+    ae.status()
+    return _to_numpy(out)
+
+
+def defend_sor(ae, adversarial_pc, source_pc, num_knn=2, alpha=1.1):
+    """defend_sor_device for numpy callers."""
+    out = defend_sor_device(ae, adversarial_pc, source_pc, num_knn, alpha)
+    ae.status()
+    return _to_numpy(out)
+
+
+def defend_srs(ae, adversarial_pc, source_pc, drop_num=500, seed=0):
+    """defend_srs_device for numpy callers."""
+    out = defend_srs_device(ae, adversarial_pc, source_pc, drop_num, seed)
     ae.status()
     return _to_numpy(out)

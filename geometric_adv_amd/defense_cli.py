@@ -65,7 +65,11 @@ def write_defense_configuration(folder, output_path, output_path_orig, defense_a
 
 
 def run_defense(flags, kind):
-    """The per-class loop of run_defense_surface.py (kind 'surface') or run_defense_critical.py (kind 'critical')."""
+    """The per-class loop of run_defense_surface.py (kind 'surface') or run_defense_critical.py (kind 'critical'), and of the
+    two defenses the reference does not have: statistical outlier removal (kind 'sor': ops.sor_filter on kNN distances computed
+    on the device, no kNN files) and simple random sampling (kind 'srs': ops.random_drop with counter = the class's position in
+    pc_classes, slot = row for the adversarial half and number of rows + row for the _orig half, so a rerun reproduces the
+    files).  Both write the surface defense's files; adversarial_critical_* / original_*critical* hold the removed points."""
     import torch
     from . import ops
     from .autoencoder import PointNetAE
@@ -75,11 +79,18 @@ def run_defense(flags, kind):
                           ['point_clouds_test_set', 'latent_vectors_test_set', 'ae_loss_test_set', 'reconstructions_test_set'])
     assert np.all(folder.arrays['ae_loss_test_set'] > 0), 'Note: not all autoencoder loss values are larger than 0 as they should!'
     bottleneck_size = folder.arrays['latent_vectors_test_set'].shape[1]
+    if kind == 'srs' and not 0 <= flags.drop_num < folder.arrays['point_clouds_test_set'].shape[1]:
+        raise ValueError('--drop_num must be in [0, %d), the number of points of a cloud (got %d)'
+                         % (folder.arrays['point_clouds_test_set'].shape[1], flags.drop_num))
     output_path = create_dir(osp.join(folder.attack_dir, flags.output_folder_name))
     output_path_orig = create_dir(osp.join(folder.attack_dir, flags.output_folder_name + '_orig'))
     defense_args = {}
     if kind == 'surface':
         defense_args = dict(num_knn_for_defense=flags.num_knn_for_defense, knn_dist_thresh=flags.knn_dist_thresh)
+    elif kind == 'sor':
+        defense_args = dict(num_knn_for_defense=flags.num_knn_for_defense, sor_alpha=flags.sor_alpha)
+    elif kind == 'srs':
+        defense_args = dict(drop_num=flags.drop_num, seed=flags.seed)
     write_defense_configuration(folder, output_path, output_path_orig, defense_args)
 
     point_clouds = folder.arrays['point_clouds_test_set']
@@ -117,6 +128,18 @@ def run_defense(flags, kind):
             knn_src = torch.from_numpy(np.load(knn_files[1])).to(ae.device)
             a_pts, a_idx, a_num, a_def = ops.outlier_filter(adv, knn_adv, flags.knn_dist_thresh, top_k=flags.num_knn_for_defense)
             s_pts, s_idx, s_num, s_def = ops.outlier_filter(src, knn_src, flags.knn_dist_thresh, top_k=flags.num_knn_for_defense)
+        elif kind == 'sor':
+            a_pts, a_idx, a_num, a_def = ops.sor_filter(adv, None, k=flags.num_knn_for_defense, alpha=flags.sor_alpha)
+            s_pts, s_idx, s_num, s_def = ops.sor_filter(src, None, k=flags.num_knn_for_defense, alpha=flags.sor_alpha)
+        elif kind == 'srs':
+            rows = int(adv.shape[0])
+            a_def, a_idx = ops.random_drop(adv, flags.drop_num, flags.seed, counter=i, slot_offset=0, return_idx=True)
+            s_def, s_idx = ops.random_drop(src, flags.drop_num, flags.seed, counter=i, slot_offset=rows, return_idx=True)
+            a_pts = torch.gather(adv, 1, a_idx.long().unsqueeze(-1).expand(-1, -1, 3))
+            s_pts = torch.gather(src, 1, s_idx.long().unsqueeze(-1).expand(-1, -1, 3))
+            a_idx, s_idx = a_idx.to(torch.int16), s_idx.to(torch.int16)           # (n <= 32767: the other defenses' dtype)
+            a_num = torch.full((rows,), flags.drop_num, dtype=torch.int16, device=adv.device)
+            s_num = torch.full((int(src.shape[0]),), flags.drop_num, dtype=torch.int16, device=src.device)
         else:
             mv, mi = ae.max_and_argmax(adv)
             a_pts, a_idx, a_num, a_crit, a_def = ops.critical_split(adv, mv, mi)
@@ -162,7 +185,7 @@ def run_defense(flags, kind):
                                     adv_source_err, np.divide(adv_source_err, source_ae_loss_ref).astype(dtype)], axis=-1)[None]
         defense_source_metrics = np.stack([s_def_err, np.divide(s_def_err, source_ae_loss_ref),
                                            source_ae_loss_ref, np.ones_like(source_ae_loss_ref)], axis=-1)
-        if kind == 'surface':       # data above the class's max number of outliers can be discarded (run_defense_surface.py:216-220)
+        if kind in ('surface', 'sor'):   # data above the class's max number of outliers can be discarded (run_defense_surface.py:216-220)
             a_max, s_max = int(a_num.max(initial=0)), int(s_num.max(initial=0))
             a_pts, a_idx = a_pts[:, :a_max], a_idx[:, :a_max]
             s_pts, s_idx = s_pts[:, :s_max], s_idx[:, :s_max]

@@ -403,6 +403,83 @@ def outlier_filter(point_clouds, knn_dists, knn_dist_thresh, top_k=None, want_ou
     return o_pc, o_idx, o_num, inlier
 
 
+STAT_DEFENSE_MAX_POINTS = 32767                             # include/geoadv.h geoadv_sor_filter / geoadv_random_drop (int16 indices)
+SOR_MAX_KNN = 64
+_knn_dists_op = knn_dists                                   # (sor_filter has an argument of that name)
+
+
+def sor_filter(point_clouds, knn_dists=None, k=2, alpha=1.1, want_outliers=True, return_stats=False):
+    """Statistical outlier removal (csrc/stat_defense.hip, the rule in include/geoadv.h): per cloud the float64 mean mu and
+    sample variance var of the score s_p = mean(knn_dists[p, :k]), summed in a fixed order; a point is an inlier iff s_p is
+    finite and s_p <= mu + alpha * sqrt(var) (tested as (s_p - mu)^2 <= alpha^2 var, without a square root).
+    point_clouds (b,n,3), 1 <= n <= 32767.  knn_dists: None (ops.knn_dists(point_clouds, k) is computed here), (b,n,stride)
+    with 1 <= k <= stride <= 64, or (b,n), a per-point score of the caller's (k is then 1); squared distances give
+    IF-Defense's variant.  alpha >= 0.
+    -> (outlier_pc (b,n,3), outlier_idx (b,n) int16, outlier_num (b,) int16, inlier_pc (b,n,3)[, stats (b,3) float64 = mu, var,
+    the number of finite scores]), packed and padded as outlier_filter's.  want_outliers=False skips the three outlier
+    outputs (None)."""
+    pc = _f32(point_clouds, "point_clouds", 3)
+    if pc.shape[2] != 3:
+        raise ValueError("sor_filter only accepts 3d point sets")
+    b, n, _ = pc.shape
+    if not 1 <= n <= STAT_DEFENSE_MAX_POINTS:
+        raise ValueError("sor_filter needs clouds of 1 <= n <= %d points (got n=%d)" % (STAT_DEFENSE_MAX_POINTS, n))
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and alpha != float("inf")):
+        raise ValueError("alpha must be finite and >= 0 (got %r)" % alpha)
+    k = int(k)
+    if knn_dists is None:
+        if not 1 <= k <= min(SOR_MAX_KNN, n - 1):
+            raise ValueError("k must be in [1, min(%d, n - 1)] (got k=%d for n=%d)" % (SOR_MAX_KNN, k, n))
+        kd, stride = _knn_dists_op(pc, k), k
+    elif isinstance(knn_dists, torch.Tensor) and knn_dists.dim() == 2:
+        kd, stride, k = _f32(knn_dists, "knn_dists", 2), 1, 1
+    else:
+        kd = _f32(knn_dists, "knn_dists", 3)
+        stride = kd.shape[2]
+    if tuple(kd.shape[:2]) != (b, n):
+        raise ValueError("knn_dists must be of shape (batch, num_points[, k]); got %s for clouds %s" % (tuple(kd.shape), tuple(pc.shape)))
+    if not 1 <= k <= stride <= SOR_MAX_KNN:
+        raise ValueError("sor_filter needs 1 <= k <= knn_dists.shape[2] <= %d (got k=%d, %d columns)" % (SOR_MAX_KNN, k, stride))
+    inlier = torch.empty_like(pc)
+    o_pc = torch.empty_like(pc) if want_outliers else None
+    o_idx = torch.empty((b, n), dtype=torch.int16, device=pc.device) if want_outliers else None
+    o_num = torch.empty((b,), dtype=torch.int16, device=pc.device) if want_outliers else None
+    stats = torch.empty((b, 3), dtype=torch.float64, device=pc.device) if return_stats else None
+    with torch.cuda.device(pc.device):
+        _call("geoadv_sor_filter", b, n, _lib.ptr(pc), _lib.ptr(kd), int(stride), k, C.c_double(alpha),
+              _lib.ptr(o_pc), _lib.ptr(o_idx), _lib.ptr(o_num), _lib.ptr(inlier), _lib.ptr(stats))
+    return (o_pc, o_idx, o_num, inlier) + ((stats,) if return_stats else ())
+
+
+def random_drop(point_clouds, drop, seed, counter=0, slot_offset=0, return_idx=False):
+    """Simple random sampling (csrc/stat_defense.hip, the rule in include/geoadv.h): every cloud of point_clouds (b,n,3) loses
+    the `drop` points with the smallest counter-based 64-bit draws r(seed, counter, slot_offset + cloud, point) -> kept (b,n,3):
+    the other points in point order, padded with the last of them[, dropped_idx (b,drop) int32, ascending].
+    0 <= drop < n <= 32767; drop == 0 copies the bits.  The result depends on (seed, counter, slot, point) alone, not on the
+    batch, torch's generator or the data: ranks that pass slot_offset = rank * local batch draw what one rank would."""
+    pc = _f32(point_clouds, "point_clouds", 3)
+    if pc.shape[2] != 3:
+        raise ValueError("random_drop only accepts 3d point sets")
+    b, n, _ = pc.shape
+    drop, seed, counter, slot_offset = int(drop), int(seed), int(counter), int(slot_offset)
+    if not 1 <= n <= STAT_DEFENSE_MAX_POINTS:
+        raise ValueError("random_drop needs clouds of 1 <= n <= %d points (got n=%d)" % (STAT_DEFENSE_MAX_POINTS, n))
+    if not 0 <= drop < n:
+        raise ValueError("drop must be in [0, n) (got drop=%d for n=%d)" % (drop, n))
+    for name, v in (("seed", seed), ("counter", counter)):
+        if not 0 <= v < 1 << 64:
+            raise ValueError("%s must be in [0, 2^64) (got %d)" % (name, v))
+    if not 0 <= slot_offset <= (1 << 32) - b:
+        raise ValueError("slot_offset must be >= 0 with slot_offset + batch <= 2^32 (got %d)" % slot_offset)
+    kept = torch.empty_like(pc)
+    idx = torch.empty((b, drop), dtype=torch.int32, device=pc.device) if return_idx else None
+    with torch.cuda.device(pc.device):
+        _call("geoadv_random_drop", b, n, _lib.ptr(pc), drop, C.c_ulonglong(seed), C.c_ulonglong(counter), C.c_ulonglong(slot_offset),
+              _lib.ptr(kept), _lib.ptr(idx))
+    return (kept, idx) if return_idx else kept
+
+
 def critical_split(point_clouds, max_val, max_idx):
     """get_critical_pc_non_critical_pc (ae_utils.py:51-80) from (np.max, np.argmax)(pre_symmetry, axis=1) on GPU tensors ->
     (critical_points (b,c,3), critical_idx (b,c) int16, critical_num (b,) int16, critical_pc (b,n,3), non_critical_pc (b,n,3)).

@@ -238,6 +238,49 @@ int geoadv_farthest_point_sample_plan(int n, int form, int *form_out, int *waves
  * outlier_num may be NULL. */
 int geoadv_outlier_filter(int b, int n, const float *pc, const float *knn_dists, int knn_stride, int top_k, float thresh,
                           float *outlier_pc, short *outlier_idx, short *outlier_num, float *inlier_pc, void *stream);
+
+/* Statistical outlier removal (SOR; the baseline defense of DUP-Net and IF-Defense; not part of the reference): the scale-free
+ * form of geoadv_outlier_filter, with a per-cloud threshold mean + alpha * std of the kNN score in place of one absolute
+ * threshold.  One 1024-thread workgroup per cloud (csrc/stat_defense.hip).  The rule, all float64, every product and sum
+ * rounded on its own (no fused multiply-add):
+ *   s_p = (((double)knn_dists[p][0] + (double)knn_dists[p][1]) + ... + (double)knn_dists[p][k-1]) / (double)k
+ *   a non-finite s_p (NaN, +-inf) stays out of the statistics and makes p an outlier;  m = the number of finite scores
+ *   mu  = SUM(s_p) / m                    (0 for m = 0)
+ *   var = SUM((s_p - mu) * (s_p - mu)) / (m - 1)      (0 for m < 2)
+ *   p is an INLIER iff s_p is finite and (s_p <= mu or (s_p - mu) * (s_p - mu) <= (alpha * alpha) * var)
+ * which is s_p <= mu + alpha * sigma without a square root, so that the outcome does not hang on how a device rounds sqrt.
+ * SUM runs over ALL points, a non-finite score adding +0.0, in a FIXED order that is part of the rule, with T = 1024:
+ *   1. thread t of T starts at +0.0 and adds the terms of points t, t + T, t + 2T, ... in ascending order,
+ *   2. the 64 threads 64w .. 64w+63 of wave w combine in the xor butterfly v += v[lane ^ mask], mask = 1, 2, 4, 8, 16, 32,
+ *   3. the T / 64 = 16 wave sums are added in ascending order of w, starting from wave 0's.
+ * knn_dists is (b,n,knn_stride); any per-point array serves (squared distances give IF-Defense's variant).
+ * Outputs as geoadv_outlier_filter's: inlier_pc / outlier_pc (b,n,3) packed in point order and padded with the last packed
+ * point (zeros if none), outlier_idx (b,n) int16 zero-padded, outlier_num (b) int16; outlier_pc / outlier_idx / outlier_num
+ * may be NULL.  stats (may be NULL) [b,3] = (mu, var, (double)m) per cloud.
+ * Enqueues on `stream` only.  GEOADV_EINVAL, before any launch: alpha < 0 or not finite, k < 1, k > knn_stride,
+ * knn_stride > 64, n < 1, n > 32767 (int16 never wraps), b < 0, pc, knn_dists or inlier_pc NULL with b > 0.  b == 0 is a no-op. */
+int geoadv_sor_filter(int b, int n, const float *pc /* [b,n,3] */, const float *knn_dists /* [b,n,knn_stride] */, int knn_stride,
+                      int k, double alpha, float *outlier_pc, short *outlier_idx, short *outlier_num, float *inlier_pc,
+                      double *stats /* [b,3] or NULL */, void *stream);
+
+/* Simple random sampling (SRS; the other baseline defense of the point-cloud attack literature; not part of the reference):
+ * every cloud loses `drop` points chosen by a counter-based draw.  mix = splitmix64's finaliser, G = 0x9e3779b97f4a7c15,
+ * 64-bit wrap-around; for the cloud slot s = slot_offset + i of cloud i and point p
+ *   r(p) = mix(mix(mix(mix(seed + G) ^ counter) ^ (s << 32 | p)) + 48 * G)
+ * (the key of geoadv_batch_gather, stream 48: batch_gather uses streams 1..3 and augment_batch 16..32).  The dropped points are
+ * the `drop` points with the smallest (r(p), p) in lexicographic order (r is a bijection of p within a slot, so the draws
+ * of a cloud never tie).  kept_pc (b,n,3): the other n - drop points in point order (the bits of pc), padded with the last
+ * kept point.  dropped_idx (may be NULL) [b,drop]: the dropped points, ascending.  drop == 0 copies the bits of pc.
+ * The result depends on (seed, counter, s, p) alone -- not on b, the grid or the data: ranks that pass slot_offset = rank *
+ * local batch draw what one rank would have drawn.
+ * One 1024-thread workgroup per cloud (csrc/stat_defense.hip): the drop-th smallest draw is found by an 8-bit radix select
+ * over the 64-bit words on an LDS histogram (8 passes, O(n) each; no all-pairs form at any size), then two stable packings.
+ * Enqueues on `stream` only.  GEOADV_EINVAL, before any launch: b < 0, n < 1, n > 32767, drop < 0, drop >= n,
+ * slot_offset + b > 2^32, pc or kept_pc NULL with b > 0, kept_pc overlapping pc.  b == 0 is a no-op. */
+int geoadv_random_drop(int b, int n, const float *pc /* [b,n,3] */, int drop, unsigned long long seed, unsigned long long counter,
+                       unsigned long long slot_offset, float *kept_pc /* [b,n,3] */, int *dropped_idx /* [b,drop] or NULL */,
+                       void *stream);
+
 /* get_critical_points + get_critical_pc_non_critical_pc (src/ae_utils.py:12-80) on the device, from (max_val, max_idx) =
  * (np.max, np.argmax)(pre_symmetry, axis=1) as geoadv_ae_critical returns them: (b,c) each.  critical_points (b,c,3) /
  * critical_idx (b,c) int16: the distinct arg-max points of the channels with max_val > 0, the point owning most channels first,
