@@ -37,7 +37,8 @@ struct SymRequest {
     bool screen = true;              // the process-wide screen switch (chamfer_sym_screen_on), read ONCE by whoever builds the request
 };
 // Launch shape of the symmetric scan: how the 8 waves of a workgroup are laid over rows and columns, and how many
-// columns a workgroup takes so that the grid fills the chip (256 / 128 / 64; `groups` = live (pair, cloud) groups).
+// columns a workgroup takes so that the grid fills the chip (the plain kernel: 256 / 128 / 64 per stage; the screened one: always 256;
+// `groups` = live (pair, cloud) groups).
 struct SymShape { int rw, cw, rtiles, C, S, cslices; bool mx; };
 struct SymBlocks { int first, count; };
 // Every decision of one launch, made once by chamfer_sym_plan() -- a pure host function: no device, no global -- read by the
@@ -45,7 +46,7 @@ struct SymBlocks { int first, count; };
 struct SymPlan {
     SymRequest req;
     SymShape shape;
-    int kernel;                      // 0: the plain kernel; 2 / 4 / 8: the screened one at 64 / 128 / 256 columns per stage
+    int kernel;                      // 0: the plain kernel; 8: the screened one (8 column tiles = 256 columns per stage, its only form)
     int rslices;                     // row partials per row (column slices x column waves)
     int rows;                        // how the row minima leave the launch: GEOADV_PLAN_ROWS_* (include/geoadv.h)
     SymBlocks search, scan, jac, loss;   // block ranges in grid order (count 0: absent); grid = their sum

@@ -423,21 +423,19 @@ bool chamfer_sym_screen_on() { return g_mx_on.load() != 0; }
 // would queue behind it, and its own serial phases (operands, column finish, uncertified queries: ~9 of ~24 us per 2048 x 256
 // tile) are only amortised when a CU gets several tiles.  Measured (tools/debug/mx_check.py, us per operator call, alternating in
 // one process): 32 x 2048^2 33.5 against 37.8 unscreened, 64 x 2048^2 55.0 / 60.7, 128 x 2048^2 87.0 / 108.2, 32 x 8192^2
-// 272 / 383; with 128-column slices (16 x 2048^2) 29.2 / 27.0; inside the B = 32 all-pairs loop with the Jacobian rider behind it
+// 272 / 383; with 128-column slices, an instantiation since removed (16 x 2048^2), 29.2 / 27.0; inside the B = 32 all-pairs loop with the Jacobian rider behind it
 // (two tiles per CU, tools/debug/mx_loop_ab.py) 156.7 us per iteration against 151.4.  So: operators from one 256-column tile
 // per CU on, the loop from four.
 static SymShape sym_shape(long groups, int n, int m, bool loop, bool screen) {
     SymShape s;
     s.mx = false;
     if (screen && n > 1024 && (long)cdiv(n, MX_ROWS) * cdiv(m, MX_CMAX) * groups >= (loop ? 4 : 1) * (long)kCUs) {
-        // the matrix-pipe-screened kernel (chamfer_mx.h): eight row-waves always, a slice of 256 / 128 / 64 columns per stage so that
-        // the grid covers the chip (same rule as below), several stages per workgroup while two workgroups per CU remain (one is
-        // resident at a time: 256 registers a wave)
+        // the matrix-pipe-screened kernel (chamfer_mx.h): eight row-waves always, 256 columns per stage always (the condition above
+        // says that 256-column tiles already cover the chip, so the rule below that halves the slices never applies), several
+        // stages per workgroup while two workgroups per CU remain (one is resident at a time: 256 registers a wave)
         s.mx = true; s.rw = MX_WAVES; s.cw = 1;
         s.rtiles = cdiv(n, MX_ROWS);
         s.C = MX_CMAX;
-        while (s.C > 64 && (long)s.rtiles * cdiv(m, s.C) * groups < kCUs &&
-               (s.C > 128 || (long)s.rtiles * cdiv(m, s.C / 2) * groups <= kCUs)) s.C /= 2;
         // column stages per workgroup: ONE workgroup is resident per CU, so the launch takes rounds(S) x (operands + S x stage) with
         // rounds = ceil(workgroups / CUs) -- ~6 + 18 S us per workgroup at 256-column stages.  More stages amortise the
         // operands and save whole rounds (512 tiles: two rounds of one stage 48, one round of two stages 42; 1600 tiles: 168 / 156 /
@@ -485,7 +483,7 @@ SymPlan chamfer_sym_plan(const SymRequest &r) {
     // (a second pair gated by `need1` usually has no work at all -- the grid search answers it -- so it does not count)
     const int np_live = r.need1 ? 1 : r.np;
     const SymShape s = p.shape = sym_shape((long)r.b * np_live, r.n, r.m, r.loop, r.screen);
-    p.kernel = !s.mx ? 0 : s.C == 256 ? 8 : s.C == 128 ? 4 : 2;
+    p.kernel = s.mx ? 8 : 0;                                // (the screened kernel has one instantiation: 8 column tiles = 256 columns a stage)
     p.rslices = s.cslices * s.cw;
     p.group_floats = 2 * (size_t)p.rslices * r.n + (s.rtiles > 1 ? 2 * (size_t)s.rtiles * r.m : 0);
     const size_t groups = (size_t)r.np * r.b;
@@ -593,8 +591,6 @@ int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *worksp
     if (int rc = attr.run([]() -> int {
             const int need = (int)std::max(std::max(std::max(CS_LDS_BYTES, MX_LDS_BYTES), chamfer_grid_lds_bytes(GR_MAX_N)), JAC_LDS_BYTES);
             GA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_sym_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, need));
-            GA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_mx_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, need));
-            GA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_mx_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, need));
             GA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_mx_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, need));
             return GEOADV_OK;
         })) return rc;
@@ -607,9 +603,7 @@ int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *worksp
     else a.loss.done = nullptr;
     a.loss.first_block = p.loss.first; a.loss.blocks = p.loss.count; a.loss.clouds = r.b;
     if (p.kernel == 0) chamfer_sym_kernel<<<p.grid, CS_THREADS, p.lds_bytes, stream>>>(a);
-    else if (p.kernel == 8) chamfer_mx_kernel<8><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
-    else if (p.kernel == 4) chamfer_mx_kernel<4><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
-    else chamfer_mx_kernel<2><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
+    else chamfer_mx_kernel<8><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
     GA_LAUNCH_CHECK();
     if (p.rows != GEOADV_PLAN_ROWS_MERGE_LAUNCH) return GEOADV_OK;   // final, or the caller's next launch reads partials / packed words
     chamfer_sym_merge_kernel<<<dim3(cdiv(std::max(r.n, r.m), 256), r.b * r.np), 256, 0, stream>>>(a);

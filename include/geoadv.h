@@ -999,7 +999,7 @@ int geoadv_attack_test_plan(geoadv_attack *at, int plan[GEOADV_PLAN_COUNT], int 
  * request[GEOADV_SYM_REQ_COUNT]: problems (1 or 2), clouds, rows, columns; flags: the loop's launch rule, second pair gated, the
  * search / Jacobian / loss riders asked for (+ workgroups per cloud of the loss riders, + hosted wherever possible), the caller takes
  * deferred rows, has a packed buffer (+ the fewest partials per row that are packed); clouds of the second operand of an all-pairs
- * matrix (0: cloud c against cloud c); the screen switch.  out[GEOADV_SYM_OUT_COUNT]: screened, kernel (0 plain, 2 / 4 / 8 screened),
+ * matrix (0: cloud c against cloud c); the screen switch.  out[GEOADV_SYM_OUT_COUNT]: screened, kernel (0 plain, 8 screened),
  * the launch shape, row partials per row, GEOADV_PLAN_ROWS_*, (first block, blocks) of the search, the scan, the Jacobian and the loss
  * riders, the grid, dynamic LDS bytes, arrivals a cloud's loss counter gains, the Jacobian riders' priority flag, scratch floats per
  * (pair, cloud) group and the offsets of the four partial arrays in floats (sizes saturate at INT_MAX). */

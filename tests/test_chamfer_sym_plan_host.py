@@ -67,7 +67,7 @@ def _check(p, b, n, np_, riders, where):
         assert p["loss_arrivals"] > 0, where
     else:
         assert p["loss_arrivals"] == 0, where
-    assert (p["kernel"] != 0) == bool(p["screened"]) and p["kernel"] in (0, 2, 4, 8), where
+    assert (p["kernel"] != 0) == bool(p["screened"]) and p["kernel"] in (0, 8), where
     assert p["rw"] * p["cw"] == 8 and p["rslices"] == p["cslices"] * p["cw"], where
     # exactly one row exit, and each only where its reader can take it
     assert p["rows"] in (FINAL, PARTIALS, PACKED, MERGE_LAUNCH), where

@@ -65,13 +65,15 @@ def test_paired_grid_search_on_shapes(kind, n, scale):
 
 
 @pytest.mark.parametrize("kind", ["sphere", "clusters", "duplicates", "lattice"])
-@pytest.mark.parametrize("b", [32, 16, 8, 4, 2])
-@pytest.mark.parametrize("prune", ["always", False])
+@pytest.mark.parametrize("prune,b", [(p, b) for b in (32, 16, 8, 4, 2) for p in ("always", False)] + [(False, 64)],
+                         ids=lambda v: str(v))
 def test_attack_loop_indices_on_shapes(kind, b, prune):
     """The loop's four index arrays after a few iterations on non-uniform clouds equal ops.nn_distance on the loop's own clouds, and
     its loss_ae / input_dist rows the means of ops.nn_distance's distances: B = 32 runs the symmetric scan with its row partials
     merged by the loss launch (8 column slices), B = 16 / 8 / 4 the same scan with narrow slices and the row minima folded into
-    packed words by 64-bit atomic minima, B = 2 the gated two-scan kernel; prune on / off = grid search / all-pairs."""
+    packed words by 64-bit atomic minima, B = 2 the gated two-scan kernel; prune on / off = grid search / all-pairs.  B = 64
+    (all-pairs only) is the smallest batch at which the loop's launch is the matrix-pipe-screened kernel (four 2048 x 256 tiles per
+    CU): the only other loop test on that kernel runs uniform cubes."""
     import torch
     from geometric_adv_amd import ops, weights as W
     from geometric_adv_amd.adv_ae import AdvAE, Configuration
@@ -86,6 +88,7 @@ def test_attack_loop_indices_on_shapes(kind, b, prune):
     at.init_pert(None, reset_optimizer=True)
     hist = torch.empty((4, 6, b), device=ae.device)
     at.run(0, 4, 2, hist)
+    assert at._test_plan()["screened"] == (b == 64)                         # GEOADV_PLAN_SCREENED of the forward that ran last
     p = at.peek()
     d1, i1, d2, i2 = ops.nn_distance(p["recon"], _t(gt), kernel="scan")     # the public op's own kernel, not the loop's
     assert torch.equal(p["idx_r1"], i1) and torch.equal(p["idx_r2"], i2)
