@@ -3,6 +3,8 @@ is missing or a call fails, this raises -- the product never routes through a CP
 import ctypes as C
 import os
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgeoadv.so")
 
@@ -23,20 +25,16 @@ def lib():
                 "g.build()'` or `make -C geometric_adv_amd/csrc` (needs hipcc, --offload-arch=gfx950)." % LIB_PATH)
         import torch  # noqa: F401  -- first: libgeoadv.so must bind to the HIP runtime torch ships, not to a second copy
         _lib = C.CDLL(LIB_PATH)
-        _lib.geoadv_last_error.restype = C.c_char_p
-        for name in ("geoadv_approx_match_temp_floats", "geoadv_ae_workspace_bytes", "geoadv_chamfer_matrix_workspace_floats",
-                     "geoadv_emd_cost_grad1_temp_floats", "geoadv_nn_distance_sym_workspace_floats",
-                     "geoadv_knn_workspace_bytes", "geoadv_group_point_grad_workspace_bytes", "geoadv_match_cost_workspace_floats",
-                     "geoadv_cls_workspace_bytes", "geoadv_cls_evaluate_workspace_bytes", "geoadv_atlas_workspace_bytes", "geoadv_fold_workspace_bytes",
-                     "geoadv_train_gemm_partial_floats"):
-            getattr(_lib, name).restype = C.c_size_t
+        for name in _abi.SIGNATURES:         # every call converts its arguments by the header's types, or raises TypeError
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = _abi.ctypes_signature(name)
     return _lib
 
 
 def check(status, what):
     if status != 0:
         msg = lib().geoadv_last_error().decode("utf-8", "replace")
-        if status == 1:
+        if status == _abi.GEOADV_EINVAL:
             raise ValueError("%s: %s" % (what, msg))
         raise GeoAdvError("%s failed (status %d): %s" % (what, status, msg))
 

@@ -10,7 +10,8 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
+from ._abi import AttackConfig as _AttackConfig
 from .adversary import init_pert_value
 from .autoencoder import PointNetAE
 
@@ -67,18 +68,9 @@ class Configuration:
         self.loss_in_scan = loss_in_scan                     # False: the loss + gradient pass always as a launch of its own; "always": riding wherever possible
 
 
-CHAMFER_KERNELS = {"auto": 0, "two_scan": 1, "symmetric": 2}
-ENCODER_BACKWARDS = {"auto": 0, "masked": 1, "jacobian": 2}
-
-
-class _AttackConfig(C.Structure):
-    _fields_ = [("batch", C.c_int), ("loss_adv_type", C.c_int), ("loss_dist_type", C.c_int),
-                ("max_point_pert_weight", C.c_float), ("max_point_dist_weight", C.c_float),
-                ("learning_rate", C.c_float), ("emd_weight", C.c_float), ("all_pairs_source_dist", C.c_int),
-                ("emd_weight_mode", C.c_int), ("recompute_backward", C.c_int), ("encoder_backward", C.c_int),
-                ("separate_adam", C.c_int), ("chamfer_kernel", C.c_int), ("loss_in_scan", C.c_int)]
-
-
+CHAMFER_KERNELS = {"auto": _abi.GEOADV_CHAMFER_AUTO, "two_scan": _abi.GEOADV_CHAMFER_TWO_SCAN, "symmetric": _abi.GEOADV_CHAMFER_SYMMETRIC}
+ENCODER_BACKWARDS = {"auto": _abi.GEOADV_ENC_BWD_AUTO, "masked": _abi.GEOADV_ENC_BWD_MASKED, "jacobian": _abi.GEOADV_ENC_BWD_JACOBIAN}
+# kernel classes of the profiler in the order of their codes, GEOADV_PROF_<NAME> = 0 .. GEOADV_PROF_COUNT - 1
 PROF_NAMES = ["encoder_fwd", "decoder_fwd", "chamfer_fwd", "loss_grad", "decoder_bwd", "encoder_bwd", "adam"]
 
 
@@ -98,9 +90,12 @@ class AdvAE:
                                                        encoder_arith=getattr(c, "encoder_arith", None))
         self.n = c.n_input[0]
         self.B = c.batch_size
-        cfg = _AttackConfig(self.B, 1 if c.loss_adv_type == "latent" else 0, 1 if c.loss_dist_type == "pert" else 0,
+        emd_mode = (_abi.GEOADV_EMD_REFERENCE if getattr(c, "emd_reference_weights", False) else _abi.GEOADV_EMD_FAST) | \
+                   (_abi.GEOADV_EMD_DENSE_LEVELS if getattr(c, "emd_dense_levels", False) else 0)
+        cfg = _AttackConfig(self.B, _abi.GEOADV_LOSS_ADV_LATENT if c.loss_adv_type == "latent" else _abi.GEOADV_LOSS_ADV_CHAMFER,
+                            _abi.GEOADV_LOSS_DIST_PERT if c.loss_dist_type == "pert" else _abi.GEOADV_LOSS_DIST_CHAMFER,
                             c.max_point_pert_weight, c.max_point_dist_weight, c.learning_rate, c.emd_weight,
-                            {True: 0, "pinned": 0, False: 1, "always": 2}[getattr(c, "chamfer_prune", True)], (1 if getattr(c, "emd_reference_weights", False) else 0) | (0x100 if getattr(c, "emd_dense_levels", False) else 0),
+                            {True: 0, "pinned": 0, False: 1, "always": 2}[getattr(c, "chamfer_prune", True)], emd_mode,
                             1 if getattr(c, "recompute_backward", False) else 0, ENCODER_BACKWARDS[getattr(c, "encoder_backward", "auto")],
                             1 if getattr(c, "separate_adam", False) else 0,
                             CHAMFER_KERNELS[getattr(c, "chamfer_kernel", "auto")], {True: 0, False: 1, "always": 2}[getattr(c, "loss_in_scan", True)])
@@ -213,9 +208,9 @@ class AdvAE:
         out = dict(pert=f(B, n, 3), adv=f(B, n, 3), recon=f(B, n, 3), latent=f(B, 128), grad=f(B, n, 3),
                    idx_r1=i(B, n), idx_r2=i(B, n), idx_a1=i(B, n), idx_a2=i(B, n))
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().geoadv_attack_peek(self._h, *[_lib.ptr(out[k]) for k in
-                       ("pert", "adv", "recon", "latent", "grad", "idx_r1", "idx_r2", "idx_a1", "idx_a2")],
-                       _lib.stream_handle()), "attack_peek")
+            p = {k: _lib.ptr(t) for k, t in out.items()}
+            _lib.check(_lib.lib().geoadv_attack_peek(self._h, p["pert"], p["adv"], p["recon"], p["latent"], p["grad"], p["idx_r1"],
+                                                     p["idx_r2"], p["idx_a1"], p["idx_a2"], _lib.stream_handle()), "attack_peek")
         if self.ae.bneck != 128:
             out["latent"] = out["latent"][:, :self.ae.bneck].contiguous()
         return out
@@ -231,8 +226,9 @@ class AdvAE:
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         out = dict(g_recon=f(B, n, 3), g_dist=f(B, n, 3), losses=f(8, B), dist_r1=f(B, n), dist_a1=f(B, n))
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().geoadv_attack_test_loss_state(self._h, *[_lib.ptr(out[k]) for k in
-                       ("g_recon", "g_dist", "losses", "dist_r1", "dist_a1")], _lib.stream_handle()), "attack_test_loss_state")
+            p = {k: _lib.ptr(t) for k, t in out.items()}
+            _lib.check(_lib.lib().geoadv_attack_test_loss_state(self._h, p["g_recon"], p["g_dist"], p["losses"], p["dist_r1"],
+                                                                p["dist_a1"], _lib.stream_handle()), "attack_test_loss_state")
         return out
 
     def _test_plan(self):
@@ -240,7 +236,7 @@ class AdvAE:
         (bool), rtiles, rslices, H, range (int: parts of the fixed-point gradient body and receiving points per part), rows ('final' | 'partials' | 'packed' | 'merge_launch'), loss ('metrics' | 'fused' |
         'riders'), grad ('none' | 'fused_1pass' | 'fused_general' | 'step_fx_1pass' | 'step_fx_general' | 'step_sorted') -- and
         jstar [2, B] (GPU tensor): the arg-max points its loss row found for the max-point terms (distance, perturbation)."""
-        plan = (C.c_int * 9)()                     # GEOADV_PLAN_COUNT
+        plan = (C.c_int * _abi.GEOADV_PLAN_COUNT)()
         jstar = torch.empty((2, self.B), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_attack_test_plan(self._h, plan, _lib.ptr(jstar), _lib.stream_handle()), "attack_test_plan")

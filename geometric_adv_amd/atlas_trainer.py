@@ -16,20 +16,16 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, atlas_weights as AW
-from .atlasnet import AtlasNetAE, _AtlasConfig, _AtlasWeights
+from . import _abi, _lib, atlas_weights as AW
+from ._abi import AtlasConfig as _AtlasConfig, AtlasTrainConfig as _AtlasTrainConfig, AtlasWeights as _AtlasWeights
+from .atlasnet import AtlasNetAE
 
-_STATE = {"bn_mean": 0, "bn_var": 1, "running_mean": 2, "running_var": 3, "bn_inv": 4, "bn_shift": 5, "pre_bn": 6, "gmax_row": 7,
-          "template": 8, "latent": 9, "recon": 10, "chamfer_idx": 11, "slot1": 12, "slot2": 13}
+_STATE = {k: getattr(_abi, "GEOADV_ATLAS_STATE_" + k.upper()) for k in (
+    "bn_mean", "bn_var", "running_mean", "running_var", "bn_inv", "bn_shift", "pre_bn", "gmax_row", "template", "latent", "recon",
+    "chamfer_idx", "slot1", "slot2")}
 _INT_STATES = ("gmax_row", "chamfer_idx")
 _PER_LAYER = ("bn_mean", "bn_var", "running_mean", "running_var", "bn_inv", "bn_shift", "pre_bn")
-MAX_TRAIN_LAYERS = 12
-
-
-class _AtlasTrainConfig(C.Structure):
-    """ctypes mirror of geoadv_atlas_train_config."""
-    _fields_ = [("batch", C.c_int), ("n_points", C.c_int), ("points_per_primitive", C.c_int), ("learning_rate", C.c_float),
-                ("seed", C.c_longlong), ("initial_step", C.c_longlong), ("initial_tracked", C.c_longlong)]
+MAX_TRAIN_LAYERS = _abi.GEOADV_ATLAS_ENC_LAYERS + _abi.GEOADV_ATLAS_MAX_DEC_LAYERS      # what geoadv_atlas_trainer_layout writes
 
 
 def check_batch(batch_size):
@@ -107,8 +103,7 @@ class AtlasNetTrainer:
         self._eval = None
         if slots is not None:
             s1, s2 = self._flatten(slots["exp_avg"]), self._flatten(slots["exp_avg_sq"])
-            _lib.check(L.geoadv_atlas_trainer_set_slots(self._h, C.c_void_p(s1.ctypes.data), C.c_void_p(s2.ctypes.data)),
-                       "atlas_trainer_set_slots")
+            _lib.check(L.geoadv_atlas_trainer_set_slots(self._h, s1.ctypes.data, s2.ctypes.data), "atlas_trainer_set_slots")
 
     def __del__(self):
         try:
@@ -194,7 +189,7 @@ class AtlasNetTrainer:
 
     def set_learning_rate(self, learning_rate, reset_optimizer=False):
         """reset_optimizer: a NEW Adam, as the reference builds at its decay epochs (slots and step count start again)."""
-        _lib.check(_lib.lib().geoadv_atlas_trainer_set_learning_rate(self._h, C.c_float(float(learning_rate)), int(bool(reset_optimizer))),
+        _lib.check(_lib.lib().geoadv_atlas_trainer_set_learning_rate(self._h, float(learning_rate), int(bool(reset_optimizer))),
                    "atlas_trainer_set_learning_rate")
         self.learning_rate = float(learning_rate)
 

@@ -15,22 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib, atlas_weights as AW, ops
+from ._abi import AtlasConfig as _AtlasConfig, AtlasWeights as _AtlasWeights
 from ._model import DeviceModel
-
-N_ENC = len(AW.ENC_LAYERS)
-N_DEC = 3 + AW.MAX_LAYERS
-
-
-class _AtlasConfig(C.Structure):
-    """ctypes mirror of geoadv_atlas_config."""
-    _fields_ = [(f, C.c_int) for f in ("nb_primitives", "points_per_primitive", "dim_template", "bottleneck_size",
-                                        "hidden_neurons", "num_layers", "activation", "decoder_bn")]
-
-
-class _AtlasWeights(C.Structure):
-    """ctypes mirror of geoadv_atlas_weights."""
-    _fields_ = [(p + f, C.c_void_p * n) for p, n in (("enc_", N_ENC), ("dec_", N_DEC))
-                for f in ("w", "b", "gamma", "beta", "mean", "var")]
 
 
 class AtlasNetAE(DeviceModel):
@@ -69,7 +55,7 @@ class AtlasNetAE(DeviceModel):
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_atlas_create(C.byref(self._h), C.byref(cfg), C.byref(hw),
-                                                      self.template.ctypes.data_as(C.c_void_p)), "atlas_create")
+                                                      self.template.ctypes.data), "atlas_create")
 
     def forward(self, x):
         """(latent (b, 1024), recon (b, P, 3)) float32 device tensors of EncoderDecoder.forward(x, train=False), fused

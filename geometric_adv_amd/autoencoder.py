@@ -10,19 +10,11 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops, weights as W
+from . import _abi, _lib, ops, weights as W
+from ._abi import AEWeights as _AEWeights
 from ._model import DeviceModel
 
-
-class _AEWeights(C.Structure):
-    _fields_ = [("n_points", C.c_int), ("enc_dims", C.c_int * 6), ("dec_dims", C.c_int * 4),
-                ("enc_w", C.c_void_p * 5), ("enc_b", C.c_void_p * 5),
-                ("bn_gamma", C.c_void_p * 5), ("bn_beta", C.c_void_p * 5),
-                ("bn_mean", C.c_void_p * 5), ("bn_var", C.c_void_p * 5),
-                ("dec_w", C.c_void_p * 3), ("dec_b", C.c_void_p * 3)]
-
-
-ENCODER_ARITH = {"f32": 0, "bf16x3": 1, "f16x2": 2}     # GEOADV_ENC_ARITH_*
+ENCODER_ARITH = {"f32": _abi.GEOADV_ENC_ARITH_F32, "bf16x3": _abi.GEOADV_ENC_ARITH_BF16X3, "f16x2": _abi.GEOADV_ENC_ARITH_F16X2}
 
 
 class PointNetAE(DeviceModel):
@@ -47,14 +39,14 @@ class PointNetAE(DeviceModel):
         hw.n_points = self.n_points
         hw.enc_dims[:] = W.enc_dims()
         hw.dec_dims[:] = W.dec_dims(self.n_points)
-        for i in range(5):
+        for i in range(_abi.GEOADV_ENC_LAYERS):
             hw.enc_w[i] = self._canon["enc_w"][i].ctypes.data
             hw.enc_b[i] = self._canon["enc_b"][i].ctypes.data
             hw.bn_gamma[i] = self._canon["gamma"][i].ctypes.data
             hw.bn_beta[i] = self._canon["beta"][i].ctypes.data
             hw.bn_mean[i] = self._canon["mean"][i].ctypes.data
             hw.bn_var[i] = self._canon["var"][i].ctypes.data
-        for k in range(3):
+        for k in range(_abi.GEOADV_DEC_LAYERS):
             hw.dec_w[k] = self._canon["dec_w"][k].ctypes.data
             hw.dec_b[k] = self._canon["dec_b"][k].ctypes.data
         self._h = C.c_void_p()

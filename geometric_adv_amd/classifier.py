@@ -14,18 +14,11 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, cls_weights as CW
+from . import _abi, _lib, cls_weights as CW
+from ._abi import ClsWeights as _ClsWeights
 from ._model import DeviceModel
 
-N_LAYERS = len(CW.LAYERS)
-
-
-class _ClsWeights(C.Structure):
-    """ctypes mirror of geoadv_cls_weights."""
-    _fields_ = [("num_classes", C.c_int),
-                ("w", C.c_void_p * N_LAYERS), ("b", C.c_void_p * N_LAYERS),
-                ("gamma", C.c_void_p * N_LAYERS), ("beta", C.c_void_p * N_LAYERS),
-                ("mean", C.c_void_p * N_LAYERS), ("var", C.c_void_p * N_LAYERS)]
+N_LAYERS = _abi.GEOADV_CLS_LAYERS
 
 
 class PointNetClassifier(DeviceModel):

@@ -14,19 +14,14 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, cls_weights as CW
-from .classifier import PointNetClassifier, _ClsWeights
+from . import _abi, _lib, cls_weights as CW
+from ._abi import ClsTrainConfig as _ClsTrainConfig, ClsWeights as _ClsWeights
+from .classifier import PointNetClassifier
 
-OPTIMIZERS = {"adam": 0, "momentum": 1}               # GEOADV_CLS_OPT_*
-_STATE = {"bn_mean": 0, "bn_var": 1, "moving_mean": 2, "moving_var": 3, "dropout_mask": 4, "pool_argmax": 5, "t1": 6,
-          "t2": 7, "logits": 8, "slot1": 9, "slot2": 10, "pre_bn": 11, "bn_inv": 12, "bn_shift": 13}
-
-
-class _ClsTrainConfig(C.Structure):
-    """ctypes mirror of geoadv_cls_train_config."""
-    _fields_ = [("batch", C.c_int), ("n_points", C.c_int), ("optimizer", C.c_int), ("learning_rate", C.c_float),
-                ("momentum", C.c_float), ("decay_step", C.c_int), ("decay_rate", C.c_float), ("initial_step", C.c_int),
-                ("dropout_seed", C.c_int)]
+OPTIMIZERS = {"adam": _abi.GEOADV_CLS_OPT_ADAM, "momentum": _abi.GEOADV_CLS_OPT_MOMENTUM}
+_STATE = {k: getattr(_abi, "GEOADV_CLS_STATE_" + k.upper()) for k in (
+    "bn_mean", "bn_var", "moving_mean", "moving_var", "dropout_mask", "pool_argmax", "t1", "t2", "logits", "slot1", "slot2", "pre_bn",
+    "bn_inv", "bn_shift")}
 
 
 def _loss64(logits, labels, t2):
@@ -72,7 +67,7 @@ class PointNetClassifierTrainer:
         pp, gp, cnt = C.c_void_p(), C.c_void_p(), C.c_size_t()
         _lib.check(L.geoadv_cls_trainer_buffers(self._h, C.byref(pp), C.byref(gp), C.byref(cnt)), "cls_trainer_buffers")
         self._count, self._params_ptr, self._grads_ptr = int(cnt.value), pp.value, gp.value
-        offs, moffs = (C.c_size_t * 80)(), (C.c_size_t * 20)()
+        offs, moffs = (C.c_size_t * (4 * _abi.GEOADV_CLS_LAYERS))(), (C.c_size_t * _abi.GEOADV_CLS_LAYERS)()
         _lib.check(L.geoadv_cls_trainer_layout(self._h, offs, moffs), "cls_trainer_layout")
         self._offsets, self._moving_offsets = list(offs), list(moffs)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -174,10 +169,8 @@ class PointNetClassifierTrainer:
             b1, b2 = float(slots["beta1_power"]), float(slots["beta2_power"])
         else:
             s1, s2, b1, b2 = self._flatten(slots, "/Momentum"), None, 0.9, 0.999
-        # host pointers as c_void_p: a bare Python int would be passed as a 32-bit C int
-        _lib.check(_lib.lib().geoadv_cls_trainer_set_slots(self._h, C.c_void_p(s1.ctypes.data),
-                                                           C.c_void_p(s2.ctypes.data if s2 is not None else 0),
-                                                           C.c_float(b1), C.c_float(b2)), "cls_trainer_set_slots")
+        _lib.check(_lib.lib().geoadv_cls_trainer_set_slots(self._h, s1.ctypes.data, s2.ctypes.data if s2 is not None else None, b1, b2),
+                   "cls_trainer_set_slots")
 
     def parameters(self):
         """Host copy of the flat parameter buffer."""

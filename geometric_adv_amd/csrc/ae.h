@@ -57,6 +57,44 @@ struct FusedAdam {
     float alpha, one_minus_b1, one_minus_b2, eps;
 };
 
+// Scratch of one forward, carved from a caller's workspace (ae.hip)
+struct ForwardScratch {
+    float *pmax; int *parg; int *pcnt;   // [b][tiles][128]
+    float *z; int *crit; int *zcnt;      // [b][128]
+    int *dense;                          // [b]
+    float *d1, *d2;                      // [b][256]
+    size_t bytes;
+};
+ForwardScratch carve_forward_scratch(void *base, int b, int n_points);
+
+// ---- launchers of encoder.hip (each is described at its definition) ----
+int encoder_tiles(const DeviceAE &A, int b);
+int encoder_tiles_max(int n);
+int encoder_mask_words();
+int launch_encoder_fwd(const DeviceAE &A, int b, const float *x, const float *pert, float *adv_out, float *pmax,
+                       int *parg, int *pcnt, unsigned *masks, hipStream_t stream, hipEvent_t start = nullptr, hipEvent_t stop = nullptr,
+                       const FusedAdam *fused = nullptr);
+int launch_encoder_bwd(const DeviceAE &A, int b, const float *adv, const int *crit_rows, const float *z,
+                       const int *zcnt, const float *dz, const int *dense_flag, float *g_enc, const unsigned *masks,
+                       hipStream_t stream);
+int launch_encoder_bwd_dense(const DeviceAE &A, int b, const float *adv, const float *z, const int *zcnt, const float *dz,
+                             const int *dense_flag, float *g_enc, hipStream_t stream);
+
+// ---- launchers of decoder.hip ----
+int launch_latent_decode(const DeviceAE &A, int b, const float *pmax, const int *parg, const int *pcnt, float *z,
+                         int *crit, int *zcnt, int *dense, float *d1, float *d2, hipStream_t stream);
+int launch_latent_decode_and_grid(const DeviceAE &A, int b, const float *pmax, const int *parg, const int *pcnt, float *z, int *crit,
+                                  int *zcnt, int *dense, float *d1, float *d2, const float *P, const float *Q, float *gd1, int *gi1,
+                                  float *gd2, int *gi2, int n, int *need, int call, const float *box, hipStream_t stream);
+int launch_latent_fc(const DeviceAE &A, int b, const float *z, float *d2, hipStream_t stream);
+int launch_decoder_fc2(const DeviceAE &A, int b, const float *d2, float *recon, hipStream_t stream, unsigned long long *fill = nullptr,
+                       size_t fill_count = 0);
+int launch_decoder_fc2_bwd(const DeviceAE &A, int b, const float *g_recon, float *partial, hipStream_t stream);
+int launch_decoder_bwd(const DeviceAE &A, int b, const float *g_recon, const float *d1, const float *d2, float *partial,
+                       float *dz, hipStream_t stream, const int *crit = nullptr, const float *jac = nullptr, const int *dense = nullptr,
+                       float *g_enc = nullptr);
+int decoder_bwd_chunks(const DeviceAE &A);
+
 }  // namespace geoadv
 
 namespace geoadv { int ae_range_check(const geoadv_ae *ae, hipStream_t stream, const char *who); }

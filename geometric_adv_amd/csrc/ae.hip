@@ -10,16 +10,6 @@
 
 namespace geoadv {
 
-int launch_encoder_fwd(const DeviceAE &A, int b, const float *x, const float *pert, float *adv_out, float *pmax,
-                       int *parg, int *pcnt, unsigned *masks, hipStream_t stream, hipEvent_t start = nullptr, hipEvent_t stop = nullptr,
-                       const FusedAdam *fused = nullptr);
-int launch_latent_decode(const DeviceAE &A, int b, const float *pmax, const int *parg, const int *pcnt, float *z,
-                         int *crit, int *zcnt, int *dense, float *d1, float *d2, hipStream_t stream);
-int launch_decoder_fc2(const DeviceAE &A, int b, const float *d2, float *recon, hipStream_t stream, unsigned long long *fill = nullptr,
-                       size_t fill_count = 0);
-int launch_latent_fc(const DeviceAE &A, int b, const float *z, float *d2, hipStream_t stream);
-int encoder_tiles_max(int n);
-
 // bf16 pieces of an fp32 (encoder_x3.h): round to nearest even, the remainders exact
 static inline uint16_t bf16_rne(float f) {
     uint32_t u;
@@ -111,14 +101,6 @@ static void pack_h2(uint32_t *img, const float *const W[ENC_L], const int *C, co
             }
     }
 }
-
-struct ForwardScratch {
-    float *pmax; int *parg; int *pcnt;   // [b][tiles][128]
-    float *z; int *crit; int *zcnt;      // [b][128]
-    int *dense;                          // [b]
-    float *d1, *d2;                      // [b][256]
-    size_t bytes;
-};
 
 ForwardScratch carve_forward_scratch(void *base, int b, int n_points) {
     ForwardScratch s;

@@ -27,42 +27,6 @@
 
 namespace geoadv {
 
-// ---- from the other translation units ------------------------------------------------------
-struct ChamferScan { const float *query; const float *target; float *dist; int *idx; int nq, nt; const int *need; };
-int launch_chamfer_scans(const ChamferScan *scans, int nscan, int b, hipStream_t stream);
-int launch_encoder_jac(const DeviceAE &A, int b, const JacArgs &a, hipStream_t stream);
-int launch_encoder_bwd_dense(const DeviceAE &A, int b, const float *adv, const float *z, const int *zcnt, const float *dz,
-                             const int *dense_flag, float *g_enc, hipStream_t stream);
-int launch_decoder_fc2_bwd(const DeviceAE &A, int b, const float *g_recon, float *partial, hipStream_t stream);
-int launch_decoder_tail_dense(const DeviceAE &A, const TailDenseArgs &a, hipStream_t stream);
-bool chamfer_grid_rides(int n);
-int launch_chamfer_grid(const float *P, const float *Q, float *d1, int *i1, float *d2, int *i2, int b, int n, int *need, int call, const float *box,
-                        hipStream_t stream);
-bool chamfer_grid_supports(int n, int m);
-int launch_latent_decode_and_grid(const DeviceAE &A, int b, const float *pmax, const int *parg, const int *pcnt, float *z, int *crit,
-                                  int *zcnt, int *dense, float *d1, float *d2, const float *P, const float *Q, float *gd1, int *gi1,
-                                  float *gd2, int *gi2, int n, int *need, int call, const float *box, hipStream_t stream);
-int launch_chamfer_grid_box(const float *Q, int b, int n, float *box, hipStream_t stream);
-struct ForwardScratch {
-    float *pmax; int *parg; int *pcnt; float *z; int *crit; int *zcnt; int *dense; float *d1, *d2; size_t bytes;
-};
-ForwardScratch carve_forward_scratch(void *base, int b, int n_points);
-int launch_encoder_fwd(const DeviceAE &A, int b, const float *x, const float *pert, float *adv_out, float *pmax,
-                       int *parg, int *pcnt, unsigned *masks, hipStream_t stream, hipEvent_t start = nullptr, hipEvent_t stop = nullptr,
-                       const FusedAdam *fused = nullptr);
-int encoder_mask_words();
-int launch_latent_decode(const DeviceAE &A, int b, const float *pmax, const int *parg, const int *pcnt, float *z,
-                         int *crit, int *zcnt, int *dense, float *d1, float *d2, hipStream_t stream);
-int launch_decoder_fc2(const DeviceAE &A, int b, const float *d2, float *recon, hipStream_t stream, unsigned long long *fill = nullptr,
-                       size_t fill_count = 0);
-int launch_decoder_bwd(const DeviceAE &A, int b, const float *g_recon, const float *d1, const float *d2, float *partial,
-                       float *dz, hipStream_t stream, const int *crit = nullptr, const float *jac = nullptr, const int *dense = nullptr,
-                       float *g_enc = nullptr);
-int decoder_bwd_chunks(const DeviceAE &A);
-int launch_encoder_bwd(const DeviceAE &A, int b, const float *adv, const int *crit_rows, const float *z,
-                       const int *zcnt, const float *dz, const int *dense_flag, float *g_enc, const unsigned *masks,
-                       hipStream_t stream);
-
 __global__ __launch_bounds__(256) void loss_metrics_kernel(LossArgs a) { loss_metrics_body(a, blockIdx.x, gridDim.x); }
 
 // chamfer_dist = reduce_mean(dist1, axis=1) + reduce_mean(dist2, axis=1) (get_dists_per_point.py:75, prepare_indices_for_attack.py:114)

@@ -17,6 +17,7 @@
 // 20*B*(N+M) algorithmic bytes.
 #include "common.h"
 #include "chamfer_grad.h"
+#include "chamfer_sym.h"
 #include <limits.h>
 #include <math.h>
 #include <stdlib.h>
@@ -25,15 +26,6 @@
 
 namespace geoadv {
 
-struct ChamferScan {
-    const float *query;   // [b, nq, 3]
-    const float *target;  // [b, nt, 3]
-    float *dist;          // [b, nq]
-    int *idx;             // [b, nq]
-    int nq, nt;
-    const int *need;      // null = every cloud; else int[8 * b] (16-byte aligned): cloud c is scanned only if one of its 8
-                          // flags is set (a workgroup of the paired grid search, chamfer_grid.hip, gave up on it)
-};
 struct ChamferArgs {
     ChamferScan s[4];
     int tiles, clouds, scans;   // 1-D grid decomposition (XCD aware, see the kernel)

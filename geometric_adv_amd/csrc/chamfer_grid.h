@@ -331,4 +331,11 @@ __device__ __forceinline__ bool grid_rider_block(const GridRider &r) {   // true
 
 inline size_t chamfer_grid_lds_bytes(int n) { return sizeof(float4) * (size_t)n + sizeof(unsigned) * GR_CELLS + sizeof(unsigned short) * (GR_CELLS + 2); }
 
+// ---- host side (chamfer_grid.hip) ----
+bool chamfer_grid_supports(int n, int m);
+bool chamfer_grid_rides(int n);
+int launch_chamfer_grid(const float *P, const float *Q, float *d1, int *i1, float *d2, int *i2, int b, int n, int *need, int call, const float *box,
+                        hipStream_t stream);
+int launch_chamfer_grid_box(const float *Q, int b, int n, float *box, hipStream_t stream);
+
 }  // namespace geoadv

@@ -122,6 +122,18 @@ struct CGradProblem {
 };
 int launch_chamfer_grad(const CGradProblem *pr, int np, int B, int n, hipStream_t st);
 
+// One direction of the two-scan kernel (chamfer.hip): up to four scans share a launch
+struct ChamferScan {
+    const float *query;   // [b, nq, 3]
+    const float *target;  // [b, nt, 3]
+    float *dist;          // [b, nq]
+    int *idx;             // [b, nq]
+    int nq, nt;
+    const int *need;      // null = every cloud; else int[8 * b] (16-byte aligned): cloud c is scanned only if one of its 8
+                          // flags is set (a workgroup of the paired grid search, chamfer_grid.hip, gave up on it)
+};
+int launch_chamfer_scans(const ChamferScan *scans, int nscan, int b, hipStream_t stream);
+
 // the reference's rule for a NaN distance to candidate 0, applied to finished nn_distance outputs (chamfer.hip)
 int launch_nn_nonfinite_fix(int b, int n, const float *xyz1, int m, const float *xyz2, float *dist1, int *idx1, float *dist2,
                             int *idx2, hipStream_t stream);

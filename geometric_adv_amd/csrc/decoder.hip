@@ -13,8 +13,6 @@
 
 namespace geoadv {
 
-int encoder_tiles(const DeviceAE &A, int b);
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int acc_row16(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }

@@ -211,5 +211,6 @@ struct TailDenseArgs {
     unsigned epoch;
     int *spin_timeout;            // set to 1 if a dense block ever gave up waiting (never observed; bounds the spin)
 };
+int launch_decoder_tail_dense(const DeviceAE &A, const TailDenseArgs &a, hipStream_t stream);
 
 }  // namespace geoadv

@@ -38,6 +38,7 @@ struct JacArgs {
     const int *dense_flag;      // [b] clouds with a tied maximum: skipped
     float *jac;                 // [b][128][3]
 };
+int launch_encoder_jac(const DeviceAE &A, int b, const JacArgs &a, hipStream_t stream);   // a launch of its own (encoder.hip)
 
 // channels [16 bx, 16 bx + 16) of cloud b; lds: JAC_LDS_BYTES, 16-byte aligned; all 8 waves (512 threads) take part.
 // AHEAD: request every layer's weights one layer ahead of their use (a launch of its own: 145 VGPRs) or just in time (as a

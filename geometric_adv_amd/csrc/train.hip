@@ -26,7 +26,7 @@
 
 namespace geoadv {
 
-// ---- from the other translation units (the Chamfer pieces of the attack loop) ----
+// (the Chamfer pieces of the attack loop that the step uses are declared in chamfer_sym.h)
 
 constexpr int TR_THREADS = 512;
 constexpr int TR_ROWS = 64;

@@ -16,22 +16,17 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, fold_weights as FW
-from .foldingnet import FoldingNetAE, _FoldWeights, PICKS_DEVICE, PICKS_GIVEN, SAMPLINGS, K, G2
+from . import _abi, _lib, fold_weights as FW
+from ._abi import FoldTrainConfig as _FoldTrainConfig, FoldWeights as _FoldWeights
+from .foldingnet import FoldingNetAE, PICKS_DEVICE, PICKS_GIVEN, SAMPLINGS, K, G2
 
-_STATE = {"bn_mean": 0, "bn_var": 1, "running_mean": 2, "running_var": 3, "bn_inv": 4, "bn_shift": 5, "pre_bn": 6,
-          "pool_winner": 7, "gmax_row": 8, "hidden": 9, "picks": 10, "cols": 11, "cov": 12, "code": 13, "mid": 14, "recon": 15,
-          "chamfer_idx": 16, "slot1": 17, "slot2": 18}
+_STATE = {k: getattr(_abi, "GEOADV_FOLD_STATE_" + k.upper()) for k in (
+    "bn_mean", "bn_var", "running_mean", "running_var", "bn_inv", "bn_shift", "pre_bn", "pool_winner", "gmax_row", "hidden", "picks",
+    "cols", "cov", "code", "mid", "recon", "chamfer_idx", "slot1", "slot2")}
 _INT_STATES = ("pool_winner", "gmax_row", "picks", "cols", "chamfer_idx")
 # (state-dict prefix, fan_in, fan_out, conv, BN index or None) in geoadv_fold_trainer_layout's order
 LAYERS = [("encoder." + name, fi, fo, conv, i + 1 if i < 6 else None) for i, (name, fi, fo, conv) in enumerate(FW.ENC_LAYERS)] + \
          [("decoder." + name, fi, fo, True, None) for name, fi, fo in FW.DEC_LAYERS]
-
-
-class _FoldTrainConfig(C.Structure):
-    """ctypes mirror of geoadv_fold_train_config."""
-    _fields_ = [("batch", C.c_int), ("n_points", C.c_int), ("learning_rate", C.c_float), ("weight_decay", C.c_float),
-                ("seed", C.c_longlong), ("initial_step", C.c_longlong), ("initial_ordinal", C.c_longlong)]
 
 
 def check_batch(batch_size):
@@ -83,9 +78,7 @@ class FoldingNetTrainer:
         self._graph_model = None
         if slots is not None:
             s1, s2 = self._flatten(slots["exp_avg"]), self._flatten(slots["exp_avg_sq"])
-            # host pointers as c_void_p: a bare Python int would be passed as a 32-bit C int
-            _lib.check(L.geoadv_fold_trainer_set_slots(self._h, C.c_void_p(s1.ctypes.data), C.c_void_p(s2.ctypes.data)),
-                       "fold_trainer_set_slots")
+            _lib.check(L.geoadv_fold_trainer_set_slots(self._h, s1.ctypes.data, s2.ctypes.data), "fold_trainer_set_slots")
 
     def __del__(self):
         try:

@@ -23,20 +23,15 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, fold_weights as FW, ops
+from . import _abi, _lib, fold_weights as FW, ops
+from ._abi import FoldWeights as _FoldWeights
 from ._model import DeviceModel
 
 G2 = FW.GRID * FW.GRID
 K = FW.NUM_NEIGHBOURS
-PICKS_GIVEN, PICKS_DEVICE = 0, 1
+PICKS_GIVEN, PICKS_DEVICE = _abi.GEOADV_FOLD_PICKS_GIVEN, _abi.GEOADV_FOLD_PICKS_DEVICE
 REFERENCE_CHUNK = 4
 SAMPLINGS = ("device", "reference")
-
-
-class _FoldWeights(C.Structure):
-    """ctypes mirror of geoadv_fold_weights."""
-    _fields_ = [("enc_" + f, C.c_void_p * len(FW.ENC_LAYERS)) for f in ("w", "b", "gamma", "beta", "mean", "var")] + \
-               [("dec_" + f, C.c_void_p * len(FW.DEC_LAYERS)) for f in ("w", "b")]
 
 
 class FoldingNetAE(DeviceModel):
@@ -124,7 +119,7 @@ class FoldingNetAE(DeviceModel):
         s = (self.seed if seed is None else int(seed)) & ((1 << 64) - 1)
         with torch.cuda.device(dev):
             ws = self._workspace(_lib.lib().geoadv_fold_workspace_bytes(self._h, b, n))
-            st = _lib.lib().geoadv_fold_forward(self._h, b, n, _lib.ptr(x), mode, C.c_ulonglong(s), C.c_longlong(int(cloud_offset)),
+            st = _lib.lib().geoadv_fold_forward(self._h, b, n, _lib.ptr(x), mode, s, int(cloud_offset),
                                                 _lib.ptr(pk), _lib.ptr(out["cols"]), _lib.ptr(out["code"]),
                                                 _lib.ptr(out.get("p1")), _lib.ptr(out["recon"]), _lib.ptr(ws),
                                                 _lib.stream_handle())

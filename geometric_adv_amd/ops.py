@@ -10,7 +10,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
+from ._abi import BatchAugment, CloudAugment    # noqa: F401  -- part of this module's interface
 
 
 def _f32(t, name, rank):
@@ -96,7 +97,7 @@ def nn_distance_sym(xyz1, xyz2):
     ws = torch.empty((wf,), dtype=torch.float32, device=xyz1.device)
     with torch.cuda.device(xyz1.device):
         st = _lib.lib().geoadv_nn_distance_sym(b, n, _lib.ptr(xyz1), m, _lib.ptr(xyz2), _lib.ptr(dist1), _lib.ptr(idx1),
-                                               _lib.ptr(dist2), _lib.ptr(idx2), _lib.ptr(ws), C.c_size_t(wf), _lib.stream_handle())
+                                               _lib.ptr(dist2), _lib.ptr(idx2), _lib.ptr(ws), wf, _lib.stream_handle())
     _lib.check(st, "nn_distance_sym")
     return dist1, idx1, dist2, idx2
 
@@ -197,7 +198,7 @@ def query_ball_point(radius, nsample, xyz1, xyz2):
     idx = torch.zeros((b, m, int(nsample)), dtype=torch.int32, device=xyz1.device)
     cnt = torch.zeros((b, m), dtype=torch.int32, device=xyz1.device)
     with torch.cuda.device(xyz1.device):
-        _call("geoadv_query_ball_point", b, n, m, C.c_float(radius), int(nsample), _lib.ptr(xyz1), _lib.ptr(xyz2),
+        _call("geoadv_query_ball_point", b, n, m, float(radius), int(nsample), _lib.ptr(xyz1), _lib.ptr(xyz2),
               _lib.ptr(idx), _lib.ptr(cnt))
     return idx, cnt
 
@@ -241,11 +242,12 @@ def group_point_grad(points, idx, grad_out):
     with torch.cuda.device(points.device):
         wb = int(_lib.lib().geoadv_group_point_grad_workspace_bytes(b, n, c, m, ns))
         ws = torch.empty(wb, dtype=torch.uint8, device=points.device)       # caller-owned scratch (torch's caching allocator)
-        _call("geoadv_group_point_grad_ws", b, n, c, m, ns, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(gp), _lib.ptr(ws), C.c_size_t(wb))
+        _call("geoadv_group_point_grad_ws", b, n, c, m, ns, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(gp), _lib.ptr(ws), wb)
     return gp
 
 
-KNN_KERNELS = {"auto": 0, "all_points": 1, "grid": 2, "grid_shells": 3}     # include/geoadv.h GEOADV_KNN_*
+KNN_KERNELS = {"auto": _abi.GEOADV_KNN_AUTO, "all_points": _abi.GEOADV_KNN_ALL_POINTS, "grid": _abi.GEOADV_KNN_GRID,
+               "grid_shells": _abi.GEOADV_KNN_GRID_SHELLS}
 _knn_default = "auto"
 
 
@@ -271,7 +273,7 @@ def knn_point(k, xyz1, xyz2, kernel=None):
         wb = int(_lib.lib().geoadv_knn_workspace_bytes(b, n, m, int(k)))
         ws = torch.empty(wb, dtype=torch.uint8, device=xyz1.device)
         _call("geoadv_knn_point_ws", _knn_kernel(kernel), b, n, m, int(k), _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(val), _lib.ptr(idx),
-              _lib.ptr(ws), C.c_size_t(wb))
+              _lib.ptr(ws), wb)
     return val, idx
 
 
@@ -297,12 +299,12 @@ def knn_dists(pc, num_knn, kernel=None):
     with torch.cuda.device(pc.device):
         wb = int(_lib.lib().geoadv_knn_workspace_bytes(b, n, n, int(num_knn) + 1))
         ws = torch.empty(wb, dtype=torch.uint8, device=pc.device)
-        _call("geoadv_knn_dists_ws", _knn_kernel(kernel), b, n, int(num_knn), _lib.ptr(pc), _lib.ptr(out), _lib.ptr(ws), C.c_size_t(wb))
+        _call("geoadv_knn_dists_ws", _knn_kernel(kernel), b, n, int(num_knn), _lib.ptr(pc), _lib.ptr(out), _lib.ptr(ws), wb)
     return out
 
 
 FPS_MAX_POINTS = 16384                                      # include/geoadv.h geoadv_farthest_point_sample
-FPS_FORMS = {"auto": 0, "workgroup": 1, "wave": 2}          # GEOADV_FPS_*
+FPS_FORMS = {"auto": _abi.GEOADV_FPS_AUTO, "workgroup": _abi.GEOADV_FPS_WORKGROUP, "wave": _abi.GEOADV_FPS_WAVE}
 
 
 def _fps_form(form):
@@ -398,7 +400,7 @@ def outlier_filter(point_clouds, knn_dists, knn_dist_thresh, top_k=None, want_ou
     o_idx = torch.empty((b, n), dtype=torch.int16, device=pc.device) if want_outliers else None
     o_num = torch.empty((b,), dtype=torch.int16, device=pc.device) if want_outliers else None
     with torch.cuda.device(pc.device):
-        _call("geoadv_outlier_filter", b, n, _lib.ptr(pc), _lib.ptr(kd), int(stride), int(top_k), C.c_float(float(knn_dist_thresh)),
+        _call("geoadv_outlier_filter", b, n, _lib.ptr(pc), _lib.ptr(kd), int(stride), int(top_k), float(knn_dist_thresh),
               _lib.ptr(o_pc), _lib.ptr(o_idx), _lib.ptr(o_num), _lib.ptr(inlier))
     return o_pc, o_idx, o_num, inlier
 
@@ -447,7 +449,7 @@ def sor_filter(point_clouds, knn_dists=None, k=2, alpha=1.1, want_outliers=True,
     o_num = torch.empty((b,), dtype=torch.int16, device=pc.device) if want_outliers else None
     stats = torch.empty((b, 3), dtype=torch.float64, device=pc.device) if return_stats else None
     with torch.cuda.device(pc.device):
-        _call("geoadv_sor_filter", b, n, _lib.ptr(pc), _lib.ptr(kd), int(stride), k, C.c_double(alpha),
+        _call("geoadv_sor_filter", b, n, _lib.ptr(pc), _lib.ptr(kd), int(stride), k, alpha,
               _lib.ptr(o_pc), _lib.ptr(o_idx), _lib.ptr(o_num), _lib.ptr(inlier), _lib.ptr(stats))
     return (o_pc, o_idx, o_num, inlier) + ((stats,) if return_stats else ())
 
@@ -475,7 +477,7 @@ def random_drop(point_clouds, drop, seed, counter=0, slot_offset=0, return_idx=F
     kept = torch.empty_like(pc)
     idx = torch.empty((b, drop), dtype=torch.int32, device=pc.device) if return_idx else None
     with torch.cuda.device(pc.device):
-        _call("geoadv_random_drop", b, n, _lib.ptr(pc), drop, C.c_ulonglong(seed), C.c_ulonglong(counter), C.c_ulonglong(slot_offset),
+        _call("geoadv_random_drop", b, n, _lib.ptr(pc), drop, seed, counter, slot_offset,
               _lib.ptr(kept), _lib.ptr(idx))
     return (kept, idx) if return_idx else kept
 
@@ -544,13 +546,6 @@ def _gather_index(index, num_clouds, dev):
     return b, idx
 
 
-class BatchAugment(C.Structure):
-    """geoadv_batch_augment (include/geoadv.h): the noise generator's key (seed, counter, slot_offset), the noise (mu, sigma,
-    clip; sigma 0 = none, clip <= 0 = unclamped) and the order of noise and rotation.  rot_count is filled in by batch_gather."""
-    _fields_ = [("seed", C.c_ulonglong), ("counter", C.c_ulonglong), ("slot_offset", C.c_int), ("noise_mu", C.c_float),
-                ("noise_sigma", C.c_float), ("noise_clip", C.c_float), ("rot_count", C.c_int), ("rotate_first", C.c_int)]
-
-
 def batch_gather(data, index=None, augment=None, rot=None, want_clean=False):
     """One training batch out of resident clouds in one launch (csrc/dataset.hip, geoadv_batch_gather).
     data: GPU float32 (num_clouds, n, 3).  index: the source cloud of every output cloud -- a host sequence / numpy array
@@ -596,7 +591,7 @@ def batch_gather(data, index=None, augment=None, rot=None, want_clean=False):
     feed = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
     clean = torch.empty_like(feed) if want_clean else None
     with torch.cuda.device(dev):
-        _call("geoadv_batch_gather", b, n, _lib.ptr(data), C.c_longlong(num_clouds), _lib.ptr(idx),
+        _call("geoadv_batch_gather", b, n, _lib.ptr(data), num_clouds, _lib.ptr(idx),
               C.byref(aug) if aug is not None else None, _lib.ptr(rot_dev), _lib.ptr(clean), _lib.ptr(feed))
     return (clean, feed) if want_clean else feed
 
@@ -604,7 +599,8 @@ def batch_gather(data, index=None, augment=None, rot=None, want_clean=False):
 # ---------------------------------------------------------------------------------------------
 # AtlasNet's data side (transfer/atlasnet/dataset/pointcloud_processor.py, augmenter.py), device side
 # ---------------------------------------------------------------------------------------------
-NORMALIZATIONS = {"Identity": 0, "UnitBall": 1, "BoundingBox": 2}
+NORMALIZATIONS = {"Identity": _abi.GEOADV_NORMALIZE_IDENTITY, "UnitBall": _abi.GEOADV_NORMALIZE_UNIT_BALL,
+                  "BoundingBox": _abi.GEOADV_NORMALIZE_BOUNDING_BOX}
 
 
 def normalize_clouds(point_clouds, normalization="UnitBall"):
@@ -625,17 +621,7 @@ def normalize_clouds(point_clouds, normalization="UnitBall"):
     return out
 
 
-AUGMENT_RECORD = 45     # GEOADV_AUGMENT_RECORD: 3 axial matrices, the 3-D matrix, scale, flip, translation
-
-
-class CloudAugment(C.Structure):
-    """geoadv_cloud_augment (include/geoadv.h): the generator's key (seed, counter, slot_offset), sample (points drawn with
-    replacement) and the Augmenter's operators: rot_axes / flip_axes are bit sets of the axes, rot_3d / scale / translate
-    switches.  The ranges default to the reference's: range_rot 360, scale 0.75 .. 1.25, translate_scale 0.03."""
-    _fields_ = [("seed", C.c_ulonglong), ("counter", C.c_ulonglong), ("slot_offset", C.c_int), ("sample", C.c_int),
-                ("rot_axes", C.c_int), ("range_rot", C.c_float), ("rot_3d", C.c_int), ("scale", C.c_int), ("scale_min", C.c_float),
-                ("scale_max", C.c_float), ("flip_axes", C.c_int), ("translate", C.c_int), ("translate_scale", C.c_float)]
-    DEFAULTS = dict(range_rot=360.0, scale_min=0.75, scale_max=1.25, translate_scale=0.03)
+AUGMENT_RECORD = _abi.GEOADV_AUGMENT_RECORD     # 3 axial matrices, the 3-D matrix, scale, flip, translation
 
 
 def augment_batch(data, index=None, config=None, params=None, n_out=None, want_params=False):
@@ -677,7 +663,7 @@ def augment_batch(data, index=None, config=None, params=None, n_out=None, want_p
     out = torch.empty((b, n_out, 3), dtype=torch.float32, device=dev)
     par_out = torch.empty((b, AUGMENT_RECORD), dtype=torch.float32, device=dev) if want_params else None
     with torch.cuda.device(dev):
-        _call("geoadv_augment_batch", b, n_out, _lib.ptr(data), C.c_longlong(num_clouds), n_src, _lib.ptr(idx),
+        _call("geoadv_augment_batch", b, n_out, _lib.ptr(data), num_clouds, n_src, _lib.ptr(idx),
               C.byref(cfg) if cfg is not None else None, _lib.ptr(par), _lib.ptr(par_out), _lib.ptr(out))
     return (out, par_out) if want_params else out
 
@@ -697,16 +683,16 @@ def rotate_point_cloud_by_angle(batch_data, rotation_angle):
     b, n, _ = pc.shape
     out = torch.empty_like(pc)
     with torch.cuda.device(pc.device):
-        _call("geoadv_rotate_y", b, n, _lib.ptr(pc), C.c_double(float(np.cos(rotation_angle))),
-              C.c_double(float(np.sin(rotation_angle))), _lib.ptr(out))
+        _call("geoadv_rotate_y", b, n, _lib.ptr(pc), float(np.cos(rotation_angle)),
+              float(np.sin(rotation_angle)), _lib.ptr(out))
     return out
 
 
 # ---------------------------------------------------------------------------------------------
 # external/structural_losses/tf_approxmatch.py
 # ---------------------------------------------------------------------------------------------
-EMD_FAST, EMD_REFERENCE = 0, 1          # include/geoadv.h: how the pair weight expf(level * d2) is evaluated
-EMD_DENSE_LEVELS = 0x100                # ... | this flag: every sweep of the call dense (no cell-grid form of the first three levels)
+EMD_FAST, EMD_REFERENCE = _abi.GEOADV_EMD_FAST, _abi.GEOADV_EMD_REFERENCE      # how the pair weight expf(level * d2) is evaluated
+EMD_DENSE_LEVELS = _abi.GEOADV_EMD_DENSE_LEVELS                          # ... | this flag: every sweep of the call dense (no cell-grid form of the first three levels)
 
 
 def emd_sparse_levels(on):
@@ -754,7 +740,7 @@ def match_cost(xyz1, xyz2, match):
     with torch.cuda.device(xyz1.device):
         wf = int(_lib.lib().geoadv_match_cost_workspace_floats(b, n, m))
         ws = torch.empty(wf, dtype=torch.float32, device=xyz1.device)
-        _call("geoadv_match_cost_ws", b, n, m, _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(match), _lib.ptr(cost), _lib.ptr(ws), C.c_size_t(wf))
+        _call("geoadv_match_cost_ws", b, n, m, _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(match), _lib.ptr(cost), _lib.ptr(ws), wf)
     return cost
 
 
@@ -827,7 +813,7 @@ def chamfer_dist_matrix(pcs_a, pcs_b, max_workspace_bytes=2 << 30):
         nfl = int(min(want, max(max_workspace_bytes // 4, _lib.lib().geoadv_chamfer_matrix_workspace_floats(1, 1, n, m))))
         ws = torch.empty(nfl, dtype=torch.float32, device=a.device)
         st = _lib.lib().geoadv_chamfer_matrix(na, nb, n, m, _lib.ptr(a), _lib.ptr(b), _lib.ptr(out), _lib.ptr(ws),
-                                              C.c_size_t(nfl), _lib.stream_handle())
+                                              nfl, _lib.stream_handle())
     _lib.check(st, "chamfer_matrix")
     return out
 
@@ -873,16 +859,15 @@ def train_gemm(kernel, a, a_strides, b, b_strides, c, c_strides, bias, bias_stri
     for t, name in ((a, "a"), (b, "b"), (c, "c")) + (((bias, "bias"),) if bias is not None else ()):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
             raise ValueError("%s must be a float32 GPU tensor" % name)
-    ll = C.c_longlong
     ks = C.c_int(0)
     with torch.cuda.device(c.device):
         part, nf = None, 0
         if kernel == TRAIN_GEMM_SPLITK:
             nf = int(_lib.lib().geoadv_train_gemm_partial_floats())
             part = torch.empty(nf, dtype=torch.float32, device=c.device)      # caller-owned scratch (torch's caching allocator)
-        st = _lib.lib().geoadv_train_gemm(int(kernel), _lib.ptr(a), ll(a_strides[0]), ll(a_strides[1]), ll(a_strides[2]), _lib.ptr(b),
-                                          ll(b_strides[0]), ll(b_strides[1]), ll(b_strides[2]), _lib.ptr(c), ll(c_strides[0]),
-                                          ll(c_strides[1]), _lib.ptr(bias), ll(bias_stride), int(m), int(n), int(k), int(batch),
-                                          _lib.ptr(part), C.c_size_t(nf), C.byref(ks), _lib.stream_handle())
+        st = _lib.lib().geoadv_train_gemm(int(kernel), _lib.ptr(a), int(a_strides[0]), int(a_strides[1]), int(a_strides[2]), _lib.ptr(b),
+                                          int(b_strides[0]), int(b_strides[1]), int(b_strides[2]), _lib.ptr(c), int(c_strides[0]),
+                                          int(c_strides[1]), _lib.ptr(bias), int(bias_stride), int(m), int(n), int(k), int(batch),
+                                          _lib.ptr(part), nf, C.byref(ks), _lib.stream_handle())
     _lib.check(st, "train_gemm")
     return ks.value

@@ -18,27 +18,22 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, weights as W
-from .autoencoder import _AEWeights
-
-
-class _TrainConfig(C.Structure):
-    _fields_ = [("batch", C.c_int), ("learning_rate", C.c_float), ("bn_decay", C.c_float), ("loss", C.c_int),
-                ("max_workgroups", C.c_int)]
+from . import _abi, _lib, weights as W
+from ._abi import AEWeights as _AEWeights, TrainConfig as _TrainConfig
 
 
 def _fill_weights_struct(hw, canon, n_points):
     hw.n_points = n_points
     hw.enc_dims[:] = W.enc_dims()
     hw.dec_dims[:] = W.dec_dims(n_points)
-    for i in range(5):
+    for i in range(_abi.GEOADV_ENC_LAYERS):
         hw.enc_w[i] = canon["enc_w"][i].ctypes.data
         hw.enc_b[i] = canon["enc_b"][i].ctypes.data
         hw.bn_gamma[i] = canon["gamma"][i].ctypes.data
         hw.bn_beta[i] = canon["beta"][i].ctypes.data
         hw.bn_mean[i] = canon["mean"][i].ctypes.data
         hw.bn_var[i] = canon["var"][i].ctypes.data
-    for k in range(3):
+    for k in range(_abi.GEOADV_DEC_LAYERS):
         hw.dec_w[k] = canon["dec_w"][k].ctypes.data
         hw.dec_b[k] = canon["dec_b"][k].ctypes.data
 
@@ -88,11 +83,12 @@ class PointNetAETrainer:
         if loss not in ("chamfer", "emd"):                       # conf.loss (src/pointnet_ae.py:74-79)
             raise ValueError("loss must be 'chamfer' or 'emd'")
         self.loss = loss
-        cfg = _TrainConfig(self.batch_size, float(learning_rate), float(bn_decay), 1 if loss == "emd" else 0, int(max_workgroups))
+        cfg = _TrainConfig(self.batch_size, float(learning_rate), float(bn_decay),
+                           _abi.GEOADV_TRAIN_LOSS_EMD if loss == "emd" else _abi.GEOADV_TRAIN_LOSS_CHAMFER, int(max_workgroups))
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_trainer_create(C.byref(self._h), C.byref(hw), C.byref(cfg)), "trainer_create")
-        offs = (C.c_size_t * 26)()
+        offs = (C.c_size_t * (4 * _abi.GEOADV_ENC_LAYERS + 2 * _abi.GEOADV_DEC_LAYERS))()
         _lib.check(_lib.lib().geoadv_trainer_layout(self._h, offs), "trainer_layout")
         self._offsets = [int(o) for o in offs]
         pp, gp, cnt = C.c_void_p(), C.c_void_p(), C.c_size_t()
@@ -118,8 +114,10 @@ class PointNetAETrainer:
         """The library-owned flat buffer as a torch tensor (no copy): what the gradient all-reduce runs on."""
         return _lib.device_view(ptr, self._count, "<f4", self.device)
 
-    _STATE = {"act": 0, "mean": 1, "inv_std": 2, "scale": 3, "shift": 4, "idx1": 5, "idx2": 6, "pool_max": 7, "pool_ties": 8,
-               "d1": 9, "d2": 10}                           # GEOADV_TRAIN_STATE_*
+    _STATE = {"act": _abi.GEOADV_TRAIN_STATE_ACT, "mean": _abi.GEOADV_TRAIN_STATE_BN_MEAN, "inv_std": _abi.GEOADV_TRAIN_STATE_BN_INV_STD,
+              "scale": _abi.GEOADV_TRAIN_STATE_BN_SCALE, "shift": _abi.GEOADV_TRAIN_STATE_BN_SHIFT, "idx1": _abi.GEOADV_TRAIN_STATE_IDX1,
+              "idx2": _abi.GEOADV_TRAIN_STATE_IDX2, "pool_max": _abi.GEOADV_TRAIN_STATE_POOL_MAX,
+              "pool_ties": _abi.GEOADV_TRAIN_STATE_POOL_TIES, "d1": _abi.GEOADV_TRAIN_STATE_DEC1, "d2": _abi.GEOADV_TRAIN_STATE_DEC2}
 
     def _state_view(self, what, layer=0):
         """Read-only test view (no copy) of what the last step kept on the device (geoadv_trainer_state): the pre-BN
@@ -218,7 +216,7 @@ class PointNetAETrainer:
 
     def apply(self, grad_scale=1.0):
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().geoadv_trainer_apply(self._h, C.c_float(grad_scale), _lib.stream_handle()), "trainer_apply")
+            _lib.check(_lib.lib().geoadv_trainer_apply(self._h, float(grad_scale), _lib.stream_handle()), "trainer_apply")
 
     def partial_fit(self, X, GT=None, want_recon=True, sync=True):
         """AutoEncoder.partial_fit (autoencoder.py:105-125): -> (recon, loss) of the pre-update weights.
