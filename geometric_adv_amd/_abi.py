@@ -103,6 +103,9 @@ SIGNATURES = {      # in the header's order
     "geoadv_fold_trainer_layout": "i:ppp",
     "geoadv_fold_trainer_counters": "i:ppp",
     "geoadv_fold_trainer_state": "i:piipp",
+    "geoadv_fold_train_pool": "i:iiippppp",
+    "geoadv_fold_train_pool_grad": "i:iiippppppp",
+    "geoadv_fold_train_gmax": "i:iiipppppp",
     "geoadv_atlas_trainer_create": "i:pppp",
     "geoadv_atlas_trainer_destroy": "v:p",
     "geoadv_atlas_trainer_set_slots": "i:ppp",

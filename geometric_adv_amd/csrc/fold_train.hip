@@ -132,6 +132,21 @@ enum { E1 = 0, E2, E3, E4, E5, F1, F2, D0, D1, D2, D3, D4, D5, NL };
 const int kIn[NL] = {12, 64, 64, 64, 128, FT_LAT, FT_CODE, FT_CODE + 2, 512, 512, FT_CODE + 3, 512, 512};
 const int kOut[NL] = {64, 64, 64, 128, FT_LAT, FT_CODE, FT_CODE, 512, 512, 3, 512, 512, 3};
 bool bn_of(int l) { return l <= F1; }
+
+// The one launch of each pool kernel and of the global maximum: the step (Run) and the geoadv_fold_train_pool / _pool_grad /
+// _gmax entries all go through these.  rows = b * n.
+void ft_launch_graph_pool(Launch &q, const float *h, const int *cols, size_t rows, int n, int C, float *g, int *win) {
+    const size_t total = rows * C;
+    q.launch(ft_graph_pool_kernel, dim3(blocks_of(total)), dim3(256), h, cols, n, C, total, g, win);
+}
+void ft_launch_pool_bwd(Launch &q, const float *dg, const int *win, const int *off, const int *deg, const int *col, size_t rows, int n, int C,
+                        float *dh) {
+    const size_t total = rows * C;
+    q.launch(ft_pool_bwd_kernel, dim3(blocks_of(total)), dim3(256), dg, win, off, deg, col, n, C, total, dh);
+}
+void ft_launch_gmax(Launch &q, const float *a, int B, int n, int C, const float *inv, const float *shift, float *pooled, int *arg) {
+    q.launch(tb_gmax_kernel, dim3(cdiv(C, 64), B), dim3(256), a, n, C, inv, shift, pooled, arg);
+}
 }  // namespace
 
 struct geoadv_fold_trainer {
@@ -188,8 +203,7 @@ struct Run : Launch {
         if (y) bn_relu(l, y);
     }
     void graph_pool(const float *h, int which, int C, float *g, int *win) {
-        const size_t total = (size_t)t->R * C;
-        launch(ft_graph_pool_kernel, dim3(blocks_of(total)), dim3(256), h, t->graph.cols + (size_t)which * t->R * FT_NB, t->n, C, total, g, win);
+        ft_launch_graph_pool(*this, h, t->graph.cols + (size_t)which * t->R * FT_NB, (size_t)t->R, t->n, C, g, win);
     }
     void relu(float *y, size_t total) { launch(ft_relu_kernel, dim3(blocks_of(total)), dim3(256), y, total); }
     void mask(float *d, const float *H, size_t total) { launch(ft_mask_kernel, dim3(blocks_of(total)), dim3(256), d, H, total); }
@@ -262,8 +276,7 @@ struct Run : Launch {
                    iv, sh, t->m1 + o, t->m2 + o, FT_EPS, da);
     }
     void pool_bwd(const float *dg, const int *win, int C, float *dh) {
-        const size_t total = (size_t)t->R * C;
-        launch(ft_pool_bwd_kernel, dim3(blocks_of(total)), dim3(256), dg, win, t->graph.off, t->graph.deg, t->graph.col, t->n, C, total, dh);
+        ft_launch_pool_bwd(*this, dg, win, t->graph.off, t->graph.deg, t->graph.col, (size_t)t->R, t->n, C, dh);
     }
     // one fold backward: dout [rows][3] -> every gradient of layers l0 .. l0 + 2, dcode (=|+=), dpts [rows][D] (or null)
     void fold_bwd(int l0, const float *pts, int D, const float *H1, const float *H2, const float *dout, float *dpts, int acc_code) {
@@ -299,8 +312,7 @@ int run_step(geoadv_fold_trainer *t, const float *x, hipStream_t st) {
     q.bn_layer(E4, t->g1, t->h[3]);
     q.graph_pool(t->h[3], 1, 128, t->g2, t->win2);
     q.bn_layer(E5, t->g2, nullptr);
-    q.launch(tb_gmax_kernel, dim3(FT_LAT / 64, B), dim3(256), t->a[E5], t->n, FT_LAT, t->inv + t->o_mv[E5], t->shift + t->o_mv[E5], t->pooled,
-             t->arg);
+    ft_launch_gmax(q, t->a[E5], B, t->n, FT_LAT, t->inv + t->o_mv[E5], t->shift + t->o_mv[E5], t->pooled, t->arg);
     q.bn_layer(F1, t->pooled, t->h6);
     q.linear_fwd(F2, t->h6, t->code, B, 0, FT_CODE, true);
     q.fold_fwd(D0, t->grid, 2, t->H[0], t->H[1], t->mid);
@@ -541,4 +553,45 @@ extern "C" int geoadv_fold_trainer_state(const geoadv_fold_trainer *t, int what,
     }
     set_error("fold_trainer_state: unknown state %d", what);
     return GEOADV_EINVAL;
+}
+
+namespace {
+int check_kernel_sizes(const char *who, int b, int n, int c) {
+    GA_REQUIRE(b >= 1 && b <= 1024, "%s: b %d out of range [1, 1024]", who, b);
+    GA_REQUIRE(n >= 1, "%s: n %d must be >= 1", who, n);
+    GA_REQUIRE((long long)b * n <= FOLD_TRAIN_MAX_ROWS, "%s: b * n = %lld exceeds 2^17 rows", who, (long long)b * n);
+    GA_REQUIRE(c >= 1 && c <= 65536, "%s: c %d out of range [1, 65536]", who, c);
+    return GEOADV_OK;
+}
+int finish(const char *who, const Launch &q) {
+    if (q.ok()) return GEOADV_OK;
+    set_error("%s: %s", who, hipGetErrorString(q.err));
+    return GEOADV_EHIP;
+}
+}  // namespace
+
+extern "C" int geoadv_fold_train_pool(int b, int n, int c, const float *h, const int *cols, float *g, int *win, void *stream) {
+    GA_REQUIRE(h && cols && g && win, "fold_train_pool: null argument");
+    if (int rc = check_kernel_sizes("fold_train_pool", b, n, c)) return rc;
+    Launch q{as_stream(stream)};
+    ft_launch_graph_pool(q, h, cols, (size_t)b * n, n, c, g, win);
+    return finish("fold_train_pool", q);
+}
+
+extern "C" int geoadv_fold_train_pool_grad(int b, int n, int c, const float *dg, const int *win, const int *off, const int *deg,
+                                           const int *col, float *dh, void *stream) {
+    GA_REQUIRE(dg && win && off && deg && col && dh, "fold_train_pool_grad: null argument");
+    if (int rc = check_kernel_sizes("fold_train_pool_grad", b, n, c)) return rc;
+    Launch q{as_stream(stream)};
+    ft_launch_pool_bwd(q, dg, win, off, deg, col, (size_t)b * n, n, c, dh);
+    return finish("fold_train_pool_grad", q);
+}
+
+extern "C" int geoadv_fold_train_gmax(int b, int n, int c, const float *a, const float *inv, const float *shift, float *pooled, int *arg,
+                                      void *stream) {
+    GA_REQUIRE(a && inv && shift && pooled && arg, "fold_train_gmax: null argument");
+    if (int rc = check_kernel_sizes("fold_train_gmax", b, n, c)) return rc;
+    Launch q{as_stream(stream)};
+    ft_launch_gmax(q, a, b, n, c, inv, shift, pooled, arg);
+    return finish("fold_train_gmax", q);
 }

@@ -871,3 +871,41 @@ def train_gemm(kernel, a, a_strides, b, b_strides, c, c_strides, bias, bias_stri
                                           _lib.ptr(part), nf, C.byref(ks), _lib.stream_handle())
     _lib.check(st, "train_gemm")
     return ks.value
+
+
+# ---------------------------------------------------------------------------------------------
+# the FoldingNet training step's pool and global-maximum kernels on their own (tests and tools)
+# ---------------------------------------------------------------------------------------------
+def _train_buffers(*named):
+    for t, name, dtype in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError("%s must be a %s GPU tensor" % (name, str(dtype).replace("torch.", "")))
+
+
+def fold_train_pool(b, n, c, h, cols, g, win):
+    """geoadv_fold_train_pool: the training step's graph pool (csrc/fold_train.hip) through the step's own launch.  h float32
+    [b n][c], cols int32 [b n][16] rows of the point's cloud in [0, n) -> g float32 [b n][c], win int32 [b n][c] (written).  The
+    tensors are read and written from their first element on: nothing is reshaped or copied, the caller owns the layout."""
+    _train_buffers((h, "h", torch.float32), (cols, "cols", torch.int32), (g, "g", torch.float32), (win, "win", torch.int32))
+    with torch.cuda.device(h.device):
+        _call("geoadv_fold_train_pool", int(b), int(n), int(c), _lib.ptr(h), _lib.ptr(cols), _lib.ptr(g), _lib.ptr(win))
+
+
+def fold_train_pool_grad(b, n, c, dg, win, off, deg, col, dh):
+    """geoadv_fold_train_pool_grad: the pool's backward through the step's own launch.  dg float32 and win int32 [b n][c]; off, deg
+    int32 [b n] and col int32 [b][32 n], the adjacency rows in the layout of csrc/fold_graph.h -> dh float32 [b n][c] (written)."""
+    _train_buffers((dg, "dg", torch.float32), (win, "win", torch.int32), (off, "off", torch.int32), (deg, "deg", torch.int32),
+                   (col, "col", torch.int32), (dh, "dh", torch.float32))
+    with torch.cuda.device(dg.device):
+        _call("geoadv_fold_train_pool_grad", int(b), int(n), int(c), _lib.ptr(dg), _lib.ptr(win), _lib.ptr(off), _lib.ptr(deg),
+              _lib.ptr(col), _lib.ptr(dh))
+
+
+def fold_train_gmax(b, n, c, a, inv, shift, pooled, arg):
+    """geoadv_fold_train_gmax: the global maximum of the FoldingNet training step (csrc/train_bn.h, fold_train.hip's copy) through
+    the step's own launch.  a float32 [b n][c]; inv, shift float32 [c] -> pooled float32 [b][c], arg int32 [b][c] (written)."""
+    _train_buffers((a, "a", torch.float32), (inv, "inv", torch.float32), (shift, "shift", torch.float32),
+                   (pooled, "pooled", torch.float32), (arg, "arg", torch.int32))
+    with torch.cuda.device(a.device):
+        _call("geoadv_fold_train_gmax", int(b), int(n), int(c), _lib.ptr(a), _lib.ptr(inv), _lib.ptr(shift), _lib.ptr(pooled),
+              _lib.ptr(arg))

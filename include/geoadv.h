@@ -772,6 +772,22 @@ int geoadv_fold_trainer_counters(const geoadv_fold_trainer *t, long long *step, 
 #define GEOADV_FOLD_STATE_SLOT2        18
 int geoadv_fold_trainer_state(const geoadv_fold_trainer *t, int what, int layer, const void **ptr, size_t *count);
 
+/* TESTS / TOOLS: three kernels of the FoldingNet training step on caller-supplied DEVICE buffers, each through the launch the step
+ * itself uses (csrc/fold_train.hip).  b in 1 ... 1024, n >= 1, b * n <= 2^17, c in 1 ... 65536; no pointer may be NULL.
+ * pool: the graph pool and its ReLU.  h [b n][c]; cols [b n][16] rows of the point's own cloud, each in [0, n).
+ *   g [b n][c] = the maximum over (the point itself, its 16 columns) where that is positive, else +0; win [b n][c] = the row that
+ *   attained it -- the point itself first, then the lowest slot -- or -1.
+ * pool_grad: the pool's backward, gathered by destination.  dg, win as above; off / deg [b n] and col [b][32 n]: the sorted row of
+ *   point i of cloud k is col[k * 32 n + off[k n + i] ...], deg[k n + i] entries (csrc/fold_graph.h), which must hold every i' != i
+ *   with win[i'][.] == i.  dh [b n][c] = [win[i] == i] dg[i] + the dg[i'] of those i', added in the row's order.
+ * gmax: pooled [b][c] = the maximum over the n rows of each cloud of a * inv + shift (a [b n][c]; inv, shift [c]; two rounded
+ *   operations), arg [b][c] = its first row. */
+int geoadv_fold_train_pool(int b, int n, int c, const float *h, const int *cols, float *g, int *win, void *stream);
+int geoadv_fold_train_pool_grad(int b, int n, int c, const float *dg, const int *win, const int *off, const int *deg, const int *col,
+                                float *dh, void *stream);
+int geoadv_fold_train_gmax(int b, int n, int c, const float *a, const float *inv, const float *shift, float *pooled, int *arg,
+                           void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * AtlasNet training: one step of transfer/atlasnet/training/trainer.py's train_iteration for the point-cloud
  * auto-encoder -- EncoderDecoder.forward(x, train=True) (batch statistics, eps 1e-5, running statistics 0.9 / 0.1 with the

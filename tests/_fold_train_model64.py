@@ -16,6 +16,12 @@ Pinning fp64's own decisions reproduces the unpinned step.  res["disagree"][name
 number of pins, the largest fp64 distance from its boundary of a differing pin: |ReLU input|, or own maximum minus the
 pinned element's value, or pinned distance minus the smallest).
 
+tie: candidates within `tie` of a maximum count as attaining it, and the first of them wins (pools and the global maximum).
+0.0, the default, is the plain first maximum.  A cloud whose points share their pooled features (n = 17: every point pools over
+nearly all others) has rows that are EQUAL in exact arithmetic and on the device, where equal inputs meet equal arithmetic, while
+float64 matrix products of equal rows differ by their own rounding (1e-15): a `tie` far above that and far below any fp32 ulp
+lets the float64 model see those ties as the ties they are.
+
 perturb (tests only) restates the step wrongly: "no_weight_decay", "tf_adam_eps" (sqrt(v) + eps before the bias correction),
 "biased_running_var", "bn_no_m2" = i (bn<i>'s backward without its xhat * mean(dy xhat) term), "pool_all" (the pool gradient
 credited to all 16 columns as well), "pool_no_self", "chamfer_no_batch_mean" (gradient without 1 / B), "relu_after_bn5".
@@ -38,7 +44,7 @@ def _t(a):
     return torch.as_tensor(np.asarray(a, np.float64)).to(DTYPE[0])
 
 
-def forward(P, run, pc, cov, cols, pins=None, perturb=None):
+def forward(P, run, pc, cov, cols, pins=None, perturb=None, tie=0.0):
     """P: {parameter key: float64 tensor in torch's shape}; run: {bn index: [running_mean, running_var]} updated in place.
     Returns (loss, mid_loss, extras)."""
     pins, perturb = pins or {}, perturb or {}
@@ -90,8 +96,8 @@ def forward(P, run, pc, cov, cols, pins=None, perturb=None):
             cand_rows = c
         hd = h.detach()
         cand = hd[ar, cand_rows]                                                # (B, n, 17, C)
-        first = cand.numpy().argmax(axis=2)                                     # first maximum
         own_val = cand.max(dim=2)[0]
+        first = (cand >= own_val[:, :, None, :] - tie).numpy().argmax(axis=2)   # first maximum
         own = np.take_along_axis(cand_rows.numpy()[:, :, :, None], first[:, :, None, :], 2)[:, :, 0, :]
         own = np.where(own_val.numpy() > 0, own, -1)
         win = own
@@ -118,7 +124,7 @@ def forward(P, run, pc, cov, cols, pins=None, perturb=None):
     if perturb.get("relu_after_bn5"):
         y5 = torch.relu(y5)
     yn = y5.detach().numpy()
-    own = yn.argmax(axis=1)
+    own = (yn >= yn.max(axis=1, keepdims=True) - tie).argmax(axis=1)
     row = own
     if "gmax" in pins:
         row = np.asarray(pins["gmax"], np.int64)
@@ -194,7 +200,7 @@ def decisions(state, pc, cov, cols, dtype=torch.float64):
     return out
 
 
-def step(state, pc, cov, cols, lr=1e-4, weight_decay=1e-6, steps_done=0, slots=None, pins=None, perturb=None):
+def step(state, pc, cov, cols, lr=1e-4, weight_decay=1e-6, steps_done=0, slots=None, pins=None, perturb=None, tie=0.0):
     """One training step in float64.  state: {state-dict key: array} (running statistics included); slots: {key: (exp_avg,
     exp_avg_sq)} of the PARAM_KEYS, None = fresh.  Returns a dict: loss, mid_loss, code, mid, recon, grads {key: array},
     new_state, slots, bn_mean / bn_var {bn index: array}, relu / win / gmax / hidden / chamfer (the decisions used) and
@@ -203,7 +209,7 @@ def step(state, pc, cov, cols, lr=1e-4, weight_decay=1e-6, steps_done=0, slots=N
     P = {k: _t(state[k]).clone().requires_grad_(True) for k in PARAM_KEYS}
     run = {i: [_t(state["encoder.bn%d.running_mean" % i]).clone(), _t(state["encoder.bn%d.running_var" % i]).clone()]
            for i in range(1, 7)}
-    loss, mid_loss, ex = forward(P, run, np.asarray(pc, np.float64), cov, cols, pins, perturb)
+    loss, mid_loss, ex = forward(P, run, np.asarray(pc, np.float64), cov, cols, pins, perturb, tie)
     loss.backward()
     grads = {k: P[k].grad.numpy().copy() for k in PARAM_KEYS}
     wd = 0.0 if perturb.get("no_weight_decay") else weight_decay

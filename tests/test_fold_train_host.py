@@ -201,14 +201,19 @@ def test_train_mode_forward_equals_the_references_own_modules():
         assert int(g["encoder.bn%d.num_batches_tracked" % i]) == 1
 
 
-# the input batches of test_gpu_fold_train.py: (weights seed, B, n, batch seed, sampler seed or None = given picks, ordinal)
-GPU_BATCHES = [(0, 8, 2048, 1, 5, 0), (1, 2, 256, -2, None, 0), (2, 3, 1001, 4, 5, 11), (0, 32, 2048, 6, 5, 0), (0, 4, 512, 7, 9, 3),
-               (0, 4, 512, 8, 9, 0), (0, 4, 512, 13, 5, 0), (0, 3, 128, 15, 5, 0)]
+# the input batches of test_gpu_fold_train.py: (weights seed, B, n, batch seed, sampler seed or None = given picks, ordinal,
+# every third batch-norm gamma negated)
+GPU_BATCHES = [(0, 8, 2048, 1, 5, 0, False), (1, 2, 256, -2, None, 0, False), (2, 3, 1001, 4, 5, 11, False), (0, 32, 2048, 6, 5, 0, False),
+               (0, 4, 512, 7, 9, 3, False), (0, 4, 512, 8, 9, 0, False), (0, 4, 512, 13, 5, 0, False), (0, 3, 128, 15, 5, 0, False),
+               (0, 4, 512, 31, 5, 0, True), (0, 3, 17, 32, 5, 0, False)]
 
 
-@pytest.mark.parametrize("wseed,B,n,seed,sampler,ordinal", GPU_BATCHES)
-def test_float32_and_float64_decide_alike_on_the_gpu_tests_batches(wseed, B, n, seed, sampler, ordinal):
+@pytest.mark.parametrize("wseed,B,n,seed,sampler,ordinal,signed", GPU_BATCHES,
+                         ids=["-".join(str(v) for v in c[:6]) + ("-signed" if c[6] else "") for c in GPU_BATCHES])
+def test_float32_and_float64_decide_alike_on_the_gpu_tests_batches(wseed, B, n, seed, sampler, ordinal, signed):
     w, x = FW.synthetic_state(wseed), (G._batch(B, n, seed) if seed >= 0 else G._two_shapes(n, -seed))      # seed < 0: the two-shape batch
+    if signed:
+        w = G.signed_gammas(w)
     cov, rows = F64.graph_from_knn(x, F64.knn(x))
     picks = G._given_picks(x, 3) if sampler is None else F64.device_picks(sampler, np.arange(ordinal, ordinal + B), F64.degrees(rows))
     cols = F64.resolve(rows, picks)

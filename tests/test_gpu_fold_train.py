@@ -17,6 +17,14 @@ maximum over points: their gradients are zero in exact arithmetic and rounding n
 into full-size updates), so they are compared as noise (the noise tolerance, of the layer's BN-weight gradient) and left out of the
 parameter and slot checks.  Every step is checked against the model started from the handle's own state before that step
 (its exported fp32 parameters, running statistics and slots), so three steps are three independent one-step checks.
+
+Held EXACTLY besides, in every case (exact_decisions): both pools' winners and the global maximum's rows equal the rules of
+tests/_fold_pool_model.py applied to the step's own state -- pool 0's input is max(pre_bn[2] * inv + shift, 0), pool 1's
+max(pre_bn[3] * inv + shift, 0), the global maximum runs over pre_bn[4] * inv + shift, each formed in float32 as two rounded
+operations.  The rebuilt inputs equal the device's to the bit: the library is built without contraction, so tb_bn_relu_kernel
+rounds the product and the sum separately as numpy does (only the sign of a zero may differ, which no comparison sees).  The
+pinned model alone cannot hold these rules: among equal values every winner lies 0 from the maximum.  The rules at exact ties
+are held on the kernels themselves in test_gpu_fold_train_kernels.py.
 """
 import os
 import sys
@@ -27,6 +35,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import _fold_model64 as F64  # noqa: E402
+import _fold_pool_model as P  # noqa: E402
 import _fold_train_model64 as M  # noqa: E402
 from geometric_adv_amd import fold_weights as FW  # noqa: E402
 
@@ -40,6 +49,11 @@ STAT_TOL = (2.0 ** -22, 2.0 ** -20)
 # Each constant is at most 4 x the worst value measured on the MI355X over the cases below (MEASURED).
 MEASURED = {"well": dict(loss=6.9e-6, out=1.3e-5, grad=9.1e-5, noise=6.6e-7, param=6.7e-6, slot=1.4e-4, running=7.7e-7)}
 PROFILES = {"well": dict(loss=2.5e-5, out=5e-5, grad=1.1e-4, noise=2.5e-6, param=2.5e-5, slot=2e-4, running=1.4e-6)}
+# "small": 3 x 17, where bn1 .. bn5 take their statistics over 51 rows and the backward's cancellations (train_bn.h) leave more of
+# the fp32 rounding; its loss, out and param constants are "well"'s own, the other four are at most 4 x its measured values.
+MEASURED["small"] = dict(loss=3.88e-6, out=3.52e-5, grad=7.08e-4, noise=1.31e-5, param=0.0, slot=8.65e-4, running=2.55e-6)
+PROFILES["small"] = dict(PROFILES["well"], grad=2.8e-3, noise=5.2e-5, slot=3.4e-3, running=1.0e-5)
+TIE = 1e-12              # the float64 model's ties in the smallest cloud (_fold_train_model64: tie)
 GRAD_TOL, PARAM_TOL, RUNNING_TOL = (PROFILES["well"][k] for k in ("grad", "param", "running"))
 
 FED_BIASES = ["encoder.conv%d.bias" % i for i in range(1, 6)] + ["encoder.fc1.bias", "encoder.bn5.bias"]
@@ -57,7 +71,35 @@ def _batch(B, n, seed):
     return (np.random.default_rng(seed).random((B, n, 3)) - 0.5).astype(np.float32)
 
 
+SLAB_ROWS = 65536        # rows of a device-side slab read at a time: 32 clouds of 2048 points
+
+
+def exact_decisions(tr):
+    """Both pools' winners and the global maximum's rows of the last step against tests/_fold_pool_model.py on the step's own
+    stored pre-BN activations, folded constants and neighbour columns, in slabs of whole clouds read from the device."""
+    B, n = tr.batch_size, tr.num_points
+    slab = max(1, SLAB_ROWS // n)
+    cols = tr.state("cols")
+    for p, l in ((0, 2), (1, 3)):
+        a, win = tr.state("pre_bn", l, device=True), tr.state("pool_winner", p, device=True)
+        inv, shift = tr.state("bn_inv", l), tr.state("bn_shift", l)
+        for b0 in range(0, B, slab):
+            b1 = min(B, b0 + slab)
+            h = np.maximum(P.pre(a[b0 * n:b1 * n].cpu().numpy(), inv, shift), np.float32(0)).reshape(b1 - b0, n, -1)
+            want = P.pool(h, cols[p, b0:b1])[1]
+            got = win[b0:b1].cpu().numpy()
+            assert np.array_equal(got, want), ("pool", p, b0, float(np.mean(got != want)))
+        del a, win
+    a, inv, shift, arg = tr.state("pre_bn", 4, device=True), tr.state("bn_inv", 4), tr.state("bn_shift", 4), tr.state("gmax_row")
+    for b0 in range(0, B, slab):
+        b1 = min(B, b0 + slab)
+        want = P.gmax(a[b0 * n:b1 * n].cpu().numpy().reshape(b1 - b0, n, -1), inv, shift)[1]
+        assert np.array_equal(arg[b0:b1], want), ("gmax", b0, float(np.mean(arg[b0:b1] != want)))
+    del a
+
+
 def gpu_decisions(tr):
+    exact_decisions(tr)
     pins = {"relu": {}, "win": [tr.state("pool_winner", p).astype(np.int64) for p in (0, 1)],
             "gmax": tr.state("gmax_row").astype(np.int64), "hidden": [tr.state("hidden", k) > 0 for k in range(4)],
             "chamfer": (tr.state("chamfer_idx", 0).astype(np.int64), tr.state("chamfer_idx", 1).astype(np.int64))}
@@ -87,9 +129,9 @@ def param_error(new, new64, old64, g64):
     return max(0.0, float(diff)) / max(np.linalg.norm((new64 - old64)[sel]), 1e-300)
 
 
-def run_steps(w, x, steps=1, picks=None, seed=5, ordinal=0, weight_decay=1e-6, step0=0, slots0=None, keep=None):
+def run_steps(w, x, steps=1, picks=None, seed=5, ordinal=0, weight_decay=1e-6, step0=0, slots0=None, keep=None, probe=None, tie=0.0):
     """`steps` steps of one handle on x, each followed by the model pinned to that step's decisions and started from the
-    handle's own state before the step.  Returns the list of per-step error dicts."""
+    handle's own state before the step.  Returns the list of per-step error dicts.  probe(tr) is called after every step."""
     B, n = x.shape[:2]
     tr = _trainer(w, B, n, seed=seed, ordinal=ordinal, weight_decay=weight_decay, step=step0, slots=slots0)
     out = []
@@ -100,8 +142,10 @@ def run_steps(w, x, steps=1, picks=None, seed=5, ordinal=0, weight_decay=1e-6, s
         slots64 = {k: (sl["exp_avg"][k].astype(np.float64), sl["exp_avg_sq"][k].astype(np.float64)) for k in M.PARAM_KEYS}
         loss, mid = tr.train_step(x, picks=picks)
         pins, stats = gpu_decisions(tr)
+        if probe is not None:
+            probe(tr)
         ref = M.step(state64, x.astype(np.float64), tr.state("cov"), tr.state("cols"), steps_done=step0 + s, slots=slots64, pins=pins,
-                     weight_decay=weight_decay)
+                     weight_decay=weight_decay, tie=tie)
         if keep is not None:
             keep.append((state64, slots64, pins, tr.state("cov"), tr.state("cols"), tr.export_state_dict(), ref))
         err = {"stats": stats, "loss": abs(loss - ref["loss"]) / ref["loss"], "mid": abs(mid - ref["mid_loss"]) / ref["mid_loss"],
@@ -211,6 +255,97 @@ def test_batch_32():
     check(errs)
 
 
+def signed_gammas(w, every=3):
+    """w with every third entry of encoder.bn1 .. bn6.weight negated."""
+    w = dict(w)
+    for i in range(1, 7):
+        g = np.array(w["encoder.bn%d.weight" % i], copy=True)
+        g[::every] = -g[::every]
+        w["encoder.bn%d.weight" % i] = g
+    return w
+
+
+def test_signed_gammas():
+    """Closes the gap of the negative batch-norm gamma: synthetic_state draws every gamma from [0.8, 1.2], so neither the ReLU
+    masks under a negative inv nor bn5's branch, where the maximum over points of a * inv + shift is a MINIMUM of the activation,
+    had ever run.  Every third gamma of bn1 .. bn6 is negated.  In the negated bn5 channels the global maximum's row must be the
+    first minimum of the stored activation over each cloud's rows, and differ from the row a positive gamma would choose (the
+    first maximum) in at least 90 % of the (cloud, channel) pairs."""
+    w, x = signed_gammas(FW.synthetic_state(0)), _batch(4, 512, 31)
+    seen = {}
+
+    def probe(tr):
+        seen.update(a=tr.state("pre_bn", 4).reshape(4, 512, 1024), row=tr.state("gmax_row"), inv=tr.state("bn_inv", 4))
+
+    errs = run_steps(w, x, steps=1, probe=probe)
+    report("4 x 512 signed gammas", errs)
+    neg = np.arange(0, 1024, 3)
+    assert (seen["inv"][neg] < 0).all() and (np.delete(seen["inv"], neg) > 0).all()
+    a, row = seen["a"][:, :, neg], seen["row"][:, neg]
+    differ = float(np.mean(row != np.argmax(a, axis=1)))
+    print("gmax rows in the negated channels that a positive gamma would not choose: %.4g" % differ)
+    assert np.array_equal(row, np.argmin(a, axis=1))
+    assert differ >= 0.9, differ
+    check(errs)
+
+
+def test_smallest_cloud():
+    """Closes the gap at the smallest n the trainer accepts: 3 x 17, where every point's adjacency is all other points (the
+    complete graph, against the sparse one of n = 128, the smallest tested before) and the picks take 16 of 16 or 17.
+    Every point then pools over nearly the whole cloud, many points share their pooled features, and conv4 / conv5 give them
+    EQUAL rows -- on the device to the bit, in the float64 model up to its own 1e-15 rounding, which by itself would order 5 %
+    of pool 1's winners and 17 % of the global maximum's rows differently (measured: at most 2.9e-14 from the boundary).  The
+    model therefore takes the first candidate within TIE of the maximum here; the device's rule at those ties is held exactly by
+    exact_decisions, as in every case.  Measured on the MI355X: MEASURED["small"]."""
+    w, x = FW.synthetic_state(0), _batch(3, 17, 32)
+    seen = {}
+    errs = run_steps(w, x, steps=1, probe=lambda tr: seen.update(deg=tr.degrees(x).cpu().numpy()), tie=TIE)
+    report("3 x 17", errs)
+    assert seen["deg"].min() >= 16 and seen["deg"].max() <= 17
+    check(errs, "small")
+
+
+LIMITS = [(64, 2048, 41), (8, 16384, 42), (256, 512, 43)]
+
+
+@pytest.mark.parametrize("B,n,seed", LIMITS, ids=lambda v: str(v))
+def test_largest_row_count(B, n, seed):
+    """2^17 rows, the most geoadv_fold_trainer_create accepts, without the model: at the reference's n (64 x 2048), at the
+    largest n (8 x 16384) and at a batch well above the 256-row statistics chunk (256 x 512).  The loss, the mid loss and every
+    gradient are finite; every BN layer's batch mean and variance are the float64 moments of its stored activation (STAT_TOL),
+    taken over device-side slabs of SLAB_ROWS rows; both pools' winners and the global maximum's rows are the rules' (exact_decisions)."""
+    import time
+    import torch
+    t0 = time.time()
+    tr = _trainer(FW.synthetic_state(0), B, n, seed=5)
+    loss, mid = tr.train_step(_batch(B, n, seed))
+    t1 = time.time()
+    assert np.isfinite(loss) and np.isfinite(mid) and loss > 0 and mid > 0
+    assert all(np.isfinite(v).all() for v in tr.gradients().values())
+    worst = [0.0, 0.0]
+    for l in range(6):
+        a = tr.state("pre_bn", l, device=True)
+        rows = a.shape[0]
+        assert rows == (B * n if l < 5 else B)
+        k0 = a[0].double()                                       # shift: sums of (a - a[0]) keep the variance
+        s1 = s2 = 0
+        for r0 in range(0, rows, SLAB_ROWS):
+            d = a[r0:r0 + SLAB_ROWS].double() - k0
+            s1, s2 = s1 + d.sum(0), s2 + (d * d).sum(0)
+        m64, v64 = (k0 + s1 / rows).cpu().numpy(), (s2 / rows - (s1 / rows) ** 2).cpu().numpy()
+        del a, d, k0, s1, s2
+        mg, vg = tr.state("bn_mean", l).astype(np.float64), tr.state("bn_var", l).astype(np.float64)
+        em, ev = np.abs(mg - m64) / (np.abs(m64) + np.sqrt(v64)), np.abs(vg - v64) / (v64 + 1e-30)
+        worst = [max(worst[0], float(em.max())), max(worst[1], float(ev.max()))]
+        assert em.max() <= STAT_TOL[0] and ev.max() <= STAT_TOL[1], (l, float(em.max()), float(ev.max()))
+    t2 = time.time()
+    exact_decisions(tr)
+    print("\n%d x %d: loss %.6g mid %.6g | statistics worst mean %.3g var %.3g (relative) | step %.1f s, statistics %.1f s, decisions %.1f s"
+          % (B, n, loss, mid, worst[0], worst[1], t1 - t0, t2 - t1, time.time() - t2))
+    del tr
+    torch.cuda.synchronize()
+
+
 def test_two_steps_from_equal_state_are_bitwise_equal_and_picks_follow_the_ordinals():
     w, x = FW.synthetic_state(0), _batch(4, 512, 7)
     got = []
@@ -257,6 +392,39 @@ def test_refuses_one_cloud_on_the_device_side_too():
     assert _lib.lib().geoadv_fold_trainer_create(C.byref(h), C.byref(hw), C.byref(cfg)) != 0
     _lib.lib().geoadv_last_error.restype = C.c_char_p
     assert b"bn6" in _lib.lib().geoadv_last_error()
+
+
+REFUSED = [(65, 2048, "2^17"), (9, 16384, "2^17"), (2, 16385, "[17, 16384]"), (2, 16, "[17, 16384]"), (1025, 17, "[2, 1024]")]
+
+
+def test_sizes_outside_the_limits_are_refused_by_name_and_the_smallest_is_created():
+    """geoadv_fold_trainer_create's limits -- batch in [2, 1024], n in [17, 16384], batch * n <= 2^17 -- through
+    FoldingNetTrainer and through the C entry itself: each refusal names the bound that was broken; (2, 17) creates."""
+    import ctypes as C
+    from geometric_adv_amd import _lib
+    from geometric_adv_amd.fold_trainer import _FoldTrainConfig
+    from geometric_adv_amd.foldingnet import _FoldWeights
+    w = FW.synthetic_state(0)
+    canon = FW.canonical(w)
+    hw = _FoldWeights()
+    for key, arrays in canon.items():
+        for i, a in enumerate(arrays):
+            getattr(hw, key)[i] = a.ctypes.data if a is not None else None
+    L = _lib.lib()
+    for B, n, bound in REFUSED:
+        with pytest.raises(ValueError) as e:
+            _trainer(w, B, n)
+        assert bound in str(e.value), (B, n, str(e.value))
+        h = C.c_void_p()
+        cfg = _FoldTrainConfig(B, n, 1e-4, 1e-6, 0, 0, 0)
+        assert L.geoadv_fold_trainer_create(C.byref(h), C.byref(hw), C.byref(cfg)) == 1 and not h.value
+        assert bound.encode() in L.geoadv_last_error(), (B, n, L.geoadv_last_error())
+    h = C.c_void_p()
+    cfg = _FoldTrainConfig(2, 17, 1e-4, 1e-6, 0, 0, 0)
+    assert L.geoadv_fold_trainer_create(C.byref(h), C.byref(hw), C.byref(cfg)) == 0 and h.value
+    L.geoadv_fold_trainer_destroy(h)
+    tr = _trainer(w, 2, 17)
+    assert tr.counters() == (0, 0)
 
 
 def test_train_foldingnet_checkpoints_resume_and_load(tmp_path):
