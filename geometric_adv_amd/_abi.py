@@ -75,6 +75,8 @@ SIGNATURES = {      # in the header's order
     "geoadv_cls_destroy": "v:p",
     "geoadv_cls_workspace_bytes": "z:pii",
     "geoadv_cls_forward": "i:piippppppp",
+    "geoadv_cls_input_grad_workspace_bytes": "z:pii",
+    "geoadv_cls_input_grad": "i:piippifpppppp",
     "geoadv_rotate_y": "i:iipddpp",
     "geoadv_cls_evaluate_workspace_bytes": "z:pii",
     "geoadv_cls_evaluate": "i:piippippppppp",
@@ -171,6 +173,7 @@ GEOADV_AUGMENT_RECORD = 45
 GEOADV_ENC_LAYERS, GEOADV_DEC_LAYERS = 5, 3
 GEOADV_ENC_ARITH_AUTO, GEOADV_ENC_ARITH_F32, GEOADV_ENC_ARITH_BF16X3, GEOADV_ENC_ARITH_F16X2 = -1, 0, 1, 2
 GEOADV_CLS_LAYERS = 20
+GEOADV_CLS_LOSS_XENT, GEOADV_CLS_LOSS_CW_TARGETED, GEOADV_CLS_LOSS_CW_UNTARGETED = 0, 1, 2
 GEOADV_CLS_OPT_ADAM, GEOADV_CLS_OPT_MOMENTUM = 0, 1
 (GEOADV_CLS_STATE_BN_MEAN, GEOADV_CLS_STATE_BN_VAR, GEOADV_CLS_STATE_MOVING_MEAN, GEOADV_CLS_STATE_MOVING_VAR,
  GEOADV_CLS_STATE_DROPOUT_MASK, GEOADV_CLS_STATE_POOL_ARGMAX, GEOADV_CLS_STATE_T1, GEOADV_CLS_STATE_T2, GEOADV_CLS_STATE_LOGITS,

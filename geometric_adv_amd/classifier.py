@@ -19,6 +19,8 @@ from ._abi import ClsWeights as _ClsWeights
 from ._model import DeviceModel
 
 N_LAYERS = _abi.GEOADV_CLS_LAYERS
+LOSS_KINDS = {"xent": _abi.GEOADV_CLS_LOSS_XENT, "cw_targeted": _abi.GEOADV_CLS_LOSS_CW_TARGETED,
+              "cw_untargeted": _abi.GEOADV_CLS_LOSS_CW_UNTARGETED}
 
 
 class PointNetClassifier(DeviceModel):
@@ -70,6 +72,40 @@ class PointNetClassifier(DeviceModel):
                                       _lib.ptr(t2), _lib.ptr(ws), _lib.stream_handle())
         _lib.check(st, "cls_forward")
         return (logits, labels, t1, t2) if transforms else (logits, labels)
+
+    def input_gradient(self, x, labels, loss="xent", kappa=0.0, return_logits=False, return_winners=False):
+        """One geoadv_cls_input_grad call (csrc/cls_grad.hip) on the current stream, no host synchronisation: the gradient of
+        a logit loss with respect to the points, through the graph of forward() with both T-Nets differentiated.  labels: an
+        int32 device tensor (b,) -- the class of the cross entropy ('xent') and of 'cw_untargeted', the target of
+        'cw_targeted'.  Returns device tensors (loss (b,) float32 per cloud, grad (b, n, 3)[, logits (b, C) -- forward()'s
+        bits][, winners (b, 3, 1024) int32: the row each of the three max pools chose per column])."""
+        if loss not in LOSS_KINDS:
+            raise ValueError("loss must be one of %s" % sorted(LOSS_KINDS))
+        x = self._as_dev(x)
+        b, n = int(x.shape[0]), int(x.shape[1])
+        dev = self.device
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.device != x.device \
+                or tuple(labels.shape) != (b,):
+            raise ValueError("labels must be an int32 tensor of shape (%d,) on %s" % (b, x.device))
+        labels = labels.contiguous()
+        out_loss = torch.empty((b,), dtype=torch.float32, device=dev)
+        grad = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=dev) if return_logits else None
+        winners = torch.empty((b, 3, 1024), dtype=torch.int32, device=dev) if return_winners else None
+        if b:
+            L = _lib.lib()
+            with torch.cuda.device(dev):
+                ws = self._workspace(L.geoadv_cls_input_grad_workspace_bytes(self._h, b, n))
+                st = L.geoadv_cls_input_grad(self._h, b, n, _lib.ptr(x), _lib.ptr(labels), LOSS_KINDS[loss], float(kappa),
+                                             _lib.ptr(out_loss), _lib.ptr(logits), _lib.ptr(winners), _lib.ptr(grad),
+                                             _lib.ptr(ws), _lib.stream_handle())
+            _lib.check(st, "cls_input_grad")
+        out = (out_loss, grad)
+        if return_logits:
+            out += (logits,)
+        if return_winners:
+            out += (winners,)
+        return out
 
     def logits(self, x):
         """float32 device tensor (b, num_classes) of the classifier's logits (pointnet_cls.py: fc3's output)."""

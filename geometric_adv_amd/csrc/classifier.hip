@@ -22,39 +22,11 @@
 //
 // Batch norm is folded at create time (eps 1e-3, tf_util.batch_norm_template): y = relu((x @ W) * scale + shift),
 // scale = gamma * rsqrt(var + eps), shift = b * scale + (beta - mean * scale).
-#include "point_tile.h"
-#include "host_util.h"
+#include "cls_model.h"
 #include <math.h>
 #include <string.h>
 
 namespace geoadv {
-
-constexpr int CLS_MAX_GRID_Y = 65535;
-
-struct ClsLayerDev {                                // one per-point layer
-    PackedLayer L;                                  // packed fragments (mid / wide layers); L.w of cloud c = L.w + c * cloud_stride
-    const float *scale, *shift;
-    int cloud_stride;                               // floats; 0 = shared by all clouds
-};
-struct ClsChainArgs {
-    const float *x;                                 // [b][n][3]
-    const float *w0; int w0_cloud_stride;           // layer 0 (fan-in 3): [3][64] row-major
-    const float *sc0, *sh0;
-    ClsLayerDev mid[3];                             // narrow MFMA layers
-    ClsLayerDev wide;                               // 128 -> 1024, pooled
-    unsigned *pooled;                               // [b][1024] float bits, zeroed before the launch
-    int n, slices;
-};
-
-// narrow layer: out[64][NOUT] = relu((in @ W) * scale + shift)
-template <int NOUT>
-__device__ __forceinline__ void cls_mid(const float *in, int s_in, const ClsLayerDev &d, int cloud, float *out, int s_out) {
-    PackedLayer L = d.L;
-    L.w += (size_t)cloud * d.cloud_stride;
-    layer_gemm<PT_ROWS, NOUT, 1>(in, s_in, L, nullptr, [&](int row, int col, float a) {
-        out[row * s_out + col] = fmaxf(a * d.scale[col] + d.shift[col], 0.f);
-    });
-}
 
 template <int NMID>
 __global__ __launch_bounds__(PT_THREADS, 2) void cls_chain_kernel(ClsChainArgs A, int cloud0) {
@@ -166,22 +138,10 @@ __global__ __launch_bounds__(PT_THREADS) void cls_head_kernel(ClsHeadArgs H, int
 using namespace geoadv;
 
 namespace {
-enum {   // GEOADV_CLS_* layer order (include/geoadv.h)
-    T1C1 = 0, T1C2, T1C3, T1F1, T1F2, T1XYZ, C1, C2, T2C1, T2C2, T2C3, T2F1, T2F2, T2FEAT, C3, C4, C5, F1, F2, F3
-};
 const int kIn[GEOADV_CLS_LAYERS] = {3, 64, 128, 1024, 512, 256, 3, 64, 64, 64, 128, 1024, 512, 256, 64, 64, 128, 1024, 512, 256};
 const int kOut[GEOADV_CLS_LAYERS] = {64, 128, 1024, 512, 256, 9, 64, 64, 64, 128, 1024, 512, 256, 4096, 64, 128, 1024, 512, 256, 0};
 bool has_bn(int l) { return l != T1XYZ && l != T2FEAT && l != F3; }
 }  // namespace
-
-struct geoadv_cls {
-    int num_classes;
-    void *arena;
-    const float *raw[GEOADV_CLS_LAYERS];      // row-major [in][out] (head layers, layer 0s, the fold operands)
-    const float *packed[GEOADV_CLS_LAYERS];   // MFMA fragments (per-point layers of fan-in >= 64)
-    const float *scale[GEOADV_CLS_LAYERS], *shift[GEOADV_CLS_LAYERS];
-    const float *bias[GEOADV_CLS_LAYERS];     // linear layers: b (+ the identity for the two transforms)
-};
 
 extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw) {
     GA_REQUIRE(out && hw, "cls_create: null argument");
@@ -200,6 +160,7 @@ extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw)
     HostArena arena;
     std::vector<float> &host = arena.host;
     size_t o_raw[GEOADV_CLS_LAYERS], o_pk[GEOADV_CLS_LAYERS], o_sc[GEOADV_CLS_LAYERS], o_sh[GEOADV_CLS_LAYERS], o_b[GEOADV_CLS_LAYERS];
+    size_t o_pt[GEOADV_CLS_LAYERS], o_rt[GEOADV_CLS_LAYERS];
     for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) {
         const int K = kIn[l], N = outw[l];
         o_raw[l] = arena.reserve((size_t)K * N);
@@ -208,6 +169,17 @@ extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw)
         if (l == T1C2 || l == T1C3 || l == C2 || l == T2C1 || l == T2C2 || l == T2C3 || l == C4 || l == C5) {   // MFMA operands
             o_pk[l] = arena.reserve((size_t)K * N);
             pack_fragments(&host[o_pk[l]], hw->w[l], K, N);
+        }
+        o_pt[l] = o_rt[l] = 0;
+        if (l == T1C2 || l == C2 || l == T2C1 || l == T2C2 || l == C4) {   // W^T as MFMA operands: the input gradient's narrow layers
+            o_pt[l] = arena.reserve((size_t)K * N);
+            const float *W = hw->w[l];
+            pack_fragments(&host[o_pt[l]], N, K, N, K, [&](int k, int n) { return W[(size_t)n * N + k]; });
+        }
+        if (l == T1C3 || l == T2C3 || l == C5) {                          // W^T row-major: its pooled layers
+            o_rt[l] = arena.reserve((size_t)K * N);
+            for (int k = 0; k < K; ++k)
+                for (int n = 0; n < N; ++n) host[o_rt[l] + (size_t)n * K + k] = hw->w[l][(size_t)k * N + n];
         }
         o_sc[l] = o_sh[l] = o_b[l] = 0;
         if (has_bn(l)) {   // TF's fold, eps 1e-3 -- not host_util.h's fold_bn_torch, which rounds the shift differently
@@ -236,6 +208,8 @@ extern "C" int geoadv_cls_create(geoadv_cls **out, const geoadv_cls_weights *hw)
     for (int l = 0; l < GEOADV_CLS_LAYERS; ++l) {
         m->raw[l] = base + o_raw[l];
         m->packed[l] = o_pk[l] ? base + o_pk[l] : nullptr;
+        m->packed_t[l] = o_pt[l] ? base + o_pt[l] : nullptr;
+        m->raw_t[l] = o_rt[l] ? base + o_rt[l] : nullptr;
         m->scale[l] = has_bn(l) ? base + o_sc[l] : nullptr;
         m->shift[l] = has_bn(l) ? base + o_sh[l] : nullptr;
         m->bias[l] = has_bn(l) ? nullptr : base + o_b[l];
@@ -251,23 +225,6 @@ extern "C" void geoadv_cls_destroy(geoadv_cls *cls) {
 }
 
 namespace {
-struct ClsScratch {
-    unsigned *pooled;        // [3][b][1024]
-    float *t1, *w1f;         // [b][9], [b][192]
-    float *t2, *w3p;         // [b][4096] each
-    size_t bytes;
-};
-ClsScratch carve_cls(void *workspace, int b) {
-    ClsScratch s;
-    Carver cv(workspace);
-    s.pooled = cv.take<unsigned>(3 * (size_t)b * PT_POOL);
-    s.t1 = cv.take<float>((size_t)b * 9);
-    s.w1f = cv.take<float>((size_t)b * 192);
-    s.t2 = cv.take<float>((size_t)b * 4096);
-    s.w3p = cv.take<float>((size_t)b * 4096);
-    s.bytes = cv.bytes();
-    return s;
-}
 int chunk_of(int b) { return b < CLS_MAX_GRID_Y ? b : CLS_MAX_GRID_Y; }
 ClsLayerDev layer_dev(const geoadv_cls *m, int l, int K, int N) {
     return ClsLayerDev{PackedLayer{m->packed[l], K, N}, m->scale[l], m->shift[l], 0};

@@ -212,7 +212,7 @@ EvalScratch carve_eval(void *workspace, const geoadv_cls *cls, int b, int n, int
     s.bytes = cv.bytes();
     return s;
 }
-// geoadv_cls is defined in classifier.hip; its first member is `int num_classes`, and a pointer to a standard-layout struct
+// geoadv_cls is defined in cls_model.h (classifier.hip's handle); its first member is `int num_classes`, and a pointer to a standard-layout struct
 // points to its first member
 int classes_of(const geoadv_cls *cls) { return *reinterpret_cast<const int *>(cls); }
 }  // namespace

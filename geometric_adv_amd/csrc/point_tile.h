@@ -70,6 +70,54 @@ __device__ __forceinline__ void pooled_wide_layer(const float *buf, int stride, 
     }
 }
 
+// load_points_conv1 for a tile of GATHERED rows: row s of the tile is point rows[s] of the cloud x[n][3] (s < live; rows
+// past `live` zero).  The same products and sums per row, so a gathered row's activations carry the bits its own tile gave it.
+__device__ __forceinline__ void gather_points_conv1(const float *x, const int *rows, int live, const float *w0, const float *sc0,
+                                                    const float *sh0, float *pts, float *bufA) {
+    if (threadIdx.x < PT_ROWS * 3) {
+        const int r = threadIdx.x / 3;
+        pts[threadIdx.x] = r < live ? x[(size_t)rows[r] * 3 + (threadIdx.x - 3 * r)] : 0.f;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < PT_ROWS * 64; e += PT_THREADS) {
+        const int r = e >> 6, c = e & 63;
+        const float a = pts[3 * r] * w0[c] + pts[3 * r + 1] * w0[64 + c] + pts[3 * r + 2] * w0[128 + c];
+        bufA[r * PT_SA + c] = fmaxf(a * sc0[c] + sh0[c], 0.f);
+    }
+    __syncthreads();
+}
+
+// The recomputing pass behind pooled_wide_layer: the same blocks, chains and keys, compared with the finished pool
+// `pooled` [1024]; win[col] = min(win[col], row0 + row) over the tile's live rows whose key equals pooled[col] != 0 -- the
+// lowest row among equal maxima, whatever the order of tiles.  `win` is preset to a value above every row.
+template <class Key>
+__device__ __forceinline__ void pooled_wide_winners(const float *buf, int stride, const PackedLayer &L, const float *scale,
+                                                    const float *shift, int slice, int slices, int live, int row0,
+                                                    const unsigned *pooled, int *win, Key key) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int h = lane >> 5, i = lane & 31;
+    const int nblk = (PT_POOL / 32) / slices;
+    for (int j = wave; j < nblk; j += PT_THREADS / 64) {
+        const int cb = slice * nblk + j;
+        f32x16 acc[2] = {};
+        gemm_chain<2>(buf, stride, 0, L, cb, 0, 128 / 8, acc);
+        const int col = cb * 32 + i;
+        const float sc = scale[col], sh = shift[col];
+        const unsigned want = pooled[col];
+        int best = 0x7fffffff;
+#pragma unroll
+        for (int rm = 0; rm < 2; ++rm)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rm * 32 + acc_row(r, h);
+                const unsigned v = key(acc[rm][r] * sc + sh);
+                if (row < live && v == want) best = min(best, row0 + row);
+            }
+        best = min(best, __shfl_xor(best, 32));
+        if (h == 0 && want != 0 && best != 0x7fffffff) atomicMin(win + col, best);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ FC head (M = clouds)
 // One workgroup: 64 output columns (a lane each) x 8 clouds, the K inputs split in four quarters over the 4 waves and summed
 // in a fixed order -- the same for every cloud, whatever the batch size.  Grid (N / 64, ceil(b / 8)).

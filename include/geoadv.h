@@ -526,6 +526,32 @@ int geoadv_cls_forward(const geoadv_cls *cls, int b, int n, const float *pc, flo
                        float *transform_in, float *transform_feat, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The classifier's INPUT GRADIENT: d loss / d pc through exactly the graph of geoadv_cls_forward (is_training = False),
+ * both T-Nets included -- T1 and T2 are differentiated as functions of the points.  Not in the reference: the primitive of
+ * the white-box classifier attacks (cls_attack.py), of saliency maps and of point dropping.  csrc/cls_grad.hip.
+ * ---------------------------------------------------------------------------------------- */
+#define GEOADV_CLS_LOSS_XENT           0   /* softmax cross entropy of labels[c], per cloud (no batch mean): dZ = softmax - onehot */
+#define GEOADV_CLS_LOSS_CW_TARGETED    1   /* labels[c] = target t: max(max_{i != t} Z_i - Z_t, -kappa)                        */
+#define GEOADV_CLS_LOSS_CW_UNTARGETED  2   /* labels[c] = true class y: max(Z_y - max_{i != y} Z_i, -kappa)                    */
+/* Device scratch of geoadv_cls_input_grad for a batch of b clouds of n points. */
+size_t geoadv_cls_input_grad_workspace_bytes(const geoadv_cls *cls, int b, int n);
+/* pc[b,n,3], labels[b] (DEVICE int32) -> grad[b,n,3] = d loss[c] / d pc[c], with loss[b] (per cloud), logits[b,C] (bit-equal
+ * to geoadv_cls_forward's) and winners[b,3,1024] on request (each may be NULL).
+ * Rules (csrc/cls_train.hip's): the ReLU gradient is [output > 0]; a max pool passes its gradient to ONE row per (cloud,
+ * column), the lowest point index among equal maxima; a pooled value of +0 passes none.  winners[c][p][k] is the row pool p
+ * chose for column k (p = 0: T-Net1's pool, 1: T-Net2's, 2: the classifier's), 0 where the pooled value is +0.  A point
+ * that wins no column of any pool gets a gradient of exactly zero.
+ * The loss is computed in float64 from the fp32 logits Z and rounded once.  The CW kinds take the FIRST maximum over the
+ * other classes, at j: if the unclamped value is > -kappa (strictly), dZ is +1 / -1 at (j, t) (targeted) or (y, j)
+ * (untargeted); otherwise the cloud's gradient is exactly zero.  They need num_classes >= 2.
+ * 1 <= n <= 16384, b >= 1, kappa >= 0 and finite, a known loss_kind, else GEOADV_EINVAL and nothing is written.  A label
+ * outside [0, C) makes that cloud's loss and gradient NaN, reads nothing out of bounds and touches no other cloud; a cloud
+ * with non-finite coordinates affects no other cloud.  All on `stream`, no host synchronisation; two calls on the same
+ * input give the same bits; a cloud's outputs do not depend on its batch neighbours or on b. */
+int geoadv_cls_input_grad(const geoadv_cls *cls, int b, int n, const float *pc, const int *labels, int loss_kind, float kappa,
+                          float *loss, float *logits, int *winners, float *grad, void *ws, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Voted evaluation of the classifier (classifier/tst_classifier.py eval_one_epoch, one batch) and the rotation it votes
  * over (classifier/provider.py rotate_point_cloud_by_angle).  csrc/cls_eval.hip.
  * ---------------------------------------------------------------------------------------- */

@@ -1,0 +1,254 @@
+"""CPU: the float64 yardstick of the classifier's input gradient (tests/_cls_grad_model64.py) against central finite
+differences of tests/_cls_model64.py's numpy model, the three logit losses with their sub-gradient rules on hand-made logits,
+and cls_attack's Adam, keep-best and box rules with the classifier replaced by a float64 stub."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import _cls_grad_model64 as G
+import _cls_model64 as M
+
+# FINITE DIFFERENCES.  Inside one linear region the network is linear in the points and the CW losses linear in the logits,
+# so a central difference is exact up to the loss's own rounding, eps64 * |L| / h; the cross entropy adds its curvature,
+# h^2 |L'''| / 6.  The margin is a distance in units of a layer's largest pre-activation, and a unit step of a coordinate
+# moves such a normalised pre-activation by no more than a few tens on the synthetic weights (the gradients below, 100 ...
+# 460 per unit of input for logits of order 10, are the composed slopes): h = margin / 300 keeps every unit well inside its
+# region.  MIN_MARGIN is the comfort asked of a cloud: 1e-5 gives h >= 3e-8 and a rounding term of 2.2e-16 * |L| / h <= 1e-7
+# for |L| <= 15 -- against gradients of order 100, i.e. about 1e-9 relative.  FD_TOL = 1e-6 leaves two orders over what the
+# test prints (<= 1.6e-8 on the seven of the eight clouds of FD_SEED that reach MIN_MARGIN); a missed ReLU or pool path
+# shows at 1e-2 and more.
+MIN_MARGIN = 1e-5
+FD_TOL = 1e-6
+FD_SEED, FD_CLOUDS, FD_POINTS, C = 3, 8, 6, 13
+
+
+@functools.lru_cache(maxsize=None)
+def _weights():
+    from geometric_adv_amd import cls_weights as CW
+    return CW.synthetic_weights(C, seed=C)
+
+
+def _fd_case(loss):
+    rng = np.random.default_rng(FD_SEED)
+    x = rng.random((FD_CLOUDS, FD_POINTS, 3)) - 0.5
+    am = np.argmax(M.numpy_model(_weights(), x)[0], axis=1)
+    y = am if loss == "cw_untargeted" else (am + 1 + rng.integers(0, C - 1, FD_CLOUDS)) % C
+    return x, y
+
+
+@pytest.mark.parametrize("loss", G.LOSSES)
+def test_model_gradient_equals_finite_differences(loss):
+    w = _weights()
+    x, y = _fd_case(loss)
+    kappa = 0.5
+    r = G.grad_model(w, x, y, loss, kappa)
+    assert np.allclose(r["logits"], M.numpy_model(w, x)[0], rtol=0, atol=1e-10)
+    assert np.allclose(r["loss"], G.loss_numpy(r["logits"], y, loss, kappa), rtol=0, atol=1e-12)
+    good = np.nonzero(r["margin"] >= MIN_MARGIN)[0]
+    assert len(good) >= 4, r["margin"]
+    for c in good:
+        h = r["margin"][c] / 300.0
+        fd = np.zeros((FD_POINTS, 3))
+        for p in range(FD_POINTS):
+            for d in range(3):
+                lo, hi = x[c:c + 1].copy(), x[c:c + 1].copy()
+                lo[0, p, d] -= h
+                hi[0, p, d] += h
+                f = [G.loss_numpy(M.numpy_model(w, z)[0], y[c:c + 1], loss, kappa)[0] for z in (lo, hi)]
+                fd[p, d] = (f[1] - f[0]) / (2 * h)
+        scale = np.abs(fd).max()
+        assert scale > 0
+        err = np.abs(r["grad"][c] - fd).max() / scale
+        print("loss %s cloud %d margin %.2e step %.2e max |grad| %.3g relative error %.2e" % (loss, c, r["margin"][c], h, scale, err))
+        assert err <= FD_TOL
+
+
+def test_detached_transforms_change_the_gradient():
+    """Holding T1 and T2 constant is another function: the model can tell the two apart (the GPU guard relies on it)."""
+    w = _weights()
+    x, y = _fd_case("xent")
+    full = G.grad_model(w, x, y, "xent")["grad"]
+    cut = G.grad_model(w, x, y, "xent", detach_transforms=True)["grad"]
+    assert np.abs(full - cut).max() > 1e-2 * np.abs(full).max()
+
+
+def test_handed_in_winners_are_used():
+    w = _weights()
+    x, y = _fd_case("xent")
+    own = G.grad_model(w, x, y, "xent")
+    again = G.grad_model(w, x, y, "xent", winners=own["winners"])
+    assert np.array_equal(own["grad"], again["grad"])
+    moved = own["winners"].copy()
+    k = int(np.argmax(own["pooled"][0, 2]))                        # a live column of the classifier's pool
+    moved[0, 2, k] = (moved[0, 2, k] + 1) % FD_POINTS
+    other = G.grad_model(w, x, y, "xent", winners=moved)
+    assert not np.array_equal(own["grad"][0], other["grad"][0]) and np.array_equal(own["grad"][1:], other["grad"][1:])
+
+
+# ------------------------------------------------------------------------------------------------ the three losses
+def _dz(Z, labels, loss, kappa):
+    Zt = torch.tensor(Z, dtype=torch.float64, requires_grad=True)
+    L, active = G.loss_torch(Zt, labels, loss, kappa)
+    L.sum().backward()
+    return L.detach().numpy(), Zt.grad.numpy(), active
+
+
+def test_cross_entropy_is_per_cloud_softmax_minus_onehot():
+    Z = np.array([[1.0, 2.0, 0.5], [3.0, -1.0, 3.0]])
+    y = np.array([1, 2])
+    L, dZ, _ = _dz(Z, y, "xent", 0.0)
+    p = np.exp(Z) / np.exp(Z).sum(1, keepdims=True)
+    assert np.allclose(L, -np.log(p[[0, 1], y]), atol=1e-14) and np.allclose(L, G.loss_numpy(Z, y, "xent"), atol=1e-14)
+    onehot = np.eye(3)[y]
+    assert np.allclose(dZ, p - onehot, atol=1e-14)                 # no batch mean
+
+
+def test_cw_targeted_rules():
+    #             t = 0;   others: first maximum at j
+    Z = np.array([[1.0, 4.0, 4.0, 2.0],       # a tie in max_{i != t}: index 1 takes the gradient
+                  [5.0, 1.0, 3.0, 2.0],       # m - Z_t = -2 > -kappa = -2.5: active
+                  [5.0, 1.0, 3.0, 2.0],       # with kappa = 2 (below): exactly on the clamp: NOT active (strict)
+                  [9.0, 1.0, 3.0, 2.0]])      # m - Z_t = -6 < -kappa: clamped
+    y = np.zeros(4, np.int64)
+    L, dZ, active = _dz(Z[:2], y[:2], "cw_targeted", 2.5)
+    assert np.array_equal(L, [3.0, -2.0]) and active.all()
+    assert np.array_equal(dZ, [[-1, 1, 0, 0], [-1, 0, 1, 0]])
+    L, dZ, active = _dz(Z[2:], y[2:], "cw_targeted", 2.0)
+    assert np.array_equal(L, [-2.0, -2.0]) and not active.any() and not dZ.any()
+    assert np.array_equal(G.loss_numpy(Z, y, "cw_targeted", 2.0), [3.0, -2.0, -2.0, -2.0])
+
+
+def test_cw_untargeted_rules():
+    Z = np.array([[6.0, 4.0, 4.0, 2.0],       # y = 0: Z_y - m = 2, the tie's first index 1 takes -1
+                  [1.0, 0.0, 3.0, 2.0],       # already misclassified by 2: -2 > -kappa = -3: still active
+                  [1.0, 0.0, 3.0, 2.0]])      # kappa = 2: on the clamp, not active
+    y = np.zeros(3, np.int64)
+    L, dZ, active = _dz(Z[:2], y[:2], "cw_untargeted", 3.0)
+    assert np.array_equal(L, [2.0, -2.0]) and active.all()
+    assert np.array_equal(dZ, [[1, -1, 0, 0], [1, 0, -1, 0]])
+    L, dZ, active = _dz(Z[2:], y[2:], "cw_untargeted", 2.0)
+    assert np.array_equal(L, [-2.0]) and not active.any() and not dZ.any()
+
+
+# ------------------------------------------------------------------------------------------------ cls_attack on a stub
+class _Stub:
+    """A float64 'classifier': logits = mean_points(x) @ A + c.  Exposes what ClassifierAttack uses."""
+    device, dtype, batch_size, num_classes = torch.device("cpu"), torch.float64, 3, 4
+
+    def __init__(self, seed=0):
+        rng = np.random.default_rng(seed)
+        self.A = torch.tensor(rng.normal(size=(3, 4)) * 4.0)
+        self.c = torch.tensor(rng.normal(size=4) * 0.1)
+        self.calls = 0
+
+    def input_gradient(self, x, labels, loss="xent", kappa=0.0, return_logits=False, return_winners=False):
+        assert labels.dtype == torch.int32
+        self.calls += 1
+        xv = x.detach().clone().requires_grad_(True)
+        Z = xv.mean(1) @ self.A + self.c
+        L, _ = G.loss_torch(Z, labels.numpy(), loss, kappa)
+        L.sum().backward()
+        return (L.detach(), xv.grad) + ((Z.detach(),) if return_logits else ())
+
+    def logits(self, x):
+        return torch.as_tensor(x, dtype=torch.float64).mean(1) @ self.A + self.c
+
+
+def _stub_case(seed=1, num=5, n=7):
+    rng = np.random.default_rng(seed)
+    stub = _Stub(seed)
+    x = rng.random((num, n, 3)) - 0.5
+    true = stub.logits(x).argmax(1).numpy()
+    target = (true + 1 + rng.integers(0, 3, num)) % 4
+    return stub, x, true, target
+
+
+def _tf_adam(grads, lr):
+    """numpy: TF's ApplyAdam on a variable from zero, one step per gradient."""
+    p = np.zeros_like(grads[0])
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    for t, g in enumerate(grads, 1):
+        alpha = lr * np.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t)
+        m += (g - m) * (1 - 0.9)
+        v += (g * g - v) * (1 - 0.999)
+        p = p - alpha * m / (np.sqrt(v) + 1e-8)
+    return p
+
+
+def test_cw_is_tf_form_adam_on_the_total_gradient():
+    from geometric_adv_amd.cls_attack import ClassifierAttack
+    stub, x, true, target = _stub_case()
+    seen = []
+    lr, wgt = 0.02, 0.7
+    atk = ClassifierAttack(stub, method="cw", targeted=True, dist_type="l2", dist_weight=wgt, kappa=50.0, learning_rate=lr,
+                           num_iterations=3, history=lambda it, adv, ok, D, loss: seen.append(adv.numpy().copy()))
+    # replay: the total gradient at every iterate, from the stub
+    lab = torch.from_numpy(target.astype(np.int32))
+    grads = []
+    for it in range(3):
+        pert = _tf_adam(grads, lr) if grads else np.zeros_like(x)
+        g = np.concatenate([stub.input_gradient(torch.tensor(x[s:s + 3] + pert[s:s + 3]), lab[s:s + 3], "cw_targeted", 50.0)[1].numpy()
+                            for s in range(0, len(x), 3)])
+        grads.append(g + wgt * 2.0 * pert)
+    want = x + _tf_adam(grads, lr)
+    stub.calls = 0
+    metrics, adv = atk.attack(x, target)
+    assert stub.calls == 3 * 2                                     # one input_gradient per iteration and chunk (5 clouds, chunks of 3)
+    assert metrics.shape == (5, 4) and metrics.dtype == np.float32 and adv.dtype == np.float32
+    none = metrics[:, 0] == 0
+    assert np.array_equal(metrics[none, 2], -np.ones(none.sum()))
+    assert np.allclose(adv[none], want[none].astype(np.float32), rtol=0, atol=1e-7)
+    # the first step: -lr g / (|g| + 1e-8 / sqrt(1 - beta2))
+    g0 = grads[0]
+    first = np.concatenate([seen[1], seen[4]]) - x               # history: 3 iterates of chunk 0, then 3 of chunk 1
+    assert np.allclose(first, -lr * g0 / (np.abs(g0) + 1e-8 / np.sqrt(1 - 0.999)), rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("method,targeted", [("cw", True), ("cw", False), ("ifgsm", True), ("ifgsm", False)])
+def test_keep_best_returns_the_successful_iterate_of_smallest_distance(method, targeted):
+    from geometric_adv_amd.cls_attack import ClassifierAttack
+    stub, x, true, target = _stub_case(seed=2)
+    hist = []
+    atk = ClassifierAttack(stub, method=method, targeted=targeted, dist_weight=0.05, learning_rate=0.05, eps=0.6, num_iterations=40,
+                           history=lambda it, adv, ok, D, loss: hist.append((it, adv.numpy().copy(), ok.numpy().copy(), D.numpy().copy())))
+    labels = target if targeted else true
+    metrics, adv = atk.attack(x, labels)
+    assert metrics[:, 0].sum() >= 3                                # the stub is easy to fool: the rule is exercised
+    for s in range(0, len(x), 3):
+        chunk = hist[:40] if s == 0 else hist[40:]
+        for j in range(len(x[s:s + 3])):
+            ok_its = [(h[3][j], h[0]) for h in chunk if h[2][j]]
+            c = s + j
+            if not ok_its:
+                assert metrics[c, 0] == 0 and metrics[c, 2] == -1
+                continue
+            d, it = min(ok_its)                                    # smallest D; the earliest among equals
+            assert metrics[c, 0] == 1 and metrics[c, 2] == it and metrics[c, 1] == np.float32(d)
+            assert np.array_equal(adv[c], chunk[it][1][j].astype(np.float32))
+            pred = stub.logits(chunk[it][1][j][None]).argmax(1).item()
+            assert (pred == labels[c]) if targeted else (pred != labels[c])
+
+
+def test_ifgsm_stays_in_the_box_and_steps_by_alpha():
+    from geometric_adv_amd.cls_attack import ClassifierAttack, box
+    stub, x, true, target = _stub_case(seed=3)
+    hist = []
+    eps = 0.03
+    atk = ClassifierAttack(stub, method="ifgsm", targeted=True, eps=eps, alpha=0.01, num_iterations=6,
+                           history=lambda it, adv, ok, D, loss: hist.append(adv.numpy().copy()))
+    metrics, adv = atk.attack(x[:3], target[:3])
+    for h in hist:
+        assert np.abs(h - x[:3]).max() <= eps
+    assert np.abs(adv - x[:3].astype(np.float32)).max() <= eps + 1e-7
+    assert np.allclose(np.abs(hist[1] - x[:3]), 0.01, atol=1e-15)  # the stub's gradient has no zero coordinate
+    assert np.allclose(np.abs(hist[5] - x[:3]).max(), eps, atol=1e-15)
+    assert ClassifierAttack(stub, method="ifgsm", eps=0.1, num_iterations=20).alpha == pytest.approx(0.005)
+    # the box in float32: the sum's rounding is undone
+    rng = np.random.default_rng(0)
+    xf = torch.tensor((rng.random((4, 500, 3)) - 0.5).astype(np.float32))
+    e32 = float(np.float32(0.05))
+    p = torch.where(torch.rand(xf.shape, generator=torch.Generator().manual_seed(0)) < 0.5, -e32, e32).to(torch.float32)
+    raw = ((xf + p) - xf).abs().max().item()
+    assert (box(xf, p, e32) - xf).abs().max().item() <= e32 < raw  # the plain sum does leave the box on this draw
