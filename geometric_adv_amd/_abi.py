@@ -55,6 +55,9 @@ SIGNATURES = {      # in the header's order
     "geoadv_outlier_filter": "i:iippiifppppp",
     "geoadv_sor_filter": "i:iippiidpppppp",
     "geoadv_random_drop": "i:iipiQQQppp",
+    "geoadv_knn_outlier_loss_workspace_bytes": "z:iii",
+    "geoadv_knn_outlier_loss": "i:iiiidppppppppzp",
+    "geoadv_debug_knn_outlier_loss_launch": "i:iiidppppzp",
     "geoadv_critical_split": "i:iiippppppppp",
     "geoadv_sort_axes": "i:iipppip",
     "geoadv_batch_gather": "i:iipqpppppp",

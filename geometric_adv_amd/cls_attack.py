@@ -16,6 +16,12 @@ method='ifgsm': Liu et al.'s iterative gradient sign (Extending Adversarial Atta
 Classifiers, ICIP 2019): x_{k+1} = clip(x_k -/+ alpha sign(g), x - eps, x + eps) with g the cross-entropy gradient --
 descending on the target label, or ascending on the true label; alpha defaults to eps / num_iterations; D = max |pert|.
 
+knn_weight != 0 (method='cw', either dist_type) adds the kNN term of Tsai, Yang and Chen's kNN attack (Robust Adversarial Objects
+against Deep Learning Models, AAAI 2020), the literature's answer to SOR: K = ops.knn_outlier_loss(x + pert, knn_k, knn_alpha),
+the mean squared kNN distance of exactly the points a statistical outlier filter would remove (csrc/knn_loss.hip).  The loss is
+f + dist_weight * (D + knn_weight * K), its gradient g + dist_weight * (dD + knn_weight * dK); keep-best still ranks by D.
+clip_linf=c clamps pert to [-c, c] after each Adam step and forms the iterate with box(), so |adv - x| <= c holds exactly.
+
 Keep-best, per cloud: among the iterates that the SAME call's logits classify adversarially (the first arg-max equals the
 target, or differs from the true label) the one of smallest D.  A cloud that never succeeds is returned as its last iterate.
 """
@@ -44,7 +50,7 @@ def box(x, pert, eps):
 
 class ClassifierAttack:
     def __init__(self, clf, method="cw", targeted=True, dist_type="l2", dist_weight=1.0, kappa=0.0, learning_rate=0.01,
-                 num_iterations=200, eps=0.05, alpha=None, history=None):
+                 num_iterations=200, eps=0.05, alpha=None, history=None, knn_weight=0.0, knn_k=5, knn_alpha=1.05, clip_linf=None):
         """clf: a PointNetClassifier (anything with input_gradient, device and batch_size).  history: None or a callable
         (iteration, adv, success, D, loss) that sees every iterate's device tensors as the keep-best rule judged them."""
         if method not in METHODS:
@@ -62,12 +68,24 @@ class ClassifierAttack:
         self.eps = float(eps)
         self.alpha = float(alpha) if alpha is not None else self.eps / max(self.num_iterations, 1)
         self.history = history
+        self.knn_weight = float(knn_weight)
+        self.knn_k = int(knn_k)
+        self.knn_alpha = float(knn_alpha)
+        self.clip_linf = float(clip_linf) if clip_linf is not None else None
         if self.num_iterations < 1:
             raise ValueError("num_iterations must be >= 1")
         if self.kappa < 0 or not np.isfinite(self.kappa):
             raise ValueError("kappa must be finite and >= 0")
         if method == "ifgsm" and not (self.eps > 0 and self.alpha > 0):
             raise ValueError("ifgsm needs eps > 0 and alpha > 0")
+        if not np.isfinite(self.knn_weight):
+            raise ValueError("knn_weight must be finite")
+        if method == "ifgsm" and self.knn_weight != 0.0:
+            raise ValueError("the kNN term belongs to method='cw' (ifgsm follows the sign of the cross-entropy gradient alone)")
+        if self.knn_weight != 0.0 and not (self.knn_k >= 1 and self.knn_alpha >= 0 and np.isfinite(self.knn_alpha)):
+            raise ValueError("the kNN term needs knn_k >= 1 and a finite knn_alpha >= 0")
+        if self.clip_linf is not None and not (self.clip_linf > 0 and np.isfinite(self.clip_linf)):
+            raise ValueError("clip_linf must be None or finite and > 0")
 
     # ------------------------------------------------------------------------------------------ distances
     def _distance(self, x, pert):
@@ -80,6 +98,12 @@ class ClassifierAttack:
         D = d1.mean(dim=1) + d2.mean(dim=1)
         D.sum().backward()
         return D.detach(), p.grad
+
+    def _iterate(self, x, pert):
+        """The cloud the classifier sees for a perturbation."""
+        if self.method == "cw" and self.clip_linf is None:
+            return x + pert
+        return box(x, pert, self.eps if self.method == "ifgsm" else self.clip_linf)
 
     def _judge(self, logits, labels):
         pred = first_argmax(logits)
@@ -98,11 +122,17 @@ class ClassifierAttack:
         last_loss = None
         loss_kind = ("cw_targeted" if self.targeted else "cw_untargeted") if self.method == "cw" else "xent"
         for it in range(T):
-            adv = x + pert if self.method == "cw" else box(x, pert, self.eps)
+            adv = self._iterate(x, pert)
             f, g, logits = clf.input_gradient(adv, labels, loss=loss_kind, kappa=self.kappa, return_logits=True)[:3]
             if self.method == "cw":
                 D, dD = self._distance(x, pert)
-                last_loss = f + self.dist_weight * D
+                if self.knn_weight != 0.0:
+                    from . import ops
+                    K, dK = ops.knn_outlier_loss(adv, self.knn_k, self.knn_alpha)
+                    last_loss = f + self.dist_weight * (D + self.knn_weight * K.to(D.dtype))
+                    dD = dD + self.knn_weight * dK
+                else:
+                    last_loss = f + self.dist_weight * D
             else:
                 D = (adv - x).abs().amax(dim=(1, 2))
                 last_loss = f
@@ -120,10 +150,12 @@ class ClassifierAttack:
                 m = m + (total - m) * (1.0 - ADAM_BETA1)
                 v = v + (total * total - v) * (1.0 - ADAM_BETA2)
                 pert = pert - alpha_t * m / (torch.sqrt(v) + ADAM_EPS)
+                if self.clip_linf is not None:
+                    pert = torch.clamp(pert, -self.clip_linf, self.clip_linf)
             else:
                 step = self.alpha * torch.sign(g)
                 pert = torch.clamp(pert - step if self.targeted else pert + step, -self.eps, self.eps)
-        last = x + pert if self.method == "cw" else box(x, pert, self.eps)
+        last = self._iterate(x, pert)
         found = best_it >= 0
         out = torch.where(found[:, None, None], best_adv, last)
         metrics = torch.stack([found.to(x.dtype), best_d, best_it.to(x.dtype), last_loss.to(x.dtype)], dim=1)

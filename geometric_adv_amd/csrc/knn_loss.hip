@@ -1,0 +1,322 @@
+// The kNN outlier loss of the kNN attack (Tsai, Yang, Chen, AAAI 2020) and its gradient with respect to every point (not in the
+// reference; the rule is written out in include/geoadv.h and restated in numpy by tests/_knn_loss_model.py, bit for bit).
+// Two steps per call: the self-kNN search (geoadv_knn_point_ws, grouping.hip) into the caller's workspace, then ONE launch of
+// knn_outlier_loss_kernel, one 1024-thread workgroup per cloud as stat_defense.hip:
+//   A  per point the k squared distances to its neighbours, recomputed from the coordinates, and the float64 score (kept in the
+//      workspace: the later phases read it back instead of gathering again); the SOR statistics in the rule's fixed order
+//   B  the mask, the loss, and per TARGET the number of masked points that list it (integer atomics on a workspace row)
+//   C  an exclusive scan of those in-degrees: every target owns a segment of the edge list in the workspace
+//   D  every masked point drops its own index into the segment of each of its neighbours (integer atomic cursor: the ORDER
+//      inside a segment is left to the hardware -- the set is not)
+//   E  every target's thread adds the gather term (its own neighbours, column order) and then its segment in ASCENDING source
+//      index, by repeatedly taking the smallest source not yet added: the order of the rule, whatever order D stored.  That is
+//      O(d^2) in the in-degree d, so it serves d <= KL_SEGMENT_CAP; a target beyond it (ties naming one low-index neighbour,
+//      a hub) is queued
+//   F  a wave per queued target walks ALL points in ascending order, 64 at a time, and adds the sources a ballot finds, lowest
+//      lane first: O(n k / 64) per hub, no bound on d, nothing truncated.
+// No float atomics anywhere: every float64 sum is formed by one thread (or redundantly by every lane of one wave) in the
+// rule's order, so two calls give the same bits.  Nothing in LDS grows with n or k: scores, in-degrees, cursors, the edge list
+// and the hub queue live in the workspace (n = 2048, k = 5: 80 KB a cloud beside the search's rows, L2-resident).
+// Visibility inside the workgroup: a word that an atomic has changed (in-degree, cursor) is only ever read by an agent-scope
+// atomic load, never by a plain load that this CU's L1 could answer from an older copy; plain stores (scores, edges, queue) are
+// read by other waves of the same workgroup after __syncthreads(), through the L1 they share.
+#include <math.h>
+#include "stat_sums.h"
+
+namespace geoadv {
+
+constexpr int KL_MAX_K = 15;              // k + 1 columns of the search fit its 17-slot register lists
+constexpr int KL_MAX_N = 32767;           // the rule's limit (the mask is the complement of sor_filter's inliers)
+constexpr int KL_SEARCH_MAX_N = 16384;    // geoadv_knn_point_ws holds a row of the cloud in LDS (grouping.hip ROW_MAX_N)
+constexpr int KL_SEGMENT_CAP = 16;        // in-degree up to which a target's own thread orders its segment
+
+struct KlLds {
+    double wsum[DF_WAVES];
+    int wcnt[DF_WAVES];
+    int nhub;
+};
+
+__device__ __forceinline__ int kl_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// neighbour c of point p: column c + 1 of the search's row (column 0 is dropped, as geoadv_knn_dists does).  The index is
+// clamped for the loads that follow: a search on non-finite input owes nobody an index inside the cloud.
+__device__ __forceinline__ int kl_neighbour(const int *nbr, int stride, int p, int c, int n) {
+    const int j = nbr[(size_t)p * stride + 1 + c];
+    return min(max(j, 0), n - 1);
+}
+
+struct KlStats { double mu, bound; };
+
+__device__ __forceinline__ bool kl_masked(double s, const KlStats &st) {
+    const double d = s - st.mu;
+    return isfinite(s) && s > st.mu && __dmul_rn(d, d) > st.bound;
+}
+
+// G += (double)x_i - (double)x_j, component by component
+__device__ __forceinline__ void kl_add_diff(double (&G)[3], const float (&xi)[3], const float *xj) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) G[a] += (double)xi[a] - (double)xj[a];
+}
+
+__global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int k, double alpha2, const float *xyz, const int *nbr_all,
+                                                                      double *sc_all, int *deg_all, int *cur_all, int *edge_all,
+                                                                      int *hub_all, double *loss, float *grad_all, double *score_all,
+                                                                      unsigned char *mask_all, int *idx_all, double *stats) {
+    __shared__ KlLds L;
+    const size_t cl = blockIdx.x;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int stride = k + 1;
+    const float *x = xyz + cl * n * 3;
+    const int *nbr = nbr_all + cl * n * stride;
+    double *sc = sc_all + cl * n;
+    int *deg = deg_all + cl * n, *cur = cur_all + cl * n, *hub = hub_all + cl * n;
+    int *edge = edge_all + cl * n * k;
+    if (t == 0) L.nhub = 0;
+
+    // ---- A: scores and statistics (the SOR rule; step 1 of the summation order: thread t adds points t, t + T, ...) --------------
+    double acc = 0.0, cnt = 0.0;
+    for (int p = t; p < n; p += DF_THREADS) {
+        const float px = x[3 * p], py = x[3 * p + 1], pz = x[3 * p + 2];
+        float val[KL_MAX_K];
+#pragma unroll
+        for (int c = 0; c < KL_MAX_K; ++c) {
+            val[c] = 0.f;
+            if (c < k) {
+                const int raw = nbr[(size_t)p * stride + 1 + c];
+                if (idx_all) idx_all[(cl * n + p) * k + c] = raw;
+                const int j = min(max(raw, 0), n - 1);
+                const float dx = px - x[3 * j], dy = py - x[3 * j + 1], dz = pz - x[3 * j + 2];
+                val[c] = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+            }
+        }
+        double s = (double)val[0];
+#pragma unroll
+        for (int c = 1; c < KL_MAX_K; ++c) if (c < k) s += (double)val[c];       // sor_score on registers: the same sums in the same order
+        s = s / (double)k;
+        sc[p] = s;
+        deg[p] = 0;
+        if (score_all) score_all[cl * n + p] = s;
+        const bool fin = isfinite(s);
+        acc += fin ? s : 0.0;
+        cnt += fin ? 1.0 : 0.0;
+    }
+    const double m = sd_block_sum64(cnt, L.wsum);
+    const double sum = sd_block_sum64(acc, L.wsum);
+    KlStats st;
+    st.mu = m > 0.0 ? sum / m : 0.0;
+    acc = 0.0;
+    for (int p = t; p < n; p += DF_THREADS) {
+        const double s = sc[p];
+        const double d = s - st.mu;
+        acc += isfinite(s) ? __dmul_rn(d, d) : 0.0;
+    }
+    const double sq = sd_block_sum64(acc, L.wsum);
+    const double var = m >= 2.0 ? sq / (m - 1.0) : 0.0;
+    st.bound = __dmul_rn(alpha2, var);
+
+    // ---- B: mask, loss, in-degrees (the barriers of the sums above order the zeroing of deg before these atomics) ----------------
+    acc = 0.0;
+    cnt = 0.0;
+    for (int p = t; p < n; p += DF_THREADS) {
+        const double s = sc[p];
+        const bool w = kl_masked(s, st);
+        if (mask_all) mask_all[cl * n + p] = w ? 1 : 0;
+        acc += w ? s : 0.0;
+        cnt += w ? 1.0 : 0.0;
+        if (w && grad_all)
+            for (int c = 0; c < k; ++c) atomicAdd(&deg[kl_neighbour(nbr, stride, p, c, n)], 1);
+    }
+    const double nmask = sd_block_sum64(cnt, L.wsum);
+    const double lsum = sd_block_sum64(acc, L.wsum);
+    if (t == 0) {
+        loss[cl] = lsum / (double)n;
+        if (stats) { stats[4 * cl] = st.mu; stats[4 * cl + 1] = var; stats[4 * cl + 2] = m; stats[4 * cl + 3] = nmask; }
+    }
+    if (!grad_all) return;
+    float *grad = grad_all + cl * n * 3;
+
+    // ---- C: exclusive scan of the in-degrees, 1024 targets a round: cur[i] = the start of target i's segment ----------------------
+    int base = 0;
+    for (int p0 = 0; p0 < n; p0 += DF_THREADS) {
+        const int p = p0 + t;
+        const int d = p < n ? kl_load(&deg[p]) : 0;
+        int incl = d;
+#pragma unroll
+        for (int s = 1; s < kWave; s <<= 1) {
+            const int v = __shfl_up(incl, s, kWave);
+            incl += lane >= s ? v : 0;
+        }
+        if (lane == 63) L.wcnt[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < DF_WAVES; ++w) {
+            const int cw = L.wcnt[w];
+            before += w < wave ? cw : 0;
+            total += cw;
+        }
+        if (p < n) cur[p] = base + before + incl - d;
+        base += total;
+        __syncthreads();
+    }
+
+    // ---- D: placement.  base <= n k: every masked point adds k edges, and the segments tile [0, base) -----------------------------
+    for (int p = t; p < n; p += DF_THREADS) {
+        if (!kl_masked(sc[p], st)) continue;
+        for (int c = 0; c < k; ++c) {
+            const int slot = atomicAdd(&cur[kl_neighbour(nbr, stride, p, c, n)], 1);
+            if (slot >= 0 && slot < n * k) edge[slot] = p;                       // (always true; the edge list has n k entries)
+        }
+    }
+    __syncthreads();
+
+    // ---- E: the gradient of every target with a short segment; the others are queued -----------------------------------------------
+    const double scale = 2.0 / ((double)n * (double)k);
+    for (int i = t; i < n; i += DF_THREADS) {
+        const int d = kl_load(&deg[i]);
+        if (d > KL_SEGMENT_CAP) {
+            hub[atomicAdd(&L.nhub, 1)] = i;
+            continue;
+        }
+        const float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]};
+        double G[3] = {0.0, 0.0, 0.0};
+        if (kl_masked(sc[i], st))
+            for (int c = 0; c < k; ++c) kl_add_diff(G, xi, x + 3 * kl_neighbour(nbr, stride, i, c, n));
+        const int end = min(kl_load(&cur[i]), n * k), start = max(end - d, 0);      // (the clamps never bind: after D, cur[i] is the segment's end)
+        int last = -1;
+        for (int done = 0; done < d;) {
+            int next = n, mult = 0;                                              // the smallest source above `last`, and how often it occurs
+            for (int e = start; e < end; ++e) {
+                const int p = edge[e];
+                if (p > last && p < next) { next = p; mult = 1; }
+                else if (p == next) ++mult;
+            }
+            if (mult == 0) break;                                                // (never: the segment holds d sources)
+            for (int r = 0; r < mult; ++r) kl_add_diff(G, xi, x + 3 * next);
+            done += mult;
+            last = next;
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) grad[3 * i + a] = (float)__dmul_rn(G[a], scale);
+    }
+    __syncthreads();
+
+    // ---- F: the queued targets, a wave each: all points in ascending order, every lane forming the same sum ------------------------
+    const int nhub = L.nhub;
+    for (int h = wave; h < nhub; h += DF_WAVES) {
+        const int i = min(max(hub[h], 0), n - 1);                                    // (a queued target is a point of the cloud)
+        const float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]};
+        double G[3] = {0.0, 0.0, 0.0};
+        if (kl_masked(sc[i], st))
+            for (int c = 0; c < k; ++c) kl_add_diff(G, xi, x + 3 * kl_neighbour(nbr, stride, i, c, n));
+        for (int p0 = 0; p0 < n; p0 += kWave) {
+            const int p = p0 + lane;
+            int mult = 0;
+            float xp[3] = {0.f, 0.f, 0.f};
+            if (p < n && kl_masked(sc[p], st)) {
+                for (int c = 0; c < k; ++c) mult += kl_neighbour(nbr, stride, p, c, n) == i ? 1 : 0;
+                xp[0] = x[3 * p]; xp[1] = x[3 * p + 1]; xp[2] = x[3 * p + 2];
+            }
+            unsigned long long hits = __ballot(mult > 0);
+            while (hits) {
+                const int src = __ffsll((long long)hits) - 1;
+                hits &= hits - 1;
+                const float xs[3] = {__shfl(xp[0], src, kWave), __shfl(xp[1], src, kWave), __shfl(xp[2], src, kWave)};
+                const int reps = __shfl(mult, src, kWave);
+                for (int r = 0; r < reps; ++r) kl_add_diff(G, xi, xs);
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) grad[3 * i + a] = (float)__dmul_rn(G[a], scale);
+        }
+    }
+}
+
+static size_t kl_up(size_t v) { return (v + 255) / 256 * 256; }
+
+struct KlLayout {
+    size_t knn, val, idx, sc, deg, cur, hub, edge, total;
+};
+
+static KlLayout kl_layout(int b, int n, int k) {
+    KlLayout o;
+    const size_t bn = (size_t)b * n;
+    size_t at = 0;
+    o.knn = at; at += kl_up(geoadv_knn_workspace_bytes(b, n, n, k + 1));
+    o.val = at; at += kl_up(bn * (k + 1) * sizeof(float));
+    o.idx = at; at += kl_up(bn * (k + 1) * sizeof(int));
+    o.sc = at; at += kl_up(bn * sizeof(double));
+    o.deg = at; at += kl_up(bn * sizeof(int));
+    o.cur = at; at += kl_up(bn * sizeof(int));
+    o.hub = at; at += kl_up(bn * sizeof(int));
+    o.edge = at; at += kl_up(bn * k * sizeof(int));
+    o.total = at + 256;                                    // (+ 256: the workspace pointer is aligned up here)
+    return o;
+}
+
+static bool kl_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const char *pa = (const char *)a, *pb = (const char *)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+static bool kl_shape_ok(int b, int n, int k) { return b >= 0 && b <= 65535 && k >= 1 && k <= KL_MAX_K && n >= k + 2 && n <= KL_MAX_N; }
+
+static int kl_check(const char *op, int b, int n, int k, double alpha, const float *xyz, const double *loss, const float *grad,
+                    const void *workspace, size_t workspace_bytes) {
+    GA_REQUIRE(b >= 0 && b <= 65535, "%s: batch %d must be in [0, 65535]", op, b);
+    GA_REQUIRE(k >= 1 && k <= KL_MAX_K, "%s: k=%d must be in [1, %d]", op, k, KL_MAX_K);
+    GA_REQUIRE(n >= k + 2 && n <= KL_MAX_N, "%s: n=%d must be in [k + 2 = %d, %d]", op, n, k + 2, KL_MAX_N);
+    GA_REQUIRE(n <= KL_SEARCH_MAX_N, "%s: the k-NN search takes at most %d points per cloud (n=%d)", op, KL_SEARCH_MAX_N, n);
+    GA_REQUIRE(alpha >= 0.0 && isfinite(alpha), "%s: alpha must be finite and >= 0 (got %g)", op, alpha);
+    if (b == 0) return GEOADV_OK;
+    GA_REQUIRE(xyz && loss, "%s: null pointer", op);
+    const size_t need = kl_layout(b, n, k).total;
+    GA_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace too small (%zu bytes, need %zu)", op, workspace_bytes, need);
+    const size_t bytes = (size_t)b * n * 3 * sizeof(float);
+    GA_REQUIRE(!grad || !kl_overlap(grad, bytes, xyz, bytes), "%s: grad overlaps xyz", op);
+    return GEOADV_OK;
+}
+
+static int kl_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad, double *score, unsigned char *mask,
+                     int *idx, double *stats, char *ws, hipStream_t st) {
+    const KlLayout o = kl_layout(b, n, k);
+    knn_outlier_loss_kernel<<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, reinterpret_cast<const int *>(ws + o.idx),
+                                                      reinterpret_cast<double *>(ws + o.sc), reinterpret_cast<int *>(ws + o.deg),
+                                                      reinterpret_cast<int *>(ws + o.cur), reinterpret_cast<int *>(ws + o.edge),
+                                                      reinterpret_cast<int *>(ws + o.hub), loss, grad, score, mask, idx, stats);
+    GA_LAUNCH_CHECK();
+    return GEOADV_OK;
+}
+
+static char *kl_align(void *p) { return reinterpret_cast<char *>((reinterpret_cast<size_t>(p) + 255) & ~(size_t)255); }
+
+}  // namespace geoadv
+
+using namespace geoadv;
+
+extern "C" size_t geoadv_knn_outlier_loss_workspace_bytes(int b, int n, int k) {
+    if (!kl_shape_ok(b, n, k) || b == 0) return 256;
+    return kl_layout(b, n, k).total;
+}
+
+extern "C" int geoadv_knn_outlier_loss(int kernel, int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad,
+                                       double *score, unsigned char *mask, int *idx, double *stats, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    GA_REQUIRE(kernel >= GEOADV_KNN_AUTO && kernel <= GEOADV_KNN_GRID_SHELLS, "knn_outlier_loss: unknown k-NN kernel %d", kernel);
+    if (int rc = kl_check("knn_outlier_loss", b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
+    if (b == 0) return GEOADV_OK;
+    const KlLayout o = kl_layout(b, n, k);
+    char *ws = kl_align(workspace);
+    if (int rc = geoadv_knn_point_ws(kernel, b, n, n, k + 1, xyz, xyz, reinterpret_cast<float *>(ws + o.val), reinterpret_cast<int *>(ws + o.idx),
+                                     ws + o.knn, kl_up(geoadv_knn_workspace_bytes(b, n, n, k + 1)), stream))
+        return rc;
+    return kl_launch(b, n, k, alpha, xyz, loss, grad, score, mask, idx, stats, ws, as_stream(stream));
+}
+
+extern "C" int geoadv_debug_knn_outlier_loss_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad,
+                                                    void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = kl_check("debug_knn_outlier_loss_launch", b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
+    if (b == 0) return GEOADV_OK;
+    return kl_launch(b, n, k, alpha, xyz, loss, grad, nullptr, nullptr, nullptr, nullptr, kl_align(workspace), as_stream(stream));
+}

@@ -454,6 +454,46 @@ def sor_filter(point_clouds, knn_dists=None, k=2, alpha=1.1, want_outliers=True,
     return (o_pc, o_idx, o_num, inlier) + ((stats,) if return_stats else ())
 
 
+KNN_LOSS_MAX_K = 15                                         # include/geoadv.h geoadv_knn_outlier_loss
+KNN_LOSS_MAX_POINTS = 16384                                 # (the rule's 32767, less what the search takes)
+
+
+def knn_outlier_loss(point_clouds, k=5, alpha=1.05, want_grad=True, return_parts=False, kernel=None):
+    """The kNN outlier loss of the kNN attack and its gradient (csrc/knn_loss.hip, the rule in include/geoadv.h): per cloud the
+    score s_p = the mean SQUARED distance of point p to its k nearest neighbours, SOR's float64 statistics mu and var of it, the
+    mask w_p = s_p > mu + alpha * sqrt(var) (tested without a square root: the complement of sor_filter's inliers), the loss
+    K = sum(w_p s_p) / n and dK / dx with the mask held constant -- the gather over a masked point's own neighbours plus the
+    scatter from the masked points that list it, summed in float64 in a fixed order (no float atomics: repeatable bits).
+    point_clouds (b,n,3) float32, 1 <= k <= 15, k + 2 <= n <= 16384, alpha >= 0.  kernel: the k-NN kernel, as knn_point.
+    -> (loss (b,) float64, grad (b,n,3) float32 or None without want_grad)[, score (b,n) float64, mask (b,n) bool,
+    idx (b,n,k) int32, stats (b,4) float64 = mu, var, the number of finite scores, the number of masked points]."""
+    pc = _f32(point_clouds, "point_clouds", 3)
+    if pc.shape[2] != 3:
+        raise ValueError("knn_outlier_loss only accepts 3d point sets")
+    b, n, _ = pc.shape
+    k = int(k)
+    if not 1 <= k <= KNN_LOSS_MAX_K:
+        raise ValueError("k must be in [1, %d] (got k=%d)" % (KNN_LOSS_MAX_K, k))
+    if not k + 2 <= n <= KNN_LOSS_MAX_POINTS:
+        raise ValueError("knn_outlier_loss needs clouds of k + 2 = %d <= n <= %d points (got n=%d)" % (k + 2, KNN_LOSS_MAX_POINTS, n))
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and alpha != float("inf")):
+        raise ValueError("alpha must be finite and >= 0 (got %r)" % alpha)
+    dev = pc.device
+    loss = torch.empty((b,), dtype=torch.float64, device=dev)
+    grad = torch.empty_like(pc) if want_grad else None
+    score = torch.empty((b, n), dtype=torch.float64, device=dev) if return_parts else None
+    mask = torch.empty((b, n), dtype=torch.uint8, device=dev) if return_parts else None
+    idx = torch.empty((b, n, k), dtype=torch.int32, device=dev) if return_parts else None
+    stats = torch.empty((b, 4), dtype=torch.float64, device=dev) if return_parts else None
+    with torch.cuda.device(dev):
+        wb = int(_lib.lib().geoadv_knn_outlier_loss_workspace_bytes(b, n, k))
+        ws = torch.empty(wb, dtype=torch.uint8, device=dev)
+        _call("geoadv_knn_outlier_loss", _knn_kernel(kernel), b, n, k, alpha, _lib.ptr(pc), _lib.ptr(loss), _lib.ptr(grad),
+              _lib.ptr(score), _lib.ptr(mask), _lib.ptr(idx), _lib.ptr(stats), _lib.ptr(ws), wb)
+    return (loss, grad) + ((score, mask.to(torch.bool), idx, stats) if return_parts else ())
+
+
 def random_drop(point_clouds, drop, seed, counter=0, slot_offset=0, return_idx=False):
     """Simple random sampling (csrc/stat_defense.hip, the rule in include/geoadv.h): every cloud of point_clouds (b,n,3) loses
     the `drop` points with the smallest counter-based 64-bit draws r(seed, counter, slot_offset + cloud, point) -> kept (b,n,3):

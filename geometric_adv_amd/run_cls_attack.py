@@ -1,7 +1,7 @@
 """White-box attack on the PointNet classifier (not in the reference; cls_attack.py):
 
     python -m geometric_adv_amd.run_cls_attack --classifier_folder log/pointnet --input clouds.npy --labels labels.npy \\
-        [--target_labels targets.npy] --method cw --output_dir cls_attack_res
+        [--target_labels targets.npy] --method cw [--knn_weight 5 --knn_k 5 --knn_alpha 1.05 --clip_linf 0.1] --output_dir cls_attack_res
 
 --input: (num, n, 3) float clouds; --labels: (num,) their true classes.  With --target_labels the attack is targeted at
 them; without, it is untargeted (away from --labels).  Paths are relative to --top_dir.  Writes into --output_dir:
@@ -9,6 +9,7 @@ them; without, it is untargeted (away from --labels).  Paths are relative to --t
   adversarial_metrics.npy       (num, 4) float32: success flag, best distance, best iteration (-1: none), last loss,
   adversarial_pred_labels.npy   (num,) int8: PointNetClassifier.classify of the written clouds,
   cls_attack_configuration.json the flags.
+--knn_weight adds the kNN attack's outlier term (ops.knn_outlier_loss) to the cw loss, the term aimed at run_defense_sor.
 The clouds are what run_defense_sor / run_defense_srs (ops.sor_filter, ops.random_drop) take.  A rerun writes the same bytes.
 """
 import argparse
@@ -33,6 +34,10 @@ def build_parser():
     p.add_argument('--learning_rate', type=float, default=0.01, help='cw: Adam step')
     p.add_argument('--eps', type=float, default=0.05, help='ifgsm: the box |adv - x| <= eps')
     p.add_argument('--alpha', type=float, default=None, help='ifgsm: step (default eps / num_iterations)')
+    p.add_argument('--knn_weight', type=float, default=0.0, help='cw: weight of the kNN outlier term inside the distance term (0 = off)')
+    p.add_argument('--knn_k', type=int, default=5, help='cw: neighbours of the kNN term')
+    p.add_argument('--knn_alpha', type=float, default=1.05, help='cw: the kNN term penalises scores above mean + knn_alpha * std')
+    p.add_argument('--clip_linf', type=float, default=None, help='cw: clamp the perturbation to [-c, c] after every step (default: none)')
     p.add_argument('--num_iterations', type=int, default=200)
     p.add_argument('--batch_size', type=int, default=10)
     p.add_argument('--output_dir', type=str, default='cls_attack_res')
@@ -65,7 +70,8 @@ def main(argv=None):
                              weights=classifier_weights_path(classifier_path, flags.classifier_restore_epoch))
     attack = ClassifierAttack(clf, method=flags.method, targeted=targeted, dist_type=flags.dist_type, dist_weight=flags.dist_weight,
                               kappa=flags.kappa, learning_rate=flags.learning_rate, num_iterations=flags.num_iterations,
-                              eps=flags.eps, alpha=flags.alpha)
+                              eps=flags.eps, alpha=flags.alpha, knn_weight=flags.knn_weight, knn_k=flags.knn_k,
+                              knn_alpha=flags.knn_alpha, clip_linf=flags.clip_linf)
     metrics, adversarial = attack.attack(clouds, goal)
     pred = clf.classify(adversarial)
 

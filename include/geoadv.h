@@ -281,6 +281,47 @@ int geoadv_random_drop(int b, int n, const float *pc /* [b,n,3] */, int drop, un
                        unsigned long long slot_offset, float *kept_pc /* [b,n,3] */, int *dropped_idx /* [b,drop] or NULL */,
                        void *stream);
 
+/* The kNN outlier loss of the kNN attack (Tsai, Yang, Chen: Robust Adversarial Objects against Deep Learning Models, AAAI 2020;
+ * not part of the reference) and its gradient: the term that penalises exactly the points geoadv_sor_filter would remove, so that
+ * a perturbation stays on the surface and survives the filter.  The search (geoadv_knn_point_ws) and ONE further launch, one
+ * 1024-thread workgroup per cloud (csrc/knn_loss.hip).  The rule, for one cloud x[n,3] (fp32), k and alpha:
+ *   neighbours  (val, N) = knn_point(k + 1, x, x) with the first column dropped (as geoadv_knn_dists drops it), in knn_point's tie
+ *               order: N[p][0..k-1] the indices, val[p][c] = ((dx*dx + dy*dy) + dz*dz) of x_p - x_N[p][c] in fp32, every product
+ *               and sum rounded on its own (no fused multiply-add), recomputed from the coordinates
+ *   score       s_p, m, mu, var and SUM: the SOR rule above, word for word, applied to val (squared distances: IF-Defense's
+ *               variant), all float64, SUM in its fixed T = 1024 order (a NaN score is a NaN; its sign and payload are no part
+ *               of the rule)
+ *   mask        w_p = 1 iff s_p is finite and s_p > mu and (s_p - mu) * (s_p - mu) > (alpha * alpha) * var
+ *               -- among finite scores exactly the complement of SOR's inlier test; a non-finite score gives w_p = 0.  The mask
+ *               is a CONSTANT of the differentiation: no gradient flows through mu or var (as in the published implementations)
+ *   loss        K = SUM(w_p ? s_p : +0.0) / (double)n, float64
+ *   gradient    accumulated in float64, per component, in an order that is part of the rule:
+ *                 G_i = +0.0
+ *                 if w_i:  for c = 0 .. k-1 ascending:  G_i += (double)x_i - (double)x_N[i][c]
+ *                 for p = 0 .. n-1 ascending with w_p = 1, within p for c ascending with N[p][c] == i:
+ *                                                        G_i += (double)x_i - (double)x_p
+ *                 grad_i = (float)(G_i * (2.0 / ((double)n * (double)k)))        one rounding to fp32
+ *               a point that no masked point lists and that is not masked itself gets +0.0.  This is the float64 gradient of K
+ *               with the mask held constant.  No float atomics: two calls give the same bits; a point's in-degree is unbounded
+ *               (ties can make many masked points name one neighbour) and nothing is truncated.
+ * Outputs: loss [b]; grad [b,n,3] or NULL (then the loss alone is formed); score [b,n] (s_p), mask [b,n] (w_p as 0 / 1),
+ * idx [b,n,k] (N), stats [b,4] = (mu, var, (double)m, the number of masked points) -- each may be NULL.
+ * workspace: geoadv_knn_outlier_loss_workspace_bytes(b,n,k) bytes of device memory, caller-owned, nothing process-wide; 256
+ * bytes for shapes the call refuses.  kernel: GEOADV_KNN_* for the search (same bits).
+ * Enqueues on `stream` only.  GEOADV_EINVAL, before any launch: b < 0, b > 65535, k < 1, k > 15, n < k + 2, n > 32767 -- and,
+ * for as long as the search keeps a row of the cloud in LDS, n > 16384 --, alpha < 0 or not finite, xyz or loss NULL with b > 0,
+ * a workspace that is too small, an unknown kernel, grad overlapping xyz.  b == 0 is a no-op. */
+size_t geoadv_knn_outlier_loss_workspace_bytes(int b, int n, int k);
+int geoadv_knn_outlier_loss(int kernel /* GEOADV_KNN_* for the search */, int b, int n, int k, double alpha,
+                            const float *xyz /* [b,n,3] */, double *loss /* [b] */, float *grad /* [b,n,3] or NULL */,
+                            double *score /* [b,n] or NULL */, unsigned char *mask /* [b,n] or NULL */,
+                            int *idx /* [b,n,k] or NULL */, double *stats /* [b,4] or NULL: mu, var, m, number masked */,
+                            void *workspace, size_t workspace_bytes, void *stream);
+/* TEST / MEASUREMENT ONLY: the launch after the search alone, on a workspace in which a geoadv_knn_outlier_loss call of the same
+ * (b, n, k) on the same xyz left its neighbours (tools/knn_loss_time.py times it).  Refuses what that call refuses. */
+int geoadv_debug_knn_outlier_loss_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad /* or NULL */,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* get_critical_points + get_critical_pc_non_critical_pc (src/ae_utils.py:12-80) on the device, from (max_val, max_idx) =
  * (np.max, np.argmax)(pre_symmetry, axis=1) as geoadv_ae_critical returns them: (b,c) each.  critical_points (b,c,3) /
  * critical_idx (b,c) int16: the distinct arg-max points of the channels with max_val > 0, the point owning most channels first,
