@@ -11,13 +11,12 @@ Template points: every step draws number_points // nb_primitives points per prim
 keyed by (seed, training step, primitive, point, coordinate) -- atlas_weights.train_template restates the generator in
 numpy.  train_step(x, template=...) takes explicit points of shape (nb_primitives, p, 2).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _abi, _lib, atlas_weights as AW
 from ._abi import AtlasConfig as _AtlasConfig, AtlasTrainConfig as _AtlasTrainConfig, AtlasWeights as _AtlasWeights
+from ._layer_trainer import LayerTrainer, seed64, torch_layer_tensors
 from .atlasnet import AtlasNetAE
 
 _STATE = {k: getattr(_abi, "GEOADV_ATLAS_STATE_" + k.upper()) for k in (
@@ -44,7 +43,10 @@ def layers(num_layers, decoder_bn):
     return out
 
 
-class AtlasNetTrainer:
+class AtlasNetTrainer(LayerTrainer):
+    _PREFIX, _STATE, _INT_STATES = "atlas", _STATE, _INT_STATES
+    # counters(): (steps the current optimizer has taken, training steps in all = num_batches_tracked)
+
     def __init__(self, weights=None, options=None, num_points=2048, batch_size=32, learning_rate=1e-3, seed=0, step=0, slots=None,
                  tracked=None, device=None):
         """weights: {state-dict key: array} (None = atlas_weights.initial_weights(seed) of the options' shape); options: the
@@ -76,42 +78,17 @@ class AtlasNetTrainer:
         self.num_points, self.batch_size = int(num_points), int(batch_size)
         self.learning_rate, self.seed = float(learning_rate), int(seed)
         self.device = torch.device(device if device is not None else "cuda:0")
-        canon = AW.canonical(weights, self.nb_primitives, self.num_layers)
         hw = _AtlasWeights()
-        for key, arrays in canon.items():
-            field = getattr(hw, key)
-            for i, a in enumerate(arrays):
-                field[i] = a.ctypes.data if a is not None else None
         cfg = _AtlasConfig(nb_primitives=self.nb_primitives, points_per_primitive=self.points_per_primitive, dim_template=2,
                            bottleneck_size=AW.BOTTLENECK, hidden_neurons=AW.HIDDEN, num_layers=self.num_layers, activation=0,
                            decoder_bn=int(self.decoder_bn))
-        sseed = self.seed & ((1 << 64) - 1)
-        tcfg = _AtlasTrainConfig(self.batch_size, self.num_points, self.points_per_primitive, self.learning_rate,
-                                 sseed - (1 << 64) if sseed >= (1 << 63) else sseed, int(step), int(step if tracked is None else tracked))
-        self._h = C.c_void_p()
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            _lib.check(L.geoadv_atlas_trainer_create(C.byref(self._h), C.byref(cfg), C.byref(hw), C.byref(tcfg)), "atlas_trainer_create")
-        pp, gp, cnt = C.c_void_p(), C.c_void_p(), C.c_size_t()
-        _lib.check(L.geoadv_atlas_trainer_buffers(self._h, C.byref(pp), C.byref(gp), C.byref(cnt)), "atlas_trainer_buffers")
-        self._count, self._params_ptr, self._grads_ptr = int(cnt.value), pp.value, gp.value
-        offs, moffs = (C.c_size_t * (4 * MAX_TRAIN_LAYERS))(), (C.c_size_t * MAX_TRAIN_LAYERS)()
-        _lib.check(L.geoadv_atlas_trainer_layout(self._h, offs, moffs), "atlas_trainer_layout")
-        self._offsets = list(offs)
+        tcfg = _AtlasTrainConfig(self.batch_size, self.num_points, self.points_per_primitive, self.learning_rate, seed64(self.seed),
+                                 int(step), int(step if tracked is None else tracked))
+        self._open(AW.canonical(weights, self.nb_primitives, self.num_layers), hw, (cfg, hw, tcfg), MAX_TRAIN_LAYERS)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._template = torch.zeros((self.nb_primitives, self.points_per_primitive, 2), dtype=torch.float32, device=self.device)
-        self._eval = None
         if slots is not None:
-            s1, s2 = self._flatten(slots["exp_avg"]), self._flatten(slots["exp_avg_sq"])
-            _lib.check(L.geoadv_atlas_trainer_set_slots(self._h, s1.ctypes.data, s2.ctypes.data), "atlas_trainer_set_slots")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                _lib.lib().geoadv_atlas_trainer_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+            self._upload_slots(self._flatten(slots["exp_avg"]), self._flatten(slots["exp_avg_sq"]))
 
     # ---- device views --------------------------------------------------------------------------------------
     def state(self, what, layer=0, primitive=None):
@@ -121,71 +98,24 @@ class AtlasNetTrainer:
         (nb_primitives, batch * p, C) -- layer 5 gives conv1(template) (nb_primitives, p, 1024), whose sum with the latent
         is that layer's pre-BN activation; 'gmax_row'; 'template'; 'latent'; 'recon'; 'chamfer_idx' 0 / 1; 'slot1';
         'slot2'.  primitive: that primitive's part of a decoder layer's array."""
-        p, cnt = C.c_void_p(), C.c_size_t()
-        _lib.check(_lib.lib().geoadv_atlas_trainer_state(self._h, _STATE[what], int(layer), C.byref(p), C.byref(cnt)), "atlas_trainer_state")
-        torch.cuda.synchronize(self.device)
-        a = _lib.device_view(p.value, cnt.value, "<i4" if what in _INT_STATES else "<f4", self.device).cpu().numpy().copy()
+        a = super().state(what, layer)
+        return a[int(primitive)] if primitive is not None and what in _PER_LAYER and int(layer) >= 5 else a
+
+    def _state_shapes(self, layer):
         B, nb, pp = self.batch_size, self.nb_primitives, self.points_per_primitive
-        if what in _PER_LAYER:
-            C_l = self.layers[int(layer)][2]
-            if int(layer) >= 5:
-                a = a.reshape(nb, -1, C_l) if what == "pre_bn" else a.reshape(nb, C_l)
-                return a if primitive is None else a[int(primitive)]
-            return a.reshape(-1, C_l) if what == "pre_bn" else a
         shapes = {"gmax_row": (B, 1024), "template": (nb, pp, 2), "latent": (B, 1024), "recon": (B, nb * pp, 3), "chamfer_idx": (B, -1)}
-        return a.reshape(shapes[what]) if what in shapes else a
+        C_l = self.layers[layer][2]
+        if layer >= 5:                                 # a decoder layer: one row per primitive
+            shapes.update(dict.fromkeys(_PER_LAYER, (nb, C_l)), pre_bn=(nb, -1, C_l))
+        else:
+            shapes["pre_bn"] = (-1, C_l)
+        return shapes
 
-    def counters(self):
-        """(steps the current optimizer has taken, training steps in all = num_batches_tracked)."""
-        s, o = C.c_longlong(), C.c_longlong()
-        _lib.check(_lib.lib().geoadv_atlas_trainer_counters(self._h, C.byref(s), C.byref(o)), "atlas_trainer_counters")
-        return int(s.value), int(o.value)
-
-    @property
-    def step(self):
-        return self.counters()[0]
-
-    def _unflatten(self, flat):
-        """{parameter key: array in torch's shape} from a flat parameter-layout buffer."""
-        out = {}
+    def _tensors(self):
         for l, (pre, fi, fo, conv, bn, dec) in enumerate(self.layers):
             o = self._offsets[4 * l: 4 * l + 4]
             for q in range(self.nb_primitives if dec else 1):
-                name, bname = (pre % q, bn % q if bn else None) if dec else (pre, bn)
-                w = flat[o[0] + q * fi * fo: o[0] + (q + 1) * fi * fo].reshape(fi, fo).T
-                out[name + ".weight"] = np.ascontiguousarray(w[:, :, None] if conv else w)
-                out[name + ".bias"] = flat[o[1] + q * fo: o[1] + (q + 1) * fo].copy()
-                if bn:
-                    out[bname + ".weight"] = flat[o[2] + q * fo: o[2] + (q + 1) * fo].copy()
-                    out[bname + ".bias"] = flat[o[3] + q * fo: o[3] + (q + 1) * fo].copy()
-        return out
-
-    def _flatten(self, named):
-        flat = np.zeros(self._count, np.float32)
-        for l, (pre, fi, fo, conv, bn, dec) in enumerate(self.layers):
-            o = self._offsets[4 * l: 4 * l + 4]
-            for q in range(self.nb_primitives if dec else 1):
-                name, bname = (pre % q, bn % q if bn else None) if dec else (pre, bn)
-                flat[o[0] + q * fi * fo: o[0] + (q + 1) * fi * fo] = np.asarray(named[name + ".weight"], np.float32).reshape(fo, fi).T.reshape(-1)
-                flat[o[1] + q * fo: o[1] + (q + 1) * fo] = np.asarray(named[name + ".bias"], np.float32).reshape(-1)
-                if bn:
-                    flat[o[2] + q * fo: o[2] + (q + 1) * fo] = np.asarray(named[bname + ".weight"], np.float32).reshape(-1)
-                    flat[o[3] + q * fo: o[3] + (q + 1) * fo] = np.asarray(named[bname + ".bias"], np.float32).reshape(-1)
-        return flat
-
-    def parameters(self):
-        """{parameter key: array} of the trainable tensors (host copies, torch's shapes)."""
-        torch.cuda.synchronize(self.device)
-        return self._unflatten(_lib.device_view(self._params_ptr, self._count, "<f4", self.device).cpu().numpy())
-
-    def gradients(self):
-        """{parameter key: d loss / d parameter} of the last step."""
-        torch.cuda.synchronize(self.device)
-        return self._unflatten(_lib.device_view(self._grads_ptr, self._count, "<f4", self.device).cpu().numpy())
-
-    def slots(self):
-        """Adam's {'exp_avg': {key: array}, 'exp_avg_sq': {key: array}}."""
-        return {"exp_avg": self._unflatten(self.state("slot1")), "exp_avg_sq": self._unflatten(self.state("slot2"))}
+                yield from torch_layer_tensors(pre % q if dec else pre, bn % q if bn and dec else bn, o, fi, fo, conv, q)
 
     def set_learning_rate(self, learning_rate, reset_optimizer=False):
         """reset_optimizer: a NEW Adam, as the reference builds at its decay epochs (slots and step count start again)."""
@@ -194,10 +124,6 @@ class AtlasNetTrainer:
         self.learning_rate = float(learning_rate)
 
     # ---- the steps -----------------------------------------------------------------------------------------
-    def _dev(self, x):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(self.device, dtype=torch.float32).contiguous()
-
     def eval_model(self):
         """The AtlasNetAE of the current weights (eval mode: running statistics, the regular template); rebuilt after every
         train_step."""

@@ -16,6 +16,7 @@ import torch
 
 from . import _abi, _lib, cls_weights as CW
 from ._abi import ClsTrainConfig as _ClsTrainConfig, ClsWeights as _ClsWeights
+from ._layer_trainer import LayerTrainer
 from .classifier import PointNetClassifier
 
 OPTIMIZERS = {"adam": _abi.GEOADV_CLS_OPT_ADAM, "momentum": _abi.GEOADV_CLS_OPT_MOMENTUM}
@@ -35,7 +36,10 @@ def _loss64(logits, labels, t2):
     return float(ce.mean() + 0.001 * 0.5 * (e ** 2).sum())
 
 
-class PointNetClassifierTrainer:
+class PointNetClassifierTrainer(LayerTrainer):
+    _PREFIX, _STATE, _INT_STATES = "cls", _STATE, ("pool_argmax",)
+    _COUNTERS = (C.c_longlong, C.c_float, C.c_float)          # counters(): (step, beta1_power, beta2_power) as they stand
+
     def __init__(self, weights=None, num_points=2048, batch_size=32, num_classes=13, learning_rate=0.001, optimizer="adam",
                  momentum=0.9, decay_step=200000, decay_rate=0.7, seed=0, step=0, slots=None, device=None):
         """weights: {name: array} with every name of cls_weights.variable_names() (None = cls_weights.initial_weights(
@@ -51,38 +55,15 @@ class PointNetClassifierTrainer:
         self.num_points, self.batch_size, self.num_classes = int(num_points), int(batch_size), int(num_classes)
         self.optimizer = optimizer
         self.device = torch.device(device if device is not None else "cuda:0")
-        canon = CW.canonical(weights, self.num_classes)
         hw = _ClsWeights()
         hw.num_classes = self.num_classes
-        for f in ("w", "b", "gamma", "beta", "mean", "var"):
-            arr = getattr(hw, f)
-            for i, a in enumerate(canon[f]):
-                arr[i] = a.ctypes.data if a is not None else None
         cfg = _ClsTrainConfig(self.batch_size, self.num_points, OPTIMIZERS[optimizer], float(learning_rate), float(momentum),
                               int(decay_step), float(decay_rate), int(step), int(seed))
-        self._h = C.c_void_p()
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            _lib.check(L.geoadv_cls_trainer_create(C.byref(self._h), C.byref(hw), C.byref(cfg)), "cls_trainer_create")
-        pp, gp, cnt = C.c_void_p(), C.c_void_p(), C.c_size_t()
-        _lib.check(L.geoadv_cls_trainer_buffers(self._h, C.byref(pp), C.byref(gp), C.byref(cnt)), "cls_trainer_buffers")
-        self._count, self._params_ptr, self._grads_ptr = int(cnt.value), pp.value, gp.value
-        offs, moffs = (C.c_size_t * (4 * _abi.GEOADV_CLS_LAYERS))(), (C.c_size_t * _abi.GEOADV_CLS_LAYERS)()
-        _lib.check(L.geoadv_cls_trainer_layout(self._h, offs, moffs), "cls_trainer_layout")
-        self._offsets, self._moving_offsets = list(offs), list(moffs)
+        self._open(CW.canonical(weights, self.num_classes), hw, (hw, cfg), _abi.GEOADV_CLS_LAYERS)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._pred = torch.zeros(self.batch_size, dtype=torch.int32, device=self.device)
-        self._eval = None
         if slots is not None:
             self._set_slots(slots)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                _lib.lib().geoadv_cls_trainer_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     @classmethod
     def restore(cls, prefix, weights_only=False, **kwargs):
@@ -102,34 +83,13 @@ class PointNetClassifierTrainer:
         return cls(weights=weights, step=int(got.pop(CW.STEP_NAME)), slots=got, **kwargs)
 
     # ---- device views --------------------------------------------------------------------------------------
-    def state(self, what, layer=0, device=False):
-        """Host copy of what the last step kept (geoadv_cls_trainer_state): 'bn_mean' / 'bn_var' / 'moving_mean' /
-        'moving_var' / 'bn_inv' / 'bn_shift' of a BN layer (GEOADV_CLS_* index), 'pre_bn' of a BN layer ([rows][C]: B * N
-        rows for a per-point layer, B for an fc layer), 'dropout_mask' 0 / 1, 'pool_argmax' 0 / 1 / 2, 't1', 't2', 'logits',
-        'slot1', 'slot2'.  device=True returns a view of the device buffer instead: it aliases the handle's memory, so it
-        changes with the next step and dangles once this trainer is destroyed -- drop the view before the trainer."""
-        p, cnt = C.c_void_p(), C.c_size_t()
-        _lib.check(_lib.lib().geoadv_cls_trainer_state(self._h, _STATE[what], int(layer), C.byref(p), C.byref(cnt)),
-                   "cls_trainer_state")
-        torch.cuda.synchronize(self.device)
-        a = _lib.device_view(p.value, cnt.value, "<i4" if what == "pool_argmax" else "<f4", self.device)
+    def _state_shapes(self, layer):
+        """state(what, layer): 'bn_mean' / 'bn_var' / 'moving_mean' / 'moving_var' / 'bn_inv' / 'bn_shift' of a BN layer
+        (GEOADV_CLS_* index), 'pre_bn' of a BN layer ([rows][C]: B * N rows for a per-point layer, B for an fc layer),
+        'dropout_mask' 0 / 1, 'pool_argmax' 0 / 1 / 2, 't1', 't2', 'logits', 'slot1', 'slot2'."""
         B = self.batch_size
-        shapes = {"dropout_mask": (B, -1), "pool_argmax": (B, 1024), "t1": (B, 3, 3), "t2": (B, 64, 64), "logits": (B, -1)}
-        if what == "pre_bn":
-            shapes["pre_bn"] = (-1, self._shapes()[int(layer)][2])
-        if not device:
-            a = a.cpu().numpy().copy()
-        return a.reshape(shapes[what]) if what in shapes else a
-
-    def counters(self):
-        """(step, beta1_power, beta2_power) as they stand."""
-        s, b1, b2 = C.c_longlong(), C.c_float(), C.c_float()
-        _lib.check(_lib.lib().geoadv_cls_trainer_counters(self._h, C.byref(s), C.byref(b1), C.byref(b2)), "cls_trainer_counters")
-        return int(s.value), float(b1.value), float(b2.value)
-
-    @property
-    def step(self):
-        return self.counters()[0]
+        return {"dropout_mask": (B, -1), "pool_argmax": (B, 1024), "t1": (B, 3, 3), "t2": (B, 64, 64), "logits": (B, -1),
+                "pre_bn": (-1, self._shapes()[layer][2])}
 
     def _shapes(self):
         nc = self.num_classes
@@ -140,57 +100,31 @@ class PointNetClassifierTrainer:
             out.append((scope, fi, fo, bn, shape))
         return out
 
-    def _unflatten(self, flat, suffix=""):
-        """{trainable name + suffix: array in its stored shape} from a flat parameter-layout buffer."""
-        out = {}
+    def _tensors(self):
         for l, (scope, fi, fo, bn, shape) in enumerate(self._shapes()):
             o = self._offsets[4 * l: 4 * l + 4]
-            out[scope + "/weights" + suffix] = flat[o[0]:o[0] + fi * fo].reshape(shape).copy()
-            out[scope + "/biases" + suffix] = flat[o[1]:o[1] + fo].copy()
+            yield scope + "/weights", o[0], fi * fo, shape, False
+            yield scope + "/biases", o[1], fo, (fo,), False
             if bn:
-                out[scope + "/bn/gamma" + suffix] = flat[o[2]:o[2] + fo].copy()
-                out[scope + "/bn/beta" + suffix] = flat[o[3]:o[3] + fo].copy()
-        return out
-
-    def _flatten(self, named, suffix):
-        flat = np.zeros(self._count, np.float32)
-        for l, (scope, fi, fo, bn, shape) in enumerate(self._shapes()):
-            o = self._offsets[4 * l: 4 * l + 4]
-            flat[o[0]:o[0] + fi * fo] = np.asarray(named[scope + "/weights" + suffix], np.float32).reshape(-1)
-            flat[o[1]:o[1] + fo] = np.asarray(named[scope + "/biases" + suffix], np.float32).reshape(-1)
-            if bn:
-                flat[o[2]:o[2] + fo] = np.asarray(named[scope + "/bn/gamma" + suffix], np.float32).reshape(-1)
-                flat[o[3]:o[3] + fo] = np.asarray(named[scope + "/bn/beta" + suffix], np.float32).reshape(-1)
-        return flat
+                yield scope + "/bn/gamma", o[2], fo, (fo,), False
+                yield scope + "/bn/beta", o[3], fo, (fo,), False
 
     def _set_slots(self, slots):
         if self.optimizer == "adam":
-            s1, s2 = self._flatten(slots, "/Adam"), self._flatten(slots, "/Adam_1")
-            b1, b2 = float(slots["beta1_power"]), float(slots["beta2_power"])
+            self._upload_slots(self._flatten(slots, "/Adam"), self._flatten(slots, "/Adam_1"), float(slots["beta1_power"]),
+                               float(slots["beta2_power"]))
         else:
-            s1, s2, b1, b2 = self._flatten(slots, "/Momentum"), None, 0.9, 0.999
-        _lib.check(_lib.lib().geoadv_cls_trainer_set_slots(self._h, s1.ctypes.data, s2.ctypes.data if s2 is not None else None, b1, b2),
-                   "cls_trainer_set_slots")
+            self._upload_slots(self._flatten(slots, "/Momentum"), None, 0.9, 0.999)
 
     def parameters(self):
         """Host copy of the flat parameter buffer."""
-        torch.cuda.synchronize(self.device)
-        return _lib.device_view(self._params_ptr, self._count, "<f4", self.device).cpu().numpy().copy()
-
-    def gradients(self):
-        """{trainable name: d loss / d variable} of the last step (host copies)."""
-        torch.cuda.synchronize(self.device)
-        return self._unflatten(_lib.device_view(self._grads_ptr, self._count, "<f4", self.device).cpu().numpy())
+        return self._host(self._params_ptr)
 
     # ---- the steps -----------------------------------------------------------------------------------------
-    def _dev(self, x, dtype):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(self.device, dtype=dtype).contiguous()
-
     def train_step(self, x, labels):
         """One sess.run([train_op, loss, pred]) at is_training = True: returns (loss of the pre-update variables, predicted
         labels (np.argmax of the logits))."""
-        x = self._dev(x, torch.float32)
+        x = self._dev(x)
         y = self._dev(labels, torch.int32).reshape(-1)
         if tuple(x.shape) != (self.batch_size, self.num_points, 3) or y.numel() != self.batch_size:
             raise ValueError("train_step takes x (%d, %d, 3) and %d labels; got %s and %d"

@@ -34,9 +34,6 @@
 // Adam (torch.optim.Adam, lr, betas .9 / .999, eps 1e-8, no weight decay): m += (g - m) * 0.1; v = 0.999 v + 0.001 g g;
 // p -= lr / (1 - 0.9^t) * m / (sqrt(v) / sqrt(1 - 0.999^t) + eps), t = steps this optimizer has taken including this one.
 #include "train_bn.h"
-#include <math.h>
-#include <string.h>
-#include <vector>
 
 namespace geoadv {
 
@@ -265,33 +262,31 @@ using namespace geoadv;
 namespace {
 // layers: the encoder's conv1, conv2, conv3, lin1, lin2, then the decoder's conv1, conv2, conv_list[0 .. L), last_conv
 enum { E1 = 0, E2, E3, L1, L2, D0, D1, MAXL = 12 };
+static_assert(MAXL <= TA_MAXL && GEOADV_ATLAS_STATE_BN_MEAN == TA_BAT_MEAN && GEOADV_ATLAS_STATE_BN_VAR == TA_BAT_VAR &&
+              GEOADV_ATLAS_STATE_RUNNING_MEAN == TA_RUN_MEAN && GEOADV_ATLAS_STATE_RUNNING_VAR == TA_RUN_VAR &&
+              GEOADV_ATLAS_STATE_BN_INV == TA_INV && GEOADV_ATLAS_STATE_BN_SHIFT == TA_SHIFT,
+              "geoadv_atlas_trainer_state passes these to TrainArena::view as they are");
 }  // namespace
 
-struct geoadv_atlas_trainer {
-    int B, n, R, nb, p, Rp, rows, m, L, dbn, NL;      // Rp = B * p rows per primitive, rows = nb * Rp, m = nb * p
-    int kin[MAXL], kout[MAXL], grp[MAXL];             // grp = 1 (encoder) or nb
+struct geoadv_atlas_trainer : TrainArena {            // a layer's groups: 1 (encoder) or nb
+    int B, n, R, nb, p, Rp, rows, m, L, dbn;          // Rp = B * p rows per primitive, rows = nb * Rp, m = nb * p
     float lr;
     long long step, tracked;
     unsigned long long seed;
-    size_t o_w[MAXL], o_b[MAXL], o_g[MAXL], o_be[MAXL], o_mv[MAXL], P, MV, MVbn;     // MVbn: the part of the BN arenas with a real norm
-    std::vector<void *> allocs;
-    float *params, *grads, *slot1, *slot2;
-    float *run_mean, *run_var, *bat_mean, *bat_var, *inv, *shift, *m1, *m2, *unbias;
     float *a[MAXL], *h[MAXL], *pooled, *t1, *dt1, *tmpl, *prim, *recon, *dprim, *drecon, *dx;
     int *arg, *i1, *i2;
     float *d1, *d2, *gd1, *gd2, *loss;
     float *Y, *Z, *T, *dz, *dsm1, *dsm2, *partials;
     double *dzq;
     double2 *part;
-    bool bn_of(int l) const { return l < D0 || (dbn && l < NL - 1); }
+    bool bn_of(int l) const { return layer[l].bn; }
 };
 
 namespace {
-struct Run : Launch {
+struct Run : TrainRun {
     geoadv_atlas_trainer *t;
 
-    float *W(int l) { return t->params + t->o_w[l]; }
-    int rows(int l) const { return l <= E3 ? t->R : l <= L2 ? t->B : t->Rp; }      // per group
+    int rows(int l) const { return t->layer[l].rows; }                             // per group
 
     // Batched over the layer's groups: C[z] = A[z] (M x K, strides) B[z] (K x N, strides) + bias[z].  The 128-tile kernel where
     // its grid fills the device, else ct_launch_gemm (split-K) -- which has one bias for all groups, so only without one.
@@ -305,16 +300,11 @@ struct Run : Launch {
     }
     // out[g] = in[g] @ W_l[g] + b_l[g]
     void linear_fwd(int l, const float *in, float *out) {
-        const int M = rows(l), K = t->kin[l], N = t->kout[l], G = t->grp[l];
+        const int M = rows(l), K = t->kin(l), N = t->kout(l), G = t->groups(l);
         gemm(in, K, 1, (long long)M * K, W(l), N, 1, (long long)K * N, out, N, (long long)M * N, t->params + t->o_b[l], N, M, N, K, G);
     }
-    void batch_stats(int l) {
-        const size_t o = t->o_mv[l];
-        bn_batch_stats(t->a[l], rows(l), t->kout[l], t->grp[l], t->part, t->params + t->o_g[l], t->params + t->o_be[l], AT_EPS, t->bat_mean + o,
-                       t->bat_var + o, t->inv + o, t->shift + o);
-    }
     void bn_relu(int l, float *y) {
-        const int Rg = rows(l), C = t->kout[l], G = t->grp[l];
+        const int Rg = rows(l), C = t->kout(l), G = t->groups(l);
         const size_t total = (size_t)G * Rg * C, o = t->o_mv[l];
         if (l == D0)
             launch(tb_bn_relu_kernel<true>, dim3(blocks_of(total)), dim3(256), t->t1, t->h[L2], total, Rg, C, t->p, t->inv + o, t->shift + o, y);
@@ -323,20 +313,19 @@ struct Run : Launch {
     }
     void bn_layer(int l, const float *in, float *y) {
         linear_fwd(l, in, t->a[l]);
-        if (t->bn_of(l)) batch_stats(l);
+        if (t->bn_of(l)) batch_stats(l, t->a[l]);
         if (y) bn_relu(l, y);
     }
 
     // ---- backward pieces ----
     // dW_l[g] = in[g]^T da[g]
     void weight_grad(int l, const float *in, const float *da) {
-        const int M = rows(l), K = t->kin[l], N = t->kout[l], G = t->grp[l];
+        const int M = rows(l), K = t->kin(l), N = t->kout(l), G = t->groups(l);
         gemm(in, 1, K, (long long)M * K, da, N, 1, (long long)M * N, t->grads + t->o_w[l], N, (long long)K * N, nullptr, 0, K, N, M, G);
     }
-    void bias_grad(int l, const float *da) { bias_colsum(da, rows(l), t->kout[l], t->grp[l], t->part, t->grads + t->o_b[l]); }
     // din[g] = da[g] W_l[g]^T
     void input_grad(int l, const float *da, float *din) {
-        const int M = rows(l), K = t->kin[l], N = t->kout[l], G = t->grp[l];
+        const int M = rows(l), K = t->kin(l), N = t->kout(l), G = t->groups(l);
         gemm(da, N, 1, (long long)M * N, W(l), 1, N, (long long)K * N, din, K, (long long)M * K, nullptr, 0, M, K, N, G);
     }
     void linear_bwd(int l, const float *in, const float *da, float *din) {
@@ -346,7 +335,7 @@ struct Run : Launch {
     }
     // BN + ReLU backward of layer l, dense dy -> da (may alias dy).  The decoder's first layer rebuilds its activation.
     void bn_bwd(int l, const float *dy, float *da) {
-        const int Rg = rows(l), C = t->kout[l], G = t->grp[l], p = t->p;
+        const int Rg = rows(l), C = t->kout(l), G = t->groups(l), p = t->p;
         const size_t o = t->o_mv[l], total = (size_t)G * Rg * C;
         const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o, *gam = t->params + t->o_g[l];
         float *dgam = t->grads + t->o_g[l], *dbeta = t->grads + t->o_be[l];
@@ -383,8 +372,8 @@ struct Run : Launch {
 };
 
 int run_step(geoadv_atlas_trainer *t, const float *x, hipStream_t st) {
-    Run q{{st}, t};
-    const int B = t->B, nb = t->nb, p = t->p, NL = t->NL, LAST = NL - 1;
+    Run q{{{st}, t, AT_EPS, t->part, t->partials}, t};
+    const int B = t->B, nb = t->nb, p = t->p, NL = t->nl, LAST = NL - 1;
     const dim3 blk(256);
     // ---- forward: encoder ----
     q.bn_layer(E1, x, t->h[E1]);
@@ -440,15 +429,7 @@ int run_step(geoadv_atlas_trainer *t, const float *x, hipStream_t st) {
         return GEOADV_EHIP;
     }
     // ---- optimizer, running statistics, counters ----
-    const double ts = (double)(t->step + 1);
-    const float bc1 = (float)(1.0 - pow(0.9, ts)), bc2s = (float)sqrt(1.0 - pow(0.999, ts));
-    hipLaunchKernelGGL(tb_adam_kernel<false>, dim3(blocks_of(t->P)), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, t->lr, 0.f, bc1,
-                       bc2s);
-    GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MVbn)), dim3(256), 0, st, t->run_mean, t->bat_mean, (const float *)nullptr, t->MVbn);
-    GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MVbn)), dim3(256), 0, st, t->run_var, t->bat_var, t->unbias, t->MVbn);
-    GA_LAUNCH_CHECK();
+    if (int rc = q.adam_and_running<false>(t->lr, 0.f, t->step)) return rc;
     t->step += 1;
     t->tracked += 1;
     return GEOADV_OK;
@@ -491,41 +472,28 @@ extern "C" int geoadv_atlas_trainer_create(geoadv_atlas_trainer **out, const geo
     }
     geoadv_atlas_trainer *t = new geoadv_atlas_trainer();
     t->B = cfg->batch; t->n = cfg->n_points; t->R = t->B * t->n; t->nb = config->nb_primitives; t->p = cfg->points_per_primitive;
-    t->Rp = t->B * t->p; t->rows = t->nb * t->Rp; t->m = t->nb * t->p; t->L = L; t->dbn = dbn; t->NL = NL;
+    t->Rp = t->B * t->p; t->rows = t->nb * t->Rp; t->m = t->nb * t->p; t->L = L; t->dbn = dbn;
     t->lr = cfg->learning_rate; t->step = cfg->initial_step; t->tracked = cfg->initial_tracked;
     t->seed = (unsigned long long)cfg->seed;
     const int ein[5] = {3, 64, 128, AT_LAT, AT_LAT}, eout[5] = {64, 128, AT_LAT, AT_LAT, AT_LAT};
-    for (int l = 0; l < NL; ++l) {
-        if (l < D0) { t->kin[l] = ein[l]; t->kout[l] = eout[l]; t->grp[l] = 1; continue; }
-        t->grp[l] = t->nb;
-        t->kin[l] = l == D0 ? 2 : l == D1 ? AT_LAT : AT_HID;
-        t->kout[l] = l == D0 ? AT_LAT : l == NL - 1 ? 3 : AT_HID;
+    TrainLayer table[MAXL];
+    TrainInit in{};
+    for (int l = 0; l < NL; ++l) {        // every layer but the last has a slot in the batch-norm arenas: identity constants without a norm
+        const int d = l - D0;
+        const bool slot = l < NL - 1;
+        if (l < D0) table[l] = {ein[l], eout[l], 1, l <= E3 ? t->R : t->B, true, slot};
+        else table[l] = {l == D0 ? 2 : l == D1 ? AT_LAT : AT_HID, l == D0 ? AT_LAT : slot ? AT_HID : 3, t->nb, t->Rp, dbn && slot, slot};
+        in.w[l] = l < D0 ? init->enc_w[l] : init->dec_w[d]; in.b[l] = l < D0 ? init->enc_b[l] : init->dec_b[d];
+        in.gamma[l] = l < D0 ? init->enc_gamma[l] : init->dec_gamma[d]; in.beta[l] = l < D0 ? init->enc_beta[l] : init->dec_beta[d];
+        in.mean[l] = l < D0 ? init->enc_mean[l] : init->dec_mean[d]; in.var[l] = l < D0 ? init->enc_var[l] : init->dec_var[d];
     }
-    size_t P = 0, MV = 0;
-    auto rup16 = [](size_t v) { return (v + 15) / 16 * 16; };
-    for (int l = 0; l < NL; ++l) {
-        const size_t G = t->grp[l];
-        t->o_w[l] = P; P = rup16(P + G * t->kin[l] * t->kout[l]);
-        t->o_b[l] = P; P = rup16(P + G * t->kout[l]);
-        t->o_g[l] = t->o_be[l] = 0;
-        if (t->bn_of(l)) {
-            t->o_g[l] = P; P = rup16(P + G * t->kout[l]);
-            t->o_be[l] = P; P = rup16(P + G * t->kout[l]);
-        }
-        t->o_mv[l] = MV;                                                  // identity constants where there is no norm
-        if (l < NL - 1) MV = rup16(MV + G * t->kout[l]);
-        if (t->bn_of(l)) t->MVbn = MV;
-    }
-    t->P = P; t->MV = MV;
+    t->lay_out(table, NL);
     const size_t R = t->R, B = t->B, rows = t->rows, nb = t->nb, p = t->p;
     hipError_t e = hipSuccess;
     std::vector<void *> &mem = t->allocs;
-    t->params = dev_alloc<float>(mem, P, e); t->grads = dev_alloc<float>(mem, P, e);
-    t->slot1 = dev_alloc<float>(mem, P, e); t->slot2 = dev_alloc<float>(mem, P, e);
-    for (float **pp : {&t->run_mean, &t->run_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2, &t->unbias})
-        *pp = dev_alloc<float>(mem, MV, e);
+    t->alloc(true, e);
     for (int l = 0; l < NL - 1; ++l) {
-        const size_t count = (l <= E3 ? R : l <= L2 ? B : rows) * t->kout[l];
+        const size_t count = (l <= E3 ? R : l <= L2 ? B : rows) * t->kout(l);
         t->a[l] = l == D0 ? nullptr : dev_alloc<float>(mem, count, e);
         t->h[l] = l == E3 ? nullptr : dev_alloc<float>(mem, count, e);
     }
@@ -544,48 +512,22 @@ extern "C" int geoadv_atlas_trainer_create(geoadv_atlas_trainer **out, const geo
     t->dzq = dev_alloc<double>(mem, nb * B * AT_LAT, e);
     t->partials = dev_alloc<float>(mem, CT_PARTIAL_FLOATS, e);
     t->part = dev_alloc<double2>(mem, std::max((size_t)cdiv((int)R, 256), nb * cdiv(t->Rp, 256)) * AT_LAT + 1024, e);
-    if (e == hipSuccess) {
-        std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f), hu(MV, 1.f), hi(MV, 1.f), g1(R, 1.f / (float)R), g2(rows, 1.f / (float)rows);
-        for (int l = 0; l < NL; ++l) {
-            const bool enc = l < D0;
-            const int d = l - D0;
-            const size_t G = t->grp[l], C = t->kout[l];
-            memcpy(&hp[t->o_w[l]], enc ? init->enc_w[l] : init->dec_w[d], sizeof(float) * G * t->kin[l] * C);
-            memcpy(&hp[t->o_b[l]], enc ? init->enc_b[l] : init->dec_b[d], sizeof(float) * G * C);
-            if (!t->bn_of(l)) continue;
-            memcpy(&hp[t->o_g[l]], enc ? init->enc_gamma[l] : init->dec_gamma[d], sizeof(float) * G * C);
-            memcpy(&hp[t->o_be[l]], enc ? init->enc_beta[l] : init->dec_beta[d], sizeof(float) * G * C);
-            memcpy(&hm[t->o_mv[l]], enc ? init->enc_mean[l] : init->dec_mean[d], sizeof(float) * G * C);
-            memcpy(&hv[t->o_mv[l]], enc ? init->enc_var[l] : init->dec_var[d], sizeof(float) * G * C);
-            const double rl = l <= E3 ? (double)R : l <= L2 ? (double)B : (double)t->Rp;
-            for (size_t c = 0; c < G * C; ++c) hu[t->o_mv[l] + c] = (float)(rl / (rl - 1.0));
-        }
-        auto up = [&](float *dst, const std::vector<float> &src) {
-            if (e == hipSuccess) e = hipMemcpy(dst, src.data(), sizeof(float) * src.size(), hipMemcpyHostToDevice);
-        };
-        up(t->params, hp); up(t->run_mean, hm); up(t->run_var, hv); up(t->unbias, hu); up(t->inv, hi); up(t->gd1, g1); up(t->gd2, g2);
-    }
+    t->upload(in, e);
+    dev_upload(t->gd1, std::vector<float>(R, 1.f / (float)R), e);
+    dev_upload(t->gd2, std::vector<float>(rows, 1.f / (float)rows), e);
     if (e != hipSuccess) {
-        dev_free_all(t->allocs);
         delete t;
-        set_error("atlas_trainer_create: %s", hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
+        return train_create_error("atlas_trainer_create", e);
     }
     *out = t;
     return GEOADV_OK;
 }
 
-extern "C" void geoadv_atlas_trainer_destroy(geoadv_atlas_trainer *t) {
-    if (!t) return;
-    dev_free_all(t->allocs);
-    delete t;
-}
+extern "C" void geoadv_atlas_trainer_destroy(geoadv_atlas_trainer *t) { delete t; }
 
 extern "C" int geoadv_atlas_trainer_set_slots(geoadv_atlas_trainer *t, const float *slot1, const float *slot2) {
     GA_REQUIRE(t, "atlas_trainer_set_slots: null handle");
-    if (slot1) GA_HIP(hipMemcpy(t->slot1, slot1, sizeof(float) * t->P, hipMemcpyHostToDevice));
-    if (slot2) GA_HIP(hipMemcpy(t->slot2, slot2, sizeof(float) * t->P, hipMemcpyHostToDevice));
-    return GEOADV_OK;
+    return t->set_slots(slot1, slot2);
 }
 
 extern "C" int geoadv_atlas_trainer_set_learning_rate(geoadv_atlas_trainer *t, float learning_rate, int reset_optimizer) {
@@ -623,22 +565,13 @@ extern "C" int geoadv_atlas_trainer_step(geoadv_atlas_trainer *t, const float *x
 
 extern "C" int geoadv_atlas_trainer_buffers(geoadv_atlas_trainer *t, float **params, float **grads, size_t *count) {
     GA_REQUIRE(t, "atlas_trainer_buffers: null handle");
-    if (params) *params = t->params;
-    if (grads) *grads = t->grads;
-    if (count) *count = t->P;
+    t->buffers(params, grads, count);
     return GEOADV_OK;
 }
 
 extern "C" int geoadv_atlas_trainer_layout(const geoadv_atlas_trainer *t, size_t *offsets48, size_t *moving_offsets12) {
     GA_REQUIRE(t && offsets48, "atlas_trainer_layout: null argument");
-    for (int l = 0; l < MAXL; ++l) {
-        const bool have = l < t->NL, bn = have && t->bn_of(l);
-        offsets48[4 * l] = have ? t->o_w[l] : (size_t)-1;
-        offsets48[4 * l + 1] = have ? t->o_b[l] : (size_t)-1;
-        offsets48[4 * l + 2] = bn ? t->o_g[l] : (size_t)-1;
-        offsets48[4 * l + 3] = bn ? t->o_be[l] : (size_t)-1;
-        if (moving_offsets12) moving_offsets12[l] = bn ? t->o_mv[l] : (size_t)-1;
-    }
+    t->export_layout(offsets48, moving_offsets12, MAXL);
     return GEOADV_OK;
 }
 
@@ -656,17 +589,14 @@ extern "C" int geoadv_atlas_trainer_state(const geoadv_atlas_trainer *t, int wha
     case GEOADV_ATLAS_STATE_BN_MEAN: case GEOADV_ATLAS_STATE_BN_VAR: case GEOADV_ATLAS_STATE_RUNNING_MEAN: case GEOADV_ATLAS_STATE_RUNNING_VAR:
     case GEOADV_ATLAS_STATE_BN_INV: case GEOADV_ATLAS_STATE_BN_SHIFT: {
         const bool folded = what == GEOADV_ATLAS_STATE_BN_INV || what == GEOADV_ATLAS_STATE_BN_SHIFT;
-        GA_REQUIRE(layer >= 0 && layer < t->NL - 1 && (folded || t->bn_of(layer)), "atlas_trainer_state: layer %d has no batch norm", layer);
-        const float *base = what == GEOADV_ATLAS_STATE_BN_MEAN ? t->bat_mean : what == GEOADV_ATLAS_STATE_BN_VAR ? t->bat_var
-                          : what == GEOADV_ATLAS_STATE_RUNNING_MEAN ? t->run_mean : what == GEOADV_ATLAS_STATE_RUNNING_VAR ? t->run_var
-                          : what == GEOADV_ATLAS_STATE_BN_INV ? t->inv : t->shift;
-        *ptr = base + t->o_mv[layer]; *count = (size_t)t->grp[layer] * t->kout[layer];
+        GA_REQUIRE(layer >= 0 && layer < t->nl - 1 && (folded || t->bn_of(layer)), "atlas_trainer_state: layer %d has no batch norm", layer);
+        t->view(what, layer, ptr, count);
         return GEOADV_OK;
     }
     case GEOADV_ATLAS_STATE_PRE_BN:
-        GA_REQUIRE(layer >= 0 && layer < t->NL - 1, "atlas_trainer_state: layer %d has no stored activation", layer);
+        GA_REQUIRE(layer >= 0 && layer < t->nl - 1, "atlas_trainer_state: layer %d has no stored activation", layer);
         if (layer == D0) { *ptr = t->t1; *count = (size_t)t->nb * t->p * AT_LAT; return GEOADV_OK; }
-        *ptr = t->a[layer]; *count = (layer <= E3 ? R : layer <= L2 ? B : rows) * t->kout[layer];
+        *ptr = t->a[layer]; *count = (layer <= E3 ? R : layer <= L2 ? B : rows) * t->kout(layer);
         return GEOADV_OK;
     case GEOADV_ATLAS_STATE_CHAMFER_IDX:
         GA_REQUIRE(layer == 0 || layer == 1, "atlas_trainer_state: Chamfer direction %d must be 0 or 1", layer);
@@ -676,8 +606,8 @@ extern "C" int geoadv_atlas_trainer_state(const geoadv_atlas_trainer *t, int wha
     case GEOADV_ATLAS_STATE_TEMPLATE: *ptr = t->tmpl; *count = (size_t)t->nb * t->p * 2; return GEOADV_OK;
     case GEOADV_ATLAS_STATE_LATENT: *ptr = t->h[L2]; *count = B * AT_LAT; return GEOADV_OK;
     case GEOADV_ATLAS_STATE_RECON: *ptr = t->recon; *count = rows * 3; return GEOADV_OK;
-    case GEOADV_ATLAS_STATE_SLOT1: *ptr = t->slot1; *count = t->P; return GEOADV_OK;
-    case GEOADV_ATLAS_STATE_SLOT2: *ptr = t->slot2; *count = t->P; return GEOADV_OK;
+    case GEOADV_ATLAS_STATE_SLOT1: t->view(TA_SLOT1, 0, ptr, count); return GEOADV_OK;
+    case GEOADV_ATLAS_STATE_SLOT2: t->view(TA_SLOT2, 0, ptr, count); return GEOADV_OK;
     default: break;
     }
     set_error("atlas_trainer_state: unknown state %d", what);

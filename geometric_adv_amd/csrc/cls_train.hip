@@ -30,9 +30,6 @@
 // Moving statistics: ExponentialMovingAverage(bn_decay) of the moments tensors (zero slots, zero_debias = False):
 // shadow -= (shadow - batch_stat) * (1 - bn_decay).
 #include "train_bn.h"
-#include <math.h>
-#include <string.h>
-#include <vector>
 
 namespace geoadv {
 
@@ -254,20 +251,17 @@ const int kOut[NL] = {64, 128, 1024, 512, 256, 9, 64, 64, 64, 128, 1024, 512, 25
 bool bn_of(int l) { return l != T1XYZ && l != T2FEAT && l != F3; }
 bool per_point(int l) { return l <= T1C3 || (l >= C1 && l <= T2C3) || (l >= C3 && l <= C5); }
 bool pooled_layer(int l) { return l == T1C3 || l == T2C3 || l == C5; }
+static_assert(NL <= TA_MAXL && GEOADV_CLS_STATE_BN_MEAN == TA_BAT_MEAN && GEOADV_CLS_STATE_BN_VAR == TA_BAT_VAR &&
+              GEOADV_CLS_STATE_MOVING_MEAN == TA_RUN_MEAN && GEOADV_CLS_STATE_MOVING_VAR == TA_RUN_VAR,
+              "geoadv_cls_trainer_state passes these to TrainArena::view as they are");
 }  // namespace
 
-struct geoadv_cls_trainer {
+struct geoadv_cls_trainer : TrainArena {           // run_mean / run_var: the moving averages
     int B, n, R, C, optimizer;
     float base_lr, momentum, decay_rate;
     long long decay_step, step;
     unsigned long long seed;
     float b1p, b2p;
-    int out[NL];
-    size_t o_w[NL], o_b[NL], o_g[NL], o_be[NL], o_mv[NL], P, MV;
-    std::vector<void *> allocs;
-    float *params, *grads, *slot1, *slot2;        // slot1 = Adam m / Momentum accum, slot2 = Adam v
-    float *mov_mean, *mov_var, *bat_mean, *bat_var;  // flat over the BN layers (offsets o_mv)
-    float *inv, *shift, *m1, *m2;                 // flat, offsets o_mv
     float *a[NL], *h[NL];                         // pre-BN outputs; post-BN(-ReLU(-dropout)) outputs of stored layers
     float *u, *v, *t1, *t2, *E, *pooled[3], *mask[2], *logits, *dlogits, *loss;
     int *arg[3], *labels, *pred;
@@ -278,11 +272,10 @@ struct geoadv_cls_trainer {
 };
 
 namespace {
-struct Run : Launch {
+struct Run : TrainRun {
     geoadv_cls_trainer *t;
 
-    // C = alpha * A B (+ bias) (+ C)
-    void gemm(const GemmArgs &g) { Launch::gemm(g, t->partials); }
+    // C = A B
     static GemmArgs plain(const float *A, const float *B, float *C, int M, int N, int K) {
         GemmArgs g{};
         g.A = A; g.sAi = K; g.sAk = 1;
@@ -291,39 +284,27 @@ struct Run : Launch {
         g.alpha = 1.f; g.M = M; g.N = N; g.K = K; g.batch = 1;
         return g;
     }
-    int rows(int l) const { return per_point(l) ? t->R : t->B; }
-    float *W(int l) { return t->params + t->o_w[l]; }
-
+    int rows(int l) const { return t->layer[l].rows; }
     // a_l = in @ W_l + b_l
-    void linear_fwd(int l, const float *in, float *outp) {
-        GemmArgs g = plain(in, W(l), outp, rows(l), t->out[l], kIn[l]);
-        g.bias = t->params + t->o_b[l];
-        gemm(g);
-    }
-    void batch_stats(int l) {
-        const size_t o = t->o_mv[l];
-        bn_batch_stats(t->a[l], rows(l), t->out[l], 1, t->part, t->params + t->o_g[l], t->params + t->o_be[l], CT_EPS, t->bat_mean + o,
-                       t->bat_var + o, t->inv + o, t->shift + o);
-    }
+    void linear_fwd(int l, const float *in, float *outp) { gemm(fwd_args(l, in, outp, rows(l), 0, kIn[l], true)); }
+    void batch_stats(int l) { TrainRun::batch_stats(l, t->a[l]); }
     // BN + ReLU (+ dropout) of a stored layer
     void bn_fwd(int l, int drop) {
-        const int R = rows(l), C = t->out[l];
+        const int R = rows(l), C = t->kout(l);
         const size_t o = t->o_mv[l];
         launch(ct_bn_fwd_kernel, dim3(blocks_of((size_t)R * C)), dim3(256), t->a[l], R, C, t->inv + o, t->shift + o, t->h[l], drop, t->seed, t->step,
                drop >= 0 ? t->mask[drop] : nullptr);
     }
     void pool(int l, int which) {
         const size_t o = t->o_mv[l];
-        launch(ct_pool_kernel, dim3(cdiv(t->out[l], 64), t->B), dim3(256), t->a[l], t->n, t->out[l], t->inv + o, t->shift + o, t->pooled[which],
+        launch(ct_pool_kernel, dim3(cdiv(t->kout(l), 64), t->B), dim3(256), t->a[l], t->n, t->kout(l), t->inv + o, t->shift + o, t->pooled[which],
                t->arg[which]);
     }
     void layer(int l, const float *in) { linear_fwd(l, in, t->a[l]); batch_stats(l); bn_fwd(l, l == F1 ? 0 : l == F2 ? 1 : -1); }
 
-    // d bias = column sums of da over the layer's rows
-    void bias_grad(int l, const float *da) { bias_colsum(da, rows(l), t->out[l], 1, t->part, t->grads + t->o_b[l]); }
     // BN backward of layer l: mode 0 dense, 1 dense through dropout mask `drop`, 2 pool `which` (dy = dpool [B][C]).
     void bn_bwd(int l, int mode, const float *dy, int aux, float *da) {
-        const int R = rows(l), C = t->out[l];
+        const int R = rows(l), C = t->kout(l);
         const size_t o = t->o_mv[l];
         const float *mean = t->bat_mean + o, *var = t->bat_var + o, *iv = t->inv + o, *sh = t->shift + o, *gam = t->params + t->o_g[l];
         const int rpc = rpc_of(R), chunks = mode == 2 ? 1 : cdiv(R, rpc);
@@ -348,28 +329,15 @@ struct Run : Launch {
     }
     // dW_l = in^T da, db_l = sum da, din (=|+=) da W_l^T
     void linear_bwd(int l, const float *in, const float *da, float *din, int accumulate) {
-        const int R = rows(l), K = kIn[l], N = t->out[l];
-        GemmArgs g{};
-        g.A = in; g.sAi = 1; g.sAk = K;             // A(i = input channel, k = row) = in[row][i]
-        g.B = da; g.sBk = N; g.sBj = 1;
-        g.C = t->grads + t->o_w[l]; g.ldc = N;
-        g.alpha = 1.f; g.M = K; g.N = N; g.K = R; g.batch = 1;
-        gemm(g);
+        gemm(wgrad_args(l, in, da, rows(l), 0, kIn[l]));
         bias_grad(l, da);
-        if (din) {
-            GemmArgs d{};
-            d.A = da; d.sAi = N; d.sAk = 1;
-            d.B = W(l); d.sBk = 1; d.sBj = N;        // B(k = output channel, j = input channel) = W[j][k]
-            d.C = din; d.ldc = K;
-            d.alpha = 1.f; d.M = R; d.N = K; d.K = N; d.batch = 1; d.accumulate = accumulate;
-            gemm(d);
-        }
+        if (din) gemm(igrad_args(l, da, din, rows(l), 0, kIn[l], accumulate));
     }
     void add_eye(float *p, int kk) { launch(ct_add_eye_kernel, dim3(cdiv(t->B * kk, 256)), dim3(256), p, t->B, kk); }
 };
 
 int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipStream_t st) {
-    Run q{{st}, t};
+    Run q{{{st}, t, CT_EPS, t->part, t->partials}, t};
     const int B = t->B, n = t->n, R = t->R, NC = t->C;
     // ---- forward ----
     q.layer(T1C1, x);
@@ -494,9 +462,9 @@ int run_step(geoadv_cls_trainer *t, const float *x, const int *labels_dev, hipSt
         hipLaunchKernelGGL(ct_momentum_kernel, dim3(pg), dim3(256), 0, st, t->params, t->slot1, t->grads, t->P, lr, t->momentum);
     GA_LAUNCH_CHECK();
     const unsigned mg = blocks_of(t->MV);
-    hipLaunchKernelGGL(ct_ema_kernel, dim3(mg), dim3(256), 0, st, t->mov_mean, t->bat_mean, t->MV, 1.f - bn_decay);
+    hipLaunchKernelGGL(ct_ema_kernel, dim3(mg), dim3(256), 0, st, t->run_mean, t->bat_mean, t->MV, 1.f - bn_decay);
     GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ct_ema_kernel, dim3(mg), dim3(256), 0, st, t->mov_var, t->bat_var, t->MV, 1.f - bn_decay);
+    hipLaunchKernelGGL(ct_ema_kernel, dim3(mg), dim3(256), 0, st, t->run_var, t->bat_var, t->MV, 1.f - bn_decay);
     GA_LAUNCH_CHECK();
     if (t->optimizer == GEOADV_CLS_OPT_ADAM) { t->b1p = t->b1p * 0.9f; t->b2p = t->b2p * 0.999f; }
     t->step += 1;
@@ -525,31 +493,23 @@ extern "C" int geoadv_cls_trainer_create(geoadv_cls_trainer **out, const geoadv_
     t->decay_step = cfg->decay_step; t->decay_rate = cfg->decay_rate; t->step = cfg->initial_step;
     t->seed = (unsigned long long)(unsigned)cfg->dropout_seed;
     t->b1p = 0.9f; t->b2p = 0.999f;
-    size_t P = 0, MV = 0;
-    auto rup = [](size_t v) { return (v + 15) / 16 * 16; };
+    TrainLayer table[NL];
+    TrainInit in{};
     for (int l = 0; l < NL; ++l) {
-        t->out[l] = l == F3 ? NC : kOut[l];
-        t->o_w[l] = P; P = rup(P + (size_t)kIn[l] * t->out[l]);
-        t->o_b[l] = P; P = rup(P + t->out[l]);
-        t->o_g[l] = t->o_be[l] = t->o_mv[l] = 0;
-        if (bn_of(l)) {
-            t->o_g[l] = P; P = rup(P + t->out[l]);
-            t->o_be[l] = P; P = rup(P + t->out[l]);
-            t->o_mv[l] = MV; MV = rup(MV + t->out[l]);
-        }
+        table[l] = {kIn[l], l == F3 ? NC : kOut[l], 1, per_point(l) ? t->R : t->B, bn_of(l), false};
+        in.w[l] = init->w[l]; in.b[l] = init->b[l]; in.gamma[l] = init->gamma[l];
+        in.beta[l] = init->beta[l]; in.mean[l] = init->mean[l]; in.var[l] = init->var[l];
     }
-    t->P = P; t->MV = MV;
+    t->lay_out(table, NL);
     const size_t R = t->R, B = t->B;
     hipError_t e = hipSuccess;
     std::vector<void *> &mem = t->allocs;
-    t->params = dev_alloc<float>(mem, P, e); t->grads = dev_alloc<float>(mem, P, e);
-    t->slot1 = dev_alloc<float>(mem, P, e); t->slot2 = dev_alloc<float>(mem, P, e);
-    for (float **p : {&t->mov_mean, &t->mov_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2}) *p = dev_alloc<float>(mem, MV, e);
+    t->alloc(false, e);
     for (int l = 0; l < NL; ++l) {
         t->a[l] = t->h[l] = nullptr;
         if (!bn_of(l)) continue;
-        t->a[l] = dev_alloc<float>(mem, (per_point(l) ? R : B) * t->out[l], e);
-        if (!pooled_layer(l)) t->h[l] = dev_alloc<float>(mem, (per_point(l) ? R : B) * t->out[l], e);
+        t->a[l] = dev_alloc<float>(mem, (per_point(l) ? R : B) * t->kout(l), e);
+        if (!pooled_layer(l)) t->h[l] = dev_alloc<float>(mem, (per_point(l) ? R : B) * t->kout(l), e);
     }
     t->u = dev_alloc<float>(mem, R * 3, e); t->v = dev_alloc<float>(mem, R * 64, e);
     t->t1 = dev_alloc<float>(mem, B * 9, e); t->t2 = dev_alloc<float>(mem, B * 4096, e); t->E = dev_alloc<float>(mem, B * 4096, e);
@@ -565,42 +525,21 @@ extern "C" int geoadv_cls_trainer_create(geoadv_cls_trainer **out, const geoadv_
     t->partials = dev_alloc<float>(mem, CT_PARTIAL_FLOATS, e);
     t->part = dev_alloc<double2>(mem, std::max((size_t)cdiv((int)R, 256) * 1024, (size_t)cdiv((int)B, 256) * 4096) + 1024, e);
     t->reg_cloud = dev_alloc<double>(mem, B, e); t->ce_cloud = dev_alloc<double>(mem, B, e);
-    if (e == hipSuccess) {
-        std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f);
-        for (int l = 0; l < NL; ++l) {
-            memcpy(&hp[t->o_w[l]], init->w[l], sizeof(float) * kIn[l] * t->out[l]);
-            memcpy(&hp[t->o_b[l]], init->b[l], sizeof(float) * t->out[l]);
-            if (!bn_of(l)) continue;
-            memcpy(&hp[t->o_g[l]], init->gamma[l], sizeof(float) * t->out[l]);
-            memcpy(&hp[t->o_be[l]], init->beta[l], sizeof(float) * t->out[l]);
-            memcpy(&hm[t->o_mv[l]], init->mean[l], sizeof(float) * t->out[l]);
-            memcpy(&hv[t->o_mv[l]], init->var[l], sizeof(float) * t->out[l]);
-        }
-        e = hipMemcpy(t->params, hp.data(), sizeof(float) * P, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(t->mov_mean, hm.data(), sizeof(float) * MV, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(t->mov_var, hv.data(), sizeof(float) * MV, hipMemcpyHostToDevice);
-    }
+    t->upload(in, e);
     if (e != hipSuccess) {
-        dev_free_all(t->allocs);
         delete t;
-        set_error("cls_trainer_create: %s", hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
+        return train_create_error("cls_trainer_create", e);
     }
     *out = t;
     return GEOADV_OK;
 }
 
-extern "C" void geoadv_cls_trainer_destroy(geoadv_cls_trainer *t) {
-    if (!t) return;
-    dev_free_all(t->allocs);
-    delete t;
-}
+extern "C" void geoadv_cls_trainer_destroy(geoadv_cls_trainer *t) { delete t; }
 
 extern "C" int geoadv_cls_trainer_set_slots(geoadv_cls_trainer *t, const float *slot1, const float *slot2, float beta1_power,
                                             float beta2_power) {
     GA_REQUIRE(t, "cls_trainer_set_slots: null handle");
-    if (slot1) GA_HIP(hipMemcpy(t->slot1, slot1, sizeof(float) * t->P, hipMemcpyHostToDevice));
-    if (slot2) GA_HIP(hipMemcpy(t->slot2, slot2, sizeof(float) * t->P, hipMemcpyHostToDevice));
+    if (int rc = t->set_slots(slot1, slot2)) return rc;
     t->b1p = beta1_power;
     t->b2p = beta2_power;
     return GEOADV_OK;
@@ -618,21 +557,13 @@ extern "C" int geoadv_cls_trainer_step(geoadv_cls_trainer *t, const float *x, co
 
 extern "C" int geoadv_cls_trainer_buffers(geoadv_cls_trainer *t, float **params, float **grads, size_t *count) {
     GA_REQUIRE(t, "cls_trainer_buffers: null handle");
-    if (params) *params = t->params;
-    if (grads) *grads = t->grads;
-    if (count) *count = t->P;
+    t->buffers(params, grads, count);
     return GEOADV_OK;
 }
 
 extern "C" int geoadv_cls_trainer_layout(const geoadv_cls_trainer *t, size_t *offsets80, size_t *moving_offsets20) {
     GA_REQUIRE(t && offsets80, "cls_trainer_layout: null argument");
-    for (int l = 0; l < NL; ++l) {
-        offsets80[4 * l] = t->o_w[l];
-        offsets80[4 * l + 1] = t->o_b[l];
-        offsets80[4 * l + 2] = bn_of(l) ? t->o_g[l] : (size_t)-1;
-        offsets80[4 * l + 3] = bn_of(l) ? t->o_be[l] : (size_t)-1;
-        if (moving_offsets20) moving_offsets20[l] = bn_of(l) ? t->o_mv[l] : (size_t)-1;
-    }
+    t->export_layout(offsets80, moving_offsets20, NL);
     return GEOADV_OK;
 }
 
@@ -648,20 +579,14 @@ extern "C" int geoadv_cls_trainer_state(const geoadv_cls_trainer *t, int what, i
     GA_REQUIRE(t && ptr && count, "cls_trainer_state: null argument");
     const size_t B = t->B;
     switch (what) {
-    case GEOADV_CLS_STATE_BN_MEAN: case GEOADV_CLS_STATE_BN_VAR: case GEOADV_CLS_STATE_MOVING_MEAN: case GEOADV_CLS_STATE_MOVING_VAR: {
-        GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "cls_trainer_state: layer %d has no batch norm", layer);
-        const float *base = what == GEOADV_CLS_STATE_BN_MEAN ? t->bat_mean : what == GEOADV_CLS_STATE_BN_VAR ? t->bat_var
-                          : what == GEOADV_CLS_STATE_MOVING_MEAN ? t->mov_mean : t->mov_var;
-        *ptr = base + t->o_mv[layer]; *count = t->out[layer];
-        return GEOADV_OK;
-    }
-    case GEOADV_CLS_STATE_PRE_BN:
-        GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "cls_trainer_state: layer %d has no batch norm", layer);
-        *ptr = t->a[layer]; *count = (size_t)(per_point(layer) ? t->R : t->B) * t->out[layer];
-        return GEOADV_OK;
+    case GEOADV_CLS_STATE_BN_MEAN: case GEOADV_CLS_STATE_BN_VAR: case GEOADV_CLS_STATE_MOVING_MEAN: case GEOADV_CLS_STATE_MOVING_VAR:
     case GEOADV_CLS_STATE_BN_INV: case GEOADV_CLS_STATE_BN_SHIFT:
         GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "cls_trainer_state: layer %d has no batch norm", layer);
-        *ptr = (what == GEOADV_CLS_STATE_BN_INV ? t->inv : t->shift) + t->o_mv[layer]; *count = t->out[layer];
+        t->view(what == GEOADV_CLS_STATE_BN_INV ? TA_INV : what == GEOADV_CLS_STATE_BN_SHIFT ? TA_SHIFT : what, layer, ptr, count);
+        return GEOADV_OK;
+    case GEOADV_CLS_STATE_PRE_BN:
+        GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "cls_trainer_state: layer %d has no batch norm", layer);
+        *ptr = t->a[layer]; *count = (size_t)(per_point(layer) ? t->R : t->B) * t->kout(layer);
         return GEOADV_OK;
     case GEOADV_CLS_STATE_DROPOUT_MASK:
         GA_REQUIRE(layer == 0 || layer == 1, "cls_trainer_state: dropout layer %d must be 0 or 1", layer);
@@ -674,8 +599,8 @@ extern "C" int geoadv_cls_trainer_state(const geoadv_cls_trainer *t, int what, i
     case GEOADV_CLS_STATE_T1: *ptr = t->t1; *count = B * 9; return GEOADV_OK;
     case GEOADV_CLS_STATE_T2: *ptr = t->t2; *count = B * 4096; return GEOADV_OK;
     case GEOADV_CLS_STATE_LOGITS: *ptr = t->logits; *count = B * t->C; return GEOADV_OK;
-    case GEOADV_CLS_STATE_SLOT1: *ptr = t->slot1; *count = t->P; return GEOADV_OK;
-    case GEOADV_CLS_STATE_SLOT2: *ptr = t->slot2; *count = t->P; return GEOADV_OK;
+    case GEOADV_CLS_STATE_SLOT1: t->view(TA_SLOT1, 0, ptr, count); return GEOADV_OK;
+    case GEOADV_CLS_STATE_SLOT2: t->view(TA_SLOT2, 0, ptr, count); return GEOADV_OK;
     default: break;
     }
     set_error("cls_trainer_state: unknown state %d", what);

@@ -31,9 +31,6 @@
 // v = 0.999 v + 0.001 g g; p -= lr / (1 - 0.9^t) * m / (sqrt(v) / sqrt(1 - 0.999^t) + eps), t = steps taken including this.
 #include "train_bn.h"
 #include "fold_graph.h"
-#include <math.h>
-#include <string.h>
-#include <vector>
 
 namespace geoadv {
 
@@ -132,6 +129,10 @@ enum { E1 = 0, E2, E3, E4, E5, F1, F2, D0, D1, D2, D3, D4, D5, NL };
 const int kIn[NL] = {12, 64, 64, 64, 128, FT_LAT, FT_CODE, FT_CODE + 2, 512, 512, FT_CODE + 3, 512, 512};
 const int kOut[NL] = {64, 64, 64, 128, FT_LAT, FT_CODE, FT_CODE, 512, 512, 3, 512, 512, 3};
 bool bn_of(int l) { return l <= F1; }
+static_assert(NL <= TA_MAXL && GEOADV_FOLD_STATE_BN_MEAN == TA_BAT_MEAN && GEOADV_FOLD_STATE_BN_VAR == TA_BAT_VAR &&
+              GEOADV_FOLD_STATE_RUNNING_MEAN == TA_RUN_MEAN && GEOADV_FOLD_STATE_RUNNING_VAR == TA_RUN_VAR &&
+              GEOADV_FOLD_STATE_BN_INV == TA_INV && GEOADV_FOLD_STATE_BN_SHIFT == TA_SHIFT,
+              "geoadv_fold_trainer_state passes these to TrainArena::view as they are");
 
 // The one launch of each pool kernel and of the global maximum: the step (Run) and the geoadv_fold_train_pool / _pool_grad /
 // _gmax entries all go through these.  rows = b * n.
@@ -149,15 +150,11 @@ void ft_launch_gmax(Launch &q, const float *a, int B, int n, int C, const float 
 }
 }  // namespace
 
-struct geoadv_fold_trainer {
+struct geoadv_fold_trainer : TrainArena {
     int B, n, R, rows;                             // rows = B * 2025
     float lr, wd;
     long long step, ordinal;
     unsigned long long seed;
-    size_t o_w[NL], o_b[NL], o_g[NL], o_be[NL], o_mv[NL], P, MV;
-    std::vector<void *> allocs;
-    float *params, *grads, *slot1, *slot2;
-    float *run_mean, *run_var, *bat_mean, *bat_var, *inv, *shift, *m1, *m2, *unbias;   // flat over the BN layers (o_mv)
     float *in0, *a[6], *h[4], *g1, *g2, *pooled, *h6, *code, *s, *H[4], *mid, *recon, *grid;
     int *win1, *win2, *arg, *picks;
     float *d1, *d2, *gd1, *gd2, *dx, *drecon, *dmid, *loss, *mid_loss;
@@ -169,29 +166,12 @@ struct geoadv_fold_trainer {
 };
 
 namespace {
-struct Run : Launch {
+struct Run : TrainRun {
     geoadv_fold_trainer *t;
 
-    void gemm(const GemmArgs &g) { Launch::gemm(g, t->partials); }
-    float *W(int l) { return t->params + t->o_w[l]; }
-    int rows(int l) const { return l <= E5 ? t->R : l <= F2 ? t->B : t->rows; }
-
+    int rows(int l) const { return t->layer[l].rows; }
     // out = in @ W_l[k0 : k0 + K] + (bias ? b_l : 0)
-    void linear_fwd(int l, const float *in, float *out, int M, int k0, int K, bool bias) {
-        const int N = kOut[l];
-        GemmArgs g{};
-        g.A = in; g.sAi = K; g.sAk = 1;
-        g.B = W(l) + (size_t)k0 * N; g.sBk = N; g.sBj = 1;
-        g.C = out; g.ldc = N;
-        g.bias = bias ? t->params + t->o_b[l] : nullptr;
-        g.alpha = 1.f; g.M = M; g.N = N; g.K = K; g.batch = 1;
-        gemm(g);
-    }
-    void batch_stats(int l) {
-        const size_t o = t->o_mv[l];
-        bn_batch_stats(t->a[l], rows(l), kOut[l], 1, t->part, t->params + t->o_g[l], t->params + t->o_be[l], FT_EPS, t->bat_mean + o,
-                       t->bat_var + o, t->inv + o, t->shift + o);
-    }
+    void linear_fwd(int l, const float *in, float *out, int M, int k0, int K, bool bias) { gemm(fwd_args(l, in, out, M, k0, K, bias)); }
     void bn_relu(int l, float *y) {
         const size_t total = (size_t)rows(l) * kOut[l], o = t->o_mv[l];
         launch(tb_bn_relu_kernel<false>, dim3(blocks_of(total)), dim3(256), t->a[l], nullptr, total, rows(l), kOut[l], 0, t->inv + o,
@@ -199,7 +179,7 @@ struct Run : Launch {
     }
     void bn_layer(int l, const float *in, float *y) {
         linear_fwd(l, in, t->a[l], rows(l), 0, kIn[l], true);
-        batch_stats(l);
+        batch_stats(l, t->a[l]);
         if (y) bn_relu(l, y);
     }
     void graph_pool(const float *h, int which, int C, float *g, int *win) {
@@ -226,29 +206,14 @@ struct Run : Launch {
 
     // ---- backward pieces ----
     // dW_l[k0 : k0 + K] = in^T da (in [M][K])
-    void weight_grad(int l, const float *in, const float *da, int M, int k0, int K) {
-        const int N = kOut[l];
-        GemmArgs g{};
-        g.A = in; g.sAi = 1; g.sAk = K;
-        g.B = da; g.sBk = N; g.sBj = 1;
-        g.C = t->grads + t->o_w[l] + (size_t)k0 * N; g.ldc = N;
-        g.alpha = 1.f; g.M = K; g.N = N; g.K = M; g.batch = 1;
-        gemm(g);
-    }
-    void bias_grad(int l, const float *da, int M) { bias_colsum(da, M, kOut[l], 1, t->part, t->grads + t->o_b[l]); }
+    void weight_grad(int l, const float *in, const float *da, int M, int k0, int K) { gemm(wgrad_args(l, in, da, M, k0, K)); }
     // din (=|+=) da W_l[k0 : k0 + K]^T
     void input_grad(int l, const float *da, float *din, int M, int k0, int K, int accumulate) {
-        const int N = kOut[l];
-        GemmArgs d{};
-        d.A = da; d.sAi = N; d.sAk = 1;
-        d.B = W(l) + (size_t)k0 * N; d.sBk = 1; d.sBj = N;
-        d.C = din; d.ldc = K;
-        d.alpha = 1.f; d.M = M; d.N = K; d.K = N; d.batch = 1; d.accumulate = accumulate;
-        gemm(d);
+        gemm(igrad_args(l, da, din, M, k0, K, accumulate));
     }
     void linear_bwd(int l, const float *in, const float *da, float *din) {
         weight_grad(l, in, da, rows(l), 0, kIn[l]);
-        bias_grad(l, da, rows(l));
+        bias_grad(l, da);
         if (din) input_grad(l, da, din, rows(l), 0, kIn[l], 0);
     }
     // BN backward of layer l; gmax: dy = dpool [B][C] at the maximum's rows (conv5), else dense dy through the ReLU
@@ -283,11 +248,11 @@ struct Run : Launch {
         const int M = t->rows;
         const size_t total = (size_t)M * 512;
         weight_grad(l0 + 2, H2, dout, M, 0, 512);
-        bias_grad(l0 + 2, dout, M);
+        bias_grad(l0 + 2, dout);
         input_grad(l0 + 2, dout, t->Y, M, 0, 512, 0);
         mask(t->Y, H2, total);                                           // d pre of the second layer
         weight_grad(l0 + 1, H1, t->Y, M, 0, 512);
-        bias_grad(l0 + 1, t->Y, M);
+        bias_grad(l0 + 1, t->Y);
         input_grad(l0 + 1, t->Y, t->Z, M, 0, 512, 0);
         mask(t->Z, H1, total);                                           // d pre of the first layer
         weight_grad(l0, pts, t->Z, M, FT_CODE, D);                       // the point rows
@@ -301,7 +266,7 @@ struct Run : Launch {
 };
 
 int run_step(geoadv_fold_trainer *t, const float *x, hipStream_t st) {
-    Run q{{st}, t};
+    Run q{{{st}, t, FT_EPS, t->part, t->partials}, t};
     const int B = t->B, R = t->R;
     // ---- forward ----
     q.launch(ft_input_kernel, dim3(cdiv(R * 12, 256)), dim3(256), x, t->graph.cov, R, t->in0);
@@ -344,15 +309,7 @@ int run_step(geoadv_fold_trainer *t, const float *x, hipStream_t st) {
         return GEOADV_EHIP;
     }
     // ---- optimizer, running statistics, counters ----
-    const double tt = (double)(t->step + 1);
-    const float bc1 = (float)(1.0 - pow(0.9, tt)), bc2s = (float)sqrt(1.0 - pow(0.999, tt));
-    hipLaunchKernelGGL(tb_adam_kernel<true>, dim3(blocks_of(t->P)), dim3(256), 0, st, t->params, t->slot1, t->slot2, t->grads, t->P, t->lr, t->wd,
-                       bc1, bc2s);
-    GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_mean, t->bat_mean, (const float *)nullptr, t->MV);
-    GA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(t->MV)), dim3(256), 0, st, t->run_var, t->bat_var, t->unbias, t->MV);
-    GA_LAUNCH_CHECK();
+    if (int rc = q.adam_and_running<true>(t->lr, t->wd, t->step)) return rc;
     t->step += 1;
     return GEOADV_OK;
 }
@@ -378,26 +335,20 @@ extern "C" int geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoad
     t->B = cfg->batch; t->n = cfg->n_points; t->R = t->B * t->n; t->rows = t->B * FT_G2;
     t->lr = cfg->learning_rate; t->wd = cfg->weight_decay; t->step = cfg->initial_step; t->ordinal = cfg->initial_ordinal;
     t->seed = (unsigned long long)cfg->seed;
-    size_t P = 0, MV = 0;
-    auto rup16 = [](size_t v) { return (v + 15) / 16 * 16; };
+    TrainLayer table[NL];
+    TrainInit in{};
     for (int l = 0; l < NL; ++l) {
-        t->o_w[l] = P; P = rup16(P + (size_t)kIn[l] * kOut[l]);
-        t->o_b[l] = P; P = rup16(P + kOut[l]);
-        t->o_g[l] = t->o_be[l] = t->o_mv[l] = 0;
-        if (bn_of(l)) {
-            t->o_g[l] = P; P = rup16(P + kOut[l]);
-            t->o_be[l] = P; P = rup16(P + kOut[l]);
-            t->o_mv[l] = MV; MV = rup16(MV + kOut[l]);
-        }
+        table[l] = {kIn[l], kOut[l], 1, l <= E5 ? t->R : l <= F2 ? t->B : t->rows, bn_of(l), false};
+        in.w[l] = l <= F2 ? init->enc_w[l] : init->dec_w[l - D0];
+        in.b[l] = l <= F2 ? init->enc_b[l] : init->dec_b[l - D0];
+        if (!bn_of(l)) continue;
+        in.gamma[l] = init->enc_gamma[l]; in.beta[l] = init->enc_beta[l]; in.mean[l] = init->enc_mean[l]; in.var[l] = init->enc_var[l];
     }
-    t->P = P; t->MV = MV;
+    t->lay_out(table, NL);
     const size_t R = t->R, B = t->B, rows = t->rows;
     hipError_t e = hipSuccess;
     std::vector<void *> &mem = t->allocs;
-    t->params = dev_alloc<float>(mem, P, e); t->grads = dev_alloc<float>(mem, P, e);
-    t->slot1 = dev_alloc<float>(mem, P, e); t->slot2 = dev_alloc<float>(mem, P, e);
-    for (float **p : {&t->run_mean, &t->run_var, &t->bat_mean, &t->bat_var, &t->inv, &t->shift, &t->m1, &t->m2, &t->unbias})
-        *p = dev_alloc<float>(mem, MV, e);
+    t->alloc(true, e);
     t->in0 = dev_alloc<float>(mem, R * 12, e);
     for (int l = 0; l <= F1; ++l) t->a[l] = dev_alloc<float>(mem, (l <= E5 ? R : B) * kOut[l], e);
     for (int l = 0; l < 4; ++l) t->h[l] = dev_alloc<float>(mem, R * kOut[l], e);
@@ -419,51 +370,29 @@ extern "C" int geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoad
     t->partials = dev_alloc<float>(mem, CT_PARTIAL_FLOATS, e);
     t->part = dev_alloc<double2>(mem, std::max((size_t)cdiv((int)R, 256) * FT_LAT, (size_t)cdiv((int)rows, 256) * 512) + 1024, e);
     t->graph_ws = dev_alloc<char>(mem, fold_train_graph_bytes(t->B, t->n), e);
+    t->upload(in, e);
     if (e == hipSuccess) {
-        std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f), hu(MV, 1.f), hg(rows * 2), g1(R, 1.f / (float)R), g2(rows, 1.f / (float)rows);
-        for (int l = 0; l < NL; ++l) {
-            const float *w = l <= F2 ? init->enc_w[l] : init->dec_w[l - D0], *b = l <= F2 ? init->enc_b[l] : init->dec_b[l - D0];
-            memcpy(&hp[t->o_w[l]], w, sizeof(float) * kIn[l] * kOut[l]);
-            memcpy(&hp[t->o_b[l]], b, sizeof(float) * kOut[l]);
-            if (!bn_of(l)) continue;
-            memcpy(&hp[t->o_g[l]], init->enc_gamma[l], sizeof(float) * kOut[l]);
-            memcpy(&hp[t->o_be[l]], init->enc_beta[l], sizeof(float) * kOut[l]);
-            memcpy(&hm[t->o_mv[l]], init->enc_mean[l], sizeof(float) * kOut[l]);
-            memcpy(&hv[t->o_mv[l]], init->enc_var[l], sizeof(float) * kOut[l]);
-            const double rl = l <= E5 ? (double)R : (double)B;
-            for (int c = 0; c < kOut[l]; ++c) hu[t->o_mv[l] + c] = (float)(rl / (rl - 1.0));
-        }
+        std::vector<float> hg(rows * 2), g1(R, 1.f / (float)R), g2(rows, 1.f / (float)rows);
         for (size_t r = 0; r < rows; ++r) {      // np.linspace(-0.3, 0.3, 45); point p = row * 45 + column is (x_column, y_row)
             const int p = (int)(r % FT_G2);
             auto lin = [](int i) { return (float)(i == FT_GRID - 1 ? 0.3 : -0.3 + i * (0.6 / (FT_GRID - 1))); };
             hg[2 * r] = lin(p % FT_GRID); hg[2 * r + 1] = lin(p / FT_GRID);
         }
-        auto up = [&](float *dst, const std::vector<float> &src) {
-            if (e == hipSuccess) e = hipMemcpy(dst, src.data(), sizeof(float) * src.size(), hipMemcpyHostToDevice);
-        };
-        up(t->params, hp); up(t->run_mean, hm); up(t->run_var, hv); up(t->unbias, hu); up(t->grid, hg); up(t->gd1, g1); up(t->gd2, g2);
+        dev_upload(t->grid, hg, e); dev_upload(t->gd1, g1, e); dev_upload(t->gd2, g2, e);
     }
     if (e != hipSuccess) {
-        dev_free_all(t->allocs);
         delete t;
-        set_error("fold_trainer_create: %s", hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
+        return train_create_error("fold_trainer_create", e);
     }
     *out = t;
     return GEOADV_OK;
 }
 
-extern "C" void geoadv_fold_trainer_destroy(geoadv_fold_trainer *t) {
-    if (!t) return;
-    dev_free_all(t->allocs);
-    delete t;
-}
+extern "C" void geoadv_fold_trainer_destroy(geoadv_fold_trainer *t) { delete t; }
 
 extern "C" int geoadv_fold_trainer_set_slots(geoadv_fold_trainer *t, const float *slot1, const float *slot2) {
     GA_REQUIRE(t, "fold_trainer_set_slots: null handle");
-    if (slot1) GA_HIP(hipMemcpy(t->slot1, slot1, sizeof(float) * t->P, hipMemcpyHostToDevice));
-    if (slot2) GA_HIP(hipMemcpy(t->slot2, slot2, sizeof(float) * t->P, hipMemcpyHostToDevice));
-    return GEOADV_OK;
+    return t->set_slots(slot1, slot2);
 }
 
 extern "C" int geoadv_fold_trainer_step(geoadv_fold_trainer *t, const float *x, int sampling, int *picks, float *loss, float *mid_loss,
@@ -486,21 +415,13 @@ extern "C" int geoadv_fold_trainer_step(geoadv_fold_trainer *t, const float *x, 
 
 extern "C" int geoadv_fold_trainer_buffers(geoadv_fold_trainer *t, float **params, float **grads, size_t *count) {
     GA_REQUIRE(t, "fold_trainer_buffers: null handle");
-    if (params) *params = t->params;
-    if (grads) *grads = t->grads;
-    if (count) *count = t->P;
+    t->buffers(params, grads, count);
     return GEOADV_OK;
 }
 
 extern "C" int geoadv_fold_trainer_layout(const geoadv_fold_trainer *t, size_t *offsets52, size_t *moving_offsets13) {
     GA_REQUIRE(t && offsets52, "fold_trainer_layout: null argument");
-    for (int l = 0; l < NL; ++l) {
-        offsets52[4 * l] = t->o_w[l];
-        offsets52[4 * l + 1] = t->o_b[l];
-        offsets52[4 * l + 2] = bn_of(l) ? t->o_g[l] : (size_t)-1;
-        offsets52[4 * l + 3] = bn_of(l) ? t->o_be[l] : (size_t)-1;
-        if (moving_offsets13) moving_offsets13[l] = bn_of(l) ? t->o_mv[l] : (size_t)-1;
-    }
+    t->export_layout(offsets52, moving_offsets13, NL);
     return GEOADV_OK;
 }
 
@@ -516,14 +437,10 @@ extern "C" int geoadv_fold_trainer_state(const geoadv_fold_trainer *t, int what,
     const size_t B = t->B, R = t->R, rows = t->rows;
     switch (what) {
     case GEOADV_FOLD_STATE_BN_MEAN: case GEOADV_FOLD_STATE_BN_VAR: case GEOADV_FOLD_STATE_RUNNING_MEAN: case GEOADV_FOLD_STATE_RUNNING_VAR:
-    case GEOADV_FOLD_STATE_BN_INV: case GEOADV_FOLD_STATE_BN_SHIFT: {
+    case GEOADV_FOLD_STATE_BN_INV: case GEOADV_FOLD_STATE_BN_SHIFT:
         GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "fold_trainer_state: layer %d has no batch norm", layer);
-        const float *base = what == GEOADV_FOLD_STATE_BN_MEAN ? t->bat_mean : what == GEOADV_FOLD_STATE_BN_VAR ? t->bat_var
-                          : what == GEOADV_FOLD_STATE_RUNNING_MEAN ? t->run_mean : what == GEOADV_FOLD_STATE_RUNNING_VAR ? t->run_var
-                          : what == GEOADV_FOLD_STATE_BN_INV ? t->inv : t->shift;
-        *ptr = base + t->o_mv[layer]; *count = kOut[layer];
+        t->view(what, layer, ptr, count);       // GEOADV_FOLD_STATE_BN_MEAN .. BN_SHIFT are TA_BAT_MEAN .. TA_SHIFT
         return GEOADV_OK;
-    }
     case GEOADV_FOLD_STATE_PRE_BN:
         GA_REQUIRE(layer >= 0 && layer < NL && bn_of(layer), "fold_trainer_state: layer %d has no batch norm", layer);
         *ptr = t->a[layer]; *count = (layer <= E5 ? R : B) * kOut[layer];
@@ -547,8 +464,8 @@ extern "C" int geoadv_fold_trainer_state(const geoadv_fold_trainer *t, int what,
     case GEOADV_FOLD_STATE_CODE: *ptr = t->code; *count = B * FT_CODE; return GEOADV_OK;
     case GEOADV_FOLD_STATE_MID: *ptr = t->mid; *count = rows * 3; return GEOADV_OK;
     case GEOADV_FOLD_STATE_RECON: *ptr = t->recon; *count = rows * 3; return GEOADV_OK;
-    case GEOADV_FOLD_STATE_SLOT1: *ptr = t->slot1; *count = t->P; return GEOADV_OK;
-    case GEOADV_FOLD_STATE_SLOT2: *ptr = t->slot2; *count = t->P; return GEOADV_OK;
+    case GEOADV_FOLD_STATE_SLOT1: t->view(TA_SLOT1, 0, ptr, count); return GEOADV_OK;
+    case GEOADV_FOLD_STATE_SLOT2: t->view(TA_SLOT2, 0, ptr, count); return GEOADV_OK;
     default: break;
     }
     set_error("fold_trainer_state: unknown state %d", what);

@@ -1,8 +1,12 @@
 // The batch-norm, column-sum, global-max, loss, Adam and running-statistics kernels of the layer-by-layer training steps
-// (cls_train.hip, fold_train.hip, atlas_train.hip), each written once, and the host plumbing the three handles share: the
-// device arena, blocks_of / rpc_of and the launch context.  As in train_tile.h every kernel is `static`: each translation
-// unit that includes this header gets its own copy.  The GEMM and its split-K stay in train_tile.h; what depends on a model
-// (dropout, ReLU pool, graph pool, the decoder's rebuilt statistics, the TensorFlow-form optimizers) stays with its trainer.
+// (cls_train.hip, fold_train.hip, atlas_train.hip), each written once, and the host plumbing the three handles share:
+// dev_alloc, blocks_of / rpc_of, the flat parameter and batch-norm arenas every handle derives from (TrainArena: layout,
+// allocation, upload of the initial weights, set_slots, buffers, layout export, state lookup), the launch context (Launch) and
+// a step on an arena (TrainRun: W, batch_stats, bias_grad, the GemmArgs of a dense layer's three products, the torch-form
+// Adam and running-statistics tail).  As in train_tile.h every kernel is `static`: each translation unit that includes this
+// header gets its own copy.  The GEMM and its split-K stay in train_tile.h; what depends on a model (its layer table and
+// buffers, bn_bwd, dropout, ReLU pool, graph pool, the decoder's rebuilt statistics, the TensorFlow-form optimizers and EMA)
+// stays with its trainer.
 //
 // BatchNorm in train mode: the BIASED batch variance normalises; eps is the trainer's (torch 1e-5, TF 1e-3) and is passed to
 // every kernel that needs it.  inv = gamma / sqrt(var + eps), shift = beta - mean * inv, y = relu(a * inv + shift).
@@ -20,6 +24,8 @@
 // rounded to fp32 would decide what is left.  Its ReLU mask is still the forward's fp32 test.
 #pragma once
 #include "train_tile.h"
+#include <math.h>
+#include <string.h>
 #include <vector>
 
 namespace geoadv {
@@ -289,8 +295,8 @@ static __global__ __launch_bounds__(256) void tb_running_kernel(float *running, 
 }
 
 // ---- host plumbing ----------------------------------------------------------------------------------------------------------
-// A handle's device arena: hipMalloc of count elements (+ 16 bytes), zero filled, recorded in `allocs`.  After a failure
-// (err set) nothing more is allocated; dev_free_all releases what was.
+// A handle's device memory: hipMalloc of count elements (+ 16 bytes), zero filled, recorded in `allocs`.  After a failure
+// (err set) nothing more is allocated or uploaded; dev_free_all releases what was.
 template <class T> T *dev_alloc(std::vector<void *> &allocs, size_t count, hipError_t &err) {
     void *p = nullptr;
     if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T) + 16);
@@ -301,9 +307,118 @@ inline void dev_free_all(std::vector<void *> &allocs) {
     for (void *p : allocs) (void)hipFree(p);
     allocs.clear();
 }
+inline void dev_upload(float *dst, const std::vector<float> &src, hipError_t &err) {
+    if (err == hipSuccess) err = hipMemcpy(dst, src.data(), sizeof(float) * src.size(), hipMemcpyHostToDevice);
+}
+// What a *_trainer_create returns after a HIP failure (the caller has deleted its handle, which frees the device memory)
+inline int train_create_error(const char *who, hipError_t err) {
+    set_error("%s: %s", who, hipGetErrorString(err));
+    return err == hipErrorOutOfMemory ? GEOADV_ENOMEM : GEOADV_EHIP;
+}
 
 inline unsigned blocks_of(size_t total) { return (unsigned)((total + 255) / 256); }
 inline int rpc_of(int R) { return std::max(1, std::min(R, 256)); }     // rows per chunk of the column sums
+
+// ---- the parameter arena ----------------------------------------------------------------------------------------------------
+// One layer of a trainer: `groups` independent kin x kout products (AtlasNet's primitives; 1 elsewhere) over `rows` rows per
+// group.  bn: a batch norm follows (gamma and beta in the arena, a slot in the batch-norm arenas).  mv_slot: a slot in the
+// batch-norm arenas even without a norm (AtlasNet's decoder without norms: identity constants, inv 1 shift 0).
+struct TrainLayer { int kin, kout, groups, rows; bool bn, mv_slot; };
+constexpr int TA_MAXL = 20;
+// The initial weights and moving statistics of every layer, as host pointers (the last four are read for bn layers only)
+struct TrainInit { const float *w[TA_MAXL], *b[TA_MAXL], *gamma[TA_MAXL], *beta[TA_MAXL], *mean[TA_MAXL], *var[TA_MAXL]; };
+enum { TA_BAT_MEAN = 0, TA_BAT_VAR, TA_RUN_MEAN, TA_RUN_VAR, TA_INV, TA_SHIFT, TA_SLOT1, TA_SLOT2 };     // TrainArena::view
+
+// The flat buffers of a layer-by-layer trainer; every handle derives from it and is created with `new T()` (zeroed).
+// params / grads / slot1 / slot2 hold P floats: per layer W [groups][kin][kout] at o_w, b at o_b, gamma at o_g, beta at o_be,
+// each rounded up to 16 floats.  The batch-norm arenas hold MV floats, [groups][kout] per slot at o_mv: running (moving) and
+// batch statistics, the folded constants inv / shift, the backward's means m1 / m2 and, where allocated, unbias = rows /
+// (rows - 1).  The slots of the layers with a real norm come first: MVbn floats.  Layers without a slot have offset 0.
+struct TrainArena {
+    int nl;                                        // layers in use, <= TA_MAXL
+    TrainLayer layer[TA_MAXL];
+    size_t o_w[TA_MAXL], o_b[TA_MAXL], o_g[TA_MAXL], o_be[TA_MAXL], o_mv[TA_MAXL], P, MV, MVbn;
+    std::vector<void *> allocs;                    // every device buffer of the handle, the model's own included
+    float *params, *grads, *slot1, *slot2;         // slot1 = Adam m / Momentum accum, slot2 = Adam v
+    float *run_mean, *run_var, *bat_mean, *bat_var, *inv, *shift, *m1, *m2, *unbias;
+
+    ~TrainArena() { dev_free_all(allocs); }
+    int kin(int l) const { return layer[l].kin; }
+    int kout(int l) const { return layer[l].kout; }
+    int groups(int l) const { return layer[l].groups; }
+    size_t width(int l) const { return (size_t)layer[l].groups * layer[l].kout; }
+
+    void lay_out(const TrainLayer *table, int layers) {
+        auto rup16 = [](size_t v) { return (v + 15) / 16 * 16; };
+        nl = layers; P = MV = MVbn = 0;
+        for (int l = 0; l < nl; ++l) {
+            layer[l] = table[l];
+            const size_t C = width(l);
+            o_w[l] = P; P = rup16(P + C * kin(l));
+            o_b[l] = P; P = rup16(P + C);
+            o_g[l] = o_be[l] = o_mv[l] = 0;
+            if (layer[l].bn) {
+                o_g[l] = P; P = rup16(P + C);
+                o_be[l] = P; P = rup16(P + C);
+            }
+            if (layer[l].bn || layer[l].mv_slot) { o_mv[l] = MV; MV = rup16(MV + C); }
+            if (layer[l].bn) MVbn = MV;
+        }
+    }
+    void alloc(bool with_unbias, hipError_t &err) {
+        for (float **p : {&params, &grads, &slot1, &slot2}) *p = dev_alloc<float>(allocs, P, err);
+        for (float **p : {&run_mean, &run_var, &bat_mean, &bat_var, &inv, &shift, &m1, &m2}) *p = dev_alloc<float>(allocs, MV, err);
+        if (with_unbias) unbias = dev_alloc<float>(allocs, MV, err);
+    }
+    void upload(const TrainInit &in, hipError_t &err) {
+        if (err != hipSuccess) return;
+        std::vector<float> hp(P, 0.f), hm(MV, 0.f), hv(MV, 0.f), hu(MV, 1.f);
+        bool identity = false;
+        for (int l = 0; l < nl; ++l) {
+            const size_t C = width(l);
+            identity = identity || layer[l].mv_slot;
+            memcpy(&hp[o_w[l]], in.w[l], sizeof(float) * C * kin(l));
+            memcpy(&hp[o_b[l]], in.b[l], sizeof(float) * C);
+            if (!layer[l].bn) continue;
+            memcpy(&hp[o_g[l]], in.gamma[l], sizeof(float) * C);
+            memcpy(&hp[o_be[l]], in.beta[l], sizeof(float) * C);
+            memcpy(&hm[o_mv[l]], in.mean[l], sizeof(float) * C);
+            memcpy(&hv[o_mv[l]], in.var[l], sizeof(float) * C);
+            const double rl = (double)layer[l].rows;
+            if (unbias) std::fill_n(&hu[o_mv[l]], C, (float)(rl / (rl - 1.0)));
+        }
+        dev_upload(params, hp, err); dev_upload(run_mean, hm, err); dev_upload(run_var, hv, err);
+        if (unbias) dev_upload(unbias, hu, err);
+        if (identity) dev_upload(inv, std::vector<float>(MV, 1.f), err);
+    }
+    int set_slots(const float *s1, const float *s2) {
+        if (s1) GA_HIP(hipMemcpy(slot1, s1, sizeof(float) * P, hipMemcpyHostToDevice));
+        if (s2) GA_HIP(hipMemcpy(slot2, s2, sizeof(float) * P, hipMemcpyHostToDevice));
+        return GEOADV_OK;
+    }
+    void buffers(float **params_out, float **grads_out, size_t *count) const {
+        if (params_out) *params_out = params;
+        if (grads_out) *grads_out = grads;
+        if (count) *count = P;
+    }
+    // offsets[4 l ...] = o_w, o_b, o_g, o_be and moving[l] = o_mv of layers 0 .. maxl; (size_t)-1 for what a layer does not have
+    void export_layout(size_t *offsets, size_t *moving, int maxl) const {
+        for (int l = 0; l < maxl; ++l) {
+            const bool have = l < nl, bn = have && layer[l].bn;
+            offsets[4 * l] = have ? o_w[l] : (size_t)-1;
+            offsets[4 * l + 1] = have ? o_b[l] : (size_t)-1;
+            offsets[4 * l + 2] = bn ? o_g[l] : (size_t)-1;
+            offsets[4 * l + 3] = bn ? o_be[l] : (size_t)-1;
+            if (moving) moving[l] = bn ? o_mv[l] : (size_t)-1;
+        }
+    }
+    // The TA_* array of layer l (the caller has checked that the layer has a slot), or a whole optimizer slot
+    void view(int which, int l, const void **ptr, size_t *count) const {
+        if (which >= TA_SLOT1) { *ptr = which == TA_SLOT1 ? slot1 : slot2; *count = P; return; }
+        const float *base[] = {bat_mean, bat_var, run_mean, run_var, inv, shift};
+        *ptr = base[which] + o_mv[l]; *count = width(l);
+    }
+};
 
 // The stream of a step and its sticky error: after the first failure nothing more is launched and `err` stays the first.
 struct Launch {
@@ -335,6 +450,71 @@ struct Launch {
         const int rpc = rpc_of(Rg);
         colsum<1>(da, Rg, C, G, rpc, part);
         launch(tb_colsum_final_kernel, dim3(cdiv(G * C, 256)), dim3(256), part, cdiv(Rg, rpc), C, G, db);
+    }
+};
+
+// A step on an arena: the batch norm's eps and the two scratch buffers of the column sums and of the split-K.
+struct TrainRun : Launch {
+    TrainArena *A;
+    float eps;
+    double2 *part;
+    float *partials;
+
+    void gemm(const GemmArgs &g) { Launch::gemm(g, partials); }
+    float *W(int l) const { return A->params + A->o_w[l]; }
+    // Batch statistics of layer l's pre-BN activation a
+    void batch_stats(int l, const float *a) {
+        const size_t o = A->o_mv[l];
+        bn_batch_stats(a, A->layer[l].rows, A->kout(l), A->groups(l), part, A->params + A->o_g[l], A->params + A->o_be[l], eps, A->bat_mean + o,
+                       A->bat_var + o, A->inv + o, A->shift + o);
+    }
+    // d bias = the column sums of da over the layer's rows
+    void bias_grad(int l, const float *da) { bias_colsum(da, A->layer[l].rows, A->kout(l), A->groups(l), part, A->grads + A->o_b[l]); }
+
+    // The products of a dense layer on rows k0 .. k0 + K of W_l (N = kout):  out = in @ W (+ b_l) with in [M][K]
+    GemmArgs fwd_args(int l, const float *in, float *out, int M, int k0, int K, bool bias) const {
+        const int N = A->kout(l);
+        GemmArgs g{};
+        g.A = in; g.sAi = K; g.sAk = 1;
+        g.B = W(l) + (size_t)k0 * N; g.sBk = N; g.sBj = 1;
+        g.C = out; g.ldc = N;
+        g.bias = bias ? A->params + A->o_b[l] : nullptr;
+        g.alpha = 1.f; g.M = M; g.N = N; g.K = K; g.batch = 1;
+        return g;
+    }
+    // dW = in^T da:  A(i = input channel, k = row) = in[row][i]
+    GemmArgs wgrad_args(int l, const float *in, const float *da, int M, int k0, int K) const {
+        const int N = A->kout(l);
+        GemmArgs g{};
+        g.A = in; g.sAi = 1; g.sAk = K;
+        g.B = da; g.sBk = N; g.sBj = 1;
+        g.C = A->grads + A->o_w[l] + (size_t)k0 * N; g.ldc = N;
+        g.alpha = 1.f; g.M = K; g.N = N; g.K = M; g.batch = 1;
+        return g;
+    }
+    // din (=|+=) da W^T:  B(k = output channel, j = input channel) = W[j][k]
+    GemmArgs igrad_args(int l, const float *da, float *din, int M, int k0, int K, int accumulate) const {
+        const int N = A->kout(l);
+        GemmArgs d{};
+        d.A = da; d.sAi = N; d.sAk = 1;
+        d.B = W(l) + (size_t)k0 * N; d.sBk = 1; d.sBj = N;
+        d.C = din; d.ldc = K;
+        d.alpha = 1.f; d.M = M; d.N = K; d.K = N; d.batch = 1; d.accumulate = accumulate;
+        return d;
+    }
+    // The tail of a torch-form step: torch.optim.Adam's step number step + 1 on the whole arena, then the running statistics
+    template <bool DECAY> int adam_and_running(float lr, float wd, long long step) {
+        const double tt = (double)(step + 1);
+        const float bc1 = (float)(1.0 - pow(0.9, tt)), bc2s = (float)sqrt(1.0 - pow(0.999, tt));
+        hipLaunchKernelGGL(tb_adam_kernel<DECAY>, dim3(blocks_of(A->P)), dim3(256), 0, st, A->params, A->slot1, A->slot2, A->grads, A->P, lr, wd,
+                           bc1, bc2s);
+        GA_LAUNCH_CHECK();
+        const size_t mv = A->MVbn;
+        hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(mv)), dim3(256), 0, st, A->run_mean, A->bat_mean, (const float *)nullptr, mv);
+        GA_LAUNCH_CHECK();
+        hipLaunchKernelGGL(tb_running_kernel, dim3(blocks_of(mv)), dim3(256), 0, st, A->run_var, A->bat_var, A->unbias, mv);
+        GA_LAUNCH_CHECK();
+        return GEOADV_OK;
     }
 };
 

@@ -11,13 +11,12 @@ running count of clouds this trainer has trained on and is stored in the checkpo
 np.random.RandomState(seed) positions on the host in the reference's order (FoldingNetAE.reference_picks).  train_step(x,
 picks=...) takes explicit positions.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _abi, _lib, fold_weights as FW
 from ._abi import FoldTrainConfig as _FoldTrainConfig, FoldWeights as _FoldWeights
+from ._layer_trainer import LayerTrainer, seed64, torch_layer_tensors
 from .foldingnet import FoldingNetAE, PICKS_DEVICE, PICKS_GIVEN, SAMPLINGS, K, G2
 
 _STATE = {k: getattr(_abi, "GEOADV_FOLD_STATE_" + k.upper()) for k in (
@@ -35,7 +34,10 @@ def check_batch(batch_size):
                          "and needs at least 2" % int(batch_size))
 
 
-class FoldingNetTrainer:
+class FoldingNetTrainer(LayerTrainer):
+    _PREFIX, _STATE, _INT_STATES = "fold", _STATE, _INT_STATES
+    # counters(): (optimizer steps taken, clouds seen)
+
     def __init__(self, weights=None, num_points=2048, batch_size=8, learning_rate=1e-4, weight_decay=1e-6, seed=0,
                  sampling="device", step=0, slots=None, ordinal=0, device=None):
         """weights: {state-dict key: array} (None = fold_weights.initial_weights(seed)).  step / slots: optimizer steps taken
@@ -53,115 +55,30 @@ class FoldingNetTrainer:
         self.seed, self.sampling = int(seed), sampling
         self.device = torch.device(device if device is not None else "cuda:0")
         self._rs = np.random.RandomState(self.seed) if sampling == "reference" else None
-        canon = FW.canonical(weights)
         hw = _FoldWeights()
-        for key, arrays in canon.items():
-            field = getattr(hw, key)
-            for i, a in enumerate(arrays):
-                field[i] = a.ctypes.data if a is not None else None
-        sseed = self.seed & ((1 << 64) - 1)
-        cfg = _FoldTrainConfig(self.batch_size, self.num_points, self.learning_rate, self.weight_decay,
-                               sseed - (1 << 64) if sseed >= (1 << 63) else sseed, int(step), int(ordinal))
-        self._h = C.c_void_p()
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            _lib.check(L.geoadv_fold_trainer_create(C.byref(self._h), C.byref(hw), C.byref(cfg)), "fold_trainer_create")
-        pp, gp, cnt = C.c_void_p(), C.c_void_p(), C.c_size_t()
-        _lib.check(L.geoadv_fold_trainer_buffers(self._h, C.byref(pp), C.byref(gp), C.byref(cnt)), "fold_trainer_buffers")
-        self._count, self._params_ptr, self._grads_ptr = int(cnt.value), pp.value, gp.value
-        offs, moffs = (C.c_size_t * (4 * len(LAYERS)))(), (C.c_size_t * len(LAYERS))()
-        _lib.check(L.geoadv_fold_trainer_layout(self._h, offs, moffs), "fold_trainer_layout")
-        self._offsets = list(offs)
+        cfg = _FoldTrainConfig(self.batch_size, self.num_points, self.learning_rate, self.weight_decay, seed64(self.seed), int(step),
+                               int(ordinal))
+        self._open(FW.canonical(weights), hw, (hw, cfg), len(LAYERS))
         self._loss = torch.zeros(2, dtype=torch.float32, device=self.device)
         self._picks = torch.zeros((2, self.batch_size, self.num_points, K), dtype=torch.int32, device=self.device)
-        self._eval = None
         self._graph_model = None
         if slots is not None:
-            s1, s2 = self._flatten(slots["exp_avg"]), self._flatten(slots["exp_avg_sq"])
-            _lib.check(L.geoadv_fold_trainer_set_slots(self._h, s1.ctypes.data, s2.ctypes.data), "fold_trainer_set_slots")
+            self._upload_slots(self._flatten(slots["exp_avg"]), self._flatten(slots["exp_avg_sq"]))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                _lib.lib().geoadv_fold_trainer_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    # ---- device views --------------------------------------------------------------------------------------
-    def state(self, what, layer=0, device=False):
-        """Host copy of what the last step kept (geoadv_fold_trainer_state): 'bn_mean' / 'bn_var' / 'running_mean' /
-        'running_var' / 'bn_inv' / 'bn_shift' / 'pre_bn' of BN layer 0 .. 5 (bn1 .. bn6), 'pool_winner' 0 / 1, 'gmax_row',
-        'hidden' 0 .. 3, 'picks', 'cols', 'cov', 'code', 'mid', 'recon', 'chamfer_idx' 0 / 1, 'slot1', 'slot2'.  device=True
-        returns a view of the handle's memory instead: drop it before the trainer."""
-        p, cnt = C.c_void_p(), C.c_size_t()
-        _lib.check(_lib.lib().geoadv_fold_trainer_state(self._h, _STATE[what], int(layer), C.byref(p), C.byref(cnt)),
-                   "fold_trainer_state")
-        torch.cuda.synchronize(self.device)
-        if not cnt.value:
-            raise ValueError("state(%r) is empty before the first step" % what)
-        a = _lib.device_view(p.value, cnt.value, "<i4" if what in _INT_STATES else "<f4", self.device)
+    def _state_shapes(self, layer):
+        """state(what, layer): 'bn_mean' / 'bn_var' / 'running_mean' / 'running_var' / 'bn_inv' / 'bn_shift' / 'pre_bn' of BN
+        layer 0 .. 5 (bn1 .. bn6), 'pool_winner' 0 / 1, 'gmax_row', 'hidden' 0 .. 3, 'picks', 'cols', 'cov', 'code', 'mid',
+        'recon', 'chamfer_idx' 0 / 1, 'slot1', 'slot2'."""
         B, n = self.batch_size, self.num_points
-        shapes = {"pre_bn": (-1, LAYERS[int(layer)][2]), "pool_winner": (B, n, -1), "gmax_row": (B, 1024), "hidden": (-1, 512),
-                  "picks": (2, B, n, K), "cols": (2, B, n, K), "cov": (B, n, 9), "code": (B, 512), "mid": (B, G2, 3),
-                  "recon": (B, G2, 3), "chamfer_idx": (B, -1)}
-        if not device:
-            a = a.cpu().numpy().copy()
-        return a.reshape(shapes[what]) if what in shapes else a
+        return {"pre_bn": (-1, LAYERS[layer][2]), "pool_winner": (B, n, -1), "gmax_row": (B, 1024), "hidden": (-1, 512),
+                "picks": (2, B, n, K), "cols": (2, B, n, K), "cov": (B, n, 9), "code": (B, 512), "mid": (B, G2, 3),
+                "recon": (B, G2, 3), "chamfer_idx": (B, -1)}
 
-    def counters(self):
-        """(optimizer steps taken, clouds seen)."""
-        s, o = C.c_longlong(), C.c_longlong()
-        _lib.check(_lib.lib().geoadv_fold_trainer_counters(self._h, C.byref(s), C.byref(o)), "fold_trainer_counters")
-        return int(s.value), int(o.value)
-
-    @property
-    def step(self):
-        return self.counters()[0]
-
-    def _unflatten(self, flat):
-        """{parameter key: array in torch's shape} from a flat parameter-layout buffer."""
-        out = {}
+    def _tensors(self):
         for l, (pre, fi, fo, conv, bn) in enumerate(LAYERS):
-            o = self._offsets[4 * l: 4 * l + 4]
-            w = flat[o[0]:o[0] + fi * fo].reshape(fi, fo).T
-            out[pre + ".weight"] = np.ascontiguousarray(w[:, :, None] if conv else w)
-            out[pre + ".bias"] = flat[o[1]:o[1] + fo].copy()
-            if bn:
-                out["encoder.bn%d.weight" % bn] = flat[o[2]:o[2] + fo].copy()
-                out["encoder.bn%d.bias" % bn] = flat[o[3]:o[3] + fo].copy()
-        return out
-
-    def _flatten(self, named):
-        flat = np.zeros(self._count, np.float32)
-        for l, (pre, fi, fo, conv, bn) in enumerate(LAYERS):
-            o = self._offsets[4 * l: 4 * l + 4]
-            flat[o[0]:o[0] + fi * fo] = np.asarray(named[pre + ".weight"], np.float32).reshape(fo, fi).T.reshape(-1)
-            flat[o[1]:o[1] + fo] = np.asarray(named[pre + ".bias"], np.float32).reshape(-1)
-            if bn:
-                flat[o[2]:o[2] + fo] = np.asarray(named["encoder.bn%d.weight" % bn], np.float32).reshape(-1)
-                flat[o[3]:o[3] + fo] = np.asarray(named["encoder.bn%d.bias" % bn], np.float32).reshape(-1)
-        return flat
-
-    def parameters(self):
-        """{parameter key: array} of the trainable tensors (host copies, torch's shapes)."""
-        torch.cuda.synchronize(self.device)
-        return self._unflatten(_lib.device_view(self._params_ptr, self._count, "<f4", self.device).cpu().numpy())
-
-    def gradients(self):
-        """{parameter key: d loss / d parameter} of the last step, without the weight-decay term."""
-        torch.cuda.synchronize(self.device)
-        return self._unflatten(_lib.device_view(self._grads_ptr, self._count, "<f4", self.device).cpu().numpy())
-
-    def slots(self):
-        """Adam's {'exp_avg': {key: array}, 'exp_avg_sq': {key: array}}."""
-        return {"exp_avg": self._unflatten(self.state("slot1")), "exp_avg_sq": self._unflatten(self.state("slot2"))}
+            yield from torch_layer_tensors(pre, "encoder.bn%d" % bn if bn else None, self._offsets[4 * l: 4 * l + 4], fi, fo, conv)
 
     # ---- the steps -----------------------------------------------------------------------------------------
-    def _dev(self, x):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(self.device, dtype=torch.float32).contiguous()
-
     def degrees(self, x):
         """(batch, n) int32 device tensor: the length of every point's adjacency row (what picks index into).  Through a
         FoldingNetAE kept for its graph build alone -- the graph does not depend on the weights, so it is built once."""
