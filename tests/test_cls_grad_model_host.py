@@ -252,3 +252,59 @@ def test_ifgsm_stays_in_the_box_and_steps_by_alpha():
     p = torch.where(torch.rand(xf.shape, generator=torch.Generator().manual_seed(0)) < 0.5, -e32, e32).to(torch.float32)
     raw = ((xf + p) - xf).abs().max().item()
     assert (box(xf, p, e32) - xf).abs().max().item() <= e32 < raw  # the plain sum does leave the box on this draw
+
+
+# ------------------------------------------------------------------------------------------------ pinned masks, open units
+def _mask_case(n=40):
+    from test_gpu_cls_grad import KAPPA, make_case
+    x, y = make_case(6, C, n, "cw_targeted", clouds=2)
+    return x, y, G.grad_model(_weights(), x, y, "cw_targeted", KAPPA), KAPPA
+
+
+def test_overriding_every_unit_with_its_own_mask_changes_no_bit():
+    x, y, own, kappa = _mask_case()
+    masks = {s: pre > 0 for s, pre in own["pres"].items()}
+    again = G.grad_model(_weights(), x, y, "cw_targeted", kappa, relu_override=masks)
+    listed = {s: [(c, None, u, m[c, u]) for c in range(2) for u in range(m.shape[1])] if m.ndim == 2 else
+              [(c, r, u, m[c, r, u]) for c in range(2) for r in range(0, m.shape[1], 7) for u in range(0, m.shape[2], 5)]
+              for s, m in masks.items()}
+    as_lists = G.grad_model(_weights(), x, y, "cw_targeted", kappa, relu_override=listed)
+    for got in (again, as_lists):
+        assert all(np.array_equal(got[k], own[k]) for k in ("grad", "loss", "logits", "winners", "pooled"))
+
+
+def test_flipping_a_unit_far_from_zero_moves_the_gradient_only():
+    """One conv3 unit on a winner row of the classifier's pool, the one farthest from zero (at or near the layer's largest
+    pre-activation): pinned the other way, the gradient of its row moves by far more than the GPU tolerance; loss, logits
+    and every other cloud stay the same bits."""
+    from test_gpu_cls_grad import TOL_GRAD
+    x, y, own, kappa = _mask_case()
+    rows = G.winner_rows(own, 0, 2)
+    pre = own["pres"]["conv3"][0]
+    r, u = np.unravel_index(np.argmax(np.abs(pre[rows])), pre[rows].shape)
+    row = int(rows[r])
+    assert abs(pre[row, u]) > 0.1 * np.abs(pre).max()
+    flipped = G.grad_model(_weights(), x, y, "cw_targeted", kappa, relu_override={"conv3": [(0, row, int(u), not pre[row, u] > 0)]})
+    assert np.array_equal(flipped["loss"], own["loss"]) and np.array_equal(flipped["logits"], own["logits"])
+    assert np.array_equal(flipped["pooled"], own["pooled"]) and np.array_equal(flipped["grad"][1], own["grad"][1])
+    moved = np.abs(flipped["grad"][0] - own["grad"][0]).max() / np.abs(own["grad"][0]).max()
+    print("conv3 unit (row %d, %d) at %.2f of the layer's maximum: gradient moved by %.2e" % (row, u, abs(pre[row, u]) / np.abs(pre).max(), moved))
+    assert moved > 100 * TOL_GRAD
+
+
+def test_open_units_at_the_ends_of_the_window():
+    x, y, own, kappa = _mask_case()
+    assert G.open_units(own, 0.0) == []                            # no pre-activation is exactly zero
+    every = G.open_units(own, 1.0)
+    assert len(set(every)) == len(every)
+    want = 0
+    for c in range(2):
+        for s in {s for under in G.UNDER.values() for s in under}:
+            rows = np.unique(np.concatenate([G.winner_rows(own, c, p) for p in range(3) if s in G.UNDER[p]]))
+            want += len(rows) * own["pres"][s].shape[2]
+            assert {k[2] for k in every if k[0] == s and k[1] == c} == set(rows.tolist())
+        want += sum(own["pres"][s].shape[1] for s in G.HEADS)
+    assert len(every) == want
+    some = G.open_units(own, {s: (0.01 if s == "conv2" else 0.0) for s in own["pres"]})
+    assert some and all(k[0] == "conv2" and abs(own["pres"]["conv2"][k[1], k[2], k[3]]) <= 0.01 * np.abs(own["pres"]["conv2"][k[1]]).max()
+                        for k in some)
