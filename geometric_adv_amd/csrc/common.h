@@ -34,6 +34,23 @@ static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Carves a workspace or an arena into blocks at `align`-byte alignment (256 unless the layout packs tighter), starting at the
+// base rounded up to 256.  Over a null base it only measures: bytes() is what the blocks taken so far occupy.  One function per
+// layout takes the blocks; run over null it gives the size a caller is told, run over the memory the pointers a kernel gets.
+class Carver {
+    char *base_, *p_;
+    size_t align_;
+public:
+    explicit Carver(void *workspace, size_t align = 256)
+        : base_(reinterpret_cast<char *>(rup(reinterpret_cast<size_t>(workspace), 256))), p_(base_), align_(align) {}
+    template <class T> T *take(size_t count) {
+        char *q = p_;
+        p_ += rup(sizeof(T) * count, align_);
+        return reinterpret_cast<T *>(q);
+    }
+    size_t bytes() const { return (size_t)(p_ - base_); }
+};
+
 constexpr int kWave = 64;   // gfx950 wavefront
 constexpr int kCUs = 256;   // MI355X: 8 XCDs x 32 CUs -- launch-SHAPE decisions only (grid sizes, slice widths): nothing is wrong on a smaller
                             // part or partition, just slower.  Anything that needs workgroups RESIDENT together (in-launch flags) asks the

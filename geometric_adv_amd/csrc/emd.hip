@@ -1235,7 +1235,7 @@ extern "C" int geoadv_match_cost_ws(int b, int n, int m, const float *xyz1, cons
                workspace_floats, geoadv_match_cost_workspace_floats(b, n, m));
     hipStream_t st = as_stream(stream);
     const int parts = cdiv(m, EMD_COST_ROWS);
-    double *partial = reinterpret_cast<double *>((reinterpret_cast<size_t>(workspace) + 7) & ~(size_t)7);
+    double *partial = emd_temp_doubles(workspace);
     emd_cost_partial_kernel<<<dim3(parts, b), 256, 0, st>>>(n, m, xyz1, xyz2, match, partial);
     emd_cost_fold_kernel<<<b, 256, 0, st>>>(parts, partial, out);
     GA_LAUNCH_CHECK();

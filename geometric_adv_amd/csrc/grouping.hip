@@ -1289,34 +1289,31 @@ static std::atomic<int> g_knn_default_mode{GEOADV_KNN_AUTO};   // geoadv_knn_gri
 static bool knn_uses_grid(int kmode, int n, int m) {
     return n <= KG_MAX_N && (kmode >= GEOADV_KNN_GRID || (kmode == GEOADV_KNN_AUTO && n >= KNN_GRID_MIN_N && m >= 64));
 }
-static size_t knn_up(size_t v) { return (v + 255) / 256 * 256; }
-// caller-owned scratch of the list kernels: the redo list (counter + one entry per query at most) and, for the grid search, the
-// sorted dataset (+ 4 entries of padding: the scalar loads read four points at a time), cell offsets, query order, grid
-static size_t knn_fast_scratch_bytes(int b, int n, int m) {
-    const size_t redo_b = sizeof(int) * ((size_t)b * m + 1), sorted_b = sizeof(float4) * ((size_t)b * n + 4);
-    const size_t cs_b = sizeof(int) * (size_t)b * (KG_MAX_CELLS + 1), qo_b = sizeof(int) * (size_t)b * m, info_b = sizeof(KnnGrid) * (size_t)b;
-    const size_t to_b = sizeof(int) * (size_t)b * cdiv(m, 64);
-    return knn_up(redo_b) + knn_up(sorted_b) + knn_up(cs_b) + knn_up(qo_b) + knn_up(info_b) + knn_up(to_b);
+// scratch of the list kernels, carved from `base` (over a null base: measured only): the redo list (counter + one entry per query
+// at most) and, for the grid search, the sorted dataset (+ 4 entries of padding: the scalar loads read four points at a time),
+// cell offsets, query order, grid, task order
+struct KnnScratch {
+    int *redo; float4 *sorted; int *cs, *qo; KnnGrid *info; int *tord;
+    size_t bytes;
+};
+static KnnScratch knn_scratch(void *base, int b, int n, int m) {
+    Carver c(base);
+    KnnScratch s;
+    s.redo = c.take<int>((size_t)b * m + 1); s.sorted = c.take<float4>((size_t)b * n + 4); s.cs = c.take<int>((size_t)b * (KG_MAX_CELLS + 1));
+    s.qo = c.take<int>((size_t)b * m); s.info = c.take<KnnGrid>(b); s.tord = c.take<int>((size_t)b * cdiv(m, 64));
+    s.bytes = c.bytes();
+    return s;
 }
 
-// kmode: GEOADV_KNN_*; scratch: knn_fast_scratch_bytes(b, n, m) bytes, 256-byte aligned
+// kmode: GEOADV_KNN_*; s: knn_scratch(base, b, n, m)
 // (lane-private 27-cell walk first -- values-only lists (knn_dists) only: with (value, index) lists the walk lost to the shells at
 // either occupancy: knn_point(8) at 256 x 2048: 378 against 343 us at one workgroup per CU, 265 against 227 us at two)
 template <int MODE, int S>
-static int launch_knn_fast(int kmode, int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx, char *scratch,
-                           hipStream_t st) {
+static int launch_knn_fast(int kmode, int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx,
+                           const KnnScratch &s, hipStream_t st) {
     const bool grid = knn_uses_grid(kmode, n, m);
-    const size_t redo_b = sizeof(int) * ((size_t)b * m + 1), sorted_b = sizeof(float4) * ((size_t)b * n + 4);
-    const size_t cs_b = sizeof(int) * (size_t)b * (KG_MAX_CELLS + 1), qo_b = sizeof(int) * (size_t)b * m, info_b = sizeof(KnnGrid) * (size_t)b;
-    auto up = knn_up;
-    int *redo = reinterpret_cast<int *>(scratch);
-    if (!grid) GA_HIP(hipMemsetAsync(redo, 0, sizeof(int), st));          // (the grid's build kernel clears the counter itself: one launch less)
+    if (!grid) GA_HIP(hipMemsetAsync(s.redo, 0, sizeof(int), st));          // (the grid's build kernel clears the counter itself: one launch less)
     if (grid) {
-        float4 *sorted = reinterpret_cast<float4 *>(scratch + up(redo_b));
-        int *cs = reinterpret_cast<int *>(scratch + up(redo_b) + up(sorted_b));
-        int *qo = reinterpret_cast<int *>(scratch + up(redo_b) + up(sorted_b) + up(cs_b));
-        KnnGrid *info = reinterpret_cast<KnnGrid *>(scratch + up(redo_b) + up(sorted_b) + up(cs_b) + up(qo_b));
-        int *tord = reinterpret_cast<int *>(scratch + up(redo_b) + up(sorted_b) + up(cs_b) + up(qo_b) + up(info_b));
         const int G = n < KNN_GRID_N_MID ? KNN_GRID_G_SMALL : (n < KNN_GRID_N_BIG ? KNN_GRID_G_MID : KNN_GRID_G_BIG);
         // knn_point (MODE 0): the keyed lists (kernel MODE 2) on the lane-private walk, unless the caller asks for the shell walk alone
         // (GEOADV_KNN_GRID_SHELLS): that one keeps the (value, index) lists, as the parity tests' second opinion
@@ -1328,7 +1325,7 @@ static int launch_knn_fast(int kmode, int b, int n, int m, int k, const float *x
                 GA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_grid_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_LDS));
                 return GEOADV_OK;
             })) return rc;
-        knn_grid_build_kernel<<<b, KG_BUILD_THREADS, KB_LDS, st>>>(n, m, G, xyz1, xyz2, sorted, cs, qo, info, tord, lane_first ? 0 : 1, redo);
+        knn_grid_build_kernel<<<b, KG_BUILD_THREADS, KB_LDS, st>>>(n, m, G, xyz1, xyz2, s.sorted, s.cs, s.qo, s.info, s.tord, lane_first ? 0 : 1, s.redo);
         constexpr int KMODE = MODE == 0 ? 2 : MODE;          // the keyed instantiation of this list length
         static DeviceOnce attr;
         if (int rc = attr.run([]() -> int {
@@ -1343,15 +1340,15 @@ static int launch_knn_fast(int kmode, int b, int n, int m, int k, const float *x
         const int tasks = cdiv(m, 64), waves = KG_THREADS / 64;
         const int split = std::max(1, std::min(std::max(1, tasks / (waves * KG_TASKS_PER_WAVE)), cdiv(2 * kCUs, b)));
         if (keyed)
-            knn_grid_kernel<KMODE, S, KG_THREADS><<<dim3(split, b), KG_THREADS, kg_lds_bytes<KMODE, S>(n, KG_THREADS, G * G * G), st>>>(n, m, k, split, sorted, cs, qo,
-                                                                                                                         info, tord, xyz2, val, idx, redo, lane_first);
+            knn_grid_kernel<KMODE, S, KG_THREADS><<<dim3(split, b), KG_THREADS, kg_lds_bytes<KMODE, S>(n, KG_THREADS, G * G * G), st>>>(n, m, k, split, s.sorted, s.cs, s.qo,
+                                                                                                                         s.info, s.tord, xyz2, val, idx, s.redo, lane_first);
         else
-            knn_grid_kernel<MODE, S, KG_THREADS><<<dim3(split, b), KG_THREADS, kg_lds_bytes<MODE, S>(n, KG_THREADS, G * G * G), st>>>(n, m, k, split, sorted, cs, qo, info,
-                                                                                                                       tord, xyz2, val, idx, redo, lane_first);
+            knn_grid_kernel<MODE, S, KG_THREADS><<<dim3(split, b), KG_THREADS, kg_lds_bytes<MODE, S>(n, KG_THREADS, G * G * G), st>>>(n, m, k, split, s.sorted, s.cs, s.qo, s.info,
+                                                                                                                       s.tord, xyz2, val, idx, s.redo, lane_first);
     } else {
-        knn_fast_kernel<MODE, S><<<dim3(cdiv(m, KF_THREADS), b), KF_THREADS, 0, st>>>(n, m, k, xyz1, xyz2, val, idx, redo);
+        knn_fast_kernel<MODE, S><<<dim3(cdiv(m, KF_THREADS), b), KF_THREADS, 0, st>>>(n, m, k, xyz1, xyz2, val, idx, s.redo);
     }
-    knn_redo_kernel<MODE><<<1024, 64, (size_t)n * 8, st>>>(n, m, k, xyz1, xyz2, val, idx, redo);
+    knn_redo_kernel<MODE><<<1024, 64, (size_t)n * 8, st>>>(n, m, k, xyz1, xyz2, val, idx, s.redo);
     GA_LAUNCH_CHECK();
     return GEOADV_OK;
 }
@@ -1386,9 +1383,9 @@ static bool knn_list_kernels(int mode, int b, int m, int k) {   // the register-
 }
 
 // mode 0: knn_point (k values + indices); mode 1: the defender's distances (k includes the dropped self column)
-// kmode: GEOADV_KNN_*; scratch: caller-owned, knn_fast_scratch_bytes (unused by the generic kernel)
+// kmode: GEOADV_KNN_*; scratch: knn_scratch (unused by the generic kernel)
 static int launch_knn(int mode, int kmode, int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx,
-                      char *scratch, hipStream_t st) {
+                      const KnnScratch &scratch, hipStream_t st) {
     if (int rc = row_lds_attr()) return rc;
     const int slots = mode == 0 ? k + 1 : k;              // register list of the fast kernel
     if (knn_list_kernels(mode, b, m, k)) {
@@ -1434,10 +1431,8 @@ static int knn_dists_check(int b, int n, int k) {
 
 extern "C" size_t geoadv_knn_workspace_bytes(int b, int n, int m, int k) {
     if (b <= 0 || n <= 0 || m <= 0 || k <= 0) return 256;
-    return knn_fast_scratch_bytes(b, n, m) + 256;          // (+ 256: the workspace pointer is aligned up here)
+    return knn_scratch(nullptr, b, n, m).bytes + 256;      // (+ 256: the workspace pointer is aligned up here)
 }
-
-static char *ws_align(void *p) { return reinterpret_cast<char *>((reinterpret_cast<size_t>(p) + 255) & ~(size_t)255); }
 
 extern "C" int geoadv_knn_point_ws(int kernel, int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx,
                                    void *workspace, size_t workspace_bytes, void *stream) {
@@ -1447,7 +1442,7 @@ extern "C" int geoadv_knn_point_ws(int kernel, int b, int n, int m, int k, const
     GA_REQUIRE(xyz1 && xyz2 && val && idx, "knn_point: null pointer");
     GA_REQUIRE(workspace && workspace_bytes >= geoadv_knn_workspace_bytes(b, n, m, k), "knn_point: workspace too small (%zu bytes, need %zu)",
                workspace_bytes, geoadv_knn_workspace_bytes(b, n, m, k));
-    return launch_knn(0, kernel, b, n, m, k, xyz1, xyz2, val, idx, ws_align(workspace), as_stream(stream));
+    return launch_knn(0, kernel, b, n, m, k, xyz1, xyz2, val, idx, knn_scratch(workspace, b, n, m), as_stream(stream));
 }
 
 extern "C" int geoadv_knn_dists_ws(int kernel, int b, int n, int k, const float *pc, float *out, void *workspace, size_t workspace_bytes,
@@ -1458,15 +1453,15 @@ extern "C" int geoadv_knn_dists_ws(int kernel, int b, int n, int k, const float 
     GA_REQUIRE(pc && out, "knn_dists: null pointer");
     GA_REQUIRE(workspace && workspace_bytes >= geoadv_knn_workspace_bytes(b, n, n, k + 1), "knn_dists: workspace too small (%zu bytes, need %zu)",
                workspace_bytes, geoadv_knn_workspace_bytes(b, n, n, k + 1));
-    return launch_knn(1, kernel, b, n, n, k + 1, pc, pc, out, nullptr, ws_align(workspace), as_stream(stream));
+    return launch_knn(1, kernel, b, n, n, k + 1, pc, pc, out, nullptr, knn_scratch(workspace, b, n, n), as_stream(stream));
 }
 
 // The reference-shaped entry points (tf_grouping.py:48-75 has no scratch argument): thin conveniences over the _ws forms with
 // stream-ordered scratch (hipMallocAsync / hipFreeAsync on the caller's stream) and the process-default kernel selection.
 static int knn_with_own_scratch(int mode, int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx, hipStream_t st) {
-    char *scratch = nullptr;
-    if (knn_list_kernels(mode, b, m, k)) GA_HIP(hipMallocAsync(reinterpret_cast<void **>(&scratch), knn_fast_scratch_bytes(b, n, m), st));
-    const int rc = launch_knn(mode, g_knn_default_mode.load(), b, n, m, k, xyz1, xyz2, val, idx, scratch, st);
+    void *scratch = nullptr;                                 // (device allocations are 256-byte aligned: carved from their first byte)
+    if (knn_list_kernels(mode, b, m, k)) GA_HIP(hipMallocAsync(&scratch, knn_scratch(nullptr, b, n, m).bytes, st));
+    const int rc = launch_knn(mode, g_knn_default_mode.load(), b, n, m, k, xyz1, xyz2, val, idx, knn_scratch(scratch, b, n, m), st);
     if (scratch) GA_HIP(hipFreeAsync(scratch, st));
     return rc;
 }
@@ -1528,11 +1523,19 @@ static void gpg_shape(int n, int m, int nsample, int &entries, int &segs, int &s
     passes = 1;
     while ((n >> (6 * passes)) != 0) ++passes;              // destinations 0 .. n (n = invalid)
 }
-// two (keys, perm) buffers, the (digit, segment) table, start[b][n + 1]
-static size_t gpg_scratch_ints(int b, int n, int m, int nsample) {
+// scratch of the sort, carved from `base` as ints back to back (over a null base: measured only): two (keys, perm) buffers, the
+// (digit, segment) table, start[b][n + 1]
+struct GpgScratch { int *keys[2], *perm[2], *table, *start; size_t bytes; };
+static GpgScratch gpg_scratch(void *base, int b, int n, int m, int nsample) {
     int entries, segs, seg_len, passes;
     gpg_shape(n, m, nsample, entries, segs, seg_len, passes);
-    return 4 * (size_t)b * entries + (size_t)b * (64 * segs + 1) + (size_t)b * (n + 1);
+    Carver c(base, sizeof(int));
+    GpgScratch s;
+    for (int i = 0; i < 2; ++i) s.keys[i] = c.take<int>((size_t)b * entries);
+    for (int i = 0; i < 2; ++i) s.perm[i] = c.take<int>((size_t)b * entries);
+    s.table = c.take<int>((size_t)b * (64 * segs + 1)); s.start = c.take<int>((size_t)b * (n + 1));
+    s.bytes = c.bytes();
+    return s;
 }
 static int gpg_check(int b, int n, int c, int m, int nsample) {
     GA_REQUIRE(b >= 0 && n >= 0 && c >= 0 && m >= 0 && nsample >= 0, "group_point_grad: negative dimension");
@@ -1542,23 +1545,20 @@ static int gpg_check(int b, int n, int c, int m, int nsample) {
 }
 
 static int launch_group_point_grad(int b, int n, int c, int m, int nsample, const float *grad_out, const int *idx, float *grad_points,
-                                   int *scratch, hipStream_t st) {
+                                   const GpgScratch &s, hipStream_t st) {
     int entries, segs, seg_len, passes;
     gpg_shape(n, m, nsample, entries, segs, seg_len, passes);
-    const size_t per = (size_t)b * entries, table_ints = (size_t)b * (64 * segs + 1);
-    int *keys[2] = {scratch, scratch + per}, *perm[2] = {scratch + 2 * per, scratch + 3 * per};
-    int *table = scratch + 4 * per, *start = table + table_ints;
     const dim3 grid(cdiv(segs, GPG_WAVES), b);
     const int *kin = idx, *pin = nullptr;
     for (int pass = 0; pass < passes; ++pass) {
-        int *kout = keys[pass & 1], *pout = perm[pass & 1];
-        gpg_pass_kernel<false><<<grid, 64 * GPG_WAVES, 0, st>>>(n, entries, 6 * pass, segs, seg_len, kin, pin, table, nullptr, nullptr);
-        gpg_scan_kernel<<<b, 1024, 0, st>>>(64 * segs, table);
-        gpg_pass_kernel<true><<<grid, 64 * GPG_WAVES, 0, st>>>(n, entries, 6 * pass, segs, seg_len, kin, pin, table, kout, pout);
+        int *kout = s.keys[pass & 1], *pout = s.perm[pass & 1];
+        gpg_pass_kernel<false><<<grid, 64 * GPG_WAVES, 0, st>>>(n, entries, 6 * pass, segs, seg_len, kin, pin, s.table, nullptr, nullptr);
+        gpg_scan_kernel<<<b, 1024, 0, st>>>(64 * segs, s.table);
+        gpg_pass_kernel<true><<<grid, 64 * GPG_WAVES, 0, st>>>(n, entries, 6 * pass, segs, seg_len, kin, pin, s.table, kout, pout);
         kin = kout; pin = pout;
     }
-    gpg_bounds_kernel<<<dim3(cdiv(n + 1, 256), b), 256, 0, st>>>(n, entries, kin, start);
-    gpg_sum_kernel<<<dim3(cdiv(n * c, 256), b), 256, 0, st>>>(n, c, entries, grad_out, start, pin, grad_points);
+    gpg_bounds_kernel<<<dim3(cdiv(n + 1, 256), b), 256, 0, st>>>(n, entries, kin, s.start);
+    gpg_sum_kernel<<<dim3(cdiv(n * c, 256), b), 256, 0, st>>>(n, c, entries, grad_out, s.start, pin, grad_points);
     GA_LAUNCH_CHECK();
     return GEOADV_OK;
 }
@@ -1566,39 +1566,35 @@ static int launch_group_point_grad(int b, int n, int c, int m, int nsample, cons
 extern "C" size_t geoadv_group_point_grad_workspace_bytes(int b, int n, int c, int m, int nsample) {
     (void)c;
     if (b <= 0 || n < 0 || m <= 0 || nsample <= 0) return 256;
-    return sizeof(int) * gpg_scratch_ints(b, n, m, nsample) + 256;
+    return gpg_scratch(nullptr, b, n, m, nsample).bytes + 256;      // (+ 256: the workspace pointer is aligned up here)
 }
 
-extern "C" int geoadv_group_point_grad_ws(int b, int n, int c, int m, int nsample, const float *grad_out, const int *idx,
-                                          float *grad_points, void *workspace, size_t workspace_bytes, void *stream) {
+// both entry points: on the caller's workspace, or (own) on stream-ordered scratch
+static int group_point_grad(int b, int n, int c, int m, int nsample, const float *grad_out, const int *idx, float *grad_points, bool own,
+                            void *workspace, size_t workspace_bytes, hipStream_t st) {
     if (int rc = gpg_check(b, n, c, m, nsample)) return rc;
     if ((size_t)b * n * c == 0) return GEOADV_OK;
     GA_REQUIRE(grad_points && (m * nsample == 0 || (grad_out && idx)), "group_point_grad: null pointer");
-    hipStream_t st = as_stream(stream);
     if (m * nsample == 0) {
         GA_HIP(hipMemsetAsync(grad_points, 0, (size_t)b * n * c * sizeof(float), st));        // tf_grouping.cpp:204
         return GEOADV_OK;
     }
-    GA_REQUIRE(workspace && workspace_bytes >= geoadv_group_point_grad_workspace_bytes(b, n, c, m, nsample),
-               "group_point_grad: workspace too small (%zu bytes, need %zu)", workspace_bytes, geoadv_group_point_grad_workspace_bytes(b, n, c, m, nsample));
-    return launch_group_point_grad(b, n, c, m, nsample, grad_out, idx, grad_points, reinterpret_cast<int *>(ws_align(workspace)), st);
+    if (own) GA_HIP(hipMallocAsync(&workspace, gpg_scratch(nullptr, b, n, m, nsample).bytes, st));      // (256-byte aligned, as every device allocation)
+    else GA_REQUIRE(workspace && workspace_bytes >= geoadv_group_point_grad_workspace_bytes(b, n, c, m, nsample),
+                    "group_point_grad: workspace too small (%zu bytes, need %zu)", workspace_bytes, geoadv_group_point_grad_workspace_bytes(b, n, c, m, nsample));
+    const int rc = launch_group_point_grad(b, n, c, m, nsample, grad_out, idx, grad_points, gpg_scratch(workspace, b, n, m, nsample), st);
+    if (own) GA_HIP(hipFreeAsync(workspace, st));
+    return rc;
+}
+
+extern "C" int geoadv_group_point_grad_ws(int b, int n, int c, int m, int nsample, const float *grad_out, const int *idx,
+                                          float *grad_points, void *workspace, size_t workspace_bytes, void *stream) {
+    return group_point_grad(b, n, c, m, nsample, grad_out, idx, grad_points, false, workspace, workspace_bytes, as_stream(stream));
 }
 
 // reference-shaped (groupPointGradLauncher has no scratch argument): stream-ordered scratch of its own
 extern "C" int geoadv_group_point_grad(int b, int n, int c, int m, int nsample, const float *grad_out, const int *idx,
                                        float *grad_points, void *stream) {
-    if (int rc = gpg_check(b, n, c, m, nsample)) return rc;
-    if ((size_t)b * n * c == 0) return GEOADV_OK;
-    GA_REQUIRE(grad_points && (m * nsample == 0 || (grad_out && idx)), "group_point_grad: null pointer");
-    hipStream_t st = as_stream(stream);
-    if (m * nsample == 0) {
-        GA_HIP(hipMemsetAsync(grad_points, 0, (size_t)b * n * c * sizeof(float), st));        // tf_grouping.cpp:204
-        return GEOADV_OK;
-    }
-    int *scratch = nullptr;
-    GA_HIP(hipMallocAsync(reinterpret_cast<void **>(&scratch), sizeof(int) * gpg_scratch_ints(b, n, m, nsample), st));
-    const int rc = launch_group_point_grad(b, n, c, m, nsample, grad_out, idx, grad_points, scratch, st);
-    GA_HIP(hipFreeAsync(scratch, st));
-    return rc;
+    return group_point_grad(b, n, c, m, nsample, grad_out, idx, grad_points, true, nullptr, 0, as_stream(stream));
 }
 GA_STAMPS_GETTER(geoadv_debug_stamps_grouping)

@@ -1,6 +1,6 @@
 // Host-side plumbing shared by the model translation units (ae.hip, classifier.hip, atlasnet.hip, foldingnet.hip): the MFMA
-// fragment packers, the create-time arena, the caller-workspace carver, the torch batch-norm fold and the pooled layer's
-// launch shape.
+// fragment packers, the create-time arena, the torch batch-norm fold and the pooled layer's launch shape.  (The workspace
+// carver, Carver, is in common.h: the operators use it too.)
 #pragma once
 #include <math.h>
 #include <vector>
@@ -62,20 +62,6 @@ struct HostArena {
         }
         return GEOADV_OK;
     }
-};
-
-// Carves a caller's workspace into blocks at 256-byte alignment, starting at the base rounded up to 256.  Over a null base
-// it only measures: bytes() is what the blocks taken so far occupy.
-class Carver {
-    char *base_, *p_;
-public:
-    explicit Carver(void *workspace) : base_(reinterpret_cast<char *>(rup(reinterpret_cast<size_t>(workspace), 256))), p_(base_) {}
-    template <class T> T *take(size_t count) {
-        char *q = p_;
-        p_ += rup(sizeof(T) * count, 256);
-        return reinterpret_cast<T *>(q);
-    }
-    size_t bytes() const { return (size_t)(p_ - base_); }
 };
 
 // Folded batch norm of N channels as torch's eval mode rounds it (eps 1e-5): scale = gamma * rsqrt(var + eps),

@@ -233,26 +233,32 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
     }
 }
 
-static size_t kl_up(size_t v) { return (v + 255) / 256 * 256; }
-
-struct KlLayout {
-    size_t knn, val, idx, sc, deg, cur, hub, edge, total;
+// The workspace, carved from `base` (over a null base: measured only): the search's own workspace, its values and indices, then
+// the launch's per-point arrays
+struct KlScratch {
+    char *knn;
+    size_t knn_bytes;
+    float *val;
+    int *idx;
+    double *sc;
+    int *deg, *cur, *hub, *edge;
+    size_t bytes;
 };
-
-static KlLayout kl_layout(int b, int n, int k) {
-    KlLayout o;
+static KlScratch kl_scratch(void *base, int b, int n, int k) {
     const size_t bn = (size_t)b * n;
-    size_t at = 0;
-    o.knn = at; at += kl_up(geoadv_knn_workspace_bytes(b, n, n, k + 1));
-    o.val = at; at += kl_up(bn * (k + 1) * sizeof(float));
-    o.idx = at; at += kl_up(bn * (k + 1) * sizeof(int));
-    o.sc = at; at += kl_up(bn * sizeof(double));
-    o.deg = at; at += kl_up(bn * sizeof(int));
-    o.cur = at; at += kl_up(bn * sizeof(int));
-    o.hub = at; at += kl_up(bn * sizeof(int));
-    o.edge = at; at += kl_up(bn * k * sizeof(int));
-    o.total = at + 256;                                    // (+ 256: the workspace pointer is aligned up here)
-    return o;
+    Carver c(base);
+    KlScratch s;
+    s.knn_bytes = geoadv_knn_workspace_bytes(b, n, n, k + 1);
+    s.knn = c.take<char>(s.knn_bytes);
+    s.val = c.take<float>(bn * (k + 1));
+    s.idx = c.take<int>(bn * (k + 1));
+    s.sc = c.take<double>(bn);
+    s.deg = c.take<int>(bn);
+    s.cur = c.take<int>(bn);
+    s.hub = c.take<int>(bn);
+    s.edge = c.take<int>(bn * k);
+    s.bytes = c.bytes();
+    return s;
 }
 
 static bool kl_overlap(const void *a, size_t na, const void *b, size_t nb) {
@@ -271,7 +277,7 @@ static int kl_check(const char *op, int b, int n, int k, double alpha, const flo
     GA_REQUIRE(alpha >= 0.0 && isfinite(alpha), "%s: alpha must be finite and >= 0 (got %g)", op, alpha);
     if (b == 0) return GEOADV_OK;
     GA_REQUIRE(xyz && loss, "%s: null pointer", op);
-    const size_t need = kl_layout(b, n, k).total;
+    const size_t need = geoadv_knn_outlier_loss_workspace_bytes(b, n, k);
     GA_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace too small (%zu bytes, need %zu)", op, workspace_bytes, need);
     const size_t bytes = (size_t)b * n * 3 * sizeof(float);
     GA_REQUIRE(!grad || !kl_overlap(grad, bytes, xyz, bytes), "%s: grad overlaps xyz", op);
@@ -279,17 +285,12 @@ static int kl_check(const char *op, int b, int n, int k, double alpha, const flo
 }
 
 static int kl_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad, double *score, unsigned char *mask,
-                     int *idx, double *stats, char *ws, hipStream_t st) {
-    const KlLayout o = kl_layout(b, n, k);
-    knn_outlier_loss_kernel<<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, reinterpret_cast<const int *>(ws + o.idx),
-                                                      reinterpret_cast<double *>(ws + o.sc), reinterpret_cast<int *>(ws + o.deg),
-                                                      reinterpret_cast<int *>(ws + o.cur), reinterpret_cast<int *>(ws + o.edge),
-                                                      reinterpret_cast<int *>(ws + o.hub), loss, grad, score, mask, idx, stats);
+                     int *idx, double *stats, const KlScratch &s, hipStream_t st) {
+    knn_outlier_loss_kernel<<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, grad, score, mask,
+                                                      idx, stats);
     GA_LAUNCH_CHECK();
     return GEOADV_OK;
 }
-
-static char *kl_align(void *p) { return reinterpret_cast<char *>((reinterpret_cast<size_t>(p) + 255) & ~(size_t)255); }
 
 }  // namespace geoadv
 
@@ -297,7 +298,7 @@ using namespace geoadv;
 
 extern "C" size_t geoadv_knn_outlier_loss_workspace_bytes(int b, int n, int k) {
     if (!kl_shape_ok(b, n, k) || b == 0) return 256;
-    return kl_layout(b, n, k).total;
+    return kl_scratch(nullptr, b, n, k).bytes + 256;       // (+ 256: the workspace pointer is aligned up here)
 }
 
 extern "C" int geoadv_knn_outlier_loss(int kernel, int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad,
@@ -306,17 +307,14 @@ extern "C" int geoadv_knn_outlier_loss(int kernel, int b, int n, int k, double a
     GA_REQUIRE(kernel >= GEOADV_KNN_AUTO && kernel <= GEOADV_KNN_GRID_SHELLS, "knn_outlier_loss: unknown k-NN kernel %d", kernel);
     if (int rc = kl_check("knn_outlier_loss", b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
     if (b == 0) return GEOADV_OK;
-    const KlLayout o = kl_layout(b, n, k);
-    char *ws = kl_align(workspace);
-    if (int rc = geoadv_knn_point_ws(kernel, b, n, n, k + 1, xyz, xyz, reinterpret_cast<float *>(ws + o.val), reinterpret_cast<int *>(ws + o.idx),
-                                     ws + o.knn, kl_up(geoadv_knn_workspace_bytes(b, n, n, k + 1)), stream))
-        return rc;
-    return kl_launch(b, n, k, alpha, xyz, loss, grad, score, mask, idx, stats, ws, as_stream(stream));
+    const KlScratch s = kl_scratch(workspace, b, n, k);
+    if (int rc = geoadv_knn_point_ws(kernel, b, n, n, k + 1, xyz, xyz, s.val, s.idx, s.knn, s.knn_bytes, stream)) return rc;
+    return kl_launch(b, n, k, alpha, xyz, loss, grad, score, mask, idx, stats, s, as_stream(stream));
 }
 
 extern "C" int geoadv_debug_knn_outlier_loss_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad,
                                                     void *workspace, size_t workspace_bytes, void *stream) {
     if (int rc = kl_check("debug_knn_outlier_loss_launch", b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
     if (b == 0) return GEOADV_OK;
-    return kl_launch(b, n, k, alpha, xyz, loss, grad, nullptr, nullptr, nullptr, nullptr, kl_align(workspace), as_stream(stream));
+    return kl_launch(b, n, k, alpha, xyz, loss, grad, nullptr, nullptr, nullptr, nullptr, kl_scratch(workspace, b, n, k), as_stream(stream));
 }

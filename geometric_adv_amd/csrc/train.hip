@@ -19,6 +19,7 @@
 #include "chamfer_sym.h"
 #include "ae.h"
 #include "mfma_tile.h"
+#include <assert.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1185,6 +1186,37 @@ static int trainer_repack(geoadv_trainer *t, hipStream_t st) {
     return GEOADV_OK;
 }
 
+// Every device buffer of a trainer, carved in one order from `base` at 256-byte alignment; returns the bytes taken.  Over a null
+// base it only measures (geoadv_trainer_create runs it twice: to size the allocation, then over it).
+static size_t carve_trainer(geoadv_trainer *t, void *base) {
+    const size_t B = t->B, n = t->N, R = t->R, P = t->L.count;
+    Carver c(base);
+    auto F = [&](size_t count) { return c.take<float>(count); };
+    auto I = [&](size_t count) { return c.take<int>(count); };
+    t->params = F(P); t->grads = F(P); t->adam_m = F(P); t->adam_v = F(P);
+    for (int i = 0; i < ENC_L; ++i) {
+        const size_t C = ENC[i + 1], W = (size_t)ENC[i] * ENC[i + 1];
+        t->mov_mean[i] = F(C); t->mov_var[i] = F(C); t->packed_fwd[i] = F(W); t->packed_bwd[i] = F(W);
+        t->bn_mean[i] = F(C); t->bn_istd[i] = F(C); t->bn_scale[i] = F(C); t->bn_shift[i] = F(C); t->bn_m1[i] = F(C); t->bn_m2[i] = F(C);
+        t->act[i] = F(R * C);
+    }
+    t->dybuf[0] = F(R * 256); t->dybuf[1] = F(R * 256);
+    t->psum = c.take<float2>((size_t)t->tiles * 256); t->qsum = c.take<float2>(R / BF_ROWS * 256);
+    t->zbits = I(B * 128); t->cnt = I(B * 128);             // adjacent: B * 512 B is a multiple of 256
+    t->d1 = F(B * 256); t->d2 = F(B * 256); t->recon = F(B * t->n3); t->g_recon = F(B * t->n3);
+    t->cham_ws = F(chamfer_sym_workspace_floats(1, t->B, t->N, t->N));
+    t->gd = F(B); t->dd2 = F(B * 256); t->dd1 = F(B * 256); t->dz = F(B * 128);
+    t->dist1 = F(B * n); t->dist2 = F(B * n); t->idx1 = I(B * n); t->idx2 = I(B * n);
+    t->dw_partial = F((size_t)t->grid_bwd * 256 * 128); t->db_partial = F((size_t)t->grid_bwd * 256);
+    t->loss = F(64);
+    const bool emd = t->loss_type == GEOADV_TRAIN_LOSS_EMD;
+    t->emd_temp = emd ? F(geoadv_emd_cost_grad1_temp_floats(t->B, t->N, t->N) + 2) : nullptr;
+    t->emd_cost = emd ? F(B) : nullptr;
+    t->xbuf = c.take<double>(10 * 512); t->lbuf = c.take<double>(10 * 512);
+    t->row_shift0 = F(64);
+    return c.bytes();
+}
+
 extern "C" int geoadv_trainer_create(geoadv_trainer **out, const geoadv_ae_weights *hw, const geoadv_train_config *cfg) {
     GA_REQUIRE(out && hw && cfg, "trainer_create: null argument");
     for (int i = 0; i <= ENC_L; ++i)
@@ -1209,58 +1241,18 @@ extern "C" int geoadv_trainer_create(geoadv_trainer **out, const geoadv_ae_weigh
     t->grid_bwd = cus * (64 / BWD_ROWS);                  // persistent backward workgroups (one per CU)
     if (t->max_wgs > 0 && t->grid_bwd > t->max_wgs) t->grid_bwd = t->max_wgs;
     t->cus = cus;
-    // carve
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t r = off; off += (bytes + 255) / 256 * 256; return r; };
+    t->loss_type = cfg->loss;
+    t->user_loss = nullptr; t->user_recon = nullptr;
+    t->world = 1;
     const size_t P = t->L.count;
-    const size_t o_params = take(4 * P), o_grads = take(4 * P), o_m = take(4 * P), o_v = take(4 * P);
-    size_t o_mm[ENC_L], o_mv[ENC_L], o_pf[ENC_L], o_pb[ENC_L], o_bn[ENC_L][6], o_act[ENC_L];
-    for (int i = 0; i < ENC_L; ++i) {
-        o_mm[i] = take(4 * ENC[i + 1]); o_mv[i] = take(4 * ENC[i + 1]);
-        o_pf[i] = take(4 * (size_t)ENC[i] * ENC[i + 1]); o_pb[i] = take(4 * (size_t)ENC[i] * ENC[i + 1]);
-        for (int k = 0; k < 6; ++k) o_bn[i][k] = take(4 * ENC[i + 1]);
-        o_act[i] = take(4 * (size_t)t->R * ENC[i + 1]);
-    }
-    const size_t o_dy0 = take(4 * (size_t)t->R * 256), o_dy1 = take(4 * (size_t)t->R * 256);
-    const size_t o_ps = take(8 * (size_t)t->tiles * 256), o_qs = take(8 * (size_t)(t->R / BF_ROWS) * 256);
-    const size_t o_z = take(4 * (size_t)B * 128), o_cnt = take(4 * (size_t)B * 128);   // adjacent: B * 512 B is a multiple of 256
-    const size_t o_d1 = take(4 * (size_t)B * 256), o_d2 = take(4 * (size_t)B * 256);
-    const size_t o_rec = take(4 * (size_t)B * t->n3), o_gr = take(4 * (size_t)B * t->n3);
-    const size_t o_cws = take(4 * chamfer_sym_workspace_floats(1, B, n, n));
-    const size_t o_gd = take(4 * (size_t)B), o_dd2 = take(4 * (size_t)B * 256), o_dd1 = take(4 * (size_t)B * 256);
-    const size_t o_dz = take(4 * (size_t)B * 128);
-    const size_t o_di1 = take(4 * (size_t)B * n), o_di2 = take(4 * (size_t)B * n), o_i1 = take(4 * (size_t)B * n), o_i2 = take(4 * (size_t)B * n);
-    const size_t o_dwp = take(4 * (size_t)t->grid_bwd * 256 * 128), o_dbp = take(4 * (size_t)t->grid_bwd * 256);
-    const size_t o_loss = take(256);
-    const bool emd = cfg->loss == GEOADV_TRAIN_LOSS_EMD;
-    const size_t o_et = take(emd ? 4 * geoadv_emd_cost_grad1_temp_floats(B, n, n) + 8 : 0), o_ec = take(emd ? 4 * (size_t)B : 0);
-    const size_t o_xb = take(8 * 10 * 512), o_lb = take(8 * 10 * 512), o_rs = take(4 * 64);
-    t->arena_bytes = off;
-    if (hipMalloc(reinterpret_cast<void **>(&t->arena), off) != hipSuccess) {
-        set_error("trainer_create: hipMalloc of %zu bytes failed", off);
+    t->arena_bytes = carve_trainer(t, nullptr);             // over a null base: measured only
+    if (hipMalloc(reinterpret_cast<void **>(&t->arena), t->arena_bytes) != hipSuccess) {
+        set_error("trainer_create: hipMalloc of %zu bytes failed", t->arena_bytes);
         delete t;
         return GEOADV_ENOMEM;
     }
-    auto F = [&](size_t o) { return reinterpret_cast<float *>(t->arena + o); };
-    t->params = F(o_params); t->grads = F(o_grads); t->adam_m = F(o_m); t->adam_v = F(o_v);
-    for (int i = 0; i < ENC_L; ++i) {
-        t->mov_mean[i] = F(o_mm[i]); t->mov_var[i] = F(o_mv[i]); t->packed_fwd[i] = F(o_pf[i]); t->packed_bwd[i] = F(o_pb[i]);
-        t->bn_mean[i] = F(o_bn[i][0]); t->bn_istd[i] = F(o_bn[i][1]); t->bn_scale[i] = F(o_bn[i][2]);
-        t->bn_shift[i] = F(o_bn[i][3]); t->bn_m1[i] = F(o_bn[i][4]); t->bn_m2[i] = F(o_bn[i][5]);
-        t->act[i] = F(o_act[i]);
-    }
-    t->dybuf[0] = F(o_dy0); t->dybuf[1] = F(o_dy1);
-    t->psum = reinterpret_cast<float2 *>(F(o_ps)); t->qsum = reinterpret_cast<float2 *>(F(o_qs));
-    t->zbits = reinterpret_cast<int *>(F(o_z)); t->cnt = reinterpret_cast<int *>(F(o_cnt));
-    t->d1 = F(o_d1); t->d2 = F(o_d2); t->recon = F(o_rec); t->g_recon = F(o_gr); t->cham_ws = F(o_cws); t->gd = F(o_gd);
-    t->dd2 = F(o_dd2); t->dd1 = F(o_dd1); t->dz = F(o_dz);
-    t->dist1 = F(o_di1); t->dist2 = F(o_di2); t->idx1 = reinterpret_cast<int *>(F(o_i1)); t->idx2 = reinterpret_cast<int *>(F(o_i2));
-    t->dw_partial = F(o_dwp); t->db_partial = F(o_dbp); t->loss = F(o_loss);
-    t->user_loss = nullptr; t->user_recon = nullptr;
-    t->loss_type = cfg->loss; t->emd_temp = emd ? F(o_et) : nullptr; t->emd_cost = emd ? F(o_ec) : nullptr;
-    t->world = 1;
-    t->xbuf = reinterpret_cast<double *>(t->arena + o_xb); t->lbuf = reinterpret_cast<double *>(t->arena + o_lb);
-    t->row_shift0 = F(o_rs);
+    const size_t carved = carve_trainer(t, t->arena);
+    assert(carved == t->arena_bytes); (void)carved;         // both passes agree
     // upload parameters
     std::vector<float> host(P, 0.f);
     const int dd[4] = {128, 256, 256, 3 * n};

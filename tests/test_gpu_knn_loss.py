@@ -12,37 +12,14 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _knn_loss_model as M  # noqa: E402
+from _guarded import DEV, FILL, Buf  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-PAD = 256                  # guard bytes before and after every buffer
-FILL = 0xA5                # guards and unwritten outputs
 EINVAL = 1
 OUTPUTS = ("loss", "grad", "score", "mask", "idx", "stats")
 OPTIONAL = ("grad", "score", "mask", "idx", "stats")
 KERNELS = {"auto": 0, "all_points": 1, "grid": 2, "grid_shells": 3}
-
-
-class Buf:
-    """A device allocation of PAD + nbytes + PAD bytes filled with FILL; the payload optionally holds `host`."""
-
-    def __init__(self, shape, dtype, host=None):
-        import torch
-        self.shape, self.dtype = tuple(shape), np.dtype(dtype)
-        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
-        self.t = torch.full((self.nbytes + 2 * PAD,), FILL, dtype=torch.uint8, device=DEV)
-        if host is not None:
-            host = np.array(host, dtype=self.dtype, order="C")       # (a copy: the shared clouds are read-only)
-            assert host.shape == self.shape
-            self.t[PAD:PAD + self.nbytes] = torch.from_numpy(host.reshape(-1).view(np.uint8)).to(DEV)
-        self.ptr = C.c_void_p(self.t.data_ptr() + PAD)
-
-    def get(self):
-        """-> the payload; asserts both guards first."""
-        raw = self.t.cpu().numpy()
-        assert (raw[:PAD] == FILL).all() and (raw[PAD + self.nbytes:] == FILL).all(), "a guard changed"
-        return raw[PAD:PAD + self.nbytes].view(self.dtype).reshape(self.shape)
 
 
 def _same_bits(a, b):

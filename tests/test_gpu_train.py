@@ -229,6 +229,21 @@ def test_bad_shapes_are_rejected():
         tr.partial_fit(np.zeros((3, 64, 3), np.float32))
 
 
+def test_arena_places_the_visible_buffers_where_recorded():
+    """tests/golden/trainer_offsets.json (tools/make_golden_trainer_offsets.py): the gradient buffer and every _state_view item,
+    in bytes from the parameter buffer, as the arena placed them before one function carved it."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import make_golden_trainer_offsets as G
+    with open(os.path.join(root, "tests", "golden", "trainer_offsets.json")) as f:
+        golden = json.load(f)
+    assert sorted(golden) == sorted(G.CASES)
+    for name in G.CASES:
+        assert G.offsets(name) == golden[name], name
+
+
 _DP_WORKER = r"""
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.getcwd())
