@@ -336,13 +336,15 @@ extern "C" int geoadv_ae_set_encoder_arith(geoadv_ae *ae, int arith) {
 }
 extern "C" int geoadv_ae_encoder_arith(const geoadv_ae *ae) { return ae ? ae->d.enc_arith : -1; }
 
-// The f16x2 range guard's verdict (encoder_x3.h): synchronises, reads and clears the model's flag.
+// The f16x2 range guard's verdict (encoder_x3.h): reads the model's flag behind everything queued on `stream`, synchronises, and
+// clears a raised flag ON `stream` -- a forward queued on that stream next runs behind the clear and keeps the flag it raises (a
+// clear on the null stream is not ordered against a non-blocking stream's later work).
 int geoadv::ae_range_check(const geoadv_ae *ae, hipStream_t stream, const char *who) {
-    GA_HIP(hipStreamSynchronize(stream));
     int flag = 0;
-    GA_HIP(hipMemcpy(&flag, ae->d.range_flag, sizeof(int), hipMemcpyDeviceToHost));
+    GA_HIP(hipMemcpyAsync(&flag, ae->d.range_flag, sizeof(int), hipMemcpyDeviceToHost, stream));
+    GA_HIP(hipStreamSynchronize(stream));
     if (!flag) return GEOADV_OK;
-    GA_HIP(hipMemset(ae->d.range_flag, 0, sizeof(int)));
+    GA_HIP(hipMemsetAsync(ae->d.range_flag, 0, sizeof(int), stream));
     set_error("%s: an encoder forward in the f16x2 arithmetic met an activation outside the fp16 range of its scaled operands (1023.5 x "
               "the magnitude its layer's batch-norm constants announce; layer scales 2^%d 2^%d 2^%d 2^%d): the latents of the clouds "
               "concerned were set to +inf.  Use GEOADV_ENC_ARITH_BF16X3 for this model", who, ilogbf(ae->d.h2_act_scale[0]),

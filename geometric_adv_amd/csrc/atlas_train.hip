@@ -534,9 +534,12 @@ extern "C" int geoadv_atlas_trainer_set_learning_rate(geoadv_atlas_trainer *t, f
     GA_REQUIRE(t, "atlas_trainer_set_learning_rate: null handle");
     GA_REQUIRE(learning_rate >= 0.f, "atlas_trainer_set_learning_rate: the learning rate must be >= 0");
     if (reset_optimizer) {
+        // no stream argument: wait for every step in flight on any stream, clear on the null stream, and return only once the
+        // clear is done -- a step queued afterwards on a non-blocking stream (which the null stream does not order) sees zeros
         GA_HIP(hipDeviceSynchronize());
-        GA_HIP(hipMemset(t->slot1, 0, sizeof(float) * t->P));
-        GA_HIP(hipMemset(t->slot2, 0, sizeof(float) * t->P));
+        GA_HIP(hipMemsetAsync(t->slot1, 0, sizeof(float) * t->P, nullptr));
+        GA_HIP(hipMemsetAsync(t->slot2, 0, sizeof(float) * t->P, nullptr));
+        GA_HIP(hipStreamSynchronize(nullptr));
         t->step = 0;
     }
     t->lr = learning_rate;

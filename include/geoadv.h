@@ -495,7 +495,10 @@ int  geoadv_set_default_encoder_arith(int arith);
 int  geoadv_ae_set_encoder_arith(geoadv_ae *ae, int arith);
 int  geoadv_ae_encoder_arith(const geoadv_ae *ae);
 /* Synchronises `stream`; GEOADV_ERANGE (message in geoadv_last_error; the flag is cleared) if an F16X2 forward of this model since
- * the last call met an activation outside its range, else GEOADV_OK.  Callers that synchronise anyway (to read results) call it. */
+ * the last call met an activation outside its range, else GEOADV_OK.  Callers that synchronise anyway (to read results) call it.
+ * The flag is read behind everything queued on `stream` and cleared ON `stream`: a forward queued on that stream directly after
+ * the call keeps the flag it raises.  Forwards of the model in flight on OTHER streams are not waited for: a caller that runs one
+ * model on several streams synchronises those itself before it trusts GEOADV_OK. */
 int  geoadv_ae_status(const geoadv_ae *ae, void *stream);
 
 /* AdversaryAutoEncoder.reconstruct / AutoEncoder.transform (adversary_autoencoder.py:75-91):
@@ -641,6 +644,8 @@ typedef struct geoadv_cls_train_config {
  * powers at 0.9 / 0.999; geoadv_cls_trainer_set_slots restores them (flat, in the parameter layout). */
 int  geoadv_cls_trainer_create(geoadv_cls_trainer **out, const geoadv_cls_weights *init, const geoadv_cls_train_config *cfg);
 void geoadv_cls_trainer_destroy(geoadv_cls_trainer *t);
+/* set_slots takes no stream: a synchronous copy from HOST memory (hipMemcpy), complete on return.  It does not wait for a step in
+ * flight: the caller must have synchronised every stream on which a step of this handle was queued. */
 int  geoadv_cls_trainer_set_slots(geoadv_cls_trainer *t, const float *slot1, const float *slot2, float beta1_power, float beta2_power);
 /* x: device [batch][n][3], labels: device int32 [batch]; loss (device float, of the PRE-update variables) and pred (device
  * int32 [batch], argmax of the logits) may be NULL.  Updates the variables, slots, moving averages and the step counter. */
@@ -793,6 +798,8 @@ typedef struct geoadv_fold_train_config {
  * slots start at zero; geoadv_fold_trainer_set_slots restores exp_avg / exp_avg_sq (flat, in the parameter layout). */
 int  geoadv_fold_trainer_create(geoadv_fold_trainer **out, const geoadv_fold_weights *init, const geoadv_fold_train_config *cfg);
 void geoadv_fold_trainer_destroy(geoadv_fold_trainer *t);
+/* set_slots takes no stream: a synchronous copy from HOST memory (hipMemcpy), complete on return.  It does not wait for a step in
+ * flight: the caller must have synchronised every stream on which a step of this handle was queued. */
 int  geoadv_fold_trainer_set_slots(geoadv_fold_trainer *t, const float *slot1, const float *slot2);
 /* x: device [batch][n][3].  sampling / picks (device int32 [2][batch][n][16]) as geoadv_fold_forward: read with
  * GEOADV_FOLD_PICKS_GIVEN, written (may be NULL) with GEOADV_FOLD_PICKS_DEVICE, where cloud k draws with ordinal
@@ -883,9 +890,13 @@ typedef struct geoadv_atlas_train_config {
 int  geoadv_atlas_trainer_create(geoadv_atlas_trainer **out, const geoadv_atlas_config *config, const geoadv_atlas_weights *init,
                                  const geoadv_atlas_train_config *cfg);
 void geoadv_atlas_trainer_destroy(geoadv_atlas_trainer *t);
+/* set_slots takes no stream: a synchronous copy from HOST memory (hipMemcpy), complete on return.  It does not wait for a step in
+ * flight: the caller must have synchronised every stream on which a step of this handle was queued. */
 int  geoadv_atlas_trainer_set_slots(geoadv_atlas_trainer *t, const float *slot1, const float *slot2);
 /* The reference builds a NEW Adam with lrate / 10 at its decay epochs: reset_optimizer != 0 zeroes both slots and the
- * Adam step count as well (num_batches_tracked goes on). */
+ * Adam step count as well (num_batches_tracked goes on).  No stream: with reset_optimizer the call synchronises the DEVICE (every
+ * step in flight on any stream finishes first), clears the slots and returns once the clear is complete, so the caller has
+ * nothing to synchronise; without it only host state changes, which the next step reads when it is queued. */
 int  geoadv_atlas_trainer_set_learning_rate(geoadv_atlas_trainer *t, float learning_rate, int reset_optimizer);
 /* x: device [batch][n_points][3].  template_points: device [nb_primitives][points_per_primitive][2], read if
  * given_template != 0, else written with the step's draw (may then be NULL).  loss (a device float, of the PRE-update
@@ -998,6 +1009,9 @@ typedef struct geoadv_attack_config {
 #define GEOADV_CHAMFER_TWO_SCAN  1
 #define GEOADV_CHAMFER_SYMMETRIC 2
 
+/* Allocates device memory; synchronous.  Its own device work -- the arena's zero fill and, for the symmetric scan, a probe launch of
+ * how the device deals workgroups to its XCDs, which writes the handle's own scratch -- runs on the null stream and is complete
+ * on return; the caller has nothing to synchronise, and no stream of the caller's is waited for. */
 int  geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, const geoadv_attack_config *cfg);
 void geoadv_attack_destroy(geoadv_attack *at);
 
@@ -1161,6 +1175,8 @@ int geoadv_trainer_apply(geoadv_trainer *t, float grad_scale, void *stream);
  * sum-all-reduces the *count doubles geoadv_trainer_exchange(t, p, ...) points at (RCCL; <= 4 KB, latency-bound) and
  * runs phase p + 1.  After the last phase: all-reduce the flat gradient buffer, geoadv_trainer_apply(t, 1.0f), and add
  * up the ranks' geoadv_trainer_fetch losses.  geoadv_trainer_set_world(t, world) switches the mode (1 = off). */
+/* set_world takes no stream: it uploads the new gradient scale with a synchronous copy from host memory, complete on return, and
+ * does not wait for a step in flight -- the caller must have synchronised every stream on which a step of this handle was queued. */
 int geoadv_trainer_set_world(geoadv_trainer *t, int world);
 int geoadv_trainer_num_phases(void);
 int geoadv_trainer_run_phase(geoadv_trainer *t, int phase, const float *x, const float *gt, void *stream);
@@ -1190,8 +1206,9 @@ int geoadv_trainer_layout(const geoadv_trainer *t, size_t *offsets26);
 #define GEOADV_TRAIN_STATE_DEC1        9
 #define GEOADV_TRAIN_STATE_DEC2        10
 int geoadv_trainer_state(const geoadv_trainer *t, int what, int layer, const void **ptr, size_t *count);
-/* Downloads the current variables (and moving averages) into the HOST buffers `dst` points to -- what
- * saver.save writes (autoencoder.py:213-215); feed them to geoadv_ae_create to attack the trained model. */
+/* Synchronises `stream` and downloads the current variables (and moving averages) into the HOST buffers `dst` points to -- what
+ * saver.save writes (autoencoder.py:213-215); feed them to geoadv_ae_create to attack the trained model.  The steps to be
+ * exported must have been queued on `stream` (or be complete). */
 int geoadv_trainer_export(geoadv_trainer *t, const geoadv_ae_weights *dst, void *stream);
 
 /* Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg).

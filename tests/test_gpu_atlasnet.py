@@ -149,17 +149,13 @@ def test_bit_exact_invariances():
 
 
 def test_non_default_stream_same_bits():
+    """The delayed-call protocol of tests/_stream_order.py: behind a pending delay on a side stream, over scratch that holds
+    another batch's values, the forward gives the default stream's bits and does not block the host."""
     import torch
+    import _stream_order as SO
     ae = _ae(25, 2, True)
-    x = torch.from_numpy(_clouds(31, 10, 1500)).to("cuda:0")
-    want = [t.clone() for t in ae.forward(x)]
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        got = ae.forward(x)
-    s.synchronize()
-    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    a, b = (torch.from_numpy(_clouds(s, 10, 1500)).to("cuda:0") for s in (30, 31))
+    SO.check_call("atlasnet.forward", ae.forward, [a], [b], keep=ae)
 
 
 def test_nonfinite_cloud_is_isolated():

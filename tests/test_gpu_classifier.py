@@ -156,17 +156,12 @@ def test_refusals():
 
 
 def test_non_default_stream_same_bits():
-    import torch
+    """The delayed-call protocol of tests/_stream_order.py: behind a pending delay on a side stream, over scratch that holds
+    another batch's values, the forward gives the default stream's bits and does not block the host."""
+    import _stream_order as SO
     clf = _clf(40)
-    x = _dev(_clouds(31, 10, 1500))
-    want = clf.logits(x)
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        got = clf.logits(x)
-    s.synchronize()
-    assert torch.equal(got, want)
+    SO.check_call("classifier.forward", lambda x: clf.forward(x, transforms=True), [_dev(_clouds(30, 10, 1500))],
+                  [_dev(_clouds(31, 10, 1500))], keep=clf)
 
 
 def _eval_folder(root, n, classes, sizes, dist_weights):

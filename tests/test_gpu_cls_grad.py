@@ -217,13 +217,12 @@ def test_bit_exact_invariances():
         batch[pos], yb[pos] = cloud[0], y[0]
         got = clf.input_gradient(_dev(batch), _dev(yb), "cw_targeted", KAPPA, return_logits=True, return_winners=True)
         assert all(torch.equal(a[pos], b[0]) for a, b in zip(got, alone)), (size, pos)
-    side = torch.cuda.Stream()
-    xd, yd = _dev(cloud), _dev(y)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        streamed = clf.input_gradient(xd, yd, "cw_targeted", KAPPA, return_logits=True, return_winners=True)
-    side.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(streamed, alone))
+    # on a side stream: the delayed-call protocol of tests/_stream_order.py (behind a pending delay, over scratch that holds
+    # another cloud's values: the default stream's bits, and the host is not blocked)
+    import _stream_order as SO
+    SO.check_call("classifier.input_gradient",
+                  lambda xd, yd: clf.input_gradient(xd, yd, "cw_targeted", KAPPA, return_logits=True, return_winners=True),
+                  [_dev(others[:1]), _dev(((y + 1) % 13).astype(y.dtype))], [_dev(cloud), _dev(y)], keep=clf)
 
 
 def test_point_permutation_permutes_winners_and_gradient():
