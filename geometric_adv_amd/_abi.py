@@ -275,7 +275,8 @@ class AttackConfig(C.Structure):
                 ("max_point_pert_weight", C.c_float), ("max_point_dist_weight", C.c_float),
                 ("learning_rate", C.c_float), ("emd_weight", C.c_float), ("all_pairs_source_dist", C.c_int),
                 ("emd_weight_mode", C.c_int), ("recompute_backward", C.c_int), ("encoder_backward", C.c_int),
-                ("separate_adam", C.c_int), ("chamfer_kernel", C.c_int), ("loss_in_scan", C.c_int)]
+                ("separate_adam", C.c_int), ("chamfer_kernel", C.c_int),
+                ("knn_weight", C.c_float), ("knn_k", C.c_int), ("knn_alpha", C.c_float), ("loss_in_scan", C.c_int)]
 
 
 class TrainConfig(C.Structure):

@@ -5,6 +5,7 @@ by a device-resident loop in libgeoadv.so (geoadv_attack_*): one fused forward p
 sparse encoder backward, CPU-ordered Chamfer gradients, TF-1.13-form Adam on the perturbation.
 """
 import ctypes as C
+import math
 import time
 
 import numpy as np
@@ -26,7 +27,8 @@ class Configuration:
                  max_point_dist_weight=0.0, num_iterations=500, num_iterations_thresh=400,
                  learning_rate=0.01, ae_name="autoencoder", emd_weight=0.0, verbose=False, batch_slots=1,
                  chamfer_prune=True, emd_reference_weights=False, recompute_backward=False, separate_adam=False,
-                 chamfer_kernel="auto", encoder_backward="auto", emd_dense_levels=False, encoder_arith=None, loss_in_scan=True):
+                 chamfer_kernel="auto", encoder_backward="auto", emd_dense_levels=False, encoder_arith=None, loss_in_scan=True,
+                 knn_weight=0.0, knn_k=5, knn_alpha=1.05):
         self.batch_size = int(batch_size)
         self.n_input = [int(n_points), 3]
         self.n_output = [int(n_points), 3]
@@ -66,11 +68,32 @@ class Configuration:
         if loss_in_scan not in (True, False, "always"):
             raise ValueError("loss_in_scan must be True (where it pays), False or 'always'")
         self.loss_in_scan = loss_in_scan                     # False: the loss + gradient pass always as a launch of its own; "always": riding wherever possible
+        # The kNN outlier term (geoadv_attack_config.knn_weight): loss_adv + dist_weight * (loss_dist + knn_weight * K(adv)), K the
+        # loss of ops.knn_outlier_loss(adv, knn_k, knn_alpha) -- the attack that keeps its points where sor_filter leaves them alone.
+        # 0 = off: knn_k and knn_alpha are then not looked at.  Refused here, before any device is touched, as the library refuses.
+        self.knn_weight, self.knn_k, self.knn_alpha = float(knn_weight), int(knn_k), float(knn_alpha)
+        if self.knn_weight != 0.0:
+            n = self.n_input[0]
+            if not math.isfinite(self.knn_weight):
+                raise ValueError("knn_weight must be finite (got %r)" % self.knn_weight)
+            if loss_dist_type == "pert":
+                raise ValueError("knn_weight needs loss_dist_type='chamfer': the 'pert' path has no Chamfer gradient to add the term to")
+            if not 1 <= self.knn_k <= KNN_TERM_MAX_K:
+                raise ValueError("knn_k must be in [1, %d] (got %d)" % (KNN_TERM_MAX_K, self.knn_k))
+            # (the library takes knn_alpha as a float: the op's alpha in the loop is float32(knn_alpha) widened to double)
+            if not (self.knn_alpha >= 0.0 and math.isfinite(self.knn_alpha) and self.knn_alpha <= 3.4028234663852886e38):
+                raise ValueError("knn_alpha must be finite and >= 0 (got %r)" % self.knn_alpha)
+            if not self.knn_k + 2 <= n <= KNN_TERM_MAX_POINTS:
+                raise ValueError("the kNN term needs clouds of knn_k + 2 = %d <= n_points <= %d (got %d)"
+                                 % (self.knn_k + 2, KNN_TERM_MAX_POINTS, n))
+            if self.batch_size > KNN_TERM_MAX_BATCH:
+                raise ValueError("the kNN term takes at most %d clouds per batch (got %d)" % (KNN_TERM_MAX_BATCH, self.batch_size))
 
 
 CHAMFER_KERNELS = {"auto": _abi.GEOADV_CHAMFER_AUTO, "two_scan": _abi.GEOADV_CHAMFER_TWO_SCAN, "symmetric": _abi.GEOADV_CHAMFER_SYMMETRIC}
 ENCODER_BACKWARDS = {"auto": _abi.GEOADV_ENC_BWD_AUTO, "masked": _abi.GEOADV_ENC_BWD_MASKED, "jacobian": _abi.GEOADV_ENC_BWD_JACOBIAN}
 # kernel classes of the profiler in the order of their codes, GEOADV_PROF_<NAME> = 0 .. GEOADV_PROF_COUNT - 1
+KNN_TERM_MAX_K, KNN_TERM_MAX_POINTS, KNN_TERM_MAX_BATCH = 15, 16384, 65535     # the limits of ops.knn_outlier_loss (include/geoadv.h)
 PROF_NAMES = ["encoder_fwd", "decoder_fwd", "chamfer_fwd", "loss_grad", "decoder_bwd", "encoder_bwd", "adam"]
 
 
@@ -98,7 +121,9 @@ class AdvAE:
                             {True: 0, "pinned": 0, False: 1, "always": 2}[getattr(c, "chamfer_prune", True)], emd_mode,
                             1 if getattr(c, "recompute_backward", False) else 0, ENCODER_BACKWARDS[getattr(c, "encoder_backward", "auto")],
                             1 if getattr(c, "separate_adam", False) else 0,
-                            CHAMFER_KERNELS[getattr(c, "chamfer_kernel", "auto")], {True: 0, False: 1, "always": 2}[getattr(c, "loss_in_scan", True)])
+                            CHAMFER_KERNELS[getattr(c, "chamfer_kernel", "auto")],
+                            float(getattr(c, "knn_weight", 0.0)), int(getattr(c, "knn_k", 5)), float(getattr(c, "knn_alpha", 1.05)),
+                            {True: 0, False: 1, "always": 2}[getattr(c, "loss_in_scan", True)])
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().geoadv_attack_create(C.byref(self._h), self.ae.handle, C.byref(cfg)), "attack_create")

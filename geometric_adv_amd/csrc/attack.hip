@@ -13,6 +13,7 @@
 #include "chamfer_grid.h"
 #include "encoder_jac.h"
 #include "decoder_tail.h"
+#include "knn_loss.h"
 #define LC_STAMP(K, I) GA_STAMP(K, I)
 #include "loss_cgrad.h"
 #include "host_util.h"
@@ -193,6 +194,8 @@ struct geoadv_attack {
     float *losses; int *jstar;
     float *best_err, *best_metrics, *best_adv, *best_recon;
     float *emd_temp, *emd_cost, *emd_g1;   // only when cfg.emd_weight > 0
+    char *knn_ws; size_t knn_ws_bytes;     // only when cfg.knn_weight != 0: the kNN outlier term's workspace (knn_loss.h) ...
+    double *knn_loss;                      // ... and K of the cached forward's adv, [B]
     float *sym_ws;                   // row / column partials of the symmetric Chamfer kernel
     unsigned long long *row64;       // [2][B][n] packed row minima of the symmetric scan's atomic form (8 or more column slices, chamfer_sym.h)
     int test_loss_form = 0;          // geoadv_attack_test_loss_form (tests only): how the row minima reach the loss launch and which bodies read them
@@ -510,6 +513,11 @@ int do_step(geoadv_attack *at, hipStream_t st) {
             if (int rc = launch_cgrad(pr, np, B, n, st)) return rc;
     }
     at->cgrad_done = false;
+    if (at->knn_ws) {   // g_dist += dist_weight[b] * (knn_weight * dK/dadv): the kNN outlier term on the cached forward's adv, mask held constant
+        ProfScope ps(at, GEOADV_PROF_LOSS_GRAD, st);
+        if (int rc = launch_knn_term(B, n, at->cfg.knn_k, (double)at->cfg.knn_alpha, at->cfg.knn_weight, at->w, at->adv, at->g_dist, at->knn_loss,
+                                     at->knn_ws, at->knn_ws_bytes, st)) return rc;
+    }
     if (adv_chamfer && at->emd_temp) {   // d(emd_weight * cost / n)/d recon, match held constant: emd_g1 came with the cached forward
         ProfScope ps(at, GEOADV_PROF_LOSS_GRAD, st);
         const size_t total = (size_t)B * n * 3;
@@ -606,6 +614,12 @@ size_t carve_arena(geoadv_attack *at, void *base) {
         at->emd_temp = F(geoadv_emd_cost_grad1_temp_floats(at->B, at->n, at->n) + 2);
         at->emd_cost = F(B); at->emd_g1 = F(bn3);
     }
+    at->knn_ws = nullptr; at->knn_ws_bytes = 0; at->knn_loss = nullptr;
+    if (cfg.knn_weight != 0.f) {
+        at->knn_ws_bytes = geoadv_knn_outlier_loss_workspace_bytes(at->B, at->n, cfg.knn_k);
+        at->knn_ws = c.take<char>(at->knn_ws_bytes);
+        at->knn_loss = c.take<double>(B);
+    }
     return c.bytes();
 }
 
@@ -641,6 +655,16 @@ extern "C" int geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, co
                "attack_create: unknown chamfer_kernel %d", cfg->chamfer_kernel);
     GA_REQUIRE(cfg->emd_weight == 0.f || cfg->loss_adv_type == GEOADV_LOSS_ADV_CHAMFER,
                "attack_create: emd_weight needs the output-space attack (loss_adv_type chamfer)");
+    if (cfg->knn_weight != 0.f) {      // (0 = off: knn_k and knn_alpha are not read)
+        const int n = ae->d.n_points;
+        GA_REQUIRE(isfinite(cfg->knn_weight), "attack_create: knn_weight must be finite (got %g)", (double)cfg->knn_weight);
+        GA_REQUIRE(cfg->loss_dist_type == GEOADV_LOSS_DIST_CHAMFER,
+                   "attack_create: knn_weight needs loss_dist_type chamfer (the 'pert' path has no Chamfer gradient g_dist to add the term to)");
+        GA_REQUIRE(cfg->knn_k >= 1 && cfg->knn_k <= 15, "attack_create: knn_k=%d must be in [1, 15]", cfg->knn_k);
+        GA_REQUIRE(cfg->knn_alpha >= 0.f && isfinite(cfg->knn_alpha), "attack_create: knn_alpha must be finite and >= 0 (got %g)", (double)cfg->knn_alpha);
+        GA_REQUIRE(n >= cfg->knn_k + 2 && n <= 16384, "attack_create: the kNN term needs clouds of knn_k + 2 = %d <= n <= 16384 points (n=%d)",
+                   cfg->knn_k + 2, n);
+    }
     geoadv_attack *at = new geoadv_attack();
     at->ae = ae; at->cfg = *cfg; at->B = cfg->batch; at->n = ae->d.n_points;
     const size_t total = at->arena_bytes = carve_arena(at, nullptr);      // over a null base: measured only

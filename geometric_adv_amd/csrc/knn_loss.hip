@@ -22,6 +22,7 @@
 // read by other waves of the same workgroup after __syncthreads(), through the L1 they share.
 #include <math.h>
 #include "stat_sums.h"
+#include "knn_loss.h"
 
 namespace geoadv {
 
@@ -58,10 +59,27 @@ __device__ __forceinline__ void kl_add_diff(double (&G)[3], const float (&xi)[3]
     for (int a = 0; a < 3; ++a) G[a] += (double)xi[a] - (double)xj[a];
 }
 
+// How a point's gradient leaves the launch.  The op (APPLY = false) stores it: grad_i = (float)(G_i * scale).  The attack loop's
+// instance (APPLY = true, launch_knn_term below) adds it, weighted, to the Chamfer gradient that is already there:
+//   g_i <- fadd_rn(g_i, fmul_rn(dist_weight[cloud], fmul_rn(knn_weight, grad_i)))       every product and the sum rounded to fp32
+template <bool APPLY>
+__device__ __forceinline__ void kl_emit(float *grad, int i, const double (&G)[3], double scale, float weight, float wb) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float d = (float)__dmul_rn(G[a], scale);
+        if (APPLY) grad[3 * i + a] = __fadd_rn(grad[3 * i + a], __fmul_rn(wb, __fmul_rn(weight, d)));
+        else grad[3 * i + a] = d;
+    }
+}
+
+// APPLY: grad_all is the loop's g_dist [b,n,3] (read and written), `weight` the handle's knn_weight, dist_weight [b] the per-cloud
+// weight the Chamfer gradient in g_dist already carries; score_all / mask_all / idx_all / stats are not looked at.
+template <bool APPLY>
 __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int k, double alpha2, const float *xyz, const int *nbr_all,
                                                                       double *sc_all, int *deg_all, int *cur_all, int *edge_all,
                                                                       int *hub_all, double *loss, float *grad_all, double *score_all,
-                                                                      unsigned char *mask_all, int *idx_all, double *stats) {
+                                                                      unsigned char *mask_all, int *idx_all, double *stats,
+                                                                      float weight, const float *dist_weight) {
     __shared__ KlLds L;
     const size_t cl = blockIdx.x;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -83,7 +101,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
             val[c] = 0.f;
             if (c < k) {
                 const int raw = nbr[(size_t)p * stride + 1 + c];
-                if (idx_all) idx_all[(cl * n + p) * k + c] = raw;
+                if (!APPLY && idx_all) idx_all[(cl * n + p) * k + c] = raw;
                 const int j = min(max(raw, 0), n - 1);
                 const float dx = px - x[3 * j], dy = py - x[3 * j + 1], dz = pz - x[3 * j + 2];
                 val[c] = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
@@ -95,7 +113,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
         s = s / (double)k;
         sc[p] = s;
         deg[p] = 0;
-        if (score_all) score_all[cl * n + p] = s;
+        if (!APPLY && score_all) score_all[cl * n + p] = s;
         const bool fin = isfinite(s);
         acc += fin ? s : 0.0;
         cnt += fin ? 1.0 : 0.0;
@@ -120,7 +138,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
     for (int p = t; p < n; p += DF_THREADS) {
         const double s = sc[p];
         const bool w = kl_masked(s, st);
-        if (mask_all) mask_all[cl * n + p] = w ? 1 : 0;
+        if (!APPLY && mask_all) mask_all[cl * n + p] = w ? 1 : 0;
         acc += w ? s : 0.0;
         cnt += w ? 1.0 : 0.0;
         if (w && grad_all)
@@ -130,10 +148,11 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
     const double lsum = sd_block_sum64(acc, L.wsum);
     if (t == 0) {
         loss[cl] = lsum / (double)n;
-        if (stats) { stats[4 * cl] = st.mu; stats[4 * cl + 1] = var; stats[4 * cl + 2] = m; stats[4 * cl + 3] = nmask; }
+        if (!APPLY && stats) { stats[4 * cl] = st.mu; stats[4 * cl + 1] = var; stats[4 * cl + 2] = m; stats[4 * cl + 3] = nmask; }
     }
     if (!grad_all) return;
     float *grad = grad_all + cl * n * 3;
+    const float wb = APPLY ? dist_weight[cl] : 1.0f;
 
     // ---- C: exclusive scan of the in-degrees, 1024 targets a round: cur[i] = the start of target i's segment ----------------------
     int base = 0;
@@ -196,8 +215,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
             done += mult;
             last = next;
         }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) grad[3 * i + a] = (float)__dmul_rn(G[a], scale);
+        kl_emit<APPLY>(grad, i, G, scale, weight, wb);
     }
     __syncthreads();
 
@@ -226,10 +244,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
                 for (int r = 0; r < reps; ++r) kl_add_diff(G, xi, xs);
             }
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) grad[3 * i + a] = (float)__dmul_rn(G[a], scale);
-        }
+        if (lane == 0) kl_emit<APPLY>(grad, i, G, scale, weight, wb);
     }
 }
 
@@ -286,8 +301,22 @@ static int kl_check(const char *op, int b, int n, int k, double alpha, const flo
 
 static int kl_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad, double *score, unsigned char *mask,
                      int *idx, double *stats, const KlScratch &s, hipStream_t st) {
-    knn_outlier_loss_kernel<<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, grad, score, mask,
-                                                      idx, stats);
+    knn_outlier_loss_kernel<false><<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, grad, score,
+                                                             mask, idx, stats, 0.f, nullptr);
+    GA_LAUNCH_CHECK();
+    return GEOADV_OK;
+}
+
+// The term of the attack loop (attack.hip: do_step; the rule at geoadv_attack_config in include/geoadv.h): the op's search with its
+// default kernel choice, then the APPLY instance of the launch, both on `st`, both on the caller's workspace
+// (geoadv_knn_outlier_loss_workspace_bytes(b, n, k) bytes).  The shape was checked when the handle was created.
+int launch_knn_term(int b, int n, int k, double alpha, float weight, const float *dist_weight, const float *xyz, float *g_dist,
+                    double *loss, void *workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int rc = kl_check("attack knn term", b, n, k, alpha, xyz, loss, g_dist, workspace, workspace_bytes)) return rc;
+    const KlScratch s = kl_scratch(workspace, b, n, k);
+    if (int rc = geoadv_knn_point_ws(GEOADV_KNN_AUTO, b, n, n, k + 1, xyz, xyz, s.val, s.idx, s.knn, s.knn_bytes, st)) return rc;
+    knn_outlier_loss_kernel<true><<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, g_dist,
+                                                            nullptr, nullptr, nullptr, nullptr, weight, dist_weight);
     GA_LAUNCH_CHECK();
     return GEOADV_OK;
 }

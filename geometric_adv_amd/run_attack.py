@@ -42,7 +42,26 @@ def build_parser():
     p.add_argument('--class_names', nargs='+', default=None, help='classes to attack / target [default: all]')
     p.add_argument('--batch_slots', type=int, default=1,
                    help='batches attacked concurrently on each GPU (AdvAE.attack; not a reference flag) [default: 1]')
+    p.add_argument('--knn_weight', type=float, default=0.0,
+                   help='weight of the kNN outlier term inside the distance loss: loss_adv + dist_weight * (loss_dist + knn_weight * K(adv)), '
+                        'the attack that keeps its points where run_defense_sor leaves them alone (not a reference flag) [default: 0 = off]')
+    p.add_argument('--knn_k', type=int, default=5, help='neighbours of the kNN outlier term [default: 5]')
+    p.add_argument('--knn_alpha', type=float, default=1.05, help="the kNN outlier term's threshold, mu + alpha * sigma [default: 1.05]")
     return p
+
+
+def knn_loss_of(adversarial_pc_input, knn_k, knn_alpha, device):
+    """adversarial_knn_loss.npy: [W, num, 2] float64 = (K, the number of masked points) of every saved adversarial cloud, from
+    ops.knn_outlier_loss(..., return_parts=True) on one dist-weight's clouds at a time."""
+    import torch
+    from . import ops
+    out = np.zeros(adversarial_pc_input.shape[:2] + (2,), np.float64)
+    for w, clouds in enumerate(adversarial_pc_input):
+        parts = ops.knn_outlier_loss(torch.as_tensor(clouds, dtype=torch.float32, device=device), knn_k, knn_alpha,
+                                     want_grad=False, return_parts=True)
+        out[w, :, 0] = parts[0].cpu().numpy()
+        out[w, :, 1] = parts[5][:, 3].cpu().numpy()
+    return out
 
 
 def victim_weights_path(ae_dir, restore_epoch):
@@ -87,17 +106,23 @@ def main(argv=None):
                          dist_weight_list=[float(w) for w in flags.dist_weight_list],
                          max_point_pert_weight=flags.max_point_pert_weight, max_point_dist_weight=flags.max_point_dist_weight,
                          num_iterations=flags.num_iterations, num_iterations_thresh=flags.num_iterations_thresh,
-                         learning_rate=flags.learning_rate, batch_slots=flags.batch_slots)
+                         learning_rate=flags.learning_rate, batch_slots=flags.batch_slots,
+                         knn_weight=flags.knn_weight, knn_k=flags.knn_k, knn_alpha=flags.knn_alpha)
+    knn_on = conf.knn_weight != 0.0
+    # a run without the term writes the bytes it always wrote: the three values appear in its files only when the term is on
+    knn_conf = {'knn_weight': conf.knn_weight, 'knn_k': conf.knn_k, 'knn_alpha': conf.knn_alpha} if knn_on else {}
+    shown_flags = flags if knn_on else argparse.Namespace(**{k: v for k, v in vars(flags).items() if not k.startswith('knn_')})
     if rank == 0:      # the reference pickles its Configuration here (run_attack.py:109; unpickling needs tflearn): same fields as JSON
         import json
         with open(osp.join(output_path, 'attack_configuration.json'), 'w') as f:
-            json.dump({'class_names': classes, 'target_pc_idx_type': flags.target_pc_idx_type,
+            json.dump({**{'class_names': classes, 'target_pc_idx_type': flags.target_pc_idx_type,
                        'num_pc_for_attack': flags.num_pc_for_attack, 'num_pc_for_target': flags.num_pc_for_target,
                        'correct_pred_only': flags.correct_pred_only, 'dist_weight_list': conf.dist_weight_list,
                        'batch_size': flags.batch_size, 'learning_rate': flags.learning_rate, 'loss_adv_type': flags.loss_adv_type,
                        'loss_dist_type': flags.loss_dist_type, 'num_iterations': flags.num_iterations,
                        'num_iterations_thresh': flags.num_iterations_thresh, 'restore_epoch': flags.restore_epoch,
-                       'max_point_pert_weight': flags.max_point_pert_weight, 'max_point_dist_weight': flags.max_point_dist_weight}, f)
+                       'max_point_pert_weight': flags.max_point_pert_weight, 'max_point_dist_weight': flags.max_point_dist_weight},
+                       **knn_conf}, f)
     import torch
     dev = torch.device("cuda", local)
     ae = None
@@ -116,7 +141,7 @@ def main(argv=None):
         target_ae_loss_ref = target_ae_loss_ref.reshape(-1)
         # rank 0 writes attack_stats.txt like the reference; the other ranks log THEIR batches to attack_stats.rank<r>.txt
         fout = open(osp.join(save_dir, 'attack_stats.txt' if rank == 0 else 'attack_stats.rank%d.txt' % rank), 'a', 1)
-        fout.write('Train flags: %s\n' % flags)
+        fout.write('Train flags: %s\n' % shown_flags)
         if world > 1:
             metrics, pc_in, pc_rec, _ = gdist.attack_sharded(adv, source_pc, target_latent, target_pc, target_ae_loss_ref,
                                                              gather_clouds=True, log_file=fout)
@@ -129,6 +154,8 @@ def main(argv=None):
             np.save(osp.join(save_dir, 'adversarial_pc_input'), pc_in)
             np.save(osp.join(save_dir, 'adversarial_pc_recon'), pc_rec)
             np.save(osp.join(save_dir, 'dist_weight'), np.array(conf.dist_weight_list))
+            if knn_on:
+                np.save(osp.join(save_dir, 'adversarial_knn_loss'), knn_loss_of(pc_in, conf.knn_k, conf.knn_alpha, dev))
 
 
 if __name__ == '__main__':

@@ -990,6 +990,30 @@ typedef struct geoadv_attack_config {
                                      * instead of riding in the next forward's point loaders                           */
     int   chamfer_kernel;           /* GEOADV_CHAMFER_AUTO (0: by batch size, GEOADV_SYM_MIN_POINTS), _TWO_SCAN (the public op's kernel),
                                      * _SYMMETRIC (one evaluation per pair serves both directions)                      */
+    /* The kNN outlier term: the defense-aware (adaptive) attack.  With knn_weight != 0 the loop minimises, per cloud b,
+     *   loss_adv + dist_weight[b] * (loss_dist + knn_weight * K(adv))
+     * K and dK/dadv EXACTLY the rule of geoadv_knn_outlier_loss above with k = knn_k and alpha = (double)knn_alpha (search knn_point(k + 1),
+     * SOR statistics in float64, mask held constant, float64 accumulation in the stated order, one rounding to fp32), applied to the
+     * fp32 cloud adv = x + pert of the cached forward -- the cloud the step's backward kernels read.  It enters the step as
+     *   g_dist[b,i] <- fadd_rn(g_dist[b,i], fmul_rn(dist_weight[b], fmul_rn(knn_weight, dK[b,i])))
+     * both products and the sum each rounded to fp32, no contraction: the loop's Chamfer gradient g_dist already carries
+     * dist_weight[b] when it is formed (Adam adds g_dist as it stands), so the term takes the same factor here.  This happens in
+     * the step after g_dist exists -- from the forward's loss launch or from the step's own gradient launch, max-point branch
+     * included -- and before the decoder / encoder backward and the Adam step, whether Adam is its own launch or rides in the next
+     * forward's loaders.  Two launches more per iteration (the search, and a second instance of the op's gradient launch that adds
+     * in place and writes nothing else), on the run's stream, counted under GEOADV_PROF_LOSS_GRAD; their workspace
+     * (geoadv_knn_outlier_loss_workspace_bytes(batch, n, knn_k)) and a double[batch] for K are part of the handle's arena.
+     * The history rows of geoadv_attack_run, geoadv_attack_get_best and its keep-best rule, geoadv_attack_peek and the TESTS ONLY
+     * read-outs are unchanged and do not contain K.
+     * geoadv_attack_create returns GEOADV_EINVAL (nothing allocated) for knn_weight != 0 with: knn_weight not finite;
+     * loss_dist_type GEOADV_LOSS_DIST_PERT (that path has no g_dist); knn_k outside 1 ... 15; knn_alpha negative or not finite;
+     * n < knn_k + 2 or n > 16384; batch > 65535. */
+    float  knn_weight;              /* 0 (default) = off: nothing below is read, reserved or launched -- arena, launches and every
+                                     * output bit are those of a handle without these members                                 */
+    int    knn_k;                   /* 1 ... 15                                                                                */
+    float  knn_alpha;               /* >= 0, finite; the op's alpha is (double)knn_alpha                                    */
+    /* (The three members above stand before loss_in_scan, which stays the struct's last member, and are all int / float: callers
+     * that fill the struct by name, or zero it and set what they need, are not affected by their position.)                  */
     int   loss_in_scan;             /* 0 (default): the loss / metrics / keep-best and Chamfer-gradient workgroups ride as the last
                                      * workgroups of the symmetric scan's launch where that pays and it can host them (the paired
                                      * search in the launch and two scan workgroups per CU: batch >= 64 at 2048 points; both losses Chamfer, no EMD
