@@ -170,6 +170,7 @@ def ctypes_signature(name):
 GEOADV_OK, GEOADV_EINVAL = 0, 1
 GEOADV_EMD_FAST, GEOADV_EMD_REFERENCE, GEOADV_EMD_DENSE_LEVELS = 0, 1, 0x100
 GEOADV_KNN_AUTO, GEOADV_KNN_ALL_POINTS, GEOADV_KNN_GRID, GEOADV_KNN_GRID_SHELLS = 0, 1, 2, 3
+GEOADV_KNN_LOSS_SURFACE = 0x100
 GEOADV_FPS_AUTO, GEOADV_FPS_WORKGROUP, GEOADV_FPS_WAVE = 0, 1, 2
 GEOADV_NORMALIZE_IDENTITY, GEOADV_NORMALIZE_UNIT_BALL, GEOADV_NORMALIZE_BOUNDING_BOX = 0, 1, 2
 GEOADV_AUGMENT_RECORD = 45
@@ -276,6 +277,7 @@ class AttackConfig(C.Structure):
                 ("learning_rate", C.c_float), ("emd_weight", C.c_float), ("all_pairs_source_dist", C.c_int),
                 ("emd_weight_mode", C.c_int), ("recompute_backward", C.c_int), ("encoder_backward", C.c_int),
                 ("separate_adam", C.c_int), ("chamfer_kernel", C.c_int),
+                ("knn_rule", C.c_int), ("knn_thresh", C.c_float),
                 ("knn_weight", C.c_float), ("knn_k", C.c_int), ("knn_alpha", C.c_float), ("loss_in_scan", C.c_int)]
 
 

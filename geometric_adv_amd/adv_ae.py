@@ -28,7 +28,7 @@ class Configuration:
                  learning_rate=0.01, ae_name="autoencoder", emd_weight=0.0, verbose=False, batch_slots=1,
                  chamfer_prune=True, emd_reference_weights=False, recompute_backward=False, separate_adam=False,
                  chamfer_kernel="auto", encoder_backward="auto", emd_dense_levels=False, encoder_arith=None, loss_in_scan=True,
-                 knn_weight=0.0, knn_k=5, knn_alpha=1.05):
+                 knn_weight=0.0, knn_k=5, knn_alpha=1.05, knn_rule="sor", knn_thresh=0.04):
         self.batch_size = int(batch_size)
         self.n_input = [int(n_points), 3]
         self.n_output = [int(n_points), 3]
@@ -71,17 +71,27 @@ class Configuration:
         # The kNN outlier term (geoadv_attack_config.knn_weight): loss_adv + dist_weight * (loss_dist + knn_weight * K(adv)), K the
         # loss of ops.knn_outlier_loss(adv, knn_k, knn_alpha) -- the attack that keeps its points where sor_filter leaves them alone.
         # 0 = off: knn_k and knn_alpha are then not looked at.  Refused here, before any device is touched, as the library refuses.
+        # knn_rule="surface" (geoadv_attack_config.knn_rule = 1): K is the hinge on the points the paper's off-surface defense would
+        # remove, ops.knn_outlier_loss(adv, knn_k, rule="surface", thresh=knn_thresh); knn_alpha is then not looked at.
         self.knn_weight, self.knn_k, self.knn_alpha = float(knn_weight), int(knn_k), float(knn_alpha)
+        self.knn_rule, self.knn_thresh = knn_rule, float(knn_thresh)
         if self.knn_weight != 0.0:
+            if knn_rule not in KNN_RULES:
+                raise ValueError("knn_rule must be one of %s (got %r)" % (sorted(KNN_RULES), knn_rule))
             n = self.n_input[0]
             if not math.isfinite(self.knn_weight):
                 raise ValueError("knn_weight must be finite (got %r)" % self.knn_weight)
             if loss_dist_type == "pert":
                 raise ValueError("knn_weight needs loss_dist_type='chamfer': the 'pert' path has no Chamfer gradient to add the term to")
-            if not 1 <= self.knn_k <= KNN_TERM_MAX_K:
-                raise ValueError("knn_k must be in [1, %d] (got %d)" % (KNN_TERM_MAX_K, self.knn_k))
+            surface = knn_rule == "surface"
+            max_k = KNN_SURFACE_MAX_K if surface else KNN_TERM_MAX_K
+            if not 1 <= self.knn_k <= max_k:
+                raise ValueError("knn_k must be in [1, %d]%s (got %d)" % (max_k, " under knn_rule='surface'" if surface else "", self.knn_k))
             # (the library takes knn_alpha as a float: the op's alpha in the loop is float32(knn_alpha) widened to double)
-            if not (self.knn_alpha >= 0.0 and math.isfinite(self.knn_alpha) and self.knn_alpha <= 3.4028234663852886e38):
+            if surface:
+                if not (self.knn_thresh >= 0.0 and math.isfinite(self.knn_thresh) and self.knn_thresh <= 3.4028234663852886e38):
+                    raise ValueError("knn_thresh must be finite and >= 0 (got %r)" % self.knn_thresh)
+            elif not (self.knn_alpha >= 0.0 and math.isfinite(self.knn_alpha) and self.knn_alpha <= 3.4028234663852886e38):
                 raise ValueError("knn_alpha must be finite and >= 0 (got %r)" % self.knn_alpha)
             if not self.knn_k + 2 <= n <= KNN_TERM_MAX_POINTS:
                 raise ValueError("the kNN term needs clouds of knn_k + 2 = %d <= n_points <= %d (got %d)"
@@ -94,6 +104,8 @@ CHAMFER_KERNELS = {"auto": _abi.GEOADV_CHAMFER_AUTO, "two_scan": _abi.GEOADV_CHA
 ENCODER_BACKWARDS = {"auto": _abi.GEOADV_ENC_BWD_AUTO, "masked": _abi.GEOADV_ENC_BWD_MASKED, "jacobian": _abi.GEOADV_ENC_BWD_JACOBIAN}
 # kernel classes of the profiler in the order of their codes, GEOADV_PROF_<NAME> = 0 .. GEOADV_PROF_COUNT - 1
 KNN_TERM_MAX_K, KNN_TERM_MAX_POINTS, KNN_TERM_MAX_BATCH = 15, 16384, 65535     # the limits of ops.knn_outlier_loss (include/geoadv.h)
+KNN_RULES = {"sor": 0, "surface": 1}                                           # geoadv_attack_config.knn_rule
+KNN_SURFACE_MAX_K = 7                                                          # geoadv_outlier_filter's top_k limit
 PROF_NAMES = ["encoder_fwd", "decoder_fwd", "chamfer_fwd", "loss_grad", "decoder_bwd", "encoder_bwd", "adam"]
 
 
@@ -122,6 +134,8 @@ class AdvAE:
                             1 if getattr(c, "recompute_backward", False) else 0, ENCODER_BACKWARDS[getattr(c, "encoder_backward", "auto")],
                             1 if getattr(c, "separate_adam", False) else 0,
                             CHAMFER_KERNELS[getattr(c, "chamfer_kernel", "auto")],
+                            KNN_RULES[getattr(c, "knn_rule", "sor")] if getattr(c, "knn_weight", 0.0) != 0.0 else 0,
+                            float(getattr(c, "knn_thresh", 0.04)),
                             float(getattr(c, "knn_weight", 0.0)), int(getattr(c, "knn_k", 5)), float(getattr(c, "knn_alpha", 1.05)),
                             {True: 0, False: 1, "always": 2}[getattr(c, "loss_in_scan", True)])
         self._h = C.c_void_p()

@@ -515,8 +515,9 @@ int do_step(geoadv_attack *at, hipStream_t st) {
     at->cgrad_done = false;
     if (at->knn_ws) {   // g_dist += dist_weight[b] * (knn_weight * dK/dadv): the kNN outlier term on the cached forward's adv, mask held constant
         ProfScope ps(at, GEOADV_PROF_LOSS_GRAD, st);
-        if (int rc = launch_knn_term(B, n, at->cfg.knn_k, (double)at->cfg.knn_alpha, at->cfg.knn_weight, at->w, at->adv, at->g_dist, at->knn_loss,
-                                     at->knn_ws, at->knn_ws_bytes, st)) return rc;
+        const bool surface = at->cfg.knn_rule == 1;       // rule 1: the off-surface defense's mask and hinge, knn_thresh in alpha's place
+        if (int rc = launch_knn_term(at->cfg.knn_rule, B, n, at->cfg.knn_k, (double)(surface ? at->cfg.knn_thresh : at->cfg.knn_alpha),
+                                     at->cfg.knn_weight, at->w, at->adv, at->g_dist, at->knn_loss, at->knn_ws, at->knn_ws_bytes, st)) return rc;
     }
     if (adv_chamfer && at->emd_temp) {   // d(emd_weight * cost / n)/d recon, match held constant: emd_g1 came with the cached forward
         ProfScope ps(at, GEOADV_PROF_LOSS_GRAD, st);
@@ -660,8 +661,14 @@ extern "C" int geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, co
         GA_REQUIRE(isfinite(cfg->knn_weight), "attack_create: knn_weight must be finite (got %g)", (double)cfg->knn_weight);
         GA_REQUIRE(cfg->loss_dist_type == GEOADV_LOSS_DIST_CHAMFER,
                    "attack_create: knn_weight needs loss_dist_type chamfer (the 'pert' path has no Chamfer gradient g_dist to add the term to)");
+        GA_REQUIRE(cfg->knn_rule == 0 || cfg->knn_rule == 1, "attack_create: unknown knn_rule %d (0 = SOR, 1 = surface)", cfg->knn_rule);
         GA_REQUIRE(cfg->knn_k >= 1 && cfg->knn_k <= 15, "attack_create: knn_k=%d must be in [1, 15]", cfg->knn_k);
-        GA_REQUIRE(cfg->knn_alpha >= 0.f && isfinite(cfg->knn_alpha), "attack_create: knn_alpha must be finite and >= 0 (got %g)", (double)cfg->knn_alpha);
+        if (cfg->knn_rule == 1) {      // (knn_alpha is not read)
+            GA_REQUIRE(cfg->knn_k <= 7, "attack_create: knn_k=%d must be in [1, 7] under knn_rule 1, as geoadv_outlier_filter's top_k", cfg->knn_k);
+            GA_REQUIRE(cfg->knn_thresh >= 0.f && isfinite(cfg->knn_thresh), "attack_create: knn_thresh must be finite and >= 0 (got %g)",
+                       (double)cfg->knn_thresh);
+        } else
+            GA_REQUIRE(cfg->knn_alpha >= 0.f && isfinite(cfg->knn_alpha), "attack_create: knn_alpha must be finite and >= 0 (got %g)", (double)cfg->knn_alpha);
         GA_REQUIRE(n >= cfg->knn_k + 2 && n <= 16384, "attack_create: the kNN term needs clouds of knn_k + 2 = %d <= n <= 16384 points (n=%d)",
                    cfg->knn_k + 2, n);
     }

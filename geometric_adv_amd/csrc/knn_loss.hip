@@ -20,6 +20,7 @@
 // Visibility inside the workgroup: a word that an atomic has changed (in-degree, cursor) is only ever read by an agent-scope
 // atomic load, never by a plain load that this CU's L1 could answer from an older copy; plain stores (scores, edges, queue) are
 // read by other waves of the same workgroup after __syncthreads(), through the L1 they share.
+#include <float.h>
 #include <math.h>
 #include "stat_sums.h"
 #include "knn_loss.h"
@@ -46,15 +47,34 @@ __device__ __forceinline__ int kl_neighbour(const int *nbr, int stride, int p, i
     return min(max(j, 0), n - 1);
 }
 
-struct KlStats { double mu, bound; };
+// The two rules of the launch (include/geoadv.h): the SOR rule, and the off-surface defense's (GEOADV_KNN_LOSS_SURFACE), whose score
+// is geoadv_outlier_filter's fp32 mean distance and whose mask is that filter's `score > thresh`.  A template parameter of
+// everything below: the SOR instances contain nothing of the surface rule (its square roots and float64 divisions least of all).
+constexpr int KL_RULE_SOR = 0, KL_RULE_SURFACE = 1;
+constexpr int KL_SURFACE_MAX_K = 7;       // geoadv_outlier_filter's limit: numpy's float32 mean of fewer than 8 elements is a left-to-right sum
 
+struct KlStats { double mu, bound; };     // (surface rule: mu = (double)thr, bound unused)
+
+template <int RULE>
 __device__ __forceinline__ bool kl_masked(double s, const KlStats &st) {
+    if (RULE == KL_RULE_SURFACE) return (float)s > (float)st.mu;         // both are floats widened: the filter's fp32 test; NaN fails, +inf passes
     const double d = s - st.mu;
     return isfinite(s) && s > st.mu && __dmul_rn(d, d) > st.bound;
 }
 
-// G += (double)x_i - (double)x_j, component by component
+// SOR rule: G += (double)x_i - (double)x_j, component by component.  Surface rule: G += ((double)x_i - (double)x_j) / (double)d with
+// d = sqrtf(fp32 squared distance) recomputed from the two points (the same bits from either end); d == 0 adds nothing.
+template <int RULE>
 __device__ __forceinline__ void kl_add_diff(double (&G)[3], const float (&xi)[3], const float *xj) {
+    if (RULE == KL_RULE_SURFACE) {
+        const float dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
+        const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+        if (d == 0.f) return;
+        const double dd = (double)d;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) G[a] += __ddiv_rn((double)xi[a] - (double)xj[a], dd);
+        return;
+    }
 #pragma unroll
     for (int a = 0; a < 3; ++a) G[a] += (double)xi[a] - (double)xj[a];
 }
@@ -74,7 +94,8 @@ __device__ __forceinline__ void kl_emit(float *grad, int i, const double (&G)[3]
 
 // APPLY: grad_all is the loop's g_dist [b,n,3] (read and written), `weight` the handle's knn_weight, dist_weight [b] the per-cloud
 // weight the Chamfer gradient in g_dist already carries; score_all / mask_all / idx_all / stats are not looked at.
-template <bool APPLY>
+// RULE: alpha2 is alpha * alpha of the SOR rule, (double)thr of the surface rule.
+template <bool APPLY, int RULE>
 __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int k, double alpha2, const float *xyz, const int *nbr_all,
                                                                       double *sc_all, int *deg_all, int *cur_all, int *edge_all,
                                                                       int *hub_all, double *loss, float *grad_all, double *score_all,
@@ -92,12 +113,13 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
     if (t == 0) L.nhub = 0;
 
     // ---- A: scores and statistics (the SOR rule; step 1 of the summation order: thread t adds points t, t + T, ...) --------------
+    constexpr int MAX_K = RULE == KL_RULE_SURFACE ? KL_SURFACE_MAX_K : KL_MAX_K;
     double acc = 0.0, cnt = 0.0;
     for (int p = t; p < n; p += DF_THREADS) {
         const float px = x[3 * p], py = x[3 * p + 1], pz = x[3 * p + 2];
-        float val[KL_MAX_K];
+        float val[MAX_K];
 #pragma unroll
-        for (int c = 0; c < KL_MAX_K; ++c) {
+        for (int c = 0; c < MAX_K; ++c) {
             val[c] = 0.f;
             if (c < k) {
                 const int raw = nbr[(size_t)p * stride + 1 + c];
@@ -107,39 +129,53 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
                 val[c] = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
             }
         }
-        double s = (double)val[0];
+        double s;
+        if (RULE == KL_RULE_SURFACE) {           // knn_score of defense.hip on registers: fp32, left to right, no division for k = 1
+            float f = sqrtf(val[0]);
 #pragma unroll
-        for (int c = 1; c < KL_MAX_K; ++c) if (c < k) s += (double)val[c];       // sor_score on registers: the same sums in the same order
-        s = s / (double)k;
+            for (int c = 1; c < MAX_K; ++c) if (c < k) f = __fadd_rn(f, sqrtf(val[c]));
+            s = (double)(k > 1 ? __fdiv_rn(f, (float)k) : f);
+        } else {
+            s = (double)val[0];
+#pragma unroll
+            for (int c = 1; c < MAX_K; ++c) if (c < k) s += (double)val[c];      // sor_score on registers: the same sums in the same order
+            s = s / (double)k;
+        }
         sc[p] = s;
         deg[p] = 0;
         if (!APPLY && score_all) score_all[cl * n + p] = s;
-        const bool fin = isfinite(s);
-        acc += fin ? s : 0.0;
+        const bool fin = RULE == KL_RULE_SURFACE ? s == s : isfinite(s);         // (surface rule: the scores that are not NaN are counted)
+        if (RULE == KL_RULE_SOR) acc += fin ? s : 0.0;                           // (surface rule: no statistics, the count alone)
         cnt += fin ? 1.0 : 0.0;
     }
     const double m = sd_block_sum64(cnt, L.wsum);
-    const double sum = sd_block_sum64(acc, L.wsum);
     KlStats st;
-    st.mu = m > 0.0 ? sum / m : 0.0;
-    acc = 0.0;
-    for (int p = t; p < n; p += DF_THREADS) {
-        const double s = sc[p];
-        const double d = s - st.mu;
-        acc += isfinite(s) ? __dmul_rn(d, d) : 0.0;
+    double var = 0.0;
+    if (RULE == KL_RULE_SURFACE) {               // no statistics: the threshold is given (the sum above was the barrier phase B needs)
+        st.mu = alpha2;
+        st.bound = 0.0;
+    } else {
+        const double sum = sd_block_sum64(acc, L.wsum);
+        st.mu = m > 0.0 ? sum / m : 0.0;
+        acc = 0.0;
+        for (int p = t; p < n; p += DF_THREADS) {
+            const double s = sc[p];
+            const double d = s - st.mu;
+            acc += isfinite(s) ? __dmul_rn(d, d) : 0.0;
+        }
+        const double sq = sd_block_sum64(acc, L.wsum);
+        var = m >= 2.0 ? sq / (m - 1.0) : 0.0;
+        st.bound = __dmul_rn(alpha2, var);
     }
-    const double sq = sd_block_sum64(acc, L.wsum);
-    const double var = m >= 2.0 ? sq / (m - 1.0) : 0.0;
-    st.bound = __dmul_rn(alpha2, var);
 
     // ---- B: mask, loss, in-degrees (the barriers of the sums above order the zeroing of deg before these atomics) ----------------
     acc = 0.0;
     cnt = 0.0;
     for (int p = t; p < n; p += DF_THREADS) {
         const double s = sc[p];
-        const bool w = kl_masked(s, st);
+        const bool w = kl_masked<RULE>(s, st);
         if (!APPLY && mask_all) mask_all[cl * n + p] = w ? 1 : 0;
-        acc += w ? s : 0.0;
+        acc += w ? (RULE == KL_RULE_SURFACE ? s - st.mu : s) : 0.0;              // surface rule: the hinge (double)s_p - (double)thr
         cnt += w ? 1.0 : 0.0;
         if (w && grad_all)
             for (int c = 0; c < k; ++c) atomicAdd(&deg[kl_neighbour(nbr, stride, p, c, n)], 1);
@@ -181,7 +217,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
 
     // ---- D: placement.  base <= n k: every masked point adds k edges, and the segments tile [0, base) -----------------------------
     for (int p = t; p < n; p += DF_THREADS) {
-        if (!kl_masked(sc[p], st)) continue;
+        if (!kl_masked<RULE>(sc[p], st)) continue;
         for (int c = 0; c < k; ++c) {
             const int slot = atomicAdd(&cur[kl_neighbour(nbr, stride, p, c, n)], 1);
             if (slot >= 0 && slot < n * k) edge[slot] = p;                       // (always true; the edge list has n k entries)
@@ -190,7 +226,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
     __syncthreads();
 
     // ---- E: the gradient of every target with a short segment; the others are queued -----------------------------------------------
-    const double scale = 2.0 / ((double)n * (double)k);
+    const double scale = (RULE == KL_RULE_SURFACE ? 1.0 : 2.0) / ((double)n * (double)k);
     for (int i = t; i < n; i += DF_THREADS) {
         const int d = kl_load(&deg[i]);
         if (d > KL_SEGMENT_CAP) {
@@ -199,8 +235,8 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
         }
         const float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]};
         double G[3] = {0.0, 0.0, 0.0};
-        if (kl_masked(sc[i], st))
-            for (int c = 0; c < k; ++c) kl_add_diff(G, xi, x + 3 * kl_neighbour(nbr, stride, i, c, n));
+        if (kl_masked<RULE>(sc[i], st))
+            for (int c = 0; c < k; ++c) kl_add_diff<RULE>(G, xi, x + 3 * kl_neighbour(nbr, stride, i, c, n));
         const int end = min(kl_load(&cur[i]), n * k), start = max(end - d, 0);      // (the clamps never bind: after D, cur[i] is the segment's end)
         int last = -1;
         for (int done = 0; done < d;) {
@@ -211,7 +247,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
                 else if (p == next) ++mult;
             }
             if (mult == 0) break;                                                // (never: the segment holds d sources)
-            for (int r = 0; r < mult; ++r) kl_add_diff(G, xi, x + 3 * next);
+            for (int r = 0; r < mult; ++r) kl_add_diff<RULE>(G, xi, x + 3 * next);
             done += mult;
             last = next;
         }
@@ -225,13 +261,13 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
         const int i = min(max(hub[h], 0), n - 1);                                    // (a queued target is a point of the cloud)
         const float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]};
         double G[3] = {0.0, 0.0, 0.0};
-        if (kl_masked(sc[i], st))
-            for (int c = 0; c < k; ++c) kl_add_diff(G, xi, x + 3 * kl_neighbour(nbr, stride, i, c, n));
+        if (kl_masked<RULE>(sc[i], st))
+            for (int c = 0; c < k; ++c) kl_add_diff<RULE>(G, xi, x + 3 * kl_neighbour(nbr, stride, i, c, n));
         for (int p0 = 0; p0 < n; p0 += kWave) {
             const int p = p0 + lane;
             int mult = 0;
             float xp[3] = {0.f, 0.f, 0.f};
-            if (p < n && kl_masked(sc[p], st)) {
+            if (p < n && kl_masked<RULE>(sc[p], st)) {
                 for (int c = 0; c < k; ++c) mult += kl_neighbour(nbr, stride, p, c, n) == i ? 1 : 0;
                 xp[0] = x[3 * p]; xp[1] = x[3 * p + 1]; xp[2] = x[3 * p + 2];
             }
@@ -241,7 +277,7 @@ __global__ __launch_bounds__(DF_THREADS) void knn_outlier_loss_kernel(int n, int
                 hits &= hits - 1;
                 const float xs[3] = {__shfl(xp[0], src, kWave), __shfl(xp[1], src, kWave), __shfl(xp[2], src, kWave)};
                 const int reps = __shfl(mult, src, kWave);
-                for (int r = 0; r < reps; ++r) kl_add_diff(G, xi, xs);
+                for (int r = 0; r < reps; ++r) kl_add_diff<RULE>(G, xi, xs);
             }
         }
         if (lane == 0) kl_emit<APPLY>(grad, i, G, scale, weight, wb);
@@ -283,10 +319,15 @@ static bool kl_overlap(const void *a, size_t na, const void *b, size_t nb) {
 
 static bool kl_shape_ok(int b, int n, int k) { return b >= 0 && b <= 65535 && k >= 1 && k <= KL_MAX_K && n >= k + 2 && n <= KL_MAX_N; }
 
-static int kl_check(const char *op, int b, int n, int k, double alpha, const float *xyz, const double *loss, const float *grad,
+static int kl_check(const char *op, int rule, int b, int n, int k, double alpha, const float *xyz, const double *loss, const float *grad,
                     const void *workspace, size_t workspace_bytes) {
+    GA_REQUIRE(rule == KL_RULE_SOR || rule == KL_RULE_SURFACE, "%s: unknown rule %d", op, rule);
     GA_REQUIRE(b >= 0 && b <= 65535, "%s: batch %d must be in [0, 65535]", op, b);
     GA_REQUIRE(k >= 1 && k <= KL_MAX_K, "%s: k=%d must be in [1, %d]", op, k, KL_MAX_K);
+    if (rule == KL_RULE_SURFACE) {        // alpha is the threshold, used as (float)alpha
+        GA_REQUIRE(k <= KL_SURFACE_MAX_K, "%s: the surface rule takes k in [1, %d] as geoadv_outlier_filter does (k=%d)", op, KL_SURFACE_MAX_K, k);
+        GA_REQUIRE(alpha >= 0.0 && alpha <= (double)FLT_MAX, "%s: the surface rule's threshold must be in [0, FLT_MAX] (got %g)", op, alpha);
+    }
     GA_REQUIRE(n >= k + 2 && n <= KL_MAX_N, "%s: n=%d must be in [k + 2 = %d, %d]", op, n, k + 2, KL_MAX_N);
     GA_REQUIRE(n <= KL_SEARCH_MAX_N, "%s: the k-NN search takes at most %d points per cloud (n=%d)", op, KL_SEARCH_MAX_N, n);
     GA_REQUIRE(alpha >= 0.0 && isfinite(alpha), "%s: alpha must be finite and >= 0 (got %g)", op, alpha);
@@ -299,10 +340,18 @@ static int kl_check(const char *op, int b, int n, int k, double alpha, const flo
     return GEOADV_OK;
 }
 
-static int kl_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad, double *score, unsigned char *mask,
-                     int *idx, double *stats, const KlScratch &s, hipStream_t st) {
-    knn_outlier_loss_kernel<false><<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, grad, score,
-                                                             mask, idx, stats, 0.f, nullptr);
+// what the kernel takes in its `alpha2` place: alpha * alpha of the SOR rule, the fp32 threshold (widened) of the surface rule
+static double kl_rule_arg(int rule, double alpha) { return rule == KL_RULE_SURFACE ? (double)(float)alpha : alpha * alpha; }
+
+static int kl_launch(int rule, int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad, double *score,
+                     unsigned char *mask, int *idx, double *stats, const KlScratch &s, hipStream_t st) {
+    const double arg = kl_rule_arg(rule, alpha);
+    if (rule == KL_RULE_SURFACE)
+        knn_outlier_loss_kernel<false, KL_RULE_SURFACE><<<b, DF_THREADS, 0, st>>>(n, k, arg, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, grad,
+                                                                                  score, mask, idx, stats, 0.f, nullptr);
+    else
+        knn_outlier_loss_kernel<false, KL_RULE_SOR><<<b, DF_THREADS, 0, st>>>(n, k, arg, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, grad,
+                                                                              score, mask, idx, stats, 0.f, nullptr);
     GA_LAUNCH_CHECK();
     return GEOADV_OK;
 }
@@ -310,13 +359,19 @@ static int kl_launch(int b, int n, int k, double alpha, const float *xyz, double
 // The term of the attack loop (attack.hip: do_step; the rule at geoadv_attack_config in include/geoadv.h): the op's search with its
 // default kernel choice, then the APPLY instance of the launch, both on `st`, both on the caller's workspace
 // (geoadv_knn_outlier_loss_workspace_bytes(b, n, k) bytes).  The shape was checked when the handle was created.
-int launch_knn_term(int b, int n, int k, double alpha, float weight, const float *dist_weight, const float *xyz, float *g_dist,
+// rule: 0 = the SOR rule with `alpha`; 1 = the surface rule, `alpha` its threshold (geoadv_attack_config.knn_rule / knn_thresh).
+int launch_knn_term(int rule, int b, int n, int k, double alpha, float weight, const float *dist_weight, const float *xyz, float *g_dist,
                     double *loss, void *workspace, size_t workspace_bytes, hipStream_t st) {
-    if (int rc = kl_check("attack knn term", b, n, k, alpha, xyz, loss, g_dist, workspace, workspace_bytes)) return rc;
+    if (int rc = kl_check("attack knn term", rule, b, n, k, alpha, xyz, loss, g_dist, workspace, workspace_bytes)) return rc;
     const KlScratch s = kl_scratch(workspace, b, n, k);
     if (int rc = geoadv_knn_point_ws(GEOADV_KNN_AUTO, b, n, n, k + 1, xyz, xyz, s.val, s.idx, s.knn, s.knn_bytes, st)) return rc;
-    knn_outlier_loss_kernel<true><<<b, DF_THREADS, 0, st>>>(n, k, alpha * alpha, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, g_dist,
-                                                            nullptr, nullptr, nullptr, nullptr, weight, dist_weight);
+    const double arg = kl_rule_arg(rule, alpha);
+    if (rule == KL_RULE_SURFACE)
+        knn_outlier_loss_kernel<true, KL_RULE_SURFACE><<<b, DF_THREADS, 0, st>>>(n, k, arg, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, g_dist,
+                                                                                 nullptr, nullptr, nullptr, nullptr, weight, dist_weight);
+    else
+        knn_outlier_loss_kernel<true, KL_RULE_SOR><<<b, DF_THREADS, 0, st>>>(n, k, arg, xyz, s.idx, s.sc, s.deg, s.cur, s.edge, s.hub, loss, g_dist,
+                                                                             nullptr, nullptr, nullptr, nullptr, weight, dist_weight);
     GA_LAUNCH_CHECK();
     return GEOADV_OK;
 }
@@ -333,17 +388,19 @@ extern "C" size_t geoadv_knn_outlier_loss_workspace_bytes(int b, int n, int k) {
 extern "C" int geoadv_knn_outlier_loss(int kernel, int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad,
                                        double *score, unsigned char *mask, int *idx, double *stats, void *workspace,
                                        size_t workspace_bytes, void *stream) {
+    const int rule = (kernel & GEOADV_KNN_LOSS_SURFACE) ? KL_RULE_SURFACE : KL_RULE_SOR;      // the one flag a kernel choice may carry
+    kernel &= ~GEOADV_KNN_LOSS_SURFACE;
     GA_REQUIRE(kernel >= GEOADV_KNN_AUTO && kernel <= GEOADV_KNN_GRID_SHELLS, "knn_outlier_loss: unknown k-NN kernel %d", kernel);
-    if (int rc = kl_check("knn_outlier_loss", b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
+    if (int rc = kl_check("knn_outlier_loss", rule, b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
     if (b == 0) return GEOADV_OK;
     const KlScratch s = kl_scratch(workspace, b, n, k);
     if (int rc = geoadv_knn_point_ws(kernel, b, n, n, k + 1, xyz, xyz, s.val, s.idx, s.knn, s.knn_bytes, stream)) return rc;
-    return kl_launch(b, n, k, alpha, xyz, loss, grad, score, mask, idx, stats, s, as_stream(stream));
+    return kl_launch(rule, b, n, k, alpha, xyz, loss, grad, score, mask, idx, stats, s, as_stream(stream));
 }
 
 extern "C" int geoadv_debug_knn_outlier_loss_launch(int b, int n, int k, double alpha, const float *xyz, double *loss, float *grad,
                                                     void *workspace, size_t workspace_bytes, void *stream) {
-    if (int rc = kl_check("debug_knn_outlier_loss_launch", b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
+    if (int rc = kl_check("debug_knn_outlier_loss_launch", KL_RULE_SOR, b, n, k, alpha, xyz, loss, grad, workspace, workspace_bytes)) return rc;
     if (b == 0) return GEOADV_OK;
-    return kl_launch(b, n, k, alpha, xyz, loss, grad, nullptr, nullptr, nullptr, nullptr, kl_scratch(workspace, b, n, k), as_stream(stream));
+    return kl_launch(KL_RULE_SOR, b, n, k, alpha, xyz, loss, grad, nullptr, nullptr, nullptr, nullptr, kl_scratch(workspace, b, n, k), as_stream(stream));
 }

@@ -458,7 +458,11 @@ KNN_LOSS_MAX_K = 15                                         # include/geoadv.h g
 KNN_LOSS_MAX_POINTS = 16384                                 # (the rule's 32767, less what the search takes)
 
 
-def knn_outlier_loss(point_clouds, k=5, alpha=1.05, want_grad=True, return_parts=False, kernel=None):
+KNN_LOSS_SURFACE_MAX_K = 7                                  # the surface rule: outlier_filter's top_k limit
+KNN_LOSS_RULES = {"sor": 0, "surface": _abi.GEOADV_KNN_LOSS_SURFACE}     # OR-ed into the call's kernel argument
+
+
+def knn_outlier_loss(point_clouds, k=5, alpha=1.05, want_grad=True, return_parts=False, kernel=None, rule="sor", thresh=0.04):
     """The kNN outlier loss of the kNN attack and its gradient (csrc/knn_loss.hip, the rule in include/geoadv.h): per cloud the
     score s_p = the mean SQUARED distance of point p to its k nearest neighbours, SOR's float64 statistics mu and var of it, the
     mask w_p = s_p > mu + alpha * sqrt(var) (tested without a square root: the complement of sor_filter's inliers), the loss
@@ -466,7 +470,12 @@ def knn_outlier_loss(point_clouds, k=5, alpha=1.05, want_grad=True, return_parts
     scatter from the masked points that list it, summed in float64 in a fixed order (no float atomics: repeatable bits).
     point_clouds (b,n,3) float32, 1 <= k <= 15, k + 2 <= n <= 16384, alpha >= 0.  kernel: the k-NN kernel, as knn_point.
     -> (loss (b,) float64, grad (b,n,3) float32 or None without want_grad)[, score (b,n) float64, mask (b,n) bool,
-    idx (b,n,k) int32, stats (b,4) float64 = mu, var, the number of finite scores, the number of masked points]."""
+    idx (b,n,k) int32, stats (b,4) float64 = mu, var, the number of finite scores, the number of masked points].
+    rule="surface" (GEOADV_KNN_LOSS_SURFACE): the rule of the paper's off-surface defense instead -- s_p the fp32 mean DISTANCE to
+    the k <= 7 nearest neighbours, w_p = s_p > float32(thresh), exactly the points outlier_filter(x, knn_dists(x, k), thresh,
+    top_k=k) removes, K = sum(w_p (s_p - thresh)) / n and its gradient (unit vectors along the masked points' edges; a zero-length
+    edge adds nothing); alpha is then not looked at, score is float64(s_p) and stats = thresh, 0, the number of scores that are
+    not NaN, the number of masked points."""
     pc = _f32(point_clouds, "point_clouds", 3)
     if pc.shape[2] != 3:
         raise ValueError("knn_outlier_loss only accepts 3d point sets")
@@ -476,9 +485,18 @@ def knn_outlier_loss(point_clouds, k=5, alpha=1.05, want_grad=True, return_parts
         raise ValueError("k must be in [1, %d] (got k=%d)" % (KNN_LOSS_MAX_K, k))
     if not k + 2 <= n <= KNN_LOSS_MAX_POINTS:
         raise ValueError("knn_outlier_loss needs clouds of k + 2 = %d <= n <= %d points (got n=%d)" % (k + 2, KNN_LOSS_MAX_POINTS, n))
-    alpha = float(alpha)
-    if not (alpha >= 0.0 and alpha != float("inf")):
-        raise ValueError("alpha must be finite and >= 0 (got %r)" % alpha)
+    if rule not in KNN_LOSS_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (sorted(KNN_LOSS_RULES), rule))
+    if rule == "surface":
+        if k > KNN_LOSS_SURFACE_MAX_K:
+            raise ValueError("rule='surface' takes k in [1, %d], as outlier_filter's top_k (got k=%d)" % (KNN_LOSS_SURFACE_MAX_K, k))
+        alpha = float(thresh)                               # the call's alpha is the threshold under the flag
+        if not 0.0 <= alpha <= 3.4028234663852886e38:
+            raise ValueError("thresh must be finite, >= 0 and within float32 (got %r)" % alpha)
+    else:
+        alpha = float(alpha)
+        if not (alpha >= 0.0 and alpha != float("inf")):
+            raise ValueError("alpha must be finite and >= 0 (got %r)" % alpha)
     dev = pc.device
     loss = torch.empty((b,), dtype=torch.float64, device=dev)
     grad = torch.empty_like(pc) if want_grad else None
@@ -489,7 +507,7 @@ def knn_outlier_loss(point_clouds, k=5, alpha=1.05, want_grad=True, return_parts
     with torch.cuda.device(dev):
         wb = int(_lib.lib().geoadv_knn_outlier_loss_workspace_bytes(b, n, k))
         ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-        _call("geoadv_knn_outlier_loss", _knn_kernel(kernel), b, n, k, alpha, _lib.ptr(pc), _lib.ptr(loss), _lib.ptr(grad),
+        _call("geoadv_knn_outlier_loss", _knn_kernel(kernel) | KNN_LOSS_RULES[rule], b, n, k, alpha, _lib.ptr(pc), _lib.ptr(loss), _lib.ptr(grad),
               _lib.ptr(score), _lib.ptr(mask), _lib.ptr(idx), _lib.ptr(stats), _lib.ptr(ws), wb)
     return (loss, grad) + ((score, mask.to(torch.bool), idx, stats) if return_parts else ())
 

@@ -47,18 +47,23 @@ def build_parser():
                         'the attack that keeps its points where run_defense_sor leaves them alone (not a reference flag) [default: 0 = off]')
     p.add_argument('--knn_k', type=int, default=5, help='neighbours of the kNN outlier term [default: 5]')
     p.add_argument('--knn_alpha', type=float, default=1.05, help="the kNN outlier term's threshold, mu + alpha * sigma [default: 1.05]")
+    p.add_argument('--knn_rule', type=str, default='sor', choices=['sor', 'surface'],
+                   help="the kNN outlier term's rule: 'sor' masks the points run_defense_sor removes; 'surface' masks the points "
+                        "run_defense_surface removes (mean distance to --knn_k <= 7 neighbours above --knn_thresh) and minimises the hinge "
+                        "on them, --knn_alpha is then not read [default: sor]")
+    p.add_argument('--knn_thresh', type=float, default=0.04, help="the surface rule's distance threshold, the defense's knn_dist_thresh [default: 0.04]")
     return p
 
 
-def knn_loss_of(adversarial_pc_input, knn_k, knn_alpha, device):
+def knn_loss_of(adversarial_pc_input, knn_k, knn_alpha, device, knn_rule='sor', knn_thresh=0.04):
     """adversarial_knn_loss.npy: [W, num, 2] float64 = (K, the number of masked points) of every saved adversarial cloud, from
-    ops.knn_outlier_loss(..., return_parts=True) on one dist-weight's clouds at a time."""
+    ops.knn_outlier_loss(..., return_parts=True) on one dist-weight's clouds at a time, under the run's rule."""
     import torch
     from . import ops
     out = np.zeros(adversarial_pc_input.shape[:2] + (2,), np.float64)
     for w, clouds in enumerate(adversarial_pc_input):
         parts = ops.knn_outlier_loss(torch.as_tensor(clouds, dtype=torch.float32, device=device), knn_k, knn_alpha,
-                                     want_grad=False, return_parts=True)
+                                     want_grad=False, return_parts=True, rule=knn_rule, thresh=knn_thresh)
         out[w, :, 0] = parts[0].cpu().numpy()
         out[w, :, 1] = parts[5][:, 3].cpu().numpy()
     return out
@@ -107,11 +112,17 @@ def main(argv=None):
                          max_point_pert_weight=flags.max_point_pert_weight, max_point_dist_weight=flags.max_point_dist_weight,
                          num_iterations=flags.num_iterations, num_iterations_thresh=flags.num_iterations_thresh,
                          learning_rate=flags.learning_rate, batch_slots=flags.batch_slots,
-                         knn_weight=flags.knn_weight, knn_k=flags.knn_k, knn_alpha=flags.knn_alpha)
+                         knn_weight=flags.knn_weight, knn_k=flags.knn_k, knn_alpha=flags.knn_alpha,
+                         knn_rule=flags.knn_rule, knn_thresh=flags.knn_thresh)
     knn_on = conf.knn_weight != 0.0
-    # a run without the term writes the bytes it always wrote: the three values appear in its files only when the term is on
+    surface = knn_on and conf.knn_rule == 'surface'
+    # a run without the term writes the bytes it always wrote: the three values appear in its files only when the term is on, and the
+    # rule's two only when the rule is 'surface'
     knn_conf = {'knn_weight': conf.knn_weight, 'knn_k': conf.knn_k, 'knn_alpha': conf.knn_alpha} if knn_on else {}
-    shown_flags = flags if knn_on else argparse.Namespace(**{k: v for k, v in vars(flags).items() if not k.startswith('knn_')})
+    if surface:
+        knn_conf.update({'knn_rule': conf.knn_rule, 'knn_thresh': conf.knn_thresh})
+    hidden = () if surface else ('knn_rule', 'knn_thresh') if knn_on else tuple(k for k in vars(flags) if k.startswith('knn_'))
+    shown_flags = argparse.Namespace(**{k: v for k, v in vars(flags).items() if k not in hidden})
     if rank == 0:      # the reference pickles its Configuration here (run_attack.py:109; unpickling needs tflearn): same fields as JSON
         import json
         with open(osp.join(output_path, 'attack_configuration.json'), 'w') as f:
@@ -155,7 +166,7 @@ def main(argv=None):
             np.save(osp.join(save_dir, 'adversarial_pc_recon'), pc_rec)
             np.save(osp.join(save_dir, 'dist_weight'), np.array(conf.dist_weight_list))
             if knn_on:
-                np.save(osp.join(save_dir, 'adversarial_knn_loss'), knn_loss_of(pc_in, conf.knn_k, conf.knn_alpha, dev))
+                np.save(osp.join(save_dir, 'adversarial_knn_loss'), knn_loss_of(pc_in, conf.knn_k, conf.knn_alpha, dev, conf.knn_rule, conf.knn_thresh))
 
 
 if __name__ == '__main__':

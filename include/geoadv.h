@@ -310,7 +310,32 @@ int geoadv_random_drop(int b, int n, const float *pc /* [b,n,3] */, int drop, un
  * bytes for shapes the call refuses.  kernel: GEOADV_KNN_* for the search (same bits).
  * Enqueues on `stream` only.  GEOADV_EINVAL, before any launch: b < 0, b > 65535, k < 1, k > 15, n < k + 2, n > 32767 -- and,
  * for as long as the search keeps a row of the cloud in LDS, n > 16384 --, alpha < 0 or not finite, xyz or loss NULL with b > 0,
- * a workspace that is too small, an unknown kernel, grad overlapping xyz.  b == 0 is a no-op. */
+ * a workspace that is too small, an unknown kernel, grad overlapping xyz.  b == 0 is a no-op.
+ *
+ * The SURFACE rule (GEOADV_KNN_LOSS_SURFACE OR-ed into `kernel`, as GEOADV_EMD_DENSE_LEVELS is OR-ed into a mode): the same call
+ * with the mask of the paper's off-surface defense -- exactly the points geoadv_outlier_filter(x, geoadv_knn_dists(x, k), thr,
+ * top_k = k) removes -- and a hinge on it.  `alpha` is then the threshold, used as thr = (float)alpha.  Without the flag nothing
+ * above changes.  For one cloud x[n,3] (fp32), k and thr:
+ *   neighbours  N and val as above (knn_point(k + 1), first column dropped, tie order kept; val recomputed in fp32, every product
+ *               and sum rounded on its own)
+ *   distance    d[p][c] = sqrtf(val[p][c]), correctly rounded fp32: the bits geoadv_knn_dists writes
+ *   score       s_p = ((d[p][0] + d[p][1]) + ... + d[p][k-1]) / (float)k, all fp32, left to right, no division for k = 1: knn_score
+ *               of csrc/defense.hip, i.e. numpy's float32 mean of fewer than 8 elements -- hence 1 <= k <= 7, geoadv_outlier_filter's limit
+ *   mask        w_p = 1 iff s_p > thr in fp32: geoadv_outlier_filter's outlier test.  A NaN score gives 0, +inf gives 1.  A constant
+ *               of the differentiation
+ *   loss        K = SUM(w_p ? (double)s_p - (double)thr : +0.0) / (double)n, float64, SUM in the SOR rule's fixed T = 1024 order; no
+ *               point over the threshold gives +0.0
+ *   gradient    float64 per component, in the order above (the gather over a masked point's own neighbours with c ascending, then
+ *               the scatter over p ascending and within p over c ascending); an edge (p, c) with j = N[p][c] adds to its endpoint i
+ *                 ((double)x_i - (double)x_other) / (double)d[p][c]       a float64 division, rounded once
+ *               where x_other is the edge's other endpoint and d[p][c] is recomputed from the two coordinates (the fp32 squared
+ *               distance has the same bits from either end); an edge with d[p][c] == 0 adds nothing (subgradient 0);
+ *                 grad_i = (float)(G_i * (1.0 / ((double)n * (double)k)))
+ * Outputs: score [b,n] = (double)s_p; mask and idx as above; stats [b,4] = ((double)thr, +0.0, the number of scores that are not
+ * NaN, the number of masked points).  The workspace size is unchanged.  GEOADV_EINVAL, before any launch, under the flag: k > 7,
+ * alpha negative, not finite or above FLT_MAX; with or without it: bits of `kernel` other than the flag and a GEOADV_KNN_* value;
+ * everything refused above.  (geoadv_debug_knn_outlier_loss_launch has no `kernel` argument: it launches the SOR rule only.) */
+#define GEOADV_KNN_LOSS_SURFACE 0x100
 size_t geoadv_knn_outlier_loss_workspace_bytes(int b, int n, int k);
 int geoadv_knn_outlier_loss(int kernel /* GEOADV_KNN_* for the search */, int b, int n, int k, double alpha,
                             const float *xyz /* [b,n,3] */, double *loss /* [b] */, float *grad /* [b,n,3] or NULL */,
@@ -1007,9 +1032,18 @@ typedef struct geoadv_attack_config {
      * read-outs are unchanged and do not contain K.
      * geoadv_attack_create returns GEOADV_EINVAL (nothing allocated) for knn_weight != 0 with: knn_weight not finite;
      * loss_dist_type GEOADV_LOSS_DIST_PERT (that path has no g_dist); knn_k outside 1 ... 15; knn_alpha negative or not finite;
-     * n < knn_k + 2 or n > 16384; batch > 65535. */
-    float  knn_weight;              /* 0 (default) = off: nothing below is read, reserved or launched -- arena, launches and every
-                                     * output bit are those of a handle without these members                                 */
+     * n < knn_k + 2 or n > 16384; batch > 65535.
+     * knn_rule = 1 swaps the rule for the SURFACE rule of geoadv_knn_outlier_loss (GEOADV_KNN_LOSS_SURFACE) with k = knn_k and
+     * thr = knn_thresh: the mask is the set geoadv_outlier_filter removes, K the hinge on it -- the attack aware of the paper's own
+     * off-surface defense.  Same launches, same place in the step, same three fp32 roundings into g_dist, same arena.  knn_alpha
+     * is then not read; with knn_weight = 0 neither member below is read; knn_rule = 0 is the handle described above, bit for bit.
+     * Further refusals with knn_weight != 0: a knn_rule other than 0 / 1; under rule 1 knn_k > 7 and a negative or non-finite
+     * knn_thresh.  (The two members stand before knn_weight: tests hold knn_weight / knn_k / knn_alpha / loss_in_scan to the
+     * struct's last four places.) */
+    int    knn_rule;                /* 0 (default) = the SOR rule, 1 = the surface rule                                         */
+    float  knn_thresh;              /* read only under knn_rule 1: >= 0, finite                                                 */
+    float  knn_weight;              /* 0 (default) = off: none of knn_rule, knn_thresh, knn_k, knn_alpha is read, nothing is reserved
+                                     * or launched -- arena, launches and every output bit are those of a handle without them */
     int    knn_k;                   /* 1 ... 15                                                                                */
     float  knn_alpha;               /* >= 0, finite; the op's alpha is (double)knn_alpha                                    */
     /* (The three members above stand before loss_in_scan, which stays the struct's last member, and are all int / float: callers
