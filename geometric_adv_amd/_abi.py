@@ -22,6 +22,8 @@ SIGNATURES = {      # in the header's order
     "geoadv_nn_distance_sym_is_screened": "i:iii",
     "geoadv_set_chamfer_screen": "i:i",
     "geoadv_nn_distance_sym": "i:iipippppppzp",
+    "geoadv_nn_distance_lists_workspace_bytes": "z:iiii",
+    "geoadv_nn_distance_lists": "i:iiipppppippppppppzp",
     "geoadv_chamfer_per_pc": "i:iiipppp",
     "geoadv_nn_distance_paired": "i:iippppppp",
     "geoadv_nn_distance_grad": "i:iipipppppppp",
@@ -139,6 +141,8 @@ SIGNATURES = {      # in the header's order
     "geoadv_debug_h2_split": "i:pipppp",
     "geoadv_debug_emd_sparse_state": "i:iiiippp",
     "geoadv_attack_search_state": "i:pppp",
+    "geoadv_attack_set_recon_lists": "i:pi",
+    "geoadv_attack_list_state": "i:ppp",
     "geoadv_trainer_create": "i:ppp",
     "geoadv_trainer_destroy": "v:p",
     "geoadv_trainer_step": "i:pppppp",
@@ -198,6 +202,10 @@ GEOADV_LOSS_ADV_CHAMFER, GEOADV_LOSS_ADV_LATENT = 0, 1
 GEOADV_LOSS_DIST_CHAMFER, GEOADV_LOSS_DIST_PERT = 0, 1
 GEOADV_ENC_BWD_AUTO, GEOADV_ENC_BWD_MASKED, GEOADV_ENC_BWD_JACOBIAN = 0, 1, 2
 GEOADV_CHAMFER_AUTO, GEOADV_CHAMFER_TWO_SCAN, GEOADV_CHAMFER_SYMMETRIC = 0, 1, 2
+GEOADV_RECON_LISTS_ADAPTIVE, GEOADV_RECON_LISTS_OFF, GEOADV_RECON_LISTS_PINNED = 0, 1, 2
+(GEOADV_LIST_STATE_ON, GEOADV_LIST_STATE_ANCHORS, GEOADV_LIST_STATE_LIST_ITERATIONS, GEOADV_LIST_STATE_CERTIFIED,
+ GEOADV_LIST_STATE_REFUSED, GEOADV_LIST_STATE_UNLISTED, GEOADV_LIST_STATE_HANDED_BACK, GEOADV_LIST_STATE_FLAGGED,
+ GEOADV_LIST_STATE_PERIOD, GEOADV_LIST_STATE_COUNT) = range(10)
 GEOADV_PLAN_COUNT = 9
 GEOADV_TRAIN_LOSS_CHAMFER, GEOADV_TRAIN_LOSS_EMD = 0, 1
 (GEOADV_TRAIN_STATE_ACT, GEOADV_TRAIN_STATE_BN_MEAN, GEOADV_TRAIN_STATE_BN_INV_STD, GEOADV_TRAIN_STATE_BN_SCALE,
@@ -276,7 +284,7 @@ class AttackConfig(C.Structure):
                 ("max_point_pert_weight", C.c_float), ("max_point_dist_weight", C.c_float),
                 ("learning_rate", C.c_float), ("emd_weight", C.c_float), ("all_pairs_source_dist", C.c_int),
                 ("emd_weight_mode", C.c_int), ("recompute_backward", C.c_int), ("encoder_backward", C.c_int),
-                ("separate_adam", C.c_int), ("chamfer_kernel", C.c_int),
+                ("separate_adam", C.c_int), ("chamfer_kernel", C.c_int), ("recon_lists", C.c_int),
                 ("knn_rule", C.c_int), ("knn_thresh", C.c_float),
                 ("knn_weight", C.c_float), ("knn_k", C.c_int), ("knn_alpha", C.c_float), ("loss_in_scan", C.c_int)]
 

@@ -28,7 +28,7 @@ class Configuration:
                  learning_rate=0.01, ae_name="autoencoder", emd_weight=0.0, verbose=False, batch_slots=1,
                  chamfer_prune=True, emd_reference_weights=False, recompute_backward=False, separate_adam=False,
                  chamfer_kernel="auto", encoder_backward="auto", emd_dense_levels=False, encoder_arith=None, loss_in_scan=True,
-                 knn_weight=0.0, knn_k=5, knn_alpha=1.05, knn_rule="sor", knn_thresh=0.04):
+                 knn_weight=0.0, knn_k=5, knn_alpha=1.05, knn_rule="sor", knn_thresh=0.04, recon_lists=True):
         self.batch_size = int(batch_size)
         self.n_input = [int(n_points), 3]
         self.n_output = [int(n_points), 3]
@@ -67,6 +67,9 @@ class Configuration:
         self.encoder_backward = encoder_backward             # "auto", "masked" (back-propagate dz) or "jacobian" (pool Jacobian)
         if loss_in_scan not in (True, False, "always"):
             raise ValueError("loss_in_scan must be True (where it pays), False or 'always'")
+        if recon_lists not in (True, False, "pinned"):
+            raise ValueError("recon_lists must be True (adaptive), False or 'pinned'")
+        self.recon_lists = recon_lists                       # nn_distance(recon, target) from exact neighbour lists between two scans (geoadv_attack_config.recon_lists): True = on, off for a batch whose clouds the scan keeps taking back (adapt_recon_lists); "pinned": on, no policy
         self.loss_in_scan = loss_in_scan                     # False: the loss + gradient pass always as a launch of its own; "always": riding wherever possible
         # The kNN outlier term (geoadv_attack_config.knn_weight): loss_adv + dist_weight * (loss_dist + knn_weight * K(adv)), K the
         # loss of ops.knn_outlier_loss(adv, knn_k, knn_alpha) -- the attack that keeps its points where sor_filter leaves them alone.
@@ -101,6 +104,8 @@ class Configuration:
 
 
 CHAMFER_KERNELS = {"auto": _abi.GEOADV_CHAMFER_AUTO, "two_scan": _abi.GEOADV_CHAMFER_TWO_SCAN, "symmetric": _abi.GEOADV_CHAMFER_SYMMETRIC}
+RECON_LISTS = {True: _abi.GEOADV_RECON_LISTS_ADAPTIVE, False: _abi.GEOADV_RECON_LISTS_OFF, "pinned": _abi.GEOADV_RECON_LISTS_PINNED}
+LIST_STATE_NAMES = ["on", "anchors", "list_iterations", "certified", "refused", "unlisted", "handed_back", "flagged", "period"]
 ENCODER_BACKWARDS = {"auto": _abi.GEOADV_ENC_BWD_AUTO, "masked": _abi.GEOADV_ENC_BWD_MASKED, "jacobian": _abi.GEOADV_ENC_BWD_JACOBIAN}
 # kernel classes of the profiler in the order of their codes, GEOADV_PROF_<NAME> = 0 .. GEOADV_PROF_COUNT - 1
 KNN_TERM_MAX_K, KNN_TERM_MAX_POINTS, KNN_TERM_MAX_BATCH = 15, 16384, 65535     # the limits of ops.knn_outlier_loss (include/geoadv.h)
@@ -134,6 +139,7 @@ class AdvAE:
                             1 if getattr(c, "recompute_backward", False) else 0, ENCODER_BACKWARDS[getattr(c, "encoder_backward", "auto")],
                             1 if getattr(c, "separate_adam", False) else 0,
                             CHAMFER_KERNELS[getattr(c, "chamfer_kernel", "auto")],
+                            RECON_LISTS[getattr(c, "recon_lists", True)],
                             KNN_RULES[getattr(c, "knn_rule", "sor")] if getattr(c, "knn_weight", 0.0) != 0.0 else 0,
                             float(getattr(c, "knn_thresh", 0.04)),
                             float(getattr(c, "knn_weight", 0.0)), int(getattr(c, "knn_k", 5)), float(getattr(c, "knn_alpha", 1.05)),
@@ -233,6 +239,44 @@ class AdvAE:
         if 2 * handed_back > self.B:
             self.set_source_search(False)
         return handed_back
+
+    def list_state(self):
+        """How nn_distance(recon, target) has been answered since the handle was created (geoadv_attack_list_state; synchronises):
+        dict of on, anchors, list_iterations, certified, refused, unlisted (queries), handed_back (cloud-iterations the scan took
+        over), flagged (clouds handed back right now), period."""
+        st = (C.c_longlong * _abi.GEOADV_LIST_STATE_COUNT)()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().geoadv_attack_list_state(self._h, st, _lib.stream_handle()), "attack_list_state")
+        out = {k: int(st[i]) for i, k in enumerate(LIST_STATE_NAMES)}
+        out["on"] = bool(out["on"])
+        return out
+
+    def set_recon_lists(self, on, period=None):
+        """nn_distance(recon, target) from the next forward on: neighbour lists between anchors (True; period: forwards per anchor,
+        2 ... 256, default 16) or a scan every time; same results."""
+        _lib.check(_lib.lib().geoadv_attack_set_recon_lists(self._h, (int(period) if period else 1) if on else 0), "attack_set_recon_lists")
+
+    def adapt_recon_lists(self):
+        """Configuration.recon_lists=True is a default, not a promise.  A list iteration saves the scan of one pair; it loses when
+        the scan has to take the cloud back anyway (then the list launch and the anchor's build are pure cost) or when many queries
+        fall to the brute-force path (a wave per query instead of a thread: a quarter of them costs what the scan costs).  Called
+        where the host synchronises anyway (end of a dist-weight run), on the counters since the last call: more than a quarter of the
+        cloud-iterations handed back, or more than a quarter of the queries refused or unlisted, switch the lists off until the
+        next set_inputs (the library switches them on again there).  Results are identical either way.  Returns the counters it
+        decided on, or None when the policy does not apply."""
+        if getattr(self.configuration, "recon_lists", True) is not True:
+            return None
+        s = self.list_state()
+        last = getattr(self, "_lists_seen", None) or {k: 0 for k in s}
+        self._lists_seen = s
+        if not s["on"]:
+            return None
+        d = {k: s[k] - last[k] for k in ("list_iterations", "certified", "refused", "unlisted", "handed_back")}
+        cloud_iters = d["list_iterations"] * self.B
+        queries = d["certified"] + d["refused"] + d["unlisted"]
+        if cloud_iters and (4 * d["handed_back"] > cloud_iters or 4 * (d["refused"] + d["unlisted"]) > max(queries, 1)):
+            self.set_recon_lists(False)
+        return d
 
     def status(self):
         """Raises GeoAdvError if an in-launch hand-off of the loop timed out since the last set_inputs / init_pert (synchronises)."""
@@ -403,6 +447,7 @@ class AdvAE:
             m_, a_, r_ = self.get_best(target_ae_loss_ref)
             self.status()                                            # the host sync of the run; raises if a hand-off ever timed out
             self.adapt_source_search()
+            self.adapt_recon_lists()
             h = hist.cpu().numpy()
             self.last_history.append(h)
             step = (c.num_iterations // 10) or 1

@@ -11,6 +11,7 @@
 #include "chamfer_sym.h"
 #include "chamfer_grad.h"
 #include "chamfer_grid.h"
+#include "chamfer_lists.h"
 #include "encoder_jac.h"
 #include "decoder_tail.h"
 #include "knn_loss.h"
@@ -223,6 +224,18 @@ struct geoadv_attack {
     int cus;                         // compute units of THIS device (hipDeviceAttributeMultiprocessorCount at create): the merged tail +
                                      // dense launch spins on in-launch flags and needs all its workgroups resident at once
     bool chamfer_sym;
+    // Neighbour lists for nn_distance(recon, target) (chamfer_lists.h): the target is fixed between set_inputs calls and recon moves by
+    // one small Adam step per iteration, so the all-pairs scan of that pair only runs every list_period-th forward (the ANCHOR, followed
+    // by the list-building pass); the forwards between answer it from the lists, exactly, and gate the scan's workgroups off.
+    ReconLists lists;                // (lists.list_row == null: this handle has none -- configuration or size)
+    bool lists_on;                   // in use from the next forward on (geoadv_attack_set_recon_lists; the adaptive policies clear it)
+    int list_age;                    // forwards since the anchor; < 0: no valid lists (set_inputs, init_pert, switched off)
+    int list_period;                 // forwards per anchor
+    int list_warm_left;              // forwards that still scan before the first anchor (the adaptive default after set_inputs / init_pert)
+    unsigned long long n_anchors, n_list_iters;   // (host) since creation
+    unsigned long long *list_hint;   // pinned host memory [5]: the device's counters as of the last build, and that build's serial; read
+                                     // without waiting for anything (stale at worst): the adaptive policy inside a long run
+    unsigned long long hint_seen[5]; // ... the copy the last decision was made from
     // host state
     float beta1_pow, beta2_pow;
     bool fwd_valid;
@@ -311,6 +324,37 @@ struct ProfScope {
 
 bool cgrad_step_sorted(int n) { return n > CG_FX_MAX_N_PLANE; }   // launch_cgrad below: the sorted kernel instead of the fixed-point bodies
 
+// Skin of the lists, per cloud, derived on the device (chamfer_lists.hip): RL_SKIN_FACTOR x the largest displacement the last
+// query of the previous period saw, clamped; RL_SKIN_FIRST without history (the first period after set_inputs / init_pert).
+// First values, not optima: DESIGN 6, "Untuned".
+constexpr float RL_SKIN_FIRST = 0.010f, RL_SKIN_FACTOR = 1.4f, RL_SKIN_MIN = 0.002f, RL_SKIN_MAX = 0.016f;
+constexpr int RL_PERIOD = 16, RL_CAPACITY = 16;
+// The adaptive default scans for the first RL_WARM_FORWARDS forwards after set_inputs / init_pert: Adam's first steps are its
+// largest, recon moves fastest there, and list iterations in forwards 21 ... 40 of the headline measured ~43 us against the scan's 40
+// (refused column queries pile up in a few workgroups).  (recon_lists PINNED: lists from the first forward.)
+constexpr int RL_WARM_FORWARDS = 48;
+
+// The adaptive default inside a run, where the host never waits: every build leaves the device's counters in pinned host memory;
+// when a whole period has been seen in which the scan took over more than a quarter of the cloud-iterations (a victim whose
+// reconstructions jump past any skin the lists can afford), the lists only cost their build and their launch -- off until the
+// next set_inputs.  What is read may be periods old; the results do not depend on it.
+void lists_adapt_from_hint(geoadv_attack *at) {
+    unsigned long long h[5];
+    h[4] = reinterpret_cast<volatile unsigned long long *>(at->list_hint)[4];
+    if (h[4] == at->hint_seen[4]) return;
+    for (int k = 0; k < 4; ++k) h[k] = reinterpret_cast<volatile unsigned long long *>(at->list_hint)[k];
+    if (reinterpret_cast<volatile unsigned long long *>(at->list_hint)[4] != h[4]) return;       // torn: a later forward reads it whole
+    if (at->hint_seen[4] >= 1) {
+        const unsigned long long periods = h[4] - at->hint_seen[4];
+        const unsigned long long handed = h[3] - at->hint_seen[3], refused = (h[1] - at->hint_seen[1]) + (h[2] - at->hint_seen[2]);
+        const unsigned long long cloud_iters = periods * (unsigned long long)(at->list_period - 1) * at->B;
+        // handed back: a scan anyway + the list launch; refused queries: a wave each instead of a thread (a quarter of them breaks even)
+        // (a clean list iteration saves ~17 us, an anchor every 16 forwards costs ~11 per forward: at a quarter handed back nothing is left)
+        if (4 * handed > cloud_iters || 4 * refused > cloud_iters * 2ull * at->n) at->lists_on = false;
+    }
+    for (int k = 0; k < 5; ++k) at->hint_seen[k] = h[k];
+}
+
 // The forward's own launch decisions, made once at its top (everything about the symmetric scan's launch is in its SymPlan):
 // pruned: nn_distance(adv, x) through the paired grid search -- adv = x + pert and most points barely move, so the exact search
 // seeded with the pairing (chamfer_grid.hip) answers it for a fraction of the all-pairs cost; clouds whose pairing has become poor
@@ -360,6 +404,17 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
     }
     const SymRows rows = chamfer_sym_rows(plan, at->sym_ws, at->row64);
     const bool packed = plan.rows == GEOADV_PLAN_ROWS_PACKED, hosted = plan.loss.count > 0;
+    // pair 0 from the neighbour lists: the symmetric plan with one row super-tile whose rows leave as packed words (every shape of
+    // up to 2048 points in the output-space attack; the list kernel stores the word the scan's atomic minima would leave)
+    // ... and only beside the paired search: with nn_distance(adv, x) on the all-pairs kernel the launch is full of that pair's scan, the
+    // list workgroups queue behind it, and a victim that makes the search give up also moves recon past any skin (measured: DESIGN 6)
+    const bool listed = at->lists.list_row && at->lists_on && adv_chamfer && at->chamfer_sym && packed && plan.shape.rtiles == 1 && !at->emd_temp && f.pruned;
+    if (listed && at->list_hint && at->cfg.recon_lists == GEOADV_RECON_LISTS_ADAPTIVE) lists_adapt_from_hint(at);
+    bool warm = false;
+    if (listed && at->lists_on && at->list_warm_left > 0) { at->list_warm_left--; warm = true; }
+    const bool list_iter = listed && !warm && at->lists_on && at->list_age >= 0 && at->list_age + 1 < at->list_period;
+    const bool list_anchor = listed && !warm && at->lists_on && !list_iter;
+    if (!listed || warm || !at->lists_on) at->list_age = -1;
     const int call = at->grid_calls;
     int *need_new = at->need_adv[f.rides_scan ? (call + 1) & 1 : 0];
     const int *need_scan = at->need_adv[f.rides_scan ? call & 1 : 0];      // what the all-pairs kernels act on in this call
@@ -440,8 +495,31 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
                 at->loss_target += plan.loss_arrivals;
                 lr = LossRider{la, ca, H, 1 + 2 * H, 0, 0, B, at->loss_done, at->loss_target, reinterpret_cast<int *>(at->tail_ready + B)};
             }
+            const int *need0 = nullptr;
+            ListRider list_rider;
+            bool rides = false;
+            if (list_iter) {   // the lists answer pair 0; the scan's workgroups of that pair leave at once
+                ListQuery lq{};
+                lq.P = at->recon; lq.Q = at->gt; lq.row64 = at->row64; lq.dist2 = at->r2; lq.idx2 = at->ir2;
+                lq.call = at->list_age; lq.answer_all = false;
+                // ... as further workgroups of the scan's launch, beside the search and the Jacobian; where the loss riders are hosted
+                // (they wait for the scan's workgroups only) or the screened kernel runs: a launch of its own ahead of the scan's
+                rides = !hosted && plan.kernel == 0;
+                if (rides) list_rider = recon_lists_rider(at->lists, lq, 512);
+                else if (int rc = launch_recon_lists_query(at->lists, lq, st)) return rc;
+                need0 = at->lists.need[at->list_age & 1];          // clouds handed back before this call: the same flags the query acted on
+                at->list_age++; at->n_list_iters++;
+            }
             if (int rc = launch_chamfer_sym(plan, pairs, at->sym_ws, f.pruned ? need_scan : nullptr, f.rides_scan ? &rider : nullptr,
-                                            f.jac_rides ? &jr : nullptr, hosted ? &lr : nullptr, at->row64, st)) return rc;
+                                            f.jac_rides ? &jr : nullptr, hosted ? &lr : nullptr, at->row64, st, need0, rides ? &list_rider : nullptr)) return rc;
+            if (list_anchor) {   // the scan's minima are exact and complete here: build the lists for the forwards that follow
+                ListBuild lb{};
+                lb.P = at->recon; lb.Q = at->gt; lb.row64 = at->row64; lb.dist2 = at->r2;
+                lb.first = RL_SKIN_FIRST; lb.factor = RL_SKIN_FACTOR; lb.lo = RL_SKIN_MIN; lb.hi = RL_SKIN_MAX;
+                lb.hint = at->list_hint; lb.serial = ++at->n_anchors;
+                if (int rc = launch_recon_lists_build(at->lists, lb, st)) return rc;
+                at->list_age = 0;
+            }
         } else {
             ChamferScan all[4] = {{at->recon, at->gt, at->r1, at->ir1, n, n}, {at->gt, at->recon, at->r2, at->ir2, n, n},
                                   {at->adv, at->x, at->a1, at->ia1, n, n}, {at->x, at->adv, at->a2, at->ia2, n, n}};
@@ -475,6 +553,14 @@ int do_forward(geoadv_attack *at, float *hist_slot, int keep, hipStream_t st) {
         pl[GEOADV_PLAN_H] = fx ? H : 0; pl[GEOADV_PLAN_RANGE] = fx ? cgrad_fx_range(n) : 0;
     }
     at->fwd_valid = true;
+    return GEOADV_OK;
+}
+
+// set_inputs / init_pert: the next forward is an anchor, and its skin starts without history
+int lists_invalidate(geoadv_attack *at, hipStream_t st) {
+    at->list_age = -1;
+    at->list_warm_left = at->cfg.recon_lists == GEOADV_RECON_LISTS_ADAPTIVE ? RL_WARM_FORWARDS : 0;
+    if (at->lists.list_row) GA_HIP(hipMemsetAsync(at->lists.dmax, 0, sizeof(float) * (size_t)at->B, st));
     return GEOADV_OK;
 }
 
@@ -615,6 +701,13 @@ size_t carve_arena(geoadv_attack *at, void *base) {
         at->emd_temp = F(geoadv_emd_cost_grad1_temp_floats(at->B, at->n, at->n) + 2);
         at->emd_cost = F(B); at->emd_g1 = F(bn3);
     }
+    at->lists = ReconLists{};
+    if (cfg.recon_lists != GEOADV_RECON_LISTS_OFF && cfg.loss_adv_type == GEOADV_LOSS_ADV_CHAMFER && cfg.emd_weight == 0.f && at->n <= RL_MAX_POINTS) {
+        ReconLists measure;
+        const size_t lb = carve_recon_lists(measure, nullptr, at->B, at->n, at->n, RL_CAPACITY, true);
+        char *p = c.take<char>(lb);
+        if (base) carve_recon_lists(at->lists, p, at->B, at->n, at->n, RL_CAPACITY, true);
+    }
     at->knn_ws = nullptr; at->knn_ws_bytes = 0; at->knn_loss = nullptr;
     if (cfg.knn_weight != 0.f) {
         at->knn_ws_bytes = geoadv_knn_outlier_loss_workspace_bytes(at->B, at->n, cfg.knn_k);
@@ -654,6 +747,8 @@ extern "C" int geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, co
                "attack_create: unknown encoder_backward %d", cfg->encoder_backward);
     GA_REQUIRE(cfg->chamfer_kernel >= GEOADV_CHAMFER_AUTO && cfg->chamfer_kernel <= GEOADV_CHAMFER_SYMMETRIC,
                "attack_create: unknown chamfer_kernel %d", cfg->chamfer_kernel);
+    GA_REQUIRE(cfg->recon_lists >= GEOADV_RECON_LISTS_ADAPTIVE && cfg->recon_lists <= GEOADV_RECON_LISTS_PINNED,
+               "attack_create: unknown recon_lists %d", cfg->recon_lists);
     GA_REQUIRE(cfg->emd_weight == 0.f || cfg->loss_adv_type == GEOADV_LOSS_ADV_CHAMFER,
                "attack_create: emd_weight needs the output-space attack (loss_adv_type chamfer)");
     if (cfg->knn_weight != 0.f) {      // (0 = off: knn_k and knn_alpha are not read)
@@ -692,6 +787,15 @@ extern "C" int geoadv_attack_create(geoadv_attack **out, const geoadv_ae *ae, co
     const size_t carved = carve_arena(at, at->arena);
     assert(carved == at->arena_bytes); (void)carved;       // both passes agree
     at->need_last = at->need_adv[0];
+    at->lists_on = at->lists.list_row != nullptr; at->list_age = -1; at->list_period = RL_PERIOD;
+    at->n_anchors = at->n_list_iters = 0; at->list_hint = nullptr;
+    at->list_warm_left = cfg->recon_lists == GEOADV_RECON_LISTS_ADAPTIVE ? RL_WARM_FORWARDS : 0;
+    for (auto &v : at->hint_seen) v = 0;
+    if (at->lists_on && cfg->recon_lists == GEOADV_RECON_LISTS_ADAPTIVE) {      // (without it: no policy inside a run, the lists stay on)
+        if (hipHostMalloc(reinterpret_cast<void **>(&at->list_hint), sizeof(unsigned long long) * 5, hipHostMallocDefault) == hipSuccess)
+            for (int k = 0; k < 5; ++k) at->list_hint[k] = 0;
+        else { at->list_hint = nullptr; (void)hipGetLastError(); }
+    }
     at->jac_valid = false;
     at->tail_epoch = 0; at->loss_target = 0; at->grid_calls = 0;      // (the arena is zeroed above: flags, counters)
     {
@@ -759,6 +863,7 @@ extern "C" void geoadv_attack_destroy(geoadv_attack *at) {
     if (!at) return;
     if (at->counted) at->ae->attack_refs.fetch_sub(1);
     for (auto e : at->ev) (void)hipEventDestroy(e);
+    if (at->list_hint) (void)hipHostFree(at->list_hint);
     (void)hipFree(at->arena);
     delete at;
 }
@@ -780,6 +885,8 @@ extern "C" int geoadv_attack_set_inputs(geoadv_attack *at, const float *source_p
     for (int i = 0; i < 2; ++i)                                                            // new clouds: every verdict is open again
         GA_HIP(hipMemsetAsync(at->need_adv[i], 0, sizeof(int) * 8 * (size_t)at->B, st));
     GA_HIP(hipMemsetAsync(at->tail_ready + at->B, 0, sizeof(unsigned), st));               // a new run starts without a failure on record
+    if (int rc = lists_invalidate(at, st)) return rc;                                     // a new target: the lists say nothing about it
+    if (at->lists.list_row && at->cfg.recon_lists == GEOADV_RECON_LISTS_ADAPTIVE) at->lists_on = true;   // ... and the policy starts over
     at->fwd_valid = false; at->adv_valid = false;
     return GEOADV_OK;
 }
@@ -802,6 +909,7 @@ extern "C" int geoadv_attack_init_pert(geoadv_attack *at, const float *init_pert
     GA_HIP(hipMemsetAsync(at->best_metrics, 0, 4 * (size_t)at->B * 4, st));
     GA_HIP(hipMemsetAsync(at->best_adv, 0, 4 * bn3, st));
     GA_HIP(hipMemsetAsync(at->best_recon, 0, 4 * bn3, st));
+    if (int rc = lists_invalidate(at, st)) return rc;      // recon jumps with the new pert
     at->fwd_valid = false; at->adv_valid = false;
     return GEOADV_OK;
 }
@@ -843,6 +951,41 @@ extern "C" int geoadv_attack_get_best(geoadv_attack *at, const float *target_ae_
 extern "C" int geoadv_attack_set_source_search(geoadv_attack *at, int on) {
     GA_REQUIRE(at, "attack_set_source_search: null handle");
     at->chamfer_prune = on != 0;           // read by every forward (do_forward); the verdict flags keep their state
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_attack_set_recon_lists(geoadv_attack *at, int on) {
+    GA_REQUIRE(at, "attack_set_recon_lists: null handle");
+    GA_REQUIRE(on >= 0 && on <= 256, "attack_set_recon_lists: on=%d must be 0, 1 or a period of 2 ... 256 forwards", on);
+    at->lists_on = on != 0 && at->lists.list_row != nullptr;      // read by every forward (do_forward); switching on starts with an anchor
+    if (on >= 2) at->list_period = on;                            // (the period sweep of docs/DEAD_ENDS.md; 1 keeps the period)
+    if (!at->lists_on || on >= 2) at->list_age = -1;
+    return GEOADV_OK;
+}
+
+extern "C" int geoadv_attack_list_state(geoadv_attack *at, long long state[GEOADV_LIST_STATE_COUNT], void *stream) {
+    GA_REQUIRE(at && state, "attack_list_state: null argument");
+    for (int i = 0; i < GEOADV_LIST_STATE_COUNT; ++i) state[i] = 0;
+    state[GEOADV_LIST_STATE_ON] = at->lists_on ? 1 : 0;
+    state[GEOADV_LIST_STATE_ANCHORS] = (long long)at->n_anchors;
+    state[GEOADV_LIST_STATE_LIST_ITERATIONS] = (long long)at->n_list_iters;
+    state[GEOADV_LIST_STATE_PERIOD] = at->list_period;
+    if (!at->lists.list_row) return GEOADV_OK;
+    hipStream_t st = as_stream(stream);
+    unsigned long long h[4];
+    std::vector<int> need(8 * (size_t)at->B);
+    const int *cur = at->lists.need[(at->list_age < 0 ? 0 : at->list_age) & 1];     // the flags the next list iteration would act on
+    GA_HIP(hipMemcpyAsync(h, at->lists.stats, sizeof(h), hipMemcpyDeviceToHost, st));
+    GA_HIP(hipMemcpyAsync(need.data(), cur, sizeof(int) * need.size(), hipMemcpyDeviceToHost, st));
+    GA_HIP(hipStreamSynchronize(st));
+    state[GEOADV_LIST_STATE_CERTIFIED] = (long long)h[0]; state[GEOADV_LIST_STATE_REFUSED] = (long long)h[1];
+    state[GEOADV_LIST_STATE_UNLISTED] = (long long)h[2]; state[GEOADV_LIST_STATE_HANDED_BACK] = (long long)h[3];
+    if (at->list_age >= 0)
+        for (int c = 0; c < at->B; ++c) {
+            int any = 0;
+            for (int k = 0; k < 8; ++k) any |= need[8 * (size_t)c + k];
+            state[GEOADV_LIST_STATE_FLAGGED] += any ? 1 : 0;
+        }
     return GEOADV_OK;
 }
 

@@ -142,11 +142,14 @@ size_t chamfer_sym_workspace_floats(int pairs, int b, int n, int m);
 struct GridArgs;
 struct JacRider;
 struct LossRider;
+struct ListRider;
 // Executes a plan.  need1: per-cloud flags (int[8 * b], 16-byte aligned) restricting the SECOND pair to the clouds that still need the
 // all-pairs kernel; rider / jac / loss: the riders the plan has block ranges for (their first_block / blocks / clouds / raise_prio
 // come from the plan; loss->target already counts plan.loss_arrivals); row64: the packed buffer when plan.rows is PACKED.
+// need0: the same kind of flags for the FIRST pair (the loop's neighbour lists answer the other clouds, chamfer_lists.h); null = every cloud.
 int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *workspace, const int *need1, const GridArgs *rider,
-                       const JacRider *jac, const LossRider *loss, unsigned long long *row64, hipStream_t stream);
+                       const JacRider *jac, const LossRider *loss, unsigned long long *row64, hipStream_t stream, const int *need0 = nullptr,
+                       const ListRider *lists = nullptr);      // lists: the list queries as further workgroups of the launch (plain kernel, no hosted loss riders)
 // the operator form: every cloud live, no rider, rows final on return
 int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, float *workspace, hipStream_t stream);
 

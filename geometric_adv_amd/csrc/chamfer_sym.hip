@@ -27,6 +27,7 @@
 #include "encoder_jac.h"
 #include "chamfer_sym.h"
 #include "chamfer_mx.h"
+#include "chamfer_lists.h"
 #include "loss_cgrad.h"
 #include <atomic>
 #include <limits.h>
@@ -54,6 +55,7 @@ struct ChamferSymArgs {
     GridRider rider;           // the attack loop: the paired grid search of (adv, source) as extra workgroups of the scan launch
     JacRider jac;              // ... and the encoder's pool Jacobian (encoder_jac.h): needed by the NEXT step's backward only
     LossRider loss;            // ... and the loop's loss + gradient workgroups (loss_cgrad.h), which wait for their cloud's scan and search
+    ListRider lists;           // ... and the neighbour-list queries of pair 0 (chamfer_lists.h): the last blocks of the grid, beyond the plan's
 };
 
 constexpr int CS_THREADS = 512;               // 8 waves
@@ -107,6 +109,7 @@ __global__ __launch_bounds__(CS_THREADS, 4) void chamfer_sym_kernel(ChamferSymAr
     if (grid_rider_block<GR_MAX_N>(a.rider)) return;
     if (jac_rider_block(a.jac, stage)) return;
     if (loss_rider_block(a.loss, reinterpret_cast<unsigned *>(stage))) return;
+    if (list_rider_block<CS_THREADS>(a.lists, reinterpret_cast<unsigned *>(stage))) return;
     GA_STAMP(0, 0);
     const int lin = blockIdx.x - a.rider.blocks;           // (the search's workgroups come first); XCD-aware mapping, see chamfer_scan_kernel
     const int xcd = lin & 7, slot = lin >> 3;
@@ -569,7 +572,7 @@ int launch_chamfer_sym(const ChamferPair *pairs, int np, int b, int n, int m, fl
 }
 
 int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *workspace, const int *need1, const GridArgs *rider,
-                       const JacRider *jac, const LossRider *loss, unsigned long long *row64, hipStream_t stream) {
+                       const JacRider *jac, const LossRider *loss, unsigned long long *row64, hipStream_t stream, const int *need0, const ListRider *lists) {
     const SymRequest &r = p.req;
     if (p.grid == 0) return GEOADV_OK;
     GA_REQUIRE((need1 != nullptr) == r.need1 && (rider != nullptr) == (p.search.count > 0) && (jac != nullptr) == (p.jac.count > 0) &&
@@ -577,7 +580,7 @@ int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *worksp
                "chamfer_sym: the launch's arguments are not the ones its plan was made for");
     const SymShape &s = p.shape;
     ChamferSymArgs a;
-    a.need[0] = nullptr; a.need[1] = need1;
+    a.need[0] = need0; a.need[1] = need1;
     a.pair_base = r.pair_base; a.q_clouds = r.q_clouds;
     for (int i = 0; i < r.np; ++i) a.pr[i] = pairs[i];
     a.n = r.n; a.m = r.m; a.clouds = r.b; a.pairs = r.np;
@@ -602,7 +605,13 @@ int launch_chamfer_sym(const SymPlan &p, const ChamferPair *pairs, float *worksp
     if (p.loss.count) a.loss = *loss;
     else a.loss.done = nullptr;
     a.loss.first_block = p.loss.first; a.loss.blocks = p.loss.count; a.loss.clouds = r.b;
-    if (p.kernel == 0) chamfer_sym_kernel<<<p.grid, CS_THREADS, p.lds_bytes, stream>>>(a);
+    a.lists.blocks = 0;
+    if (lists) {   // (the plain kernel without hosted loss riders only: those would not wait for these)
+        GA_REQUIRE(p.kernel == 0 && p.loss.count == 0, "chamfer_sym: this plan cannot host the list queries");
+        a.lists = *lists;
+        a.lists.first_block = (int)p.grid;
+    }
+    if (p.kernel == 0) chamfer_sym_kernel<<<p.grid + (unsigned)a.lists.blocks, CS_THREADS, p.lds_bytes, stream>>>(a);
     else chamfer_mx_kernel<8><<<p.grid, MX_THREADS, p.lds_bytes, stream>>>(a);
     GA_LAUNCH_CHECK();
     if (p.rows != GEOADV_PLAN_ROWS_MERGE_LAUNCH) return GEOADV_OK;   // final, or the caller's next launch reads partials / packed words

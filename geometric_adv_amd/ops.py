@@ -102,6 +102,43 @@ def nn_distance_sym(xyz1, xyz2):
     return dist1, idx1, dist2, idx2
 
 
+def nn_distance_lists(xyz1_anchor, xyz2, dist1_anchor, dist2_anchor, skin, xyz1, capacity=16):
+    """nn_distance(xyz1, xyz2) from exact neighbour lists (csrc/chamfer_lists.hip: what the attack loop does between two all-pairs
+    scans of (recon, target)): the lists are built from the anchor cloud xyz1_anchor, its exact minima against xyz2 and a skin per
+    cloud (scalar or (b,)), then queried with the moved xyz1.  Returns (dist1, idx1, dist2, idx2, state, flags): the four outputs of
+    nn_distance(xyz1, xyz2) bit for bit; state int64 (3,): queries certified from their list, listed but refused, unlisted (the
+    last two are answered by brute force in the same launch); flags int32 (b,): clouds the loop would hand back to the scan."""
+    xyz1_anchor, xyz2 = _xyz_pair(xyz1_anchor, xyz2, "NnDistanceLists")
+    xyz1 = _f32(xyz1, "xyz1", 3)
+    if tuple(xyz1.shape) != tuple(xyz1_anchor.shape):
+        raise ValueError("nn_distance_lists expects xyz1 of the anchor's shape")
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    dev = xyz1.device
+    d1a, d2a = _f32(dist1_anchor, "dist1_anchor", 2), _f32(dist2_anchor, "dist2_anchor", 2)
+    if tuple(d1a.shape) != (b, n) or tuple(d2a.shape) != (b, m):
+        raise ValueError("nn_distance_lists expects the anchor minima as (b, n) and (b, m)")
+    sk = torch.as_tensor(skin, dtype=torch.float32, device=dev).reshape(-1)
+    sk = (sk.expand(b) if sk.numel() == 1 else sk).contiguous()
+    if sk.numel() != b:
+        raise ValueError("nn_distance_lists expects one skin, or one per cloud")
+    dist1 = torch.empty((b, n), dtype=torch.float32, device=dev)
+    idx1 = torch.empty((b, n), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((b, m), dtype=torch.float32, device=dev)
+    idx2 = torch.empty((b, m), dtype=torch.int32, device=dev)
+    state = torch.zeros((4,), dtype=torch.int64, device=dev)
+    flags = torch.zeros((b,), dtype=torch.int32, device=dev)
+    wb = int(_lib.lib().geoadv_nn_distance_lists_workspace_bytes(b, n, m, int(capacity)))
+    ws = torch.empty((wb,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = _lib.lib().geoadv_nn_distance_lists(b, n, m, _lib.ptr(xyz1_anchor), _lib.ptr(xyz2), _lib.ptr(d1a), _lib.ptr(d2a),
+                                                 _lib.ptr(sk), int(capacity), _lib.ptr(xyz1), _lib.ptr(dist1), _lib.ptr(idx1),
+                                                 _lib.ptr(dist2), _lib.ptr(idx2), _lib.ptr(state), _lib.ptr(flags), _lib.ptr(ws), wb,
+                                                 _lib.stream_handle())
+    _lib.check(st, "nn_distance_lists")
+    return dist1, idx1, dist2, idx2, state[:3], flags
+
+
 def chamfer_per_pc(dist1, dist2):
     """tf.reduce_mean(dist1, axis=1) + tf.reduce_mean(dist2, axis=1) of nn_distance's outputs (adv_ae.py:121,132;
     get_dists_per_point.py:75): (b,n), (b,m) -> (b,).  Summation order = the attack loop's own metrics, so a Chamfer

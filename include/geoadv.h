@@ -69,6 +69,24 @@ int geoadv_nn_distance_sym(int b, int n, const float *xyz1, int m, const float *
                            float *dist1, int *idx1, float *dist2, int *idx2,
                            float *workspace, size_t workspace_floats, void *stream);
 
+/* nn_distance(xyz1, xyz2) from exact neighbour lists (csrc/chamfer_lists.hip; the attack loop answers nn_distance(recon, target)
+ * this way between two all-pairs scans): xyz2 is fixed and xyz1 has moved a little since an ANCHOR at which the exact minima are
+ * known.  The call builds, for every row and every column, the list of partners whose ANCHOR distance D(xyz1_anchor, xyz2) is below
+ * tau = (sqrt(minimum) + skin[cloud])^2 -- at most `capacity` (1 ... 32) entries; a query with more is unlisted -- and then answers
+ * every query for the moved xyz1: from its list where the certificate holds (no partner outside the list can reach the list's
+ * best: sqrt(best) + displacement + margin < sqrt(tau), the displacement being the row's own for a row query and the cloud's
+ * largest for a column query), by brute force over all partners otherwise.  Either way the four outputs are those of
+ * geoadv_nn_distance(xyz1, xyz2) bit for bit for finite inputs, ties to the lowest index.  dist1_anchor / dist2_anchor [b,n] / [b,m]
+ * must be the exact minima of nn_distance(xyz1_anchor, xyz2); n, m <= 2048.  state (device, 4 words): queries certified, listed but
+ * refused, unlisted; 0.  flags (device, [b]): 1 for a cloud in which a workgroup refused more than a quarter of its 256 queries
+ * (the loop hands such a cloud back to the scan until its next anchor).  Non-finite coordinates: every query they touch is
+ * refused and answered by brute force with an in-range index.  workspace: geoadv_nn_distance_lists_workspace_bytes bytes. */
+size_t geoadv_nn_distance_lists_workspace_bytes(int b, int n, int m, int capacity);
+int geoadv_nn_distance_lists(int b, int n, int m, const float *xyz1_anchor, const float *xyz2, const float *dist1_anchor,
+                             const float *dist2_anchor, const float *skin, int capacity, const float *xyz1, float *dist1,
+                             int *idx1, float *dist2, int *idx2, unsigned long long *state, int *flags, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 /* chamfer_dist[b] = reduce_mean(dist1[b,:]) + reduce_mean(dist2[b,:]) -- the scalar every caller of nn_distance forms next
  * (adv_ae.py:121,132; get_dists_per_point.py:75; prepare_indices_for_attack.py:114) -- in the summation order of the
  * attack loop's own metrics, so that a Chamfer distance recomputed from saved clouds equals adversarial_metrics[:,:,2]
@@ -1015,6 +1033,13 @@ typedef struct geoadv_attack_config {
                                      * instead of riding in the next forward's point loaders                           */
     int   chamfer_kernel;           /* GEOADV_CHAMFER_AUTO (0: by batch size, GEOADV_SYM_MIN_POINTS), _TWO_SCAN (the public op's kernel),
                                      * _SYMMETRIC (one evaluation per pair serves both directions)                      */
+    int   recon_lists;              /* nn_distance(recon, target) between two all-pairs scans from exact neighbour lists (csrc/chamfer_lists.h):
+                                     * GEOADV_RECON_LISTS_ADAPTIVE (0, default) = on from the 49th forward after set_inputs / init_pert (Adam's
+                                     * first steps move the reconstruction fastest; those forwards scan), switched off for the rest of a batch when the scan
+                                     * has to take most clouds back (a victim whose reconstructions jump past the skin) and on again by
+                                     * set_inputs; _OFF (1) = every forward scans; _PINNED (2) = on from the first forward, no policy.  Used by the output-space
+                                     * attack on clouds of up to 2048 points under the symmetric scan with the paired search in use, without the EMD term; every other
+                                     * configuration scans as before.  Same results, bit for bit.  Per handle. */
     /* The kNN outlier term: the defense-aware (adaptive) attack.  With knn_weight != 0 the loop minimises, per cloud b,
      *   loss_adv + dist_weight[b] * (loss_dist + knn_weight * K(adv))
      * K and dK/dadv EXACTLY the rule of geoadv_knn_outlier_loss above with k = knn_k and alpha = (double)knn_alpha (search knn_point(k + 1),
@@ -1066,6 +1091,9 @@ typedef struct geoadv_attack_config {
 #define GEOADV_CHAMFER_AUTO      0
 #define GEOADV_CHAMFER_TWO_SCAN  1
 #define GEOADV_CHAMFER_SYMMETRIC 2
+#define GEOADV_RECON_LISTS_ADAPTIVE 0
+#define GEOADV_RECON_LISTS_OFF      1
+#define GEOADV_RECON_LISTS_PINNED   2
 
 /* Allocates device memory; synchronous.  Its own device work -- the arena's zero fill and, for the symmetric scan, a probe launch of
  * how the device deals workgroups to its XCDs, which writes the handle's own scratch -- runs on the null stream and is complete
@@ -1188,6 +1216,20 @@ int geoadv_debug_emd_sparse_state(int fused, int b, int n, int m, const float *t
  * kernel, by configuration or batch size), *handed_back = number of clouds of the batch whose pairing the search currently
  * judges too poor (they go through the all-pairs kernel; verdicts of the last forward).  Synchronises the stream. */
 int geoadv_attack_search_state(geoadv_attack *at, int *searched, int *handed_back, void *stream);
+
+/* From the next forward on: on != 0 -- nn_distance(recon, target) from the neighbour lists where the handle has them (the first
+ * forward after it is an anchor); 0 -- the all-pairs scan in every forward; 2 ... 256 -- on, with that many forwards per anchor from
+ * the next forward on (16 when the handle is created).  Same results either way. */
+int geoadv_attack_set_recon_lists(geoadv_attack *at, int on);
+/* How nn_distance(recon, target) has been answered since the handle was created (host memory; synchronises the stream):
+ * state[GEOADV_LIST_STATE_*] = lists in use now; anchors (scan + list build) and list iterations (scan gated off for every cloud not
+ * handed back) launched; queries certified from their list, listed but refused, unlisted (both answered by brute force in the list
+ * launch); cloud-iterations the scan took over because the cloud had been handed back; clouds currently handed back; forwards
+ * per anchor. */
+enum { GEOADV_LIST_STATE_ON = 0, GEOADV_LIST_STATE_ANCHORS, GEOADV_LIST_STATE_LIST_ITERATIONS, GEOADV_LIST_STATE_CERTIFIED,
+       GEOADV_LIST_STATE_REFUSED, GEOADV_LIST_STATE_UNLISTED, GEOADV_LIST_STATE_HANDED_BACK, GEOADV_LIST_STATE_FLAGGED,
+       GEOADV_LIST_STATE_PERIOD, GEOADV_LIST_STATE_COUNT };
+int geoadv_attack_list_state(geoadv_attack *at, long long state[GEOADV_LIST_STATE_COUNT], void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Victim auto-encoder TRAINING step: PointNetAutoEncoder._create_loss / _setup_optimizer
